@@ -22,6 +22,8 @@ it: from the block resident in page-locked HOST memory to its compressed record 
   * 'H': everything on the GPU, the record is copied to host memory inside the step.
   * --bwt-only: the transform alone (output stays in HBM); with --size-mib 1024 this is
     BASELINE config 5.
+  * --dump-outputs DIR: after the clock stops, what the last timed step computed goes to
+    DIR/<name>.npy (dump_outputs), so that two builds can be compared output for output.
 Blocks are independent, so rank r works on its own blocks and no data-path collective exists;
 torch.distributed is used only for the barrier and the max-over-ranks of the elapsed time.
 Rank 0 prints ONE JSON line.
@@ -214,6 +216,32 @@ def _cgroup_throttle():
         return None
 
 
+DUMP_SAMPLE = 4 << 20       # --dump-outputs: elements kept of a longer output (16 MB as float32)
+DUMP_SEED = 20261015        # ... at the sorted, distinct indices np.unique(default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+
+
+def dump_outputs(path, outputs, meta):
+    """--dump-outputs: writes every array of `outputs` ({name: unsigned integer array}) as
+    path/<name>.npy -- 8-bit arrays as float32, 16- and 32-bit ones as float64, both exact.  An
+    array longer than DUMP_SAMPLE keeps the elements at a fixed seeded set of indices, so two runs
+    on outputs of the same length keep the same elements.  Returns `meta` with, per array, its
+    full length, the CRC-32 of its full contents and whether it was sampled (for the result line)."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    files = dict(meta, arrays={})
+    for name, a in outputs.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype.kind == "u" and a.itemsize <= 4, (name, a.dtype)
+        entry = {"dtype": str(a.dtype), "length": int(a.size), "crc32": zlib.crc32(a.view(np.uint8)), "sampled": False}
+        if a.size > DUMP_SAMPLE:
+            a = a[np.unique(np.random.default_rng(DUMP_SEED).integers(0, a.size, DUMP_SAMPLE))]
+            entry.update(sampled=True, kept=int(a.size),
+                         indices="np.unique(np.random.default_rng(%d).integers(0, length, %d))" % (DUMP_SEED, DUMP_SAMPLE))
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32 if a.itemsize == 1 else np.float64))
+        files["arrays"][name] = entry
+    return files
+
+
 def main():
     if len(sys.argv) == 6 and sys.argv[1] == "--cpu-c4-worker":
         _cpu_c4_worker(int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4]), sys.argv[5])
@@ -241,6 +269,11 @@ def main():
                     help="also time 8 pinned single-thread CPU runs at once (the CPU analogue of the 8-GPU row): cpu_baseline_c4")
     ap.add_argument("--corpus-blocks", type=int, default=16,
                     help="BWTC_CORPUS=<file>: how many blocks of --size-mib of it are coded (reported as `corpus`)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed -- the record ('B' / 'H'; the "
+                         "transformed block with --bwt-only), the LF powers and the byte frequencies -- as DIR/<name>.npy "
+                         "(rank 0; a seeded sample of a long output, see dump_outputs); the line's `dump_outputs` "
+                         "describes them")
     args = ap.parse_args()
     coder = None if args.bwt_only else args.coder
 
@@ -317,6 +350,7 @@ def main():
     h_rec = ctx.host_alloc(bound) if coder == "H" else None      # page-locked: the record comes down in one DMA
 
     pending = []                 # tickets of blocks under way ('B')
+    last = {}                    # what the latest step computed: its block index, LF powers, frequencies
     comp = [0]
     issued = [0]
     clock = {"gpu_s": 0.0, "collect_s": 0.0}
@@ -353,6 +387,7 @@ def main():
         cpu_of("copy_wait", ctx.copy_wait)               # block i has landed (its copy ran under block i-1's kernels)
         cpu_of("upload", upload, i + 1)                  # block i+1 goes up while block i is transformed
         lf, freqs = cpu_of("bwt_block_device", ctx.bwt_block_device, d_in[i % 2], d_out, size, 8)
+        last.update(i=i, lf=lf, freqs=freqs)
         if coder == "H":
             comp[0] = ctx.huffman_encode_device(d_out, size, lf, freqs, d_comp)
             rc = ctx.lib.bwtc_hip_memcpy_to_host(ctx.handle, h_rec.ctypes.data, d_comp, comp[0])
@@ -438,6 +473,22 @@ def main():
     drain_ms = 1e3 * (time.perf_counter() - t0)
     rss["after_drain"] = _rss_gb()
     comp_bytes = comp[0]
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed step's outputs, before anything else reuses its buffers: its record (for 'B' the last one
+        # drained, the pipeline being first in first out) or, with --bwt-only, the transformed block still in HBM
+        if coder == "B":
+            out_main = ring[last["i"] % len(ring)][:comp_bytes]
+        elif coder == "H":
+            out_main = h_rec[:comp_bytes]
+        else:
+            out_main = ctx.to_host(d_out, size)
+        # `block`: the step's place in the stream since the last reset -- a 'B' record also depends on the blocks
+        # before it (the models run on), so two runs compare when their `block` and `input` agree
+        src = "C3/C4 seed %d" % seeds[last["i"] % nblk] if args.workload == "c3" else args.workload
+        dumped = dump_outputs(args.dump_outputs,
+                              {"record" if coder else "bwt": out_main, "lf": last["lf"], "freqs": last["freqs"]},
+                              {"coder": coder or "bwt-only", "size": size, "block": last["i"], "input": src})
     # records the host workers finished inside the timed region: the rate the host half really
     # sustained (the records COLLECTED there may all have been finished during the fill)
     finished = (f1 - f0) if coder == "B" else args.steps
@@ -683,6 +734,8 @@ def main():
         out["degraded"] = degraded
         if corpus is not None:
             out["corpus"] = corpus
+        if dumped is not None:
+            out["dump_outputs"] = dict(dumped, dir=args.dump_outputs)
         if args.cpu_c4 and world == 1:
             out["cpu_baseline_c4"] = cpu_baseline_c4(args.cpu_size_mib or args.size_mib, coder or "", my_cpus or sorted(os.sched_getaffinity(0)))
         if world == 1 and not args.no_cpu_baseline:

@@ -68,3 +68,24 @@ def structured(rng, n):
     else:
         d = _synth().gen_dna(n, int(rng.integers(1, 1 << 30)))
     return kind, np.ascontiguousarray(d, dtype=np.uint8)
+
+
+def reference_sweep(count=400, seed=7):
+    """(block, starting points) pairs on which the oracle's sorter is held to the reference's:
+    small blocks of 1 to 256 symbols, every third one periodic, starting points 1 to 300.  The
+    reference's answers are stored in tests/golden/bwt_ref_random.json."""
+    rng = np.random.default_rng(seed)
+    for it in range(count):
+        n = int(rng.integers(1, 1200))
+        sigma = int(rng.choice([1, 2, 3, 4, 16, 256]))
+        d = rng.integers(0, sigma, n).astype(np.uint8)
+        if it % 3 == 0:
+            d = np.tile(d[:max(1, n // 7)], 8)[:n]
+        sp = int(rng.choice([1, 2, 3, 8, 256, 300]))
+        yield d, sp
+
+
+def digest(a):
+    """Short content digest of an array (its bytes as stored), for golden files."""
+    import hashlib
+    return hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest()[:20]

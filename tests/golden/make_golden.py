@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Generates tests/golden/bwt_small.json from the reference itself.
+"""Generates tests/golden/bwt_small.json, bwt_large.json and bwt_ref_random.json from the
+reference itself (`--ref-random` writes the last one alone).
 
 Run in the build container only (it needs /root/reference): the reference's own, unmodified
 libdivsufsort is compiled by oracle/Makefile into oracle/_ref/libbwtc_ref.so and driven
@@ -19,13 +20,33 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+import blockgen  # noqa: E402
 import oracle_lib  # noqa: E402
 from bwtc_amd import synth  # noqa: E402
+
+
+def ref_random():
+    """The reference's answers on blockgen.reference_sweep(): digests of the input, the BWT,
+    the LF powers and the byte frequencies, case by case."""
+    cases = []
+    for d, sp in blockgen.reference_sweep():
+        bwt, lf, freqs = oracle_lib.ref_bwt_block(d, sp)
+        cases.append({"size": int(d.size), "sp": sp, "input": blockgen.digest(d),
+                      "bwt": blockgen.digest(bwt), "lf": blockgen.digest(lf), "freqs": blockgen.digest(freqs)})
+    head = {"generator": "tests/golden/make_golden.py --ref-random (reference libdivsufsort via oracle/_ref)",
+            "digest": "blockgen.digest: the first 20 hex digits of the SHA-256 of the array's bytes "
+                      "(uint8 blocks, uint32 LF powers and frequencies)"}
+    with open(os.path.join(HERE, "bwt_ref_random.json"), "w") as f:       # one case per line
+        f.write(json.dumps(head)[:-1] + ',\n"cases": [\n' + ",\n".join(json.dumps(c) for c in cases) + "\n]}\n")
+    print("wrote %d cases" % len(cases))
 
 
 def main():
     oracle_lib.build()
     assert oracle_lib.ref() is not None, "reference build missing"
+    ref_random()
+    if "--ref-random" in sys.argv:
+        return
     rng = np.random.default_rng(20261003)
     cases = []
 

@@ -9,6 +9,7 @@ import os
 import numpy as np
 import pytest
 
+import blockgen
 from bwtc_amd import synth
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -53,19 +54,19 @@ def test_generators_are_stable():
 
 
 def test_oracle_vs_reference_build_random(oracle):
-    if oracle.ref() is None:
-        pytest.skip("oracle/_ref not built (reference sources absent)")
-    rng = np.random.default_rng(7)
-    for it in range(400):
-        n = int(rng.integers(1, 1200))
-        sigma = int(rng.choice([1, 2, 3, 4, 16, 256]))
-        d = rng.integers(0, sigma, n).astype(np.uint8)
-        if it % 3 == 0:
-            d = np.tile(d[:max(1, n // 7)], 8)[:n]
-        sp = int(rng.choice([1, 2, 3, 8, 256, 300]))
+    """400 small seeded blocks: the oracle gives the reference's answers, as stored in
+    tests/golden/bwt_ref_random.json, and those of the reference build itself where oracle/_ref
+    was built."""
+    cases = _load("bwt_ref_random.json")["cases"]
+    sweep = list(blockgen.reference_sweep())
+    assert len(cases) == len(sweep) == 400
+    for i, (c, (d, sp)) in enumerate(zip(cases, sweep)):
+        assert (d.size, sp, blockgen.digest(d)) == (c["size"], c["sp"], c["input"]), ("input", i)
         a = oracle.oracle_bwt_block(d, sp)
-        b = oracle.ref_bwt_block(d, sp)
-        assert (a[0] == b[0]).all() and (a[1] == b[1]).all() and (a[2] == b[2]).all()
+        assert [blockgen.digest(x) for x in a] == [c["bwt"], c["lf"], c["freqs"]], i
+        if oracle.ref() is not None:
+            b = oracle.ref_bwt_block(d, sp)
+            assert (a[0] == b[0]).all() and (a[1] == b[1]).all() and (a[2] == b[2]).all(), i
 
 
 def test_suffix_array_is_sorted(oracle):
