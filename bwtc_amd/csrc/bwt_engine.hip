@@ -1911,6 +1911,7 @@ int BwtEngine::init(int dev, u32 max_block_size) {
     BWTC_HIP_TRY(hipMemset(scan_chain.status, 0, ((u64)scan_chain.cap_tiles + 1) * 8));
     scan_chain.ticket = scan_chain.status + scan_chain.cap_tiles;     // the last word
     scan_chain.err = d_small + 522;                                  // kSmallError: read back with every ranking step's counts
+    scan_chain.stream = stream;                                      // the transform's, the stream kernels' (and the farm's model passes)
     scan_chain.issued = 0;
     scan_chain.epoch = 0;
   }
@@ -2762,6 +2763,24 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
 //    fin_floor characters; they share at least *h_shallow
 //   `parked` entries in (d_parkS, d_parkHP): the other groups too large for a window, and what the last
 //    pass left tied; at least *h_parked characters
+//
+// The lists a pass writes hold cap + cap / 128 + 65536 entries, and a pass needs room for its regions' worst case:
+// chunk c of 64 workgroups appends to region c mod 16 and leaves at most its workgroups' strides of entries and one
+// group more -- m + m / 64 in the wide shape (stride and group 1024).  A pass (or the local list's steps) whose room
+// would not fit is not made: the list goes to the global rounds as it stands (stats.route bit 7).
+static bool fin_room(const FinRegions& rg, u32 stride, u32 group, u64 lcap, FinOut* ob) {
+  u64 room[kFinRegions] = {};
+  const u32 grid = rg.wfirst[rg.nreg];
+  const u32 nchunks = ceil_div(grid, kFinChunk);
+  for (u32 c = 0; c < nchunks; ++c) {
+    const u32 wgs = std::min(kFinChunk, grid - c * kFinChunk);
+    room[c % kFinRegions] += (u64)wgs * stride + group;
+  }
+  u64 at = 0;
+  for (u32 r = 0; r < kFinRegions; ++r) { ob->base[r] = (u32)std::min<u64>(at, 0xFFFFFFFFu); at += room[r]; }
+  return at <= lcap;
+}
+
 int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, FinShallow shal, FinOutcome* fo, bool keep_local, int max_passes) {
   hipStream_t st = stream;
   u32* cnt = d_small + kSmallFin;      // [1] hard list, [2] its smallest depth; [3] smallest depth of what waits for the rounds; [4] shallow list, [5] its smallest depth
@@ -2779,7 +2798,16 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
   u32 groups_left = 0;
   const u32 pass_chars = 8u * (u32)fin_words * (fin_words == 2 ? (u32)fin_rounds : 1u);
   const int depth_passes = (int)((255u - 48u) / pass_chars);      // the depth byte holds 255 (a level's depth is 48 at most)
+  const u64 lcap = cap + cap / 128 + 65536;
   for (int it = 0; it < std::min(std::min(fin_max_passes, std::max(1, depth_passes)), max_passes) && m > 0; ++it) {
+    // the regions of the list this pass leaves
+    FinOut ob;
+    if (!fin_room(rg, stride, (u32)group, lcap, &ob)) {
+      stats.route |= 128u;
+      if (std::getenv("BWTC_HIP_DEBUG"))
+        std::fprintf(stderr, "finisher pass %d: %u entries would not fit the lists in this shape (%d / %d); on to the rounds\n", it, m, window, group);
+      break;
+    }
     ++stats.rounds;
     stats.active_sum += m;
     stats.finisher_entries += m;
@@ -2789,20 +2817,6 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
     stats.alg_bytes += (u64)m * (14 * 4 / 3 + (pass_chars + 8) + 5);
     BWTC_HIP_TRY(hipMemsetAsync(ncnt, 0, (kFinRegions + 1) * 4, st));
     const u32 grid = rg.wfirst[rg.nreg];
-    // the regions of the list this pass leaves: chunk c of 64 workgroups appends to region c mod 16 and leaves at most
-    // its workgroups' strides of entries and one group more
-    FinOut ob;
-    {
-      u32 room[kFinRegions] = {};
-      const u32 nchunks = ceil_div(grid, kFinChunk);
-      for (u32 c = 0; c < nchunks; ++c) {
-        const u32 wgs = std::min(kFinChunk, grid - c * kFinChunk);
-        room[c % kFinRegions] += wgs * stride + (u32)group;
-      }
-      u32 at = 0;
-      for (u32 r = 0; r < kFinRegions; ++r) { ob.base[r] = at; at += room[r]; }
-      if ((u64)at > cap + cap / 128 + 65536) return -3;
-    }
 #define BWTC_FINISH_W(G, E, NW) hipLaunchKernelGGL((k_finish<G, E, NW>), dim3(grid), dim3(kFinTPB), 0, st, a, rg, (const u8*)d_T, n, \
                                              b, ob, ncnt, d_parkS + park0, d_parkHP + park0, d_hardC, cnt + 1, shal, d_SA, re)
 #define BWTC_FINISH_R(G, E, NR) hipLaunchKernelGGL((k_finish<G, E, 2, false, NR>), dim3(grid), dim3(kFinTPB), 0, st, a, rg, (const u8*)d_T, n, \
@@ -2853,7 +2867,15 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
   if ((u64)parked > cap) return -3;
   // (a pass has run: no group above the bound is left in the list; and its groups are small -- the comparison loop costs a
   // group's size per member: a block that is one text 256 times over has groups of 256 throughout and is the global rounds')
-  if (m && keep_local && passes_done >= 1 && (u64)m * 64 >= (u64)n && (u64)groups_left * 24 >= (u64)m) {
+  // (the local list's steps leave up to kFinRegions regions of it: room for that many more windows)
+  FinRegions worst;
+  std::memset(&worst, 0, sizeof worst);
+  worst.nreg = 1; worst.wfirst[1] = ceil_div(m, stride) + kFinRegions;
+  FinOut unused;
+  const bool local_fits = fin_room(worst, stride, (u32)group, lcap, &unused);
+  const bool want_local = m && keep_local && passes_done >= 1 && (u64)m * 64 >= (u64)n && (u64)groups_left * 24 >= (u64)m;
+  if (want_local && !local_fits) stats.route |= 128u;
+  if (want_local && local_fits) {
     // deep repeats in small groups: the doubling rounds take them group by group (local_pass), not through the global sort
     FinList home{d_hardS, d_LP0, d_LH0, d_hardC};
     u32 at = 0;
@@ -2938,17 +2960,7 @@ int BwtEngine::local_pass(u32 n, u64 h_global, RrEmit& re) {
   BWTC_HIP_TRY(hipMemsetAsync(cnt + 1, 0, 4, st));
   const u32 grid = local_rg.wfirst[local_rg.nreg];
   FinOut ob;
-  {
-    u32 room[kFinRegions] = {};
-    const u32 nchunks = ceil_div(grid, kFinChunk);
-    for (u32 c = 0; c < nchunks; ++c) {
-      const u32 wgs = std::min(kFinChunk, grid - c * kFinChunk);
-      room[c % kFinRegions] += wgs * stride + (u32)group;
-    }
-    u32 a2 = 0;
-    for (u32 r = 0; r < kFinRegions; ++r) { ob.base[r] = a2; a2 += room[r]; }
-    if ((u64)a2 > cap + cap / 128 + 65536) return -3;
-  }
+  if (!fin_room(local_rg, stride, (u32)group, cap + cap / 128 + 65536, &ob)) return -3;   // (finisher_passes keeps such lists off this route)
   FinShallow none{d_parkS, d_parkHP, cnt + 4, 0u};
   FinRank rk{d_rank, (u32)at, (u32)at2, d_US, d_UR};
 #define BWTC_LOCAL(G, E) hipLaunchKernelGGL((k_finish<G, E, 2, true>), dim3(grid), dim3(kFinTPB), 0, st, local_list(local_home), local_rg, (const u8*)d_T, n, \

@@ -346,6 +346,7 @@ struct BwtEngine {
   std::weak_ptr<DeviceWaveletJob> gm_pending;   // _prepare / _queue flow: the job whose model passes wait in the workspace for their state
   bool deferred_queue = false;        // _begin is in use: a begun block joins the stream one or two calls later
   bool async_streams_copy = false;    // set by _begin around its _prepare
+  WaveletRoutes routes;               // which route each wavelet block took (bwtc_hip_wavelet_routes)
   HostPipeline* pipeline = nullptr;   // worker threads, lane engines, coder tasks ('B'; made by the first block)
   std::vector<int> worker_cpus;       // bwtc_hip_set_worker_cpus: where those threads may run (empty: anywhere)
   std::map<u64, std::shared_ptr<DeviceWaveletJob> > jobs;

@@ -510,6 +510,22 @@ int bwtc_hip_wavelet_latency(bwtc_hip_ctx* ctx, double* mean_seconds) {
   return 0;
 }
 
+int bwtc_hip_wavelet_routes(bwtc_hip_ctx* ctx, bwtc_hip_wavelet_route_counts* out, int reset) {
+  if (!ctx || !out) return -1;
+  WaveletRoutes& r = ctx->eng.routes;
+  auto take = [reset](std::atomic<uint64_t>& c) { return reset ? c.exchange(0) : c.load(); };
+  out->trees_device = take(r.trees_device);
+  out->trees_host = take(r.trees_host);
+  out->models_device = take(r.models_device);
+  out->models_rejected = take(r.models_rejected);
+  out->reject_reasons = reset ? r.reject_reasons.exchange(0) : r.reject_reasons.load();
+  out->lost_turn = take(r.lost_turn);
+  out->models_host_two_stage = take(r.host_two_stage);
+  out->models_host_fused = take(r.host_fused);
+  out->models_host_lanes = take(r.host_lanes);
+  return 0;
+}
+
 int bwtc_hip_host_staging_bytes(uint64_t* now, uint64_t* peak) {
   if (now) *now = bwtc_hip::PinnedGauge::get().now.load();
   if (peak) *peak = bwtc_hip::PinnedGauge::get().peak.load();

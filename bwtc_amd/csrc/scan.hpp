@@ -105,15 +105,22 @@ static __global__ __launch_bounds__(kScanTPB) void k_scan_apply(u32* __restrict_
 // scans, and the ticket counter runs on (the host knows where each scan's tickets start).  Spins
 // are bounded: a tile that waits absurdly long sets the error word and gives up (the caller reads
 // the word back with its results).
+// Invariant: a chain's scans run on the device in the order the host issued them -- a tile's index is
+// its ticket minus `issued` at launch, so a scan that takes its tickets before an earlier-issued one
+// would compute tiles far out of range.  Hence ONE stream per chain: `stream`.  A scan issued on any
+// other stream (the model passes on their side stream, beside the next block's transform) takes the
+// three-launch form and leaves the chain, its ticket and its error word alone.
 struct ScanChain {
   unsigned long long* status = nullptr;   // one word per tile
   unsigned long long* ticket = nullptr;   // running ticket counter
   u32* err = nullptr;                     // device word, set to 1 on a timed-out wait
   u32 cap_tiles = 0;
+  hipStream_t stream = nullptr;           // the one stream whose scans take tickets of this chain
   unsigned long long issued = 0;          // host: tickets handed to earlier scans
   u32 epoch = 0;                          // host: this many scans so far
 };
-// the chain of the context the calling thread is working for (null: three-launch scans)
+// the chain of the context the calling thread is working for (null: three-launch scans); used only for
+// scans on the chain's own stream
 inline ScanChain*& current_scan_chain() { static thread_local ScanChain* c = nullptr; return c; }
 
 constexpr unsigned long long kScanFlagSum = 1ull << 32, kScanFlagPrefix = 2ull << 32;
@@ -206,7 +213,7 @@ static inline void exclusive_scan_u32(u32* data, u64 n, u32* partial, hipStream_
     return;
   }
   ScanChain* ch = current_scan_chain();
-  if (ch && ch->status && tiles <= ch->cap_tiles) {
+  if (ch && ch->status && st == ch->stream && tiles <= ch->cap_tiles) {
     ch->epoch = (ch->epoch + 1u) & ((1u << 30) - 1u);
     if (ch->epoch == 0) ch->epoch = 1;                // status words start zeroed: epoch 0 is never used
     hipLaunchKernelGGL(k_scan_chained, dim3(tiles), dim3(kScanTPB), 0, st, data, n, ch->status, ch->ticket, ch->issued, ch->epoch, ch->err);

@@ -22,6 +22,23 @@
 
 namespace bwtc_hip {
 
+// Why the device models of a block are not used (BWTC_HIP_REJECT_*, 0: used).  h_tail: [0] state after the
+// block, [1] the passes' error flags, [2] elements counted, [3] chained-scan error; state_ok: the block
+// starts and ends in the states its stream has there.
+static u32 device_model_rejects(const u32* h_tail, u32 n_coded, bool state_ok) {
+  u32 r = 0;
+  if (h_tail[1]) r |= BWTC_HIP_REJECT_FLAGS;
+  if (h_tail[2] != n_coded) r |= BWTC_HIP_REJECT_COUNT;
+  if (h_tail[3]) r |= BWTC_HIP_REJECT_SCAN;
+  if (!state_ok) r |= BWTC_HIP_REJECT_STATE;
+  if (std::getenv("BWTC_HIP_TEST_MODELS_FALLBACK")) r |= BWTC_HIP_REJECT_TEST;     // tests: treat the block as flagged
+  return r;
+}
+static void note_rejected(WaveletRoutes& routes, u32 reasons) {
+  WaveletRoutes::bump(routes.models_rejected);
+  routes.reject_reasons.fetch_or(reasons, std::memory_order_relaxed);
+}
+
 // The device half of a block comes in two parts with a piece of host work between them:
 //   scan     run scanner + section statistics (one sweep over the transformed block); the runs go
 //            to one of the engine's two run-array buffers, not into the transform's workspace
@@ -77,12 +94,14 @@ static int wavelet_finish_device_half(BwtEngine& e, const std::shared_ptr<Device
     const auto t2 = std::chrono::steady_clock::now();
     if (!e.pipeline) {
       e.pipeline = new HostPipeline(job.host_threads, e.huge_group_elements, e.max_inflight);
+      e.pipeline->routes = &e.routes;
       if (!e.worker_cpus.empty()) e.pipeline->setWorkerCpus(e.worker_cpus);
     }
     if (on_gpu_later && e.wt_coded) {
       // (another prepared block's passes may still wait in the workspace: its turn is lost, its models
       // go to the worker threads)
-      if (std::shared_ptr<DeviceWaveletJob> other = e.gm_pending.lock()) if (!other->queued) other->gm.ready = false;
+      if (std::shared_ptr<DeviceWaveletJob> other = e.gm_pending.lock())
+        if (!other->queued && other->gm.ready) { other->gm.ready = false; WaveletRoutes::bump(e.routes.lost_turn); }
       const bool w_recycled = e.w_pool.take(&job.w_owner);
       const u64 w_bytes = ((u64)e.wt_coded * 2 + 63) / 64 * 64;
       const size_t had = job.w_owner.size();
@@ -143,6 +162,7 @@ static int wavelet_finish_device_half(BwtEngine& e, const std::shared_ptr<Device
                    std::chrono::duration<double, std::milli>(t2 - t1).count(), e.pipeline->threads());
     }
     job.streams_ready = true;
+    WaveletRoutes::bump(e.routes.trees_device);
   } else {
     // the runs themselves: symbols and start offsets, as the scanner left them
     job.host_run_sym.resize(n_runs);
@@ -155,6 +175,7 @@ static int wavelet_finish_device_half(BwtEngine& e, const std::shared_ptr<Device
       job.host_secs[s].starts = job.host_run_start.data() + st.first_run[s];
     }
     job.host_route = true;
+    WaveletRoutes::bump(e.routes.trees_host);
   }
   return 0;
 }
@@ -253,18 +274,22 @@ static int wavelet_encode_queue_unguarded(BwtEngine& e, u64 ticket, u32 state_in
     job.gm_state_in = state_in;
     job.w_end_state = after;
     *state_out = after;
-    struct Join { std::shared_ptr<DeviceWaveletJob> job; HostPipeline* pipe; u32 state_in; };
-    Join* j = new Join{jobp, e.pipeline, state_in};
+    struct Join { std::shared_ptr<DeviceWaveletJob> job; HostPipeline* pipe; u32 state_in; WaveletRoutes* routes; };
+    Join* j = new Join{jobp, e.pipeline, state_in, &e.routes};
     const hipError_t hrc = hipLaunchHostFunc(e.d2h_stream, [](void* p) {
       std::unique_ptr<Join> j(static_cast<Join*>(p));
       DeviceWaveletJob& job = *j->job;
       job.callback_seen.store(true);
       const u32 n_coded = job.coded_pos.empty() ? 0u : job.coded_pos.back();
-      const bool ok = job.h_tail[1] == 0 && job.h_tail[2] == n_coded && job.h_tail[3] == 0 && job.h_tail[0] == job.w_end_state &&
-                      !std::getenv("BWTC_HIP_TEST_MODELS_FALLBACK");
-      if (!ok) {                                      // flagged: the worker threads model it from the packed streams
+      const u32 rejects = device_model_rejects(job.h_tail, n_coded, job.h_tail[0] == job.w_end_state);
+      if (rejects) {                                  // flagged: the worker threads model it from the packed streams
+        std::fprintf(stderr, "bwtc_hip: the device models of a block were not used (flags %u, counted %u of %u, state %u/%u); "
+                     "its models run on the host instead\n", job.h_tail[1], job.h_tail[2], n_coded, job.h_tail[0], job.w_end_state);
+        note_rejected(*j->routes, rejects);
         job.w = nullptr;
         if (!job.prob.reserve(static_cast<size_t>(n_coded) + 8)) { job.failed = true; HostPipeline::finishNow(job); return; }
+      } else {
+        WaveletRoutes::bump(j->routes->models_device);
       }
       // (the state handed on came from the device's state maps: a host half that ends elsewhere means
       // the stream after this block is wrong -- reported at _end, never passed over)
@@ -300,12 +325,12 @@ static int wavelet_encode_queue_unguarded(BwtEngine& e, u64 ticket, u32 state_in
   if (job.w) {
     // modelled on the device: the copy has landed (above); the passes report themselves
     const u32 n_coded = job.coded_pos.empty() ? 0u : job.coded_pos.back();
-    if (std::getenv("BWTC_HIP_TEST_MODELS_FALLBACK")) job.h_tail[1] |= 0x80u;    // tests: pretend the passes flagged the block
-    const bool ok = job.h_tail[1] == 0 && job.h_tail[2] == n_coded && job.h_tail[3] == 0 && job.h_tail[0] < 8 && job.gm_state_in == state_in &&
-                    e.wavelet_model == 'B';
-    if (ok) {
+    const u32 rejects = device_model_rejects(job.h_tail, n_coded, job.h_tail[0] < 8 && job.gm_state_in == state_in && e.wavelet_model == 'B');
+    if (!rejects) {
       job.w_end_state = job.h_tail[0];
+      WaveletRoutes::bump(e.routes.models_device);
     } else {
+      note_rejected(e.routes, rejects);
       // never seen; kept so that a surprise costs time, not bytes: the block's models run on the
       // worker threads from its packed streams (which came down as well)
       std::fprintf(stderr, "bwtc_hip: the device models of a block were not used (flags %u, counted %u of %u, state %u/%u); "

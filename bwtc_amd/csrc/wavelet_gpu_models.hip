@@ -427,7 +427,9 @@ int wavelet_models_run(BwtEngine& e, const GmPass& g, u32 state_in, uint16_t* h_
                      d_sstart, d_order, nc, nt, d_w, d_tail + 1);
   // total of the scan = every element counted once (else the tables do not describe the streams)
   BWTC_HIP_TRY(hipMemcpyAsync(d_tail + 2, d_base + g.n_base - 1, 4, hipMemcpyDeviceToDevice, st));
-  if (e.scan_chain.err) BWTC_HIP_TRY(hipMemcpyAsync(d_tail + 3, e.scan_chain.err, 4, hipMemcpyDeviceToDevice, st));   // a timed-out scan
+  // a timed-out scan; the chain serves only the context's own stream (scan.hpp): the side stream's scans take the
+  // three-launch form, and its error word belongs to the transform running beside them
+  if (e.scan_chain.err && st == e.scan_chain.stream) BWTC_HIP_TRY(hipMemcpyAsync(d_tail + 3, e.scan_chain.err, 4, hipMemcpyDeviceToDevice, st));
   BWTC_HIP_TRY(e.ensure_d2h_stream());
   BWTC_HIP_TRY(hipEventRecord(e.ev_models, st));
   BWTC_HIP_TRY(hipStreamWaitEvent(e.d2h_stream, e.ev_models, 0));

@@ -231,6 +231,7 @@ uint32_t HostPipeline::queue(const std::shared_ptr<WaveletJob>& jobp, uint32_t f
   if (job.models_left == 0 || job.sections_left == 0) { finishNow(job); ++clock.finished; return next_state; }
   ++clock.unfinished;
   if (model == 'B' && max_fused_engines_ && job.fused) {
+    if (routes) WaveletRoutes::bump(routes->host_fused);
     job.models_left = 0;
     job.fused_groups.assign(job.coder->sectionTasks(), std::vector<bwtc::wavelet::FusedGroup>());
     job.t_modelled = job.t_queued;
@@ -238,6 +239,7 @@ uint32_t HostPipeline::queue(const std::shared_ptr<WaveletJob>& jobp, uint32_t f
       pool_.submit(0, [this] { bwtc::wavelet::runFusedLanes(fused_sections_, &clock.coder_ns); });
     return next_state;
   }
+  if (routes) WaveletRoutes::bump(model == 'B' && bwtc::wavelet::simdModelsAvailable() ? routes->host_lanes : routes->host_two_stage);
   if (model == 'B' && bwtc::wavelet::simdModelsAvailable()) {
     // Sixteen groups per thread at a time, lanes refilled across blocks (wavelet_simd.hpp,
     // BlockGroupSource).  The block's few huge groups keep scalar tasks of their own, two groups

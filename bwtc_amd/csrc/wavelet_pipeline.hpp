@@ -39,6 +39,17 @@ struct StageClock {
   std::atomic<int> unfinished{0};      // blocks begun and not yet finished by the workers
 };
 
+// The route each of a context's wavelet blocks took, one count per block (bwtc_hip_wavelet_routes): every
+// route writes the same bytes, so only these tell which one did.  The join callback of a farmed block
+// counts from HIP's callback thread: relaxed atomics, a few per block.
+struct WaveletRoutes {
+  std::atomic<uint64_t> trees_device{0}, trees_host{0};
+  std::atomic<uint64_t> models_device{0}, models_rejected{0}, lost_turn{0};
+  std::atomic<uint64_t> host_two_stage{0}, host_fused{0}, host_lanes{0};
+  std::atomic<uint32_t> reject_reasons{0};       // BWTC_HIP_REJECT_* of every rejected block, OR-ed
+  static void bump(std::atomic<uint64_t>& c) { c.fetch_add(1, std::memory_order_relaxed); }
+};
+
 // Fixed set of threads over one queue ordered by (block, submission order): whatever the
 // oldest block still needs runs first, so the block the caller will collect next is never
 // overtaken by the work of newer ones.  Rank 0 is for the cross-block model engines.
@@ -340,6 +351,7 @@ class HostPipeline {
     }
   }
   StageClock clock;
+  WaveletRoutes* routes = nullptr;     // the context's counters: which worker-thread route modelled a block
  private:
   std::atomic<uint64_t> last_begin_ns_{0}, begin_interval_ns_{0};
   enum { kSpares = 40 };

@@ -27,6 +27,15 @@ class Stats(ctypes.Structure):
                 ("route", _u32), ("finisher_entries", _u32), ("alg_bytes", _u64)]
 
 
+class WaveletRouteCounts(ctypes.Structure):
+    _fields_ = [(f, _u64) for f in ("trees_device", "trees_host", "models_device", "models_rejected", "reject_reasons",
+                                     "lost_turn", "models_host_two_stage", "models_host_fused", "models_host_lanes")]
+
+
+# reasons a block's device models were not used (bwtc_hip.h BWTC_HIP_REJECT_*)
+REJECT_FLAGS, REJECT_COUNT, REJECT_SCAN, REJECT_STATE, REJECT_TEST = 1, 2, 4, 8, 16
+
+
 class KernelTimers(ctypes.Structure):
     _fields_ = [("scatter_launches", _u64), ("scatter_bytes", _u64), ("scatter_ms", ctypes.c_double)]
 
@@ -36,7 +45,7 @@ EXPORTS = [
     "bwtc_hip_destroy", "bwtc_hip_stream", "bwtc_hip_get_stats", "bwtc_hip_set_profiling",
     "bwtc_hip_get_kernel_timers", "bwtc_hip_copy_probe", "bwtc_hip_test_gpu_lanes", "bwtc_hip_malloc", "bwtc_hip_free", "bwtc_hip_memcpy_to_device",
     "bwtc_hip_memcpy_to_host", "bwtc_hip_host_alloc", "bwtc_hip_host_free",
-    "bwtc_hip_memcpy_to_device_async", "bwtc_hip_copy_wait", "bwtc_hip_wavelet_host_clock", "bwtc_hip_wavelet_host_progress", "bwtc_hip_wavelet_latency", "bwtc_hip_host_staging_bytes", "bwtc_hip_host_usable_cpus", "bwtc_hip_n_lf", "bwtc_hip_bwt",
+    "bwtc_hip_memcpy_to_device_async", "bwtc_hip_copy_wait", "bwtc_hip_wavelet_host_clock", "bwtc_hip_wavelet_host_progress", "bwtc_hip_wavelet_latency", "bwtc_hip_wavelet_routes", "bwtc_hip_host_staging_bytes", "bwtc_hip_host_usable_cpus", "bwtc_hip_n_lf", "bwtc_hip_bwt",
     "bwtc_hip_bwt_block", "bwtc_hip_bwt_block_device", "bwtc_hip_inverse_bwt_block",
     "bwtc_hip_inverse_bwt_block_device", "bwtc_hip_compress_bound",
     "bwtc_hip_huffman_encode_device", "bwtc_hip_huffman_encode", "bwtc_hip_transform_and_encode",
@@ -93,6 +102,7 @@ def load():
     L.bwtc_hip_wavelet_host_clock.argtypes = [_vp, _vp, _vp, _vp]
     L.bwtc_hip_wavelet_host_progress.argtypes = [_vp, _vp, _vp]
     L.bwtc_hip_wavelet_latency.argtypes = [_vp, _vp]
+    L.bwtc_hip_wavelet_routes.argtypes = [_vp, _vp, ctypes.c_int]
     L.bwtc_hip_host_staging_bytes.argtypes = [_vp, _vp]
     L.bwtc_hip_numa_node.argtypes = [_vp]
     L.bwtc_hip_host_cpu_slice.argtypes = [ctypes.c_int, _u32, _u32, _vp, _u32]
@@ -360,6 +370,14 @@ class Context:
         v = ctypes.c_double(0)
         _check(self.lib.bwtc_hip_wavelet_latency(self.handle, ctypes.byref(v)), "bwtc_hip_wavelet_latency")
         return v.value
+
+    def wavelet_routes(self, reset=False):
+        """The routes this context's wavelet blocks took so far, one count per block (bwtc_hip.h):
+        dict of trees_device, trees_host, models_device, models_rejected, reject_reasons (REJECT_* bits),
+        lost_turn, models_host_two_stage, models_host_fused, models_host_lanes.  reset: start again from zero."""
+        r = WaveletRouteCounts()
+        _check(self.lib.bwtc_hip_wavelet_routes(self.handle, ctypes.byref(r), 1 if reset else 0), "bwtc_hip_wavelet_routes")
+        return {f: int(getattr(r, f)) for f, _ in WaveletRouteCounts._fields_}
 
     def numa_node(self):
         """NUMA node of the context's GPU, -1 when the system does not say."""

@@ -42,6 +42,36 @@ inline void hipFatal(int rc, const char* what) {
   }
 }
 
+// The wavelet routes of every context this process closed (bwtc_hip_wavelet_routes), summed; with
+// BWTC_HIP_DEBUG set, one line on stderr at exit: "bwtc_hip routes: name=count ...".
+struct WaveletRouteTotals {
+  bwtc_hip_wavelet_route_counts sum;
+  bool seen = false;
+  WaveletRouteTotals() { std::memset(&sum, 0, sizeof sum); }
+  ~WaveletRouteTotals() {
+    if (!seen || !std::getenv("BWTC_HIP_DEBUG")) return;
+    std::fprintf(stderr, "bwtc_hip routes: trees_device=%llu trees_host=%llu models_device=%llu models_rejected=%llu "
+                 "reject_reasons=%llu lost_turn=%llu models_host_two_stage=%llu models_host_fused=%llu models_host_lanes=%llu\n",
+                 (unsigned long long)sum.trees_device, (unsigned long long)sum.trees_host, (unsigned long long)sum.models_device,
+                 (unsigned long long)sum.models_rejected, (unsigned long long)sum.reject_reasons, (unsigned long long)sum.lost_turn,
+                 (unsigned long long)sum.models_host_two_stage, (unsigned long long)sum.models_host_fused,
+                 (unsigned long long)sum.models_host_lanes);
+  }
+  static WaveletRouteTotals& get() { static WaveletRouteTotals t; return t; }
+  // a context's counts, before it is destroyed
+  static void note(bwtc_hip_ctx* ctx) {
+    bwtc_hip_wavelet_route_counts r;
+    if (!ctx || bwtc_hip_wavelet_routes(ctx, &r, 1) != 0) return;
+    WaveletRouteTotals& t = get();
+    t.seen = true;
+    t.sum.trees_device += r.trees_device; t.sum.trees_host += r.trees_host;
+    t.sum.models_device += r.models_device; t.sum.models_rejected += r.models_rejected;
+    t.sum.reject_reasons |= r.reject_reasons; t.sum.lost_turn += r.lost_turn;
+    t.sum.models_host_two_stage += r.models_host_two_stage; t.sum.models_host_fused += r.models_host_fused;
+    t.sum.models_host_lanes += r.models_host_lanes;
+  }
+};
+
 // ---- streams ---------------------------------------------------------------------------
 class OutStream {
  public:
@@ -200,7 +230,10 @@ class HipBWTransform : public BWTransform {
   explicit HipBWTransform(uint32 maxBlockSize, int device = 0) : m_ctx(0) {
     hipFatal(bwtc_hip_create(device, maxBlockSize, &m_ctx), "bwtc_hip_create");
   }
-  virtual ~HipBWTransform() { bwtc_hip_destroy(m_ctx); }
+  virtual ~HipBWTransform() {
+    WaveletRouteTotals::note(m_ctx);
+    bwtc_hip_destroy(m_ctx);
+  }
   void doTransform(byte* begin, uint32 length, std::vector<uint32>& LF) const {
     hipFatal(bwtc_hip_bwt(m_ctx, begin, length, &LF[0], (uint32)LF.size(), 0), "bwtc_hip_bwt");
   }

@@ -101,6 +101,7 @@ class BlockFarm {
       if (w.d_comp) bwtc_hip_free(w.ctx, w.d_comp);
       // the context first: destroying it lets blocks still under way finish, and they write their records into the
       // pending buffers (a worker that gave up early leaves some behind)
+      WaveletRouteTotals::note(w.ctx);
       bwtc_hip_destroy(w.ctx);
       for (size_t i = 0; i < w.outFree.size(); ++i) std::free(w.outFree[i]);
       for (size_t i = 0; i < w.pending.size(); ++i) std::free(w.pending[i].out);

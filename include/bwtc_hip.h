@@ -34,7 +34,8 @@ typedef struct bwtc_hip_stats {
   float    ms_sort;           /* radix sort passes only                                    */
   /* round 4: which way the block went, and the algorithmic bytes of the kernels that ran      */
   uint32_t route;             /* bit 0: long-key initial sort; bit 1: finisher settled the ties;
-                                 bit 2: text rounds ran; bit 3: rank[] completed late for doubling rounds */
+                                 bit 2: text rounds ran; bit 3: rank[] completed late for doubling rounds;
+                                 bit 7: a finisher list too long for its pass's shape went to the rounds */
   uint32_t finisher_entries;  /* list entries over all finisher passes                      */
   uint64_t alg_bytes;         /* compulsory bytes of the transform's kernels: every array a kernel
                                  reads counted once, every array it writes counted once (SURVEY.md
@@ -271,6 +272,29 @@ int bwtc_hip_wavelet_host_progress(bwtc_hip_ctx* ctx, uint64_t* queued, uint64_t
  * to its finished record.  Blocks under way needed = that time / the time per block of the caller's
  * loop; a context keeps the limit it was created with (BWTC_HIP_WAVELET_DEPTH). */
 int bwtc_hip_wavelet_latency(bwtc_hip_ctx* ctx, double* mean_seconds);
+/* The routes the context's wavelet blocks took (every route writes the same bytes; these say which
+ * one did), one count per block:
+ *   trees_device / trees_host   trees built by the stream kernels / by the host's own tree builder
+ *                               (blocks planStreams declines, BWTC_HIP_WAVELET=host);
+ *   models_device               models computed by the device passes and used;
+ *   models_rejected             device passes whose result was not used, reject_reasons the OR of
+ *                               the BWTC_HIP_REJECT_* bits seen;
+ *   lost_turn                   prepared blocks (_prepare / _queue) whose device passes lost their
+ *                               turn in the workspace to a later block;
+ *   models_host_*               blocks of a device-built tree modelled on the worker threads: two-stage
+ *                               (models, then range coders), fused engines, 16-lane model engines.
+ * reset != 0: the counters start again from zero after they are read. */
+#define BWTC_HIP_REJECT_FLAGS 1u     /* the passes flagged the block */
+#define BWTC_HIP_REJECT_COUNT 2u     /* elements counted != elements coded */
+#define BWTC_HIP_REJECT_SCAN  4u     /* a chained scan timed out */
+#define BWTC_HIP_REJECT_STATE 8u     /* the state in or after the block is not the stream's */
+#define BWTC_HIP_REJECT_TEST  16u    /* BWTC_HIP_TEST_MODELS_FALLBACK */
+typedef struct bwtc_hip_wavelet_route_counts {
+  uint64_t trees_device, trees_host;
+  uint64_t models_device, models_rejected, reject_reasons, lost_turn;
+  uint64_t models_host_two_stage, models_host_fused, models_host_lanes;
+} bwtc_hip_wavelet_route_counts;
+int bwtc_hip_wavelet_routes(bwtc_hip_ctx* ctx, bwtc_hip_wavelet_route_counts* out, int reset);
 /* Host staging memory (page-locked where the system allows) held by this process for blocks under
  * way -- packed streams and w-elements of every context -- now and at its highest so far: what a
  * deployment has to provide per rank for the depth it runs (no reference counterpart; the reference

@@ -248,8 +248,13 @@ def test_baseline_full_size_256MiB_text_B_record_equals_oracle(oracle):
     with hip.Context(0, size) as ctx:
         ctx.wavelet_reset()
         rec, bwt = ctx.transform_and_encode_wavelet(d, 8)
+        routes = ctx.wavelet_routes()
         lf, freqs = None, np.bincount(d, minlength=256).astype(np.uint32)
         bwt2, lf, freqs2 = ctx.bwt_block(d, 8)
+    # the stream kernels built the block's trees and the device passes modelled it (the host routes
+    # would give the same record)
+    assert routes["trees_device"] == 1 and routes["models_device"] == 1, routes
+    assert routes["models_rejected"] == 0 and routes["lost_turn"] == 0, routes
     assert (bwt == bwt2).all() and (freqs == freqs2).all()
     del bwt2, d
     want = oracle.oracle_wavelet_encode_block(bwt, lf, freqs)
@@ -540,3 +545,55 @@ def test_deep_repeats_take_the_local_rounds(oracle):
         assert (got[0] == want[0]).all() and (got[1] == want[1]).all() and (got[2] == want[2]).all()
         back = ctx.inverse_bwt_block(got[0], got[1])
         assert (back == d).all()
+
+
+_TIED_INPUTS = []
+
+
+def _mostly_tied_inputs(oracle, size):
+    """16 MiB blocks whose finisher list is most of the block: (a) the lines of the real-text snapshot,
+    each repeated 16 times, shuffled with a fixed seed; (b) a 4 MiB text copied four times.  With the
+    reference's sorter's answer where it was built, else the oracle's."""
+    if not _TIED_INPUTS:
+        import lzma
+        with lzma.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "real_text.txt.xz")) as f:
+            lines = f.read().split(b"\n")
+        rng = np.random.default_rng(1616)
+        order = rng.permutation(np.repeat(np.arange(len(lines)), 16))
+        text = b"\n".join(lines[i] for i in order)
+        assert len(text) >= size
+        a = np.frombuffer(text[:size], np.uint8).copy()
+        b = np.tile(synth.gen_text(size // 4, 17), 4)
+        for name, d in (("repeated_lines", a), ("four_copies", b)):
+            want = oracle.ref_bwt_block(d, 8) if oracle.ref() is not None else oracle.oracle_bwt_block(d, 8)
+            _TIED_INPUTS.append((name, d, want))
+    return _TIED_INPUTS
+
+
+@pytest.mark.parametrize("shape", ["default", "BWTC_HIP_FIN_WINDOW=2048,BWTC_HIP_FIN_GROUP=1024"])
+def test_wide_finisher_shape_on_blocks_that_are_mostly_tied(oracle, monkeypatch, shape):
+    """The finisher's wide shape (windows of 2048, groups of 1024: a pass leaves its list up to m + m / 64
+    entries of room) forced on 16 MiB blocks whose list is most of the block, in a context made for
+    exactly that size: the room of such a pass exceeds the lists, and the list must go on to the rounds
+    instead of failing the block.  Bit-equal to the reference either way; the default shape shows the
+    blocks do reach the finisher with a list of at least half of the block."""
+    from bwtc_amd import hip
+    if shape != "default":
+        for one in shape.split(","):
+            name, value = one.split("=")
+            monkeypatch.setenv(name, value)
+    size = 16 << 20
+    inputs = _mostly_tied_inputs(oracle, size)
+    with hip.Context(0, size) as ctx:
+        for name, d, (wb, wlf, wfr) in inputs:
+            bwt, lf, freqs = ctx.bwt_block(d, 8)
+            st = ctx.stats()
+            assert (bwt == wb).all() and (lf == wlf).all() and (freqs == wfr).all(), (name, shape)
+            print("%s %s: route %#x, finisher entries %d, rounds %d" % (name, shape, st.route, st.finisher_entries, st.rounds))
+            if shape == "default":
+                assert st.route & 2, (name, st.route)
+                if name == "repeated_lines":
+                    assert st.finisher_entries >= d.size // 2, (name, st.finisher_entries)
+            else:
+                # a finisher pass ran, or the list was handed to the rounds because a pass would not fit
+                assert st.route & (2 | 128), (name, st.route)

@@ -124,14 +124,29 @@ def _frame(coder, rec, size):
     return coder + _packed(size) + _packed(1) + b"\x00" + rec + b"\x00"
 
 
+def _assert_device_models(r, blocks=None):
+    """Every block whose trees the stream kernels built was modelled by the device passes, and their
+    result was used: no rejection, no lost turn (route counters, bwtc_hip_wavelet_routes).  The stream
+    would be the same bytes on the fallback routes; only the counters tell them apart."""
+    assert r["models_rejected"] == 0 and r["reject_reasons"] == 0, r
+    assert r["lost_turn"] == 0, r
+    assert r["models_device"] == r["trees_device"] > 0, r
+    if blocks is not None:
+        assert r["trees_device"] == blocks, r
+
+
 def test_wavelet_B_record_matches_oracle(hip_ctx, oracle):
     """WaveletEncoder::transformAndEncode ('B') through the C ABI (GPU transform + run scanner,
     host tree/range coder) against the oracle's literal restatement; a fresh stream per input."""
+    hip_ctx.wavelet_routes(reset=True)
     for name, data, sp in _inputs():
         hip_ctx.wavelet_reset()
         rec, bwt = hip_ctx.transform_and_encode_wavelet(data, sp)
         want = oracle.oracle_compress_B(data, max(data.size, 1), sp).tobytes()
         assert _frame(b"B", rec.tobytes(), data.size) == want, name
+    r = hip_ctx.wavelet_routes()
+    assert r["models_rejected"] == 0 and r["lost_turn"] == 0, r
+    assert r["models_device"] >= 1, r
 
 
 def test_wavelet_B_golden_and_multi_block_state(hip_ctx, oracle):
@@ -144,6 +159,7 @@ def test_wavelet_B_golden_and_multi_block_state(hip_ctx, oracle):
     d = synth.gen_text(700000, 3)
     bs = 250000
     hip_ctx.wavelet_reset()
+    hip_ctx.wavelet_routes(reset=True)
     out = b"B"
     for off in range(0, d.size, bs):
         blk = d[off:off + bs]
@@ -151,6 +167,7 @@ def test_wavelet_B_golden_and_multi_block_state(hip_ctx, oracle):
         out += _packed(blk.size) + _packed(1) + b"\x00" + rec.tobytes()
     out += b"\x00"
     assert out == oracle.oracle_compress_B(d, bs, 8).tobytes()
+    _assert_device_models(hip_ctx.wavelet_routes(), blocks=3)
 
 
 def test_wavelet_B_host_tree_path_gives_the_same_bytes(hip_ctx, oracle):
@@ -164,6 +181,7 @@ def test_wavelet_B_host_tree_path_gives_the_same_bytes(hip_ctx, oracle):
     finally:
         del os.environ["BWTC_HIP_WAVELET"]
     try:
+        hip_ctx.wavelet_routes(reset=True)
         for name, data, sp in _inputs():
             if data.size > (4 << 20):
                 continue
@@ -172,6 +190,10 @@ def test_wavelet_B_host_tree_path_gives_the_same_bytes(hip_ctx, oracle):
             rec_host, _ = ctx.transform_and_encode_wavelet(data, sp)
             rec_dev, _ = hip_ctx.transform_and_encode_wavelet(data, sp)
             assert rec_host.tobytes() == rec_dev.tobytes(), name
+        r = ctx.wavelet_routes()
+        assert r["trees_device"] == 0 and r["models_device"] == 0 and r["trees_host"] >= 8, r
+        r = hip_ctx.wavelet_routes()
+        assert r["trees_device"] > 0 and r["models_rejected"] == 0, r
     finally:
         ctx.close()
 
@@ -181,14 +203,17 @@ def test_wavelet_B_large_text_block(hip_ctx, oracle):
     against the oracle (a few seconds of CPU)."""
     data = synth.gen_text(32 << 20, 5)
     hip_ctx.wavelet_reset()
+    hip_ctx.wavelet_routes(reset=True)
     rec, bwt = hip_ctx.transform_and_encode_wavelet(data, 8)
     want = oracle.oracle_compress_B(data, data.size, 8).tobytes()
     assert _frame(b"B", rec.tobytes(), data.size) == want
+    _assert_device_models(hip_ctx.wavelet_routes(reset=True), blocks=1)
     # and the other extreme of the run structure: DNA, almost every byte its own run, 4 symbols
     data = synth.gen_dna(16 << 20, 9)
     hip_ctx.wavelet_reset()
     rec, bwt = hip_ctx.transform_and_encode_wavelet(data, 8)
     assert _frame(b"B", rec.tobytes(), data.size) == oracle.oracle_compress_B(data, data.size, 8).tobytes()
+    _assert_device_models(hip_ctx.wavelet_routes(), blocks=1)
 
 
 def test_wavelet_B_overlapped_blocks_equal_the_sequential_stream(hip_ctx, oracle):
@@ -197,6 +222,7 @@ def test_wavelet_B_overlapped_blocks_equal_the_sequential_stream(hip_ctx, oracle
     d = synth.gen_text(6 << 20, 9)
     bs = 1 << 20
     hip_ctx.wavelet_reset()
+    hip_ctx.wavelet_routes(reset=True)
     bufs, tickets, sizes = [], [], []
     for off in range(0, d.size, bs):
         blk = d[off:off + bs]
@@ -216,17 +242,22 @@ def test_wavelet_B_overlapped_blocks_equal_the_sequential_stream(hip_ctx, oracle
         stream += _packed(n) + _packed(1) + b"\x00" + out[:m].tobytes()
     stream += b"\x00"
     assert stream == oracle.oracle_compress_B(d, bs, 8).tobytes()
+    _assert_device_models(hip_ctx.wavelet_routes(), blocks=6)
 
 
 def test_wavelet_B_short_structured_streams_through_the_pipeline(hip_ctx, oracle):
     """Twenty-four short streams (all-equal bytes, periods with defects, Fibonacci words, tiny
     alphabets, repeats, text, DNA; tests/blockgen.py) cut into blocks of random size, up to twelve
-    under way at once through _begin/_end: block sizes from a few hundred bytes up change the route
-    from block to block (host tree builder / device streams, models on the device), buffers are
-    recycled across sizes, and the carried state runs through all of it.  Each stream byte-equal to
-    the oracle's sequential encoder.  (The fixed-seed part of scripts/fuzz_gpu_parity.py.)"""
+    under way at once through _begin/_end: block sizes from a few hundred bytes up change the shape
+    of the streams from block to block, buffers are recycled across sizes, and the carried state runs
+    through all of it.  Each stream byte-equal to the oracle's sequential encoder.  Every block goes
+    through the stream kernels and the device models (the route counters; no block of these shapes is
+    one planStreams declines -- the host tree builder is test_wavelet_B_host_tree_path_gives_the_same_bytes').
+    (The fixed-seed part of scripts/fuzz_gpu_parity.py.)"""
     import blockgen
     rng = np.random.default_rng(424242)
+    hip_ctx.wavelet_routes(reset=True)
+    n_blocks = 0
     for case in range(24):
         total = int(rng.integers(1000, 3 << 20))
         kind, d = blockgen.structured(rng, total)
@@ -240,6 +271,7 @@ def test_wavelet_B_short_structured_streams_through_the_pipeline(hip_ctx, oracle
             records.append(_packed(n) + _packed(1) + b"\x00" + out[:m].tobytes())
         for off in range(0, d.size, bs):
             blk = d[off:off + bs]
+            n_blocks += 1
             if len(pending) >= 12:
                 collect()
             d_in = hip_ctx.dmalloc(blk.size + 16)
@@ -254,6 +286,10 @@ def test_wavelet_B_short_structured_streams_through_the_pipeline(hip_ctx, oracle
             collect()
         stream = b"B" + b"".join(records) + b"\x00"
         assert stream == oracle.oracle_compress_B(d, bs, 8).tobytes(), (case, kind, total, bs)
+    # every block's trees came from the stream kernels, and no block's device models were turned down
+    r = hip_ctx.wavelet_routes()
+    assert r["trees_device"] == n_blocks and r["trees_host"] == 0, (n_blocks, r)
+    assert r["models_rejected"] == 0 and r["lost_turn"] == 0 and r["models_device"] > 0, r
 
 
 @pytest.mark.parametrize("models", ["device", "host"])
@@ -298,6 +334,13 @@ def test_wavelet_B_prepare_queue_flow_on_one_context(models, oracle, monkeypatch
             stream += _packed(n) + _packed(1) + b"\x00" + out[:m].tobytes()
         stream += b"\x00"
         assert stream == oracle.oracle_compress_B(d, bs, 8).tobytes()
+        r = ctx.wavelet_routes()
+        assert r["trees_device"] == len(blocks) and r["models_rejected"] == 0, r
+        if models == "device":
+            # the first block's turn is lost to the second; every other block is modelled on the device
+            assert r["lost_turn"] == 1 and r["models_device"] == len(blocks) - 1, r
+        else:
+            assert r["lost_turn"] == 0 and r["models_device"] == 0, r
     finally:
         ctx.close()
 
@@ -414,7 +457,17 @@ def test_wavelet_B_models_on_the_device_and_on_the_host_give_the_same_stream(mod
         for t, out, n in pend:
             stream += _packed(n) + _packed(1) + b"\x00" + out[:ctx.wavelet_encode_end(t)].tobytes()
         stream += b"\x00"
+        r = ctx.wavelet_routes()
     assert stream == oracle.oracle_compress_B(d, bs, 8).tobytes(), models
+    assert r["trees_device"] == len(pend) and r["lost_turn"] == 0, r
+    if models == "device":
+        _assert_device_models(r)
+    elif models == "host":
+        assert r["models_device"] == 0 and r["models_rejected"] == 0, r
+    else:
+        # every block's passes ran and were turned down by the test switch alone
+        assert r["models_device"] == 0 and r["models_rejected"] == len(pend), r
+        assert r["reject_reasons"] == hip.REJECT_TEST, r
 
 
 def test_wavelet_start_with_begun_blocks_not_yet_in_their_stream(hip_ctx, oracle):
@@ -507,6 +560,7 @@ def test_wavelet_B_huge_group_tasks_at_test_size(oracle):
         ctx.wavelet_reset()
         rec, _ = ctx.transform_and_encode_wavelet(data, 8)
         assert _frame(b"B", rec.tobytes(), data.size) == oracle.oracle_compress_B(data, data.size, 8).tobytes()
+        _assert_device_models(ctx.wavelet_routes(), blocks=1)
     finally:
         ctx.close()
 
@@ -582,5 +636,42 @@ def test_wavelet_B_lane_engines_give_the_sequential_stream(switch, oracle):
             stream += _packed(n) + _packed(1) + b"\x00" + out[:m].tobytes()
         stream += b"\x00"
         assert stream == oracle.oracle_compress_B(d, bs, 8).tobytes(), switch
+        _assert_device_models(ctx.wavelet_routes())
     finally:
         ctx.close()
+
+
+@pytest.mark.parametrize("side_stream", ["1", "0"])
+def test_wavelet_B_chained_scans_beside_the_next_transform(side_stream, oracle, monkeypatch):
+    """BWTC_HIP_SCAN=chained over six 8 MiB text blocks through _begin/_end: the model passes of a block
+    (their slot-base scan spans hundreds of tiles) run on their own stream beside the next block's
+    transform, whose scans take tickets of the context's chain.  A chain serves one stream only
+    (scan.hpp): the side stream's scans must not take its tickets or read its error word.  A scan that
+    went wrong there would only send the block to the host models -- the same bytes -- so the route
+    counters are what this test checks: no block rejected, no scan error seen.  BWTC_HIP_MODELS_STREAM=0
+    keeps the passes on the context's stream (then they do use the chain)."""
+    from bwtc_amd import hip
+    monkeypatch.setenv("BWTC_HIP_SCAN", "chained")
+    monkeypatch.setenv("BWTC_HIP_MODELS_STREAM", side_stream)
+    bs = 8 << 20
+    d = np.concatenate([synth.gen_text(bs, 60 + k) for k in range(6)])
+    with hip.Context(0, bs) as ctx:
+        ctx.wavelet_reset()
+        d_in = ctx.dmalloc(bs + 64)
+        pend, stream = [], b"B"
+        try:
+            for off in range(0, d.size, bs):
+                blk = d[off:off + bs]
+                ctx.to_device(d_in, blk)
+                lf, freqs = ctx.bwt_block_device(d_in, d_in, blk.size, 8)
+                out = np.zeros(ctx.compress_bound(blk.size), np.uint8)
+                pend.append((ctx.wavelet_encode_device_begin(d_in, blk.size, lf, freqs, out, threads=4), out, blk.size))
+        finally:
+            ctx.dfree(d_in)
+        for t, out, n in pend:
+            stream += _packed(n) + _packed(1) + b"\x00" + out[:ctx.wavelet_encode_end(t)].tobytes()
+        stream += b"\x00"
+        r = ctx.wavelet_routes()
+    assert stream == oracle.oracle_compress_B(d, bs, 8).tobytes(), side_stream
+    assert not r["reject_reasons"] & hip.REJECT_SCAN, r
+    _assert_device_models(r, blocks=6)

@@ -11,6 +11,20 @@ from bwtc_amd import synth
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DEBUG = dict(os.environ, BWTC_HIP_DEBUG="1")
+
+
+def _routes(stderr):
+    """The `bwtc_hip routes: ...` line compress prints at exit under BWTC_HIP_DEBUG (the wavelet
+    routes of all its contexts, summed), as a dict."""
+    lines = [ln for ln in stderr.splitlines() if ln.startswith("bwtc_hip routes: ")]
+    assert len(lines) == 1, stderr[-2000:]
+    return {k: int(v) for k, v in (f.split("=") for f in lines[0].split(": ", 1)[1].split())}
+
+
+def _assert_no_rejection(r):
+    assert r["models_rejected"] == 0 and r["reject_reasons"] == 0, r
+    assert r["trees_device"] > 0 and r["models_device"] > 0, r
 
 
 def test_cpp_host_mirror_program():
@@ -48,8 +62,11 @@ def test_compress_cli_roundtrip(tmp_path, oracle):
     # the reference's default coder 'B' (no -e): five blocks, overlapped by the Compressor loop
     dstb = tmp_path / "input.B.bwtc"
     r = subprocess.run([exe, "-m", "4", "-s", "8", "-v", "1", str(src), str(dstb)],
-                       capture_output=True, text=True, timeout=600)
+                       capture_output=True, text=True, timeout=600, env=DEBUG)
     assert r.returncode == 0, r.stderr
+    routes = _routes(r.stderr)
+    _assert_no_rejection(routes)
+    assert routes["models_device"] == routes["trees_device"] and routes["lost_turn"] == 0, routes
     sb = dstb.read_bytes()
     assert sb[:1] == b"B"
     assert sb == oracle.oracle_compress_B(data, int(4 * 1000000 * 0.185), 8).tobytes()
@@ -88,10 +105,15 @@ def test_cli_block_farm_over_two_contexts_gives_the_sequential_stream(tmp_path, 
         one = tmp_path / ("one.%s.bwtc" % enc)
         for devices, dst in (("0,0", tmp_path / ("two.%s.bwtc" % enc)), ("0,0,0", tmp_path / ("three.%s.bwtc" % enc))):
             r = subprocess.run([exe, "-m", "1", "-e", enc, "--devices", devices, str(src), str(dst)],
-                               capture_output=True, text=True, timeout=600)
+                               capture_output=True, text=True, timeout=600, env=DEBUG)
             assert r.returncode == 0, r.stderr
-        r = subprocess.run([exe, "-m", "1", "-e", enc, str(src), str(one)], capture_output=True, text=True, timeout=600)
+            if enc == "B":
+                _assert_no_rejection(_routes(r.stderr))
+        r = subprocess.run([exe, "-m", "1", "-e", enc, str(src), str(one)], capture_output=True, text=True, timeout=600,
+                           env=DEBUG)
         assert r.returncode == 0, r.stderr
+        if enc == "B":
+            _assert_no_rejection(_routes(r.stderr))
         want = (oracle.oracle_compress_B if enc == "B" else oracle.oracle_compress_H)(data, block, 8).tobytes()
         assert one.read_bytes() == want, enc
         assert (tmp_path / ("two.%s.bwtc" % enc)).read_bytes() == want, enc
@@ -102,9 +124,17 @@ def test_cli_block_farm_over_two_contexts_gives_the_sequential_stream(tmp_path, 
     for extra in ({"BWTC_HIP_MODELS": "host"}, {"BWTC_HIP_TEST_MODELS_FALLBACK": "1"}):
         dst = tmp_path / "two.B.alt.bwtc"
         r = subprocess.run([exe, "-m", "1", "-e", "B", "--devices", "0,0", str(src), str(dst)],
-                           capture_output=True, text=True, timeout=600, env=dict(os.environ, **extra))
+                           capture_output=True, text=True, timeout=600, env=dict(DEBUG, **extra))
         assert r.returncode == 0, r.stderr
         assert dst.read_bytes() == (tmp_path / "two.B.bwtc").read_bytes(), extra
+        routes = _routes(r.stderr)
+        assert routes["models_device"] == 0, (extra, routes)
+        if "BWTC_HIP_TEST_MODELS_FALLBACK" in extra:
+            # every block whose passes ran on the device was turned down, for the test switch alone
+            assert routes["models_rejected"] > 0 and routes["reject_reasons"] == 16, routes
+            assert "the device models of a block were not used" in r.stderr
+        else:
+            assert routes["models_rejected"] == 0, routes
     out = tmp_path / "farm.out"
     r = subprocess.run([unexe, str(tmp_path / "two.B.bwtc"), str(out)], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr

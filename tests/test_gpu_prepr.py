@@ -77,8 +77,14 @@ def test_compress_cli_with_prepr_gives_the_oracles_stream(tmp_path, oracle, code
     src.write_bytes(data.tobytes())
     # --mem 1: precompressor blocks of 740 000 bytes, BWT blocks of (1 000 000 - precompressed size) / 4.5
     r = subprocess.run([exe, "-m", "1", "-s", "8", "-e", coder, "--prepr", prep, str(src), str(dst)],
-                       capture_output=True, text=True, timeout=600)
+                       capture_output=True, text=True, timeout=600, env=dict(os.environ, BWTC_HIP_DEBUG="1"))
     assert r.returncode == 0, r.stderr
+    if coder == "B":
+        # the device route made the bytes: trees by the stream kernels, models by the device passes, none turned down
+        from test_gpu_host import _routes
+        routes = _routes(r.stderr)
+        assert routes["models_rejected"] == 0 and routes["lost_turn"] == 0, routes
+        assert routes["trees_device"] > 0 and routes["models_device"] == routes["trees_device"], routes
     stream = np.frombuffer(dst.read_bytes(), np.uint8)
     want = oracle.oracle_compress_prepr(coder, prep, data, 1_000_000)
     assert stream.size == want.size and (stream == want).all()
