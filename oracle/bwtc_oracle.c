@@ -611,7 +611,7 @@ static void bic_decode(bitr *r, uint32_t *list, size_t *n, size_t lo, size_t hi,
  * HuffmanDecoder::decodeBlock (HuffmanCoders.cpp:338-616, decoded here bit by bit from
  * the canonical code instead of through its lookup tables), deserializeShape (:88-117),
  * BWTBlock::readHeader (BWTBlock.cpp:88-102), then the inverse BWT. */
-size_t orc_decompress_H(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_cap)
+static size_t decompress_H(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_cap, int inverse)
 {
     bitr r; size_t opos = 0, dpos = 0, dcap = 0, gram_n = 0;
     const uint8_t *gram = NULL;
@@ -690,7 +690,7 @@ size_t orc_decompress_H(const uint8_t *in, size_t in_size, uint8_t *out, size_t 
                 free(runseq);
             }
             if (done != bsize || r.pos - start != clen48) return (size_t)-1;
-            if (orc_inverse_bwt_block(blk, (uint32_t)bsize, lf, n_lf) != 0) return (size_t)-1;
+            if (inverse && orc_inverse_bwt_block(blk, (uint32_t)bsize, lf, n_lf) != 0) return (size_t)-1;
             dpos += bsize;
         }
         if (aside) {
@@ -703,4 +703,17 @@ size_t orc_decompress_H(const uint8_t *in, size_t in_size, uint8_t *out, size_t 
         }
     }
     return opos;
+}
+
+size_t orc_decompress_H(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_cap)
+{
+    return decompress_H(in, in_size, out, out_cap, 1);
+}
+
+/* The same decoder stopped before the inverse transform: out receives the blocks' transformed
+ * bytes.  Serves byte strings that are no real transform (the coders' limit cases), on which the
+ * inverse would fail. */
+size_t orc_decode_H_transformed(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_cap)
+{
+    return decompress_H(in, in_size, out, out_cap, 0);
 }

@@ -57,6 +57,8 @@ size_t orc_compress_H(const uint8_t *in, size_t size, size_t block_size,
                       uint32_t starting_points, uint8_t *out, size_t out_cap);
 /* returns decoded size, or (size_t)-1 on malformed input */
 size_t orc_decompress_H(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_cap);
+/* the same stopped before the inverse transform: out receives the blocks' transformed bytes */
+size_t orc_decode_H_transformed(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_cap);
 size_t orc_compress_bound(size_t size);
 
 /* ---- 'B' wavelet coder (oracle/wavelet_oracle.c; WaveletCoders.cpp, WaveletTree.hpp) ---- */
@@ -80,6 +82,8 @@ size_t orc_compress_wavelet(char coder, const uint8_t *in, size_t size, size_t b
  * malformed input; bwt_out (may be NULL) receives the transformed bytes of the blocks. */
 size_t orc_decompress_wavelet(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_cap,
                               uint8_t *bwt_out);
+/* the same stopped before the inverse transform: out receives the blocks' transformed bytes */
+size_t orc_decode_wavelet_transformed(const uint8_t *in, size_t in_size, uint8_t *out, size_t out_cap);
 
 /* ---- pair-replacing pre-stage, `--prepr p...` (oracle/prepr_oracle.cpp; preprocessors/PairReplacer.cpp,
  * Grammar.cpp, FrequencyTable.cpp, Precompressor.cpp, Postprocessor.cpp) ---- */

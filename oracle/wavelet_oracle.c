@@ -1159,7 +1159,8 @@ static uint64_t read_packed_bytes(instream *in)
  * with an empty grammar, WaveletDecoder::decodeBlock per slice, inverse transform.  Returns the
  * decoded size, or (size_t)-1 on malformed input.  If bwt_out is not NULL the transformed bytes
  * of the blocks (before the inverse transform) are copied there as well. */
-size_t orc_decompress_wavelet(const uint8_t *in_bytes, size_t in_size, uint8_t *out, size_t out_cap, uint8_t *bwt_out)
+static size_t decompress_wavelet(const uint8_t *in_bytes, size_t in_size, uint8_t *out, size_t out_cap, uint8_t *bwt_out,
+                                 int inverse)
 {
     instream in;
     model pm, gm, gapm;
@@ -1225,7 +1226,7 @@ size_t orc_decompress_wavelet(const uint8_t *in_bytes, size_t in_size, uint8_t *
             }
             if (len != bsize || in.pos - start != clen48) return (size_t)-1;
             if (bwt_out) { memcpy(bwt_out + bpos, blk, bsize); bpos += bsize; }
-            if (orc_inverse_bwt_block(blk, (uint32_t)bsize, lf, n_lf) != 0) return (size_t)-1;
+            if (inverse && orc_inverse_bwt_block(blk, (uint32_t)bsize, lf, n_lf) != 0) return (size_t)-1;
             dpos += bsize;
         }
         if (aside) {
@@ -1238,6 +1239,18 @@ size_t orc_decompress_wavelet(const uint8_t *in_bytes, size_t in_size, uint8_t *
         }
     }
     return opos;
+}
+
+size_t orc_decompress_wavelet(const uint8_t *in_bytes, size_t in_size, uint8_t *out, size_t out_cap, uint8_t *bwt_out)
+{
+    return decompress_wavelet(in_bytes, in_size, out, out_cap, bwt_out, 1);
+}
+
+/* The same decoder stopped before the inverse transform: out receives the blocks' transformed bytes
+ * (for byte strings that are no real transform, on which the inverse would fail). */
+size_t orc_decode_wavelet_transformed(const uint8_t *in_bytes, size_t in_size, uint8_t *out, size_t out_cap)
+{
+    return decompress_wavelet(in_bytes, in_size, out, out_cap, NULL, 0);
 }
 
 /* ============================================================================================

@@ -79,6 +79,10 @@ def lib():
         L.orc_compress_bound.argtypes = [_sz]
         L.orc_decompress_wavelet.restype = _sz
         L.orc_decompress_wavelet.argtypes = [_vp, _sz, _vp, _sz, _vp]
+        L.orc_decode_H_transformed.restype = _sz
+        L.orc_decode_H_transformed.argtypes = [_vp, _sz, _vp, _sz]
+        L.orc_decode_wavelet_transformed.restype = _sz
+        L.orc_decode_wavelet_transformed.argtypes = [_vp, _sz, _vp, _sz]
         L.orc_min_heap_order.restype = None
         L.orc_min_heap_order.argtypes = [_vp, _vp, _sz, _vp]
         L.orc_create_huffman_shape.restype = _sz
@@ -281,6 +285,45 @@ def oracle_decompress_wavelet(stream, max_size, want_bwt=False):
     if n == ctypes.c_size_t(-1).value:
         return (None, None) if want_bwt else None
     return (out[:n].copy(), bwt[:n].copy()) if want_bwt else out[:n].copy()
+
+
+def oracle_decode_transformed(coder, stream, max_size):
+    """A whole stream ('H', or a wavelet letter) decoded by the oracle's decoder up to the inverse
+    transform: the blocks' transformed bytes, or None on malformed input.  For byte strings that are
+    no real transform (the inverse would refuse them)."""
+    stream = np.ascontiguousarray(stream, dtype=np.uint8)
+    out = np.zeros(max(max_size, 1), np.uint8)
+    fn = lib().orc_decode_H_transformed if coder == "H" else lib().orc_decode_wavelet_transformed
+    n = fn(_ptr(stream), stream.size, _ptr(out), out.size)
+    if n == ctypes.c_size_t(-1).value:
+        return None
+    return out[:n].copy()
+
+
+def oracle_huffman_lengths(run_freqs):
+    """utils::calculateHuffmanLengths as the 'H' coder uses it: code length per symbol."""
+    f = np.ascontiguousarray(run_freqs, dtype=np.uint64)
+    clen = np.zeros(256, np.uint32)
+    lib().orc_huffman_lengths(_ptr(f), _ptr(clen))
+    return clen
+
+
+def oracle_wavelet_codes(run_freqs):
+    """Each symbol's code in the 'B' coder's symbol tree, as a string of '0' / '1' ('' when absent)."""
+    f = np.ascontiguousarray(run_freqs, dtype=np.uint64)
+    bits = np.zeros(256 * 64, np.uint8)
+    clen = np.zeros(256, np.uint32)
+    lib().orc_wavelet_symbol_codes(_ptr(f), _ptr(bits), _ptr(clen))
+    return ["".join("01"[b] for b in bits[64 * c:64 * c + int(clen[c])]) for c in range(256)]
+
+
+def oracle_wavelet_code_lengths(run_freqs):
+    """Length of each symbol's code in the 'B' coder's symbol tree (WaveletTree constructor)."""
+    f = np.ascontiguousarray(run_freqs, dtype=np.uint64)
+    bits = np.zeros(256 * 64, np.uint8)
+    clen = np.zeros(256, np.uint32)
+    lib().orc_wavelet_symbol_codes(_ptr(f), _ptr(bits), _ptr(clen))
+    return clen
 
 
 # ---- pair-replacing pre-stage (`--prepr p...`; oracle/prepr_oracle.cpp) --------------------------------
