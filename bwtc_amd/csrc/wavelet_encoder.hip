@@ -510,7 +510,7 @@ void wavelet_pipeline_release(BwtEngine& e) {
                  (unsigned long long)e.pipeline->clock.blocks.load(), e.pipeline->clock.model_ns.load() * 1e-9,
                  e.pipeline->clock.coder_ns.load() * 1e-9);
   if (e.pipeline && std::getenv("BWTC_HIP_DEBUG") && e.pipeline->clock.scalar_ns.load())
-    std::fprintf(stderr, "wavelet pipeline: %.3f s of the range coders' time in the scalar tasks of the longest sections, the rest in the lane engines\n",
+    std::fprintf(stderr, "wavelet pipeline: %.3f s of the range coders' time in the scalar loops of the longest sections (lanes stepped inside them included), the rest in lanes alone\n",
                  e.pipeline->clock.scalar_ns.load() * 1e-9);
   delete e.pipeline;                              // joins the workers (engines retire when nothing is queued)
   e.pipeline = nullptr;

@@ -56,6 +56,7 @@ HostPipeline::HostPipeline(unsigned threads, uint64_t huge_group_elements, unsig
   long_chains_.on_block_coded = [this](WaveletJob& j) { finish(j); };
   w_chains_.on_block_coded = [this](WaveletJob& j) { finish(j); };
   w_long_chains_.on_block_coded = [this](WaveletJob& j) { finish(j); };
+  w_fused_.on_block_coded = [this](WaveletJob& j) { finish(j); };
   // Device-modelled blocks leave only the range coders to the host.  A lane of the 16-lane engine
   // advances ITS chain five times slower than the scalar loop (9 ns against 1.7 per element), so
   // the block's longest section(s) get a scalar task each (they set the block's latency; queue()
@@ -78,6 +79,17 @@ HostPipeline::HostPipeline(unsigned threads, uint64_t huge_group_elements, unsig
   w_lanes_ = envNumber("BWTC_HIP_W_LANES", 16);
   w_long_chain_ = static_cast<uint64_t>(envNumber("BWTC_HIP_W_LONG_MI", 8)) << 20;
   if (std::getenv("BWTC_HIP_LONG_CHAIN_ELEMENTS")) w_long_chain_ = std::strtoull(std::getenv("BWTC_HIP_LONG_CHAIN_ELEMENTS"), nullptr, 10);   // tests
+  // The lanes stepped inside the long chains (runChainsWithLanes, BWTC_HIP_FUSED_LANES=1, the default with
+  // AVX-512): the scalar loop of a long section leaves most issue slots of its core idle, and a vector step
+  // of the lanes per six of its elements fills some of them -- so the lanes cost little beyond the long
+  // chains, where the lane engines above cost a whole thread each however full their lanes were.  Every
+  // thread but one may run such an engine (an engine without a long chain steps its lanes alone until one
+  // comes, so engines hold their threads while blocks keep coming: the one left over runs the pool's other
+  // tasks, such as freeing collected blocks).
+  const char* flanes = std::getenv("BWTC_HIP_FUSED_LANES");
+  max_w_fused_engines_ = max_w_engines_ && !(flanes && flanes[0] == '0') && !max_w_pair_engines_
+                             ? envNumber("BWTC_HIP_FUSED_LANES_ENGINES", std::max(1u, P - 1)) : 0u;
+  w_fused_k_ = static_cast<int>(envNumber("BWTC_HIP_FUSED_LANES_K", bwtc::wavelet::kChainLanesK));
 }
 
 HostPipeline::~HostPipeline() {}
@@ -170,7 +182,11 @@ uint32_t HostPipeline::queue(const std::shared_ptr<WaveletJob>& jobp, uint32_t f
     if (std::getenv("BWTC_HIP_DEBUG")) {
       std::fprintf(stderr, "w-route: %zu sections, elements (Mi):", job.coder->sectionTasks());
       for (size_t k = 0; k < job.coder->sectionTasks() && k < 12; ++k) std::fprintf(stderr, " %.1f", job.coder->sectionElements(k) / 1048576.0);
-      std::fprintf(stderr, " ...; %u lane engines at most, scalar from %.0f Mi\n", max_w_engines_, w_long_chain_ / 1048576.0);
+      if (max_w_fused_engines_)
+        std::fprintf(stderr, " ...; long chains from %.0f Mi with the lanes inside them (a vector step per %d elements), %u engines at most\n",
+                     std::max<uint64_t>(w_long_chain_, job.coder->largestSectionElements() / 5) / 1048576.0, w_fused_k_, max_w_fused_engines_);
+      else
+        std::fprintf(stderr, " ...; %u lane engines at most, scalar from %.0f Mi\n", max_w_engines_, w_long_chain_ / 1048576.0);
     }
     if (max_w_engines_) {
       // scalar tasks: sections that a lane (five times slower per chain) would hold for longer than
@@ -179,6 +195,16 @@ uint32_t HostPipeline::queue(const std::shared_ptr<WaveletJob>& jobp, uint32_t f
       const uint64_t cut = std::max<uint64_t>(w_long_chain_, job.coder->largestSectionElements() / 5);
       size_t n_long = 0;
       while (n_long < job.coder->sectionTasks() && job.coder->sectionElements(n_long) >= cut) ++n_long;
+      if (max_w_fused_engines_) {
+        // the long sections and the others on one source; an engine per long section, up to the limit,
+        // and no more than the lane route's engines for blocks without one
+        const unsigned start = w_fused_.add(jobp, n_long, job.coder->sectionTasks(), max_w_fused_engines_, max_w_engines_);
+        for (unsigned q = 0; q < start; ++q)
+          pool_.submit(0, [this] {
+            bwtc::wavelet::runChainsWithLanes(w_fused_.longs, w_fused_.shorts, w_fused_k_, &clock.coder_ns, &clock.scalar_ns);
+          });
+        return job.w_end_state;
+      }
       std::vector<std::function<void()> > own;
       if (max_w_pair_engines_ && n_long) {
         if (w_long_chains_.add(jobp, 0, n_long, max_w_pair_engines_))

@@ -8,6 +8,7 @@
 // encoder.
 #pragma once
 #include <malloc.h>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -35,6 +36,7 @@ namespace bwtc_hip {
 struct StageClock {
   std::atomic<uint64_t> model_ns{0}, coder_ns{0}, blocks{0}, finished{0};
   std::atomic<uint64_t> scalar_ns{0};               // the part of coder_ns spent in the scalar tasks of device-modelled blocks
+                                                    //   (with the lanes stepped inside the long chains: the time an engine held one)
   std::atomic<uint64_t> latency_ns{0};             // begun -> record finished, summed over the finished blocks
   std::atomic<int> unfinished{0};      // blocks begun and not yet finished by the workers
 };
@@ -191,6 +193,43 @@ class BlockChainSource : public bwtc::wavelet::ChainSource {
   struct Entry { std::shared_ptr<WaveletJob> job; size_t at, end; };
   std::mutex mu_;
   std::deque<Entry> queue_;
+  unsigned engines_;
+};
+
+// Device-modelled blocks for the engines that step sixteen lanes inside a long chain
+// (runChainsWithLanes): every block's longest sections on one queue, its other sections on the
+// other, oldest block first and largest first within a block.  One lock and one engine count for
+// both: an engine retires only when neither queue holds anything, so no section is stranded.
+class BlockLongShortSource {
+ public:
+  BlockLongShortSource() : longs(this, 0), shorts(this, 1), engines_(0) {}
+  // queues the section tasks [0, n_long) as long chains and [n_long, n) as lane chains; returns how
+  // many engines the caller should start: one per long chain up to max_engines running, and for a
+  // block without a long chain one only while fewer than max_lane_engines run (an engine without a
+  // long chain is a plain lane engine and costs a whole thread, as the lane route's engines did)
+  unsigned add(const std::shared_ptr<WaveletJob>& job, size_t n_long, size_t n, unsigned max_engines, unsigned max_lane_engines);
+  struct Side : bwtc::wavelet::ChainSource {
+    Side(BlockLongShortSource* s, int k) : src(s), kind(k) {}
+    bool next(bwtc::wavelet::ChainDesc* d) { return src->next(kind, d); }
+    void done(void* cookie) { src->done(cookie); }
+    bool retire() { return src->retire(); }
+    BlockLongShortSource* src;
+    int kind;
+  };
+  Side longs, shorts;
+  std::function<void(WaveletJob&)> on_block_coded;     // set once: the block's last section is flushed
+ private:
+  struct Entry { std::shared_ptr<WaveletJob> job; size_t at, end; };
+  bool next(int kind, bwtc::wavelet::ChainDesc* d);
+  void done(void* cookie);
+  bool retire() {
+    std::lock_guard<std::mutex> g(mu_);
+    if (!queue_[0].empty() || !queue_[1].empty()) return false;
+    --engines_;
+    return true;
+  }
+  std::mutex mu_;
+  std::deque<Entry> queue_[2];
   unsigned engines_;
 };
 
@@ -376,6 +415,9 @@ class HostPipeline {
   unsigned w_lanes_;                                 //   chains an engine holds (16: one vector, 32: two stepped alternately)
   unsigned max_w_engines_;                           //   at most this many of them (0: no lanes, every chain scalar)
   uint64_t w_long_chain_;                            //   sections this long keep a scalar task of their own
+  BlockLongShortSource w_fused_;                     //   both, for the engines that step the lanes inside the long chains
+  unsigned max_w_fused_engines_;                     //   at most this many of those (0: the scalar tasks and lane engines above)
+  int w_fused_k_;                                    //   long-chain elements per vector step of the lanes
   BlockSectionSource fused_sections_;                // fused model + coder engines
   WorkerPool pool_;
   uint64_t huge_;
@@ -462,6 +504,42 @@ inline bool BlockChainSource::next(bwtc::wavelet::ChainDesc* d) {
 inline void BlockChainSource::done(void* cookie) {
   WaveletJob* job = static_cast<WaveletJob*>(cookie);
   const std::shared_ptr<WaveletJob> keep = job->shared_from_this();   // whoever waits for the block may drop it the moment it is done
+  bool last;
+  { std::lock_guard<std::mutex> g(job->mu); last = --job->sections_left == 0; }
+  if (last) on_block_coded(*job);
+}
+
+inline unsigned BlockLongShortSource::add(const std::shared_ptr<WaveletJob>& job, size_t n_long, size_t n, unsigned max_engines,
+                                          unsigned max_lane_engines) {
+  std::lock_guard<std::mutex> g(mu_);
+  if (n_long > 0) { Entry e; e.job = job; e.at = 0; e.end = n_long; queue_[0].push_back(std::move(e)); }
+  if (n > n_long) { Entry e; e.job = job; e.at = n_long; e.end = n; queue_[1].push_back(std::move(e)); }
+  const unsigned limit = std::max(1u, n_long > 0 ? max_engines : std::min(max_engines, max_lane_engines));
+  const unsigned want = static_cast<unsigned>(std::max<size_t>(1, n_long));
+  const unsigned start = engines_ >= limit ? 0u : std::min(want, limit - engines_);
+  engines_ += start;
+  return start;
+}
+
+inline bool BlockLongShortSource::next(int kind, bwtc::wavelet::ChainDesc* d) {
+  std::shared_ptr<WaveletJob> job;
+  size_t k = 0;
+  {
+    std::lock_guard<std::mutex> g(mu_);
+    std::deque<Entry>& q = queue_[kind];
+    while (!q.empty() && q.front().at >= q.front().end) q.pop_front();
+    if (q.empty()) return false;
+    job = q.front().job;
+    k = q.front().at++;
+  }
+  job->coder->describeChainW(k, job->w, &job->outs, d);
+  d->cookie = job.get();
+  return true;
+}
+
+inline void BlockLongShortSource::done(void* cookie) {
+  WaveletJob* job = static_cast<WaveletJob*>(cookie);
+  const std::shared_ptr<WaveletJob> keep = job->shared_from_this();
   bool last;
   { std::lock_guard<std::mutex> g(job->mu); last = --job->sections_left == 0; }
   if (last) on_block_coded(*job);

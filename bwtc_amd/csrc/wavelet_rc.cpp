@@ -14,6 +14,15 @@ namespace {
 
 inline uint32_t codeAt(const uint8_t* codes, uint64_t i) { return (codes[i >> 2] >> ((i & 3) * 2)) & 3u; }
 
+// runChainW's step on one w-word x: the next size and low end, and the bytes that leave the coder
+__attribute__((always_inline)) inline void stepW(uint32_t& lo, uint32_t& size, uint8_t*& o, uint32_t x) {
+  const uint32_t bit = x >> 15, m = x & 0x7FFFu;
+  const uint32_t ns = static_cast<uint32_t>((static_cast<int64_t>(static_cast<uint64_t>(size) * m) + (static_cast<int64_t>(bit) - 2049)) >> 12);
+  lo += (bit - 1u) & (size - ns);                                       // a zero moves the low end up by t + 1 = size - ns
+  size = ns;
+  while (((lo ^ (lo + size + 1)) & 0xFF000000u) == 0) { *o++ = static_cast<uint8_t>(lo >> 24); lo <<= 8; size = (size << 8) + 510u; }
+}
+
 }  // namespace
 
 // one chain on its own: the byte output is a (badly predictable) branch, but nothing is added
@@ -56,14 +65,7 @@ void runChainW(CoderChain& c, const uint16_t* w, uint64_t until) {
   for (; b < until; b += kChunk) {
     const uint64_t ce = std::min(until, b + kChunk);
     uint8_t* o = c.room(kChunk);
-    for (uint64_t i = b; i < ce; ++i) {
-      const uint32_t x = w[i];
-      const uint32_t bit = x >> 15, m = x & 0x7FFFu;
-      const uint32_t ns = static_cast<uint32_t>((static_cast<int64_t>(static_cast<uint64_t>(size) * m) + (static_cast<int64_t>(bit) - 2049)) >> 12);
-      lo += (bit - 1u) & (size - ns);                                     // a zero moves the low end up by t + 1 = size - ns
-      size = ns;
-      while (((lo ^ (lo + size + 1)) & 0xFF000000u) == 0) { *o++ = static_cast<uint8_t>(lo >> 24); lo <<= 8; size = (size << 8) + 510u; }
-    }
+    for (uint64_t i = b; i < ce; ++i) stepW(lo, size, o, w[i]);
     c.used = static_cast<size_t>(o - c.out->data());
   }
   c.lo = lo; c.size = size; c.i = std::max(c.i, until);
@@ -118,21 +120,10 @@ void runChainPairW(CoderChain& a, const uint16_t* wa, CoderChain& b, const uint1
     uint8_t* ob = b.room(kChunk);
     uint32_t loa = a.lo, sa = a.size, lob = b.lo, sb = b.size;
     uint64_t ia = a.i, ib = b.i;
-#define BWTC_RC_W(lo, size, o, i, w)                                                                      \
-    {                                                                                                      \
-      const uint32_t x = w[i];                                                                             \
-      const uint32_t bit = x >> 15, m = x & 0x7FFFu;                                                       \
-      const uint32_t ns = static_cast<uint32_t>((static_cast<int64_t>(static_cast<uint64_t>(size) * m) + (static_cast<int64_t>(bit) - 2049)) >> 12); \
-      lo += (bit - 1u) & (size - ns);                                                                      \
-      size = ns;                                                                                           \
-      while (((lo ^ (lo + size + 1)) & 0xFF000000u) == 0) { *o++ = static_cast<uint8_t>(lo >> 24); lo <<= 8; size = (size << 8) + 510u; } \
-      ++i;                                                                                                 \
-    }
     for (uint64_t k = 0; k < n; ++k) {
-      BWTC_RC_W(loa, sa, oa, ia, wa)
-      BWTC_RC_W(lob, sb, ob, ib, wb)
+      stepW(loa, sa, oa, wa[ia++]);
+      stepW(lob, sb, ob, wb[ib++]);
     }
-#undef BWTC_RC_W
     a.lo = loa; a.size = sa; a.i = ia; a.used = static_cast<size_t>(oa - a.out->data());
     b.lo = lob; b.size = sb; b.i = ib; b.used = static_cast<size_t>(ob - b.out->data());
     left -= n;
@@ -201,8 +192,17 @@ BWTC_AVX512 inline void transpose16(__m512i r[16]) {
 // instructions from the interval to the interval (two multiplies, the byte test, the masked shift),
 // some 45 cycles of which a single vector keeps the core's pipes busy for a third; the second
 // vector's steps fill them.
-template <bool WMODE, int G>
-BWTC_AVX512 void runWords(Lanes& L, uint64_t words, uint32_t busy_mask) {
+// K > 0: a scalar w-chain rides along (runChainsWithLanes) -- after every vector step, K of its
+// elements in runChainW's step; the two have no data in common, so the core overlaps them.  The
+// rider's 16 K `words` elements from rider->x on are coded and its state is handed back.
+struct Rider {
+  uint32_t lo, size;
+  const uint16_t* x;
+  uint8_t* o;
+};
+
+template <bool WMODE, int G, int K = 0>
+BWTC_AVX512 void runWords(Lanes& L, uint64_t words, uint32_t busy_mask, Rider* rider = nullptr) {
   __m512i lo[G], size[G];
   __mmask16 kBusy[G];
   for (int g = 0; g < G; ++g) {
@@ -217,6 +217,10 @@ BWTC_AVX512 void runWords(Lanes& L, uint64_t words, uint32_t busy_mask) {
   alignas(64) uint32_t cw[kAll] = {0};
   alignas(64) uint32_t ev[G][16 * kLanes * 4 + 64];    // at most four bytes per lane and step
   alignas(64) __m512i P[G][16];
+  uint32_t rlo = 0, rsize = 0;
+  const uint16_t* rx = nullptr;
+  uint8_t* ro = nullptr;
+  if (K > 0) { rlo = rider->lo; rsize = rider->size; rx = rider->x; ro = rider->o; }
   for (uint64_t w = 0; w < words; ++w) {
     for (int g = 0; g < G; ++g) {
       for (int l = 0; l < kLanes; ++l) {
@@ -269,6 +273,10 @@ BWTC_AVX512 void runWords(Lanes& L, uint64_t words, uint32_t busy_mask) {
           if (__builtin_expect(m == 0, 1)) break;
         }
       }
+      if (K > 0) {
+        for (int k = 0; k < K; ++k) stepW(rlo, rsize, ro, rx[k]);
+        rx += K;
+      }
     }
     for (int g = 0; g < G; ++g)
       for (uint32_t k = 0; k < n[g]; ++k) { const uint32_t e = ev[g][k]; *L.out[g * kLanes + (e >> 8)]++ = static_cast<uint8_t>(e); }
@@ -277,7 +285,98 @@ BWTC_AVX512 void runWords(Lanes& L, uint64_t words, uint32_t busy_mask) {
     _mm512_store_si512(L.lo + g * kLanes, lo[g]);
     _mm512_store_si512(L.size + g * kLanes, size[g]);
   }
+  if (K > 0) { rider->lo = rlo; rider->size = rsize; rider->x = rx; rider->o = ro; }
 }
+
+// The chains an engine holds in its lanes, and the rules both lane engines (runCoderLanes,
+// runChainsWithLanes) follow for them: how a lane is refilled, how its words are handed to
+// runWords and taken back, and how the last few chains end without vectors.
+struct LaneSet {
+  CoderChain chain[kAll];
+  ChainDesc desc[kAll];
+  bool busy[kAll];
+  bool wmode = false;                  // the chains come as w-words (a source hands out one kind)
+  ChainSource& src;
+  explicit LaneSet(ChainSource& s) : src(s) { for (int l = 0; l < kAll; ++l) busy[l] = false; }
+
+  void scalar(int l, uint64_t until) {
+    if (desc[l].w) runChainW(chain[l], desc[l].w, until); else runChain(chain[l], desc[l].codes, desc[l].prob, until);
+  }
+  void finishLane(int l) {             // the rest of the lane's chain, scalar, and its flush
+    CoderChain& c = chain[l];
+    scalar(l, c.e);
+    c.finish();
+    src.done(desc[l].cookie);
+    busy[l] = false;
+  }
+  // a new chain runs scalar up to the next word boundary (all of it when it is short); sets *dry when
+  // the source had nothing; returns the busy lanes among the first `lanes`, their bits in *mask
+  int refill(int lanes, bool* dry, uint32_t* mask) {
+    int nbusy = 0;
+    *mask = 0;
+    for (int l = 0; l < lanes; ++l) {
+      while (!busy[l] && !*dry) {
+        if (!src.next(&desc[l])) { *dry = true; break; }
+        CoderChain& c = chain[l];
+        c.start(desc[l].begin, desc[l].end, desc[l].out);
+        wmode = desc[l].w != nullptr;
+        const uint64_t aligned = (c.i + 15) & ~static_cast<uint64_t>(15);
+        busy[l] = true;
+        if (c.e - c.i < kScalarOnly || aligned + 16 > c.e) { finishLane(l); continue; }
+        scalar(l, aligned);
+      }
+      if (busy[l]) { ++nbusy; *mask |= 1u << l; }
+    }
+    return nbusy;
+  }
+  // the words every busy lane has left, at most `limit`
+  uint64_t words(uint64_t limit) const {
+    for (int l = 0; l < kAll; ++l) if (busy[l]) limit = std::min(limit, (chain[l].e - chain[l].i) >> 4);
+    return limit;
+  }
+  void toVectors(Lanes& L, uint64_t words) {
+    for (int l = 0; l < kAll; ++l) {
+      if (busy[l]) {
+        CoderChain& c = chain[l];
+        L.lo[l] = c.lo; L.size[l] = c.size; L.codes[l] = desc[l].codes; L.prob[l] = wmode ? desc[l].w : desc[l].prob; L.i[l] = c.i;
+        L.out[l] = c.room(words * 16); L.advance[l] = 16;
+      } else {
+        L.lo[l] = 0; L.size[l] = 0xFFFFFFFEu; L.codes[l] = kZeroCodes; L.prob[l] = kZeroProb; L.i[l] = 0;
+        L.out[l] = nullptr; L.advance[l] = 0;
+      }
+    }
+  }
+  void fromVectors(const Lanes& L) {
+    for (int l = 0; l < kAll; ++l) {
+      if (!busy[l]) continue;
+      CoderChain& c = chain[l];
+      c.lo = L.lo[l]; c.size = L.size[l]; c.i = L.i[l];
+      c.used = static_cast<size_t>(L.out[l] - c.out->data());
+    }
+  }
+  void finishTails() {                 // lanes with less than a word left: scalar tail
+    for (int l = 0; l < kAll; ++l)
+      if (busy[l] && chain[l].e - chain[l].i < 16) finishLane(l);
+  }
+  // not worth a vector: two chains stepped alternately (or the last one alone), `slice` elements
+  // of each, so that new work -- another block's chains -- is picked up soon
+  void scalarSlice(uint64_t slice) {
+    int ids[kAll], n = 0;
+    for (int l = 0; l < kAll; ++l) if (busy[l]) ids[n++] = l;
+    if (n >= 2) {
+      const int a = ids[0], b = ids[1];
+      if (desc[a].w && desc[b].w) runChainPairW(chain[a], desc[a].w, chain[b], desc[b].w, slice);
+      else if (desc[a].w || desc[b].w) { scalar(a, std::min(chain[a].e, chain[a].i + slice)); scalar(b, std::min(chain[b].e, chain[b].i + slice)); }
+      else runChainPair(chain[a], desc[a].codes, desc[a].prob, chain[b], desc[b].codes, desc[b].prob, slice);
+      if (chain[a].i >= chain[a].e) finishLane(a);
+      if (chain[b].i >= chain[b].e) finishLane(b);
+    } else {
+      CoderChain& c = chain[ids[0]];
+      scalar(ids[0], std::min(c.e, c.i + slice));
+      if (c.i >= c.e) finishLane(ids[0]);
+    }
+  }
+};
 
 }  // namespace
 
@@ -306,38 +405,11 @@ void runCoderLanes(ChainSource& src, int max_lanes, std::atomic<uint64_t>* busy_
   const int lanes = std::max(1, std::min(max_lanes, kAll));
   const bool two = lanes > kLanes;                     // more than a vector's worth: two vectors stepped alternately
   Lanes L;
-  CoderChain chain[kAll];
-  ChainDesc desc[kAll];
-  bool busy[kAll];
-  for (int l = 0; l < kAll; ++l) busy[l] = false;
+  LaneSet S(src);
   bool sourceDry = false;
-  bool wmode = false;                                  // this engine's chains come as w-words (a source hands out one kind)
-  auto scalar = [&](int l, uint64_t until) {
-    if (desc[l].w) runChainW(chain[l], desc[l].w, until); else runChain(chain[l], desc[l].codes, desc[l].prob, until);
-  };
-  auto finishLane = [&](int l) {                       // the rest of the lane's chain, scalar, and its flush
-    CoderChain& c = chain[l];
-    scalar(l, c.e);
-    c.finish();
-    src.done(desc[l].cookie);
-    busy[l] = false;
-  };
   for (;;) {
-    // refill: a new chain runs scalar up to the next word boundary (all of it when it is short)
-    int nbusy = 0;
-    for (int l = 0; l < lanes; ++l) {
-      while (!busy[l] && !sourceDry) {
-        if (!src.next(&desc[l])) { sourceDry = true; break; }
-        CoderChain& c = chain[l];
-        c.start(desc[l].begin, desc[l].end, desc[l].out);
-        wmode = desc[l].w != nullptr;
-        const uint64_t aligned = (c.i + 15) & ~static_cast<uint64_t>(15);
-        busy[l] = true;
-        if (c.e - c.i < kScalarOnly || aligned + 16 > c.e) { finishLane(l); continue; }
-        scalar(l, aligned);
-      }
-      nbusy += busy[l];
-    }
+    uint32_t mask = 0;
+    const int nbusy = S.refill(lanes, &sourceDry, &mask);
     account();
     if (nbusy == 0) {
       if (sourceDry && src.retire()) return;
@@ -345,51 +417,92 @@ void runCoderLanes(ChainSource& src, int max_lanes, std::atomic<uint64_t>* busy_
       continue;
     }
     if (lanes < kMinLanes || (nbusy < kMinLanes && sourceDry)) {
-      // not worth a vector: two chains stepped alternately (or the last one alone), in slices so
-      // that new work -- another block's chains -- is picked up soon
-      const uint64_t kSlice = static_cast<uint64_t>(1) << 22;
-      int ids[kAll], n = 0;
-      for (int l = 0; l < kAll; ++l) if (busy[l]) ids[n++] = l;
-      if (n >= 2) {
-        const int a = ids[0], b = ids[1];
-        if (desc[a].w && desc[b].w) runChainPairW(chain[a], desc[a].w, chain[b], desc[b].w, kSlice);
-        else if (desc[a].w || desc[b].w) { scalar(a, std::min(chain[a].e, chain[a].i + kSlice)); scalar(b, std::min(chain[b].e, chain[b].i + kSlice)); }
-        else runChainPair(chain[a], desc[a].codes, desc[a].prob, chain[b], desc[b].codes, desc[b].prob, kSlice);
-        if (chain[a].i >= chain[a].e) finishLane(a);
-        if (chain[b].i >= chain[b].e) finishLane(b);
-      } else {
-        CoderChain& c = chain[ids[0]];
-        scalar(ids[0], std::min(c.e, c.i + kSlice));
-        if (c.i >= c.e) finishLane(ids[0]);
-      }
+      S.scalarSlice(static_cast<uint64_t>(1) << 22);
       sourceDry = false;                                 // ask again: other blocks may have arrived
       continue;
     }
-    uint64_t words = kMaxWords;
-    uint32_t mask = 0;
-    for (int l = 0; l < kAll; ++l) if (busy[l]) { words = std::min(words, (chain[l].e - chain[l].i) >> 4); mask |= 1u << l; }
+    const uint64_t words = S.words(kMaxWords);
     if (words > 0) {
-      for (int l = 0; l < kAll; ++l) {
-        if (busy[l]) {
-          CoderChain& c = chain[l];
-          L.lo[l] = c.lo; L.size[l] = c.size; L.codes[l] = desc[l].codes; L.prob[l] = wmode ? desc[l].w : desc[l].prob; L.i[l] = c.i;
-          L.out[l] = c.room(words * 16); L.advance[l] = 16;
-        } else {
-          L.lo[l] = 0; L.size[l] = 0xFFFFFFFEu; L.codes[l] = kZeroCodes; L.prob[l] = kZeroProb; L.i[l] = 0;
-          L.out[l] = nullptr; L.advance[l] = 0;
-        }
-      }
-      if (two && (mask >> kLanes)) { if (wmode) runWords<true, 2>(L, words, mask); else runWords<false, 2>(L, words, mask); }
-      else { if (wmode) runWords<true, 1>(L, words, mask); else runWords<false, 1>(L, words, mask); }
-      for (int l = 0; l < kAll; ++l) {
-        if (!busy[l]) continue;
-        CoderChain& c = chain[l];
-        c.lo = L.lo[l]; c.size = L.size[l]; c.i = L.i[l];
-        c.used = static_cast<size_t>(L.out[l] - c.out->data());
-      }
+      S.toVectors(L, words);
+      if (two && (mask >> kLanes)) { if (S.wmode) runWords<true, 2>(L, words, mask); else runWords<false, 2>(L, words, mask); }
+      else { if (S.wmode) runWords<true, 1>(L, words, mask); else runWords<false, 1>(L, words, mask); }
+      S.fromVectors(L);
     }
-    for (int l = 0; l < kAll; ++l)                       // lanes with less than a word left: scalar tail
-      if (busy[l] && chain[l].e - chain[l].i < 16) finishLane(l);
+    S.finishTails();
+    sourceDry = false;
+  }
+}
+
+void runChainsWithLanes(ChainSource& longs, ChainSource& lanes, int k, std::atomic<uint64_t>* busy_ns, std::atomic<uint64_t>* long_ns) {
+  auto tick = std::chrono::steady_clock::now();
+  auto account = [&](bool holding) {
+    if (!busy_ns && !long_ns) return;
+    const auto now = std::chrono::steady_clock::now();
+    const uint64_t dt = static_cast<uint64_t>(std::chrono::duration_cast<std::chrono::nanoseconds>(now - tick).count());
+    if (busy_ns) *busy_ns += dt;
+    if (holding && long_ns) *long_ns += dt;
+    tick = now;
+  };
+  const int K = k <= 4 ? 4 : k == 5 ? 5 : k <= 6 ? 6 : 8;
+  const uint64_t perWord = 16u * static_cast<uint64_t>(K);          // long-chain elements per word of the lanes
+  const uint64_t kSlice = static_cast<uint64_t>(1) << 20;           // scalar stretches between two looks at the sources
+  Lanes L;
+  LaneSet S(lanes);                                                  // sixteen lanes (one vector)
+  CoderChain lc;                                                     // the long chain held, if any
+  ChainDesc ld;
+  bool holding = false, sourceDry = false;
+  for (;;) {
+    if (!holding && longs.next(&ld)) {
+      account(false);
+      lc.start(ld.begin, ld.end, ld.out);
+      holding = true;
+    }
+    uint32_t mask = 0;
+    const int nbusy = S.refill(kLanes, &sourceDry, &mask);
+    if (holding) {
+      const uint64_t left = lc.e - lc.i;
+      if (nbusy == 0 || left < perWord) {
+        // nothing to carry, or less than a word's worth of the long chain left: the plain scalar loop
+        runChainW(lc, ld.w, nbusy ? lc.e : std::min(lc.e, lc.i + kSlice));
+      } else {
+        const uint64_t words = S.words(std::min(kMaxWords, left / perWord));
+        S.toVectors(L, words);
+        Rider r;
+        r.lo = lc.lo; r.size = lc.size; r.x = ld.w + lc.i; r.o = lc.room(words * perWord);
+        switch (K) {
+          case 4: runWords<true, 1, 4>(L, words, mask, &r); break;
+          case 5: runWords<true, 1, 5>(L, words, mask, &r); break;
+          case 6: runWords<true, 1, 6>(L, words, mask, &r); break;
+          default: runWords<true, 1, 8>(L, words, mask, &r); break;
+        }
+        lc.lo = r.lo; lc.size = r.size; lc.i += words * perWord;
+        lc.used = static_cast<size_t>(r.o - lc.out->data());
+        S.fromVectors(L);
+      }
+      if (lc.i >= lc.e) {
+        lc.finish();
+        account(true);
+        holding = false;
+        longs.done(ld.cookie);
+      }
+    } else if (nbusy == 0) {
+      account(false);
+      if (sourceDry && longs.retire()) return;
+      sourceDry = false;
+      continue;
+    } else if (nbusy < kMinLanes && sourceDry) {
+      // no long chain and only a few lanes: runCoderLanes' scalar ending, in shorter slices so that a
+      // long chain that arrives meanwhile is taken up soon
+      S.scalarSlice(kSlice);
+    } else {
+      // no long chain: a plain lane engine
+      const uint64_t words = S.words(kMaxWords);
+      S.toVectors(L, words);
+      runWords<true, 1>(L, words, mask);
+      S.fromVectors(L);
+    }
+    S.finishTails();
+    account(holding);
     sourceDry = false;
   }
 }

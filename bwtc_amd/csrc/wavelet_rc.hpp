@@ -5,6 +5,7 @@
 //   runChainPair   two chains stepped alternately by one thread (they overlap in the core)
 //   runCoderLanes  sixteen chains at a time, one per AVX-512 lane, lanes refilled from a source
 //                  that spans the blocks under way (the counterpart of runModelLanes)
+//   runChainsWithLanes  a long chain in the scalar loop with sixteen lanes stepped inside it
 #pragma once
 #include <atomic>
 #include <cstddef>
@@ -84,6 +85,23 @@ bool simdCoderAvailable();
 // their block waiting for seconds.
 // busy_ns (optional): the engine's running time is added there as it goes.
 void runCoderLanes(ChainSource& src, int max_lanes = 16, std::atomic<uint64_t>* busy_ns = nullptr);
+
+// The long chains and the lanes in one loop (w-words only).  The scalar loop of a long chain
+// (runChainW) leaves most of the core's issue slots idle -- it waits on its multiply and on the
+// byte-output branch -- so one 16-lane vector step of runCoderLanes is interleaved with every
+// `k` of its elements (k = 4, 5, 6 or 8).  Long chains come from `longs`, one at a time, and are
+// flushed and handed back through longs.done(); the lanes are refilled from `lanes` between
+// words, as runCoderLanes does.  With no long chain the thread takes the next one from `longs`
+// first; with none waiting it steps its lanes as a plain lane engine.  It returns when both
+// sources are empty and every lane has drained, after longs.retire() agreed (so `longs` decides
+// for both).  A lane advances one element per k elements of the long chain: with k = 6 a chain
+// of 44.6 Mi elements (the text block's longest short section) takes as long as the 265.6 Mi of
+// its longest one, so the source must hand out the largest chains first (the pipeline's
+// BlockLongShortSource does).
+// busy_ns: the engine's running time; long_ns: the part of it spent while a long chain was held.
+const int kChainLanesK = 6;
+void runChainsWithLanes(ChainSource& longs, ChainSource& lanes, int k = kChainLanesK,
+                        std::atomic<uint64_t>* busy_ns = nullptr, std::atomic<uint64_t>* long_ns = nullptr);
 
 }  // namespace wavelet
 }  // namespace bwtc
