@@ -24,6 +24,10 @@ it: from the block resident in page-locked HOST memory to its compressed record 
     BASELINE config 5.
   * --dump-outputs DIR: after the clock stops, what the last timed step computed goes to
     DIR/<name>.npy (dump_outputs), so that two builds can be compared output for output.
+  * --full: also what the headline does not need, each a run of its own after the clock stops --
+    the one-thread CPU baseline (cpu_baseline; --cpu-c4 adds cpu_baseline_c4), the streaming copy
+    kernel that the roofline quotes as its denominator, and the BWTC_CORPUS stream.  A plain run
+    sets up, warms up, times the steps, dumps if asked and prints the line.
 Blocks are independent, so rank r works on its own blocks and no data-path collective exists;
 torch.distributed is used only for the barrier and the max-over-ranks of the elapsed time.
 Rank 0 prints ONE JSON line.
@@ -262,19 +266,26 @@ def main():
     ap.add_argument("--workload", default="c3",
                     help="extras only (the headline is c3): realtext, pycorpus, realtext_rep, dna, random, zeros, period9, reptext -- "
                          "the inputs of scripts/r5/workloads.py instead of the C3 generator's blocks")
-    ap.add_argument("--cpu-runs", type=int, default=3, help="runs of the one-thread CPU baseline (best and median reported)")
-    ap.add_argument("--cpu-size-mib", type=int, default=0, help="CPU baseline block (0 = same as --size-mib)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements the headline does not need: the CPU baseline, the device copy kernel "
+                         "beside the roofline (`device_copy_GBps`), the BWTC_CORPUS stream and, with --cpu-c4, "
+                         "cpu_baseline_c4")
+    ap.add_argument("--cpu-runs", type=int, default=3, help="--full: runs of the one-thread CPU baseline (best and median reported)")
+    ap.add_argument("--cpu-size-mib", type=int, default=0, help="--full: CPU baseline block (0 = same as --size-mib)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the one-thread CPU baseline")
     ap.add_argument("--cpu-c4", action="store_true",
-                    help="also time 8 pinned single-thread CPU runs at once (the CPU analogue of the 8-GPU row): cpu_baseline_c4")
+                    help="with --full: also time 8 pinned single-thread CPU runs at once (the CPU analogue of the 8-GPU "
+                         "row): cpu_baseline_c4")
     ap.add_argument("--corpus-blocks", type=int, default=16,
-                    help="BWTC_CORPUS=<file>: how many blocks of --size-mib of it are coded (reported as `corpus`)")
+                    help="--full with BWTC_CORPUS=<file>: how many blocks of --size-mib of it are coded (reported as `corpus`)")
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="after the timed steps, write what the last one computed -- the record ('B' / 'H'; the "
                          "transformed block with --bwt-only), the LF powers and the byte frequencies -- as DIR/<name>.npy "
                          "(rank 0; a seeded sample of a long output, see dump_outputs); the line's `dump_outputs` "
                          "describes them")
     args = ap.parse_args()
+    if args.cpu_c4 and not args.full:
+        ap.error("--cpu-c4 is a --full measurement")
     coder = None if args.bwt_only else args.coder
 
     import torch
@@ -513,7 +524,9 @@ def main():
     kt_main, st_main = ctx.kernel_timers(), ctx.stats()    # of the timed region's blocks, before another stream runs
     corpus = None
     cpath = os.environ.get("BWTC_CORPUS")
-    if cpath and rank == 0 and coder in ("B", "H"):
+    if cpath and not args.full and rank == 0:
+        print("BWTC_CORPUS is coded with --full only", file=sys.stderr)
+    if cpath and args.full and rank == 0 and coder in ("B", "H"):
         try:
             fsize = os.path.getsize(cpath)
             nb = max(1, min(args.corpus_blocks, (fsize + size - 1) // size))
@@ -560,9 +573,9 @@ def main():
     # the spec peak beside what a streaming copy reaches on this box -- the library's own
     # 16-byte-per-lane copy kernel through the C ABI (bwtc_hip_copy_probe), and the guide's figure for the same kind
     # of kernel (6.29 TB/s).  (Until round 4 this was torch.Tensor.copy_ on uint8, which reaches 4.7 TB/s and flattered
-    # every fraction taken of it.)
+    # every fraction taken of it.)  A run of its own, so --full only; a plain line's roofline has no copy figures.
     copy_gbs = None
-    if rank == 0:
+    if args.full and rank == 0:
         try:
             copy_gbs = ctx.copy_probe(1 << 30, 5)
         except Exception:                                                    # never a reason to lose the bench line
@@ -732,13 +745,14 @@ def main():
             out["warning"] = ("only %d host threads per rank: the 'B' coder's host half needs about 16 per GPU "
                               "to keep up with the device half" % threads)
         out["degraded"] = degraded
+        out["full"] = args.full
         if corpus is not None:
             out["corpus"] = corpus
         if dumped is not None:
             out["dump_outputs"] = dict(dumped, dir=args.dump_outputs)
         if args.cpu_c4 and world == 1:
             out["cpu_baseline_c4"] = cpu_baseline_c4(args.cpu_size_mib or args.size_mib, coder or "", my_cpus or sorted(os.sched_getaffinity(0)))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_size_mib or args.size_mib, seeds[0], coder or "", args.cpu_runs)
         print(json.dumps(out), flush=True)
     farm.close()

@@ -5,7 +5,7 @@ O=gpurun_out/r3_final
 mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -m gpu -x -q > $O/tests.log 2>&1 || { tail -30 $O/tests.log; exit 1; }
 tail -2 $O/tests.log
-timeout -k 10 500 python bench.py > $O/default.json 2> $O/default.err || { tail -5 $O/default.err; exit 1; }
+timeout -k 10 500 python bench.py --full > $O/default.json 2> $O/default.err || { tail -5 $O/default.err; exit 1; }
 timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/steps20_warmup5.json 2> $O/steps20.err || exit 1
 timeout -k 10 300 python bench.py --steps 400 --no-cpu-baseline > $O/steps400.json 2> $O/steps400.err || exit 1
 timeout -k 10 300 python bench.py --depth 32 --steps 100 --no-cpu-baseline > $O/depth32_steps100.json 2> $O/depth32.err || exit 1

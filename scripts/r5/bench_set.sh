@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$ROOT"
 O=gpurun_out/r05_bench
 mkdir -p $O
-timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/n1_driver_command.json 2> $O/n1_driver_command.err || exit 1
+timeout -k 10 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/n1_driver_command.json 2> $O/n1_driver_command.err || exit 1
 timeout -k 10 300 python bench.py --steps 100 --warmup 5 --no-cpu-baseline > $O/n1_steps100.json 2> $O/n1_steps100.err || exit 1
 timeout -k 10 300 python bench.py --steps 40 --warmup 5 --coder H --no-cpu-baseline > $O/n1_coderH.json 2> $O/n1_coderH.err || exit 1
 timeout -k 10 300 python bench.py --steps 20 --warmup 3 --bwt-only --no-cpu-baseline > $O/n1_bwt_only_256.json 2> $O/n1_bwt_only_256.err || exit 1
