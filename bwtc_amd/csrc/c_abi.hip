@@ -1,6 +1,7 @@
 // extern "C" surface of libbwtc_hip.so (include/bwtc_hip.h).
 #include "bwt_engine.hpp"
 #include "gpu_lanes.hpp"
+#include "huffman_decoder.hpp"
 #include "prepr_host.hpp"
 #include <new>
 #include "radix_sort.hpp"
@@ -21,6 +22,7 @@ using namespace bwtc_hip;
 
 struct bwtc_hip_ctx {
   BwtEngine eng;
+  bwtc_hip::HDecoder* hdec = nullptr;   // 'H' decoder, made by the first decode call
 };
 struct bwtc_hip_grammar {
   bwtc::prepr::Grammar g;
@@ -92,6 +94,7 @@ int bwtc_hip_create(int device, uint32_t max_block_size, bwtc_hip_ctx** ctx_out)
 
 void bwtc_hip_destroy(bwtc_hip_ctx* ctx) {
   if (!ctx) return;
+  bwtc_hip::hdecoder_destroy(ctx->hdec);
   ctx->eng.release();
   delete ctx;
 }
@@ -289,6 +292,61 @@ int bwtc_hip_inverse_bwt_block_device(bwtc_hip_ctx* ctx, const uint8_t* d_bwt, u
 }
 
 uint64_t bwtc_hip_compress_bound(uint32_t size) { return huffman_compress_bound(size); }
+
+// ---- 'H' decoding (HuffmanCoders.cpp:324-616, InverseBWT.cpp:47-51) ----
+static HDecoder* hdecoder(bwtc_hip_ctx* ctx) {
+  if (!ctx->hdec) ctx->hdec = hdecoder_create();
+  return ctx->hdec;
+}
+
+int bwtc_hip_huffman_decode(bwtc_hip_ctx* ctx, const uint8_t* rec, uint64_t rec_bytes, uint8_t* bwt_out,
+                            uint64_t cap, uint32_t* lf_out, uint32_t* n_lf, uint32_t* size, uint64_t* consumed) {
+  if (!ctx || !rec || (!bwt_out && cap) || !lf_out || !n_lf || !size || !consumed) return -1;
+  HDecoder* d = hdecoder(ctx);
+  if (!d) return -2;
+  BwtEngine& e = ctx->eng;
+  int rc = huffman_decode(e, *d, rec, nullptr, rec_bytes, nullptr, cap, lf_out, n_lf, size, consumed);
+  if (rc) return rc;
+  if (*size) {
+    BWTC_HIP_TRY(hipMemcpyAsync(bwt_out, hdecoder_bwt_buffer(d), *size, hipMemcpyDeviceToHost, e.stream));
+    BWTC_HIP_TRY(e.wait());
+  }
+  return 0;
+}
+
+int bwtc_hip_huffman_decode_device(bwtc_hip_ctx* ctx, const uint8_t* d_rec, uint64_t rec_bytes, uint8_t* d_bwt_out,
+                                   uint64_t cap, uint32_t* lf_out, uint32_t* n_lf, uint32_t* size, uint64_t* consumed) {
+  if (!ctx || !d_rec || (!d_bwt_out && cap) || !lf_out || !n_lf || !size || !consumed) return -1;
+  HDecoder* d = hdecoder(ctx);
+  if (!d) return -2;
+  BwtEngine& e = ctx->eng;
+  // header and code shapes are parsed on the host: bring the record down (the 48-bit length says
+  // how much of the buffer it is)
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  uint8_t head[6] = {0};
+  const uint64_t nh = rec_bytes < 6 ? rec_bytes : 6;
+  if (nh) BWTC_HIP_TRY(hipMemcpy(head, d_rec, nh, hipMemcpyDeviceToHost));
+  uint64_t len = 0;
+  for (int i = 0; i < 6; ++i) len = (len << 8) | head[i];
+  const uint64_t rec_end = nh < 6 ? nh : std::min<uint64_t>(rec_bytes, 6 + len);
+  std::vector<uint8_t> host(rec_end);
+  if (rec_end) BWTC_HIP_TRY(hipMemcpyAsync(host.data(), d_rec, rec_end, hipMemcpyDeviceToHost, e.stream));
+  BWTC_HIP_TRY(e.wait());
+  return huffman_decode(e, *d, host.data(), d_rec, rec_bytes, d_bwt_out, cap, lf_out, n_lf, size, consumed);
+}
+
+int bwtc_hip_decode_block_H(bwtc_hip_ctx* ctx, const uint8_t* rec, uint64_t rec_bytes, uint8_t* out, uint64_t cap,
+                            uint32_t* size, uint64_t* consumed) {
+  if (!ctx || !rec || (!out && cap) || !size || !consumed) return -1;
+  HDecoder* d = hdecoder(ctx);
+  if (!d) return -2;
+  return huffman_decode_block(ctx->eng, *d, rec, rec_bytes, out, cap, size, consumed);
+}
+
+int bwtc_hip_huffman_decode_stats_get(bwtc_hip_ctx* ctx, bwtc_hip_huffman_decode_stats* out) {
+  if (!ctx || !out) return -1;
+  return hdecoder_stats(ctx->hdec, out);
+}
 
 int bwtc_hip_huffman_encode_device(bwtc_hip_ctx* ctx, const uint8_t* d_bwt, uint32_t size,
                                    const uint32_t* lf, uint32_t n_lf, const uint32_t* freqs,

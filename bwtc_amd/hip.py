@@ -18,7 +18,20 @@ _u64 = ctypes.c_uint64
 
 
 class BwtcHipError(RuntimeError):
-    pass
+    def __init__(self, msg, code=None):
+        super().__init__(msg)
+        self.code = code
+
+
+# return codes of a corrupt 'H' record (bwtc_hip.h BWTC_HIP_E_*)
+E_NO_CODE, E_SHAPE, E_PAST_RECORD, E_RUNS, E_CAPACITY, E_LENGTH = -10, -11, -12, -13, -14, -15
+
+
+class HuffmanDecodeStats(ctypes.Structure):
+    _fields_ = [("route", _u32), ("sections", _u32), ("streams", _u32), ("host_syncs", _u32),
+                ("retries", _u32), ("max_code_len", _u32), ("runs", _u64), ("tiles", _u64), ("map_entries", _u64),
+                ("launches", _u64), ("workspace_bytes", _u64), ("ms_entropy", ctypes.c_float),
+                ("ms_entropy_wall", ctypes.c_float), ("ms_chain_host", ctypes.c_float), ("ms_inverse", ctypes.c_float)]
 
 
 class Stats(ctypes.Structure):
@@ -40,7 +53,9 @@ class KernelTimers(ctypes.Structure):
     _fields_ = [("scatter_launches", _u64), ("scatter_bytes", _u64), ("scatter_ms", ctypes.c_double)]
 
 
+# the C ABI's lowercase names (bwtc_hip_decode_block_H is exported too; tests/test_huffman_decode_abi.py checks it)
 EXPORTS = [
+    "bwtc_hip_huffman_decode", "bwtc_hip_huffman_decode_device", "bwtc_hip_huffman_decode_stats_get",
     "bwtc_hip_device_count", "bwtc_hip_version", "bwtc_hip_workspace_bytes", "bwtc_hip_create",
     "bwtc_hip_destroy", "bwtc_hip_stream", "bwtc_hip_get_stats", "bwtc_hip_set_profiling",
     "bwtc_hip_get_kernel_timers", "bwtc_hip_copy_probe", "bwtc_hip_test_gpu_lanes", "bwtc_hip_malloc", "bwtc_hip_free", "bwtc_hip_memcpy_to_device",
@@ -121,6 +136,11 @@ def load():
                                                  ctypes.POINTER(_u64)]
     L.bwtc_hip_huffman_encode.argtypes = [_vp, _vp, _u32, _vp, _u32, _vp, _vp, _u64,
                                           ctypes.POINTER(_u64)]
+    L.bwtc_hip_huffman_decode.argtypes = [_vp, _vp, _u64, _vp, _u64, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
+                                          ctypes.POINTER(_u64)]
+    L.bwtc_hip_huffman_decode_device.argtypes = L.bwtc_hip_huffman_decode.argtypes
+    L.bwtc_hip_decode_block_H.argtypes = [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u32), ctypes.POINTER(_u64)]
+    L.bwtc_hip_huffman_decode_stats_get.argtypes = [_vp, ctypes.POINTER(HuffmanDecodeStats)]
     L.bwtc_hip_transform_and_encode.argtypes = [_vp, _vp, _u32, _u32, _vp, _u64, ctypes.POINTER(_u64)]
     L.bwtc_hip_wavelet_section_stats.argtypes = [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32]
     L.bwtc_hip_transform_and_encode_wavelet.argtypes = [_vp, _vp, _u32, _u32, _u32, _vp, _u64, ctypes.POINTER(_u64)]
@@ -178,7 +198,7 @@ def load():
 
 def _check(rc, what):
     if rc != 0:
-        raise BwtcHipError("%s failed with code %d" % (what, rc))
+        raise BwtcHipError("%s failed with code %d" % (what, rc), rc)
 
 
 def _ptr(a):
@@ -605,6 +625,48 @@ class Context:
         if buf[data.size] != 0x5A:
             raise BwtcHipError("byte after the block was modified")
         return out[:n.value].copy(), buf[:data.size].copy()
+
+    def huffman_decode(self, record, cap=None):
+        """HuffmanDecoder::decodeBlock on the GPU: an 'H' BWT-block record (it may go on past the
+        record) -> (bwt bytes, LF powers, bytes of the record consumed)."""
+        record = np.ascontiguousarray(record, dtype=np.uint8)
+        cap = self.max_block_size if cap is None else cap
+        bwt = np.empty(max(cap, 1), np.uint8)
+        lf = np.zeros(256, np.uint32)
+        n_lf, size, used = _u32(0), _u32(0), _u64(0)
+        _check(self.lib.bwtc_hip_huffman_decode(self.handle, _ptr(record), record.size, _ptr(bwt), cap, _ptr(lf),
+                                                ctypes.byref(n_lf), ctypes.byref(size), ctypes.byref(used)),
+               "bwtc_hip_huffman_decode")
+        return bwt[:size.value].copy(), lf[:n_lf.value].copy(), int(used.value)
+
+    def huffman_decode_device(self, d_rec_ptr, rec_bytes, d_bwt_ptr, cap):
+        """Same with the record and the bwt bytes in device memory: returns (size, LF powers, consumed)."""
+        lf = np.zeros(256, np.uint32)
+        n_lf, size, used = _u32(0), _u32(0), _u64(0)
+        _check(self.lib.bwtc_hip_huffman_decode_device(self.handle, _vp(d_rec_ptr), rec_bytes, _vp(d_bwt_ptr), cap,
+                                                       _ptr(lf), ctypes.byref(n_lf), ctypes.byref(size),
+                                                       ctypes.byref(used)),
+               "bwtc_hip_huffman_decode_device")
+        return int(size.value), lf[:n_lf.value].copy(), int(used.value)
+
+    def decode_block_H(self, record, cap=None, with_consumed=False):
+        """Entropy decode + inverse BWT of one 'H' record on the GPU: returns the original block
+        (and the bytes consumed when with_consumed)."""
+        record = np.ascontiguousarray(record, dtype=np.uint8)
+        cap = self.max_block_size if cap is None else cap
+        out = np.empty(max(cap, 1), np.uint8)
+        size, used = _u32(0), _u64(0)
+        _check(self.lib.bwtc_hip_decode_block_H(self.handle, _ptr(record), record.size, _ptr(out), cap,
+                                                ctypes.byref(size), ctypes.byref(used)),
+               "bwtc_hip_decode_block_H")
+        data = out[:size.value].copy()
+        return (data, int(used.value)) if with_consumed else data
+
+    def huffman_decode_stats(self):
+        s = HuffmanDecodeStats()
+        _check(self.lib.bwtc_hip_huffman_decode_stats_get(self.handle, ctypes.byref(s)),
+               "bwtc_hip_huffman_decode_stats_get")
+        return {f: getattr(s, f) for f, _ in HuffmanDecodeStats._fields_}
 
     def suffix_array(self, T):
         T = np.ascontiguousarray(T, dtype=np.uint8)

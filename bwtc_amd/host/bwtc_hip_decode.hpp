@@ -2,7 +2,9 @@
 // BWTBlock::readHeader (BWTBlock.cpp:88-102), Decompressor (Decompressor.cpp:45-94).  The
 // entropy decoder is serial host code (a section's streams have no length fields, so
 // nothing in a block can be decoded ahead); the inverse transform runs on the GPU
-// (HipInverseBWTransform).  WaveletDecoder ('B'; WaveletCoders.cpp:232-291, WaveletTree.hpp
+// (HipInverseBWTransform).  Decompressor sends 'H' blocks to the GPU decoder instead
+// (bwtc_hip_decode_block_H: the run counts and code lengths bound every stream, so the streams are
+// decoded in parallel tiles); BWTC_HIP_DECODE=host keeps this serial HuffmanDecoder for them.  WaveletDecoder ('B'; WaveletCoders.cpp:232-291, WaveletTree.hpp
 // readShape :403-500, decodeTreeBF :857-1174, message :1277-1378, BitDecoder BitCoders.cpp:115-148)
 // is serial host code for the same reason plus the adaptive models.  Coders 'H', 'B', 'b', 'u'
 // and streams without precompression are accepted.
@@ -548,6 +550,25 @@ inline EntropyDecoder* giveEntropyDecoder(char decoder) {            // EntropyC
   std::exit(1);
 }
 
+// Block size an 'H' record announces (its sections' lengths, BWTBlock::readHeader + section
+// header); 0 when the header is cut short.  Sizes the decoding context by the block, as the host
+// route sizes its inverse transformer.
+inline uint64 hRecordBlockSize(const byte* p, size_t n) {
+  if (n < 7) return 0;
+  const size_t nLF = (size_t)p[6] + 1;
+  size_t pos = 6 + (8 + 31 * nLF + 7) / 8;                          // nLF byte + LF powers, byte padded
+  if (pos >= n) return 0;
+  size_t sections = p[pos++];
+  if (sections == 0) sections = 256;
+  uint64 total = 0;
+  for (size_t s = 0; s < sections; ++s) {
+    uint64 v = 0; unsigned shift = 0; byte b;
+    do { if (pos >= n || shift > 63) return 0; b = p[pos++]; v |= (uint64)(b & 0x7f) << shift; shift += 7; } while (b & 0x80);
+    total += v;
+  }
+  return total;
+}
+
 class Decompressor {
  public:
   Decompressor(InStream* in, OutStream* out, int device = 0)
@@ -562,9 +583,16 @@ class Decompressor {
       while ((got = m_in->readBlock(&chunk[0], chunk.size())) > 0) all.insert(all.end(), chunk.begin(), chunk.begin() + got); }
     if (all.empty()) MemoryBitReader::fail("empty input");
     MemoryBitReader in(&all[0], all.size());
-    m_decoder = giveEntropyDecoder((char)in.readByte());            // readGlobalHeader, :51-56
+    const char coder = (char)in.readByte();
+    m_decoder = giveEntropyDecoder(coder);                          // readGlobalHeader, :51-56
     InverseBWTransform* ibwt = 0;
     uint32 ibwtCap = 0;
+    // 'H' blocks are entropy decoded and inverted on the GPU (bwtc_hip_decode_block_H) unless
+    // BWTC_HIP_DECODE=host asks for the serial HuffmanDecoder + GPU inverse; same bytes either way
+    const char* route = std::getenv("BWTC_HIP_DECODE");
+    const bool deviceH = coder == 'H' && !(route && std::strcmp(route, "host") == 0);
+    bwtc_hip_ctx* hctx = 0;
+    uint32 hctxCap = 0;
     size_t decompressedSize = 0;
     std::vector<byte> buf;
     for (;;) {
@@ -580,7 +608,21 @@ class Decompressor {
       const size_t room = rules ? 2 * (size_t)originalSize + 64 : (size_t)originalSize;
       buf.resize(room + 1);
       size_t used = 0;
-      for (uint64 i = 0; i < slices; ++i) {
+      for (uint64 i = 0; deviceH && i < slices; ++i) {
+        const uint64 blockSize = std::min<uint64>(hRecordBlockSize(in.here(), in.left()), room - used);
+        if (!hctx || blockSize > hctxCap) {
+          if (hctx) bwtc_hip_destroy(hctx);
+          hctxCap = (uint32)std::min<uint64>(std::max<uint64>(blockSize, 1u << 20), 0x7FFFFFF0u);
+          hipFatal(bwtc_hip_create(m_device, hctxCap, &hctx), "bwtc_hip_create");
+        }
+        uint32_t size = 0;
+        uint64_t consumed = 0;
+        const int rc = bwtc_hip_decode_block_H(hctx, in.here(), in.left(), &buf[used], room - used, &size, &consumed);
+        if (rc) { std::fprintf(stderr, "bwtc-hip: bwtc_hip_decode_block_H returned %d\n", rc); MemoryBitReader::fail("'H' record"); }
+        in.advance(consumed);
+        used += size;
+      }
+      for (uint64 i = 0; !deviceH && i < slices; ++i) {
         BWTBlock block(&buf[used], 0, true);
         m_decoder->decodeBlock(block, in, room - used);
         if (!ibwt || block.size() > ibwtCap) {
@@ -603,6 +645,7 @@ class Decompressor {
       decompressedSize += used;
     }
     delete ibwt;
+    if (hctx) bwtc_hip_destroy(hctx);
     m_out->flush();
     return decompressedSize;
   }

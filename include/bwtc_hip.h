@@ -5,7 +5,8 @@
  * boundary.  Citations are file:line relative to the reference tree.
  *
  * Return convention (mirrors divbwtf, bwtransforms/divsufsort.c:448,513-515):
- *   0 success, -1 bad arguments, -2 out of (device) memory, -3 HIP runtime error.
+ *   0 success, -1 bad arguments, -2 out of (device) memory, -3 HIP runtime error,
+ *   -10 .. -15 a corrupt 'H' record (BWTC_HIP_E_*, below).
  *
  * A context owns one device, one stream and a persistent HBM workspace sized for
  * max_block_size, the way the reference back-ends own their per-call workspace
@@ -159,6 +160,60 @@ int bwtc_hip_huffman_encode(bwtc_hip_ctx* ctx, const uint8_t* bwt, uint32_t size
 int bwtc_hip_transform_and_encode(bwtc_hip_ctx* ctx, uint8_t* block, uint32_t size,
                                   uint32_t starting_points, uint8_t* out, uint64_t out_cap,
                                   uint64_t* out_bytes);
+
+/* ---- 'H' decoding on the device ------------------------------------------------------ */
+
+/* Return codes of a corrupt 'H' record (the decoders below never write past their output and
+ * never loop without bound on any input): */
+#define BWTC_HIP_E_NO_CODE     (-10)  /* a bit pattern that is no code, or an over-full code shape */
+#define BWTC_HIP_E_SHAPE       (-11)  /* code lengths above maxLen, maxLen above 64, a bad alphabet   */
+#define BWTC_HIP_E_PAST_RECORD (-12)  /* a header, shape or stream runs past the record              */
+#define BWTC_HIP_E_RUNS        (-13)  /* run lengths that do not add up to their section's length    */
+#define BWTC_HIP_E_CAPACITY    (-14)  /* a block larger than the output's capacity                  */
+#define BWTC_HIP_E_LENGTH      (-15)  /* the 48-bit length field disagrees with what was consumed   */
+
+/* Entropy decode of one BWT-block record.  Replaces HuffmanDecoder::decodeBlock
+ * (HuffmanCoders.cpp:324-616): rec (host, rec_bytes bytes; it may go on past the record: only
+ * the 6 + <48-bit length> bytes the record announces are read and uploaded) -> the transformed
+ * block in bwt_out (host, cap bytes), its LF powers in lf_out[256] and their number in *n_lf,
+ * *size = block size, *consumed = the record's bytes.  The block may be larger than the
+ * context's max_block_size (up to cap, below 2^32).  The Huffman and gamma streams are decoded by
+ * transition maps over tiles on the GPU; the device workspace is the decoder's own, allocated by
+ * the first call and grown on demand (bwtc_hip_huffman_decode_stats: workspace_bytes). */
+int bwtc_hip_huffman_decode(bwtc_hip_ctx* ctx, const uint8_t* rec, uint64_t rec_bytes, uint8_t* bwt_out,
+                            uint64_t cap, uint32_t* lf_out, uint32_t* n_lf, uint32_t* size, uint64_t* consumed);
+/* Same with the record (d_rec) and the transformed block (d_bwt_out) in device memory; lf_out
+ * and the counts are host pointers.  The record is also read on the host (shapes, header). */
+int bwtc_hip_huffman_decode_device(bwtc_hip_ctx* ctx, const uint8_t* d_rec, uint64_t rec_bytes, uint8_t* d_bwt_out,
+                                   uint64_t cap, uint32_t* lf_out, uint32_t* n_lf, uint32_t* size, uint64_t* consumed);
+/* Entropy decode plus InverseBWTransform::doTransform (InverseBWT.cpp:47-51): record (host) ->
+ * the original block in out (host, cap bytes).  The record goes up once and the block comes
+ * down once.  The inverse runs in the context's workspace, so cap is clipped to the context's
+ * max_block_size: a larger block returns BWTC_HIP_E_CAPACITY. */
+int bwtc_hip_decode_block_H(bwtc_hip_ctx* ctx, const uint8_t* rec, uint64_t rec_bytes, uint8_t* out, uint64_t cap,
+                            uint32_t* size, uint64_t* consumed);
+/* What the last decode on this context did: route 1 = the device decoder made the bytes. */
+typedef struct bwtc_hip_huffman_decode_stats {
+  uint32_t route;             /* 1: decoded on the device                                        */
+  uint32_t sections;          /* non-empty sections                                              */
+  uint32_t streams;           /* Huffman + gamma streams                                         */
+  uint32_t host_syncs;        /* host round trips of the section chain (one per section + retries) */
+  uint32_t retries;           /* Huffman streams that outran their estimated window (mapped again) */
+  uint32_t max_code_len;      /* longest Huffman code length (maxLen) over the sections          */
+  uint64_t runs;              /* runs decoded                                                    */
+  uint64_t tiles;             /* tiles mapped (512 bits each)                                    */
+  uint64_t map_entries;       /* entries mapped, tiles x M: each entry decodes its tile to the end
+                                 (no boundary merging), so map_entries / tiles = M full-tile decodes */
+  uint64_t launches;          /* kernels launched                                                */
+  uint64_t workspace_bytes;   /* device workspace the decoder holds                              */
+  float    ms_entropy;        /* device time of the decode's kernels: every section's kernel span
+                                 plus the scan and expansion (event pairs on the stream)          */
+  float    ms_entropy_wall;   /* record upload to BWT bytes, the section chain's host round trips
+                                 and shape parsing included                                       */
+  float    ms_chain_host;     /* ms_entropy_wall - ms_entropy: what the host-driven chain adds    */
+  float    ms_inverse;        /* device time of the inverse transform (decode_block_H)           */
+} bwtc_hip_huffman_decode_stats;
+int bwtc_hip_huffman_decode_stats_get(bwtc_hip_ctx* ctx, bwtc_hip_huffman_decode_stats* out);
 
 /* ---- wavelet coders: run scanner (front-end statistics only) ---------------------------- */
 

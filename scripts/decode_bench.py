@@ -1,0 +1,110 @@
+#!/usr/bin/env python3
+"""Decode-side figures of the 'H' coder on one GPU, one JSON line per workload.
+
+For a 256 MiB C3 text block and a 256 MiB uniform-random block, both encoded by the product
+(transform_and_encode):
+  entropy_ms      device time of the entropy decode's kernels (bwtc_hip_huffman_decode statistics)
+  entropy_wall_ms the same from the record's upload to the BWT bytes, the host-driven section chain
+                  included; chain_host_ms = the difference, also per section
+  inverse_ms      device time of the inverse transform inside decode_block_H
+  decode_block_ms decode_block_H from the host record to the host bytes (the call synchronises)
+  uncompress_s    `uncompress` end to end over a file of several blocks, on the default (GPU)
+                  route and under BWTC_HIP_DECODE=host (serial HuffmanDecoder + GPU inverse)
+Best of --reps runs each.  Usage: scripts/decode_bench.py [--mib 256] [--reps 3] [--out FILE]"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+
+from bwtc_amd import hip, synth  # noqa: E402
+
+
+def _best(fn, reps):
+    best, out = None, None
+    for _ in range(reps):
+        t = time.perf_counter()
+        out = fn()
+        dt = time.perf_counter() - t
+        best = dt if best is None else min(best, dt)
+    return best, out
+
+
+def _uncompress(comp, dst, route, reps):
+    env = dict(os.environ)
+    env.pop("BWTC_HIP_DECODE", None)
+    if route:
+        env["BWTC_HIP_DECODE"] = route
+    exe = os.path.join(ROOT, "bwtc_amd", "host", "uncompress")
+    return _best(lambda: subprocess.run([exe, comp, dst], check=True, env=env), reps)[0]
+
+
+def run(name, data, reps, file_blocks_mb):
+    size = data.size
+    line = {"workload": name, "block_bytes": size}
+    with hip.Context(0, size) as ctx:
+        rec, _ = ctx.transform_and_encode(data, 8)
+        line["record_bytes"] = int(rec.size)
+        ctx.huffman_decode(rec)                              # first call: workspace
+        ent = []
+        for _ in range(reps):
+            ctx.huffman_decode(rec)
+            ent.append(ctx.huffman_decode_stats())
+        best = min(ent, key=lambda x: x["ms_entropy_wall"])
+        t, back = _best(lambda: ctx.decode_block_H(rec), reps)
+        assert back.tobytes() == data.tobytes(), name
+        st = ctx.huffman_decode_stats()
+        line.update(entropy_ms=round(best["ms_entropy"], 3), entropy_wall_ms=round(best["ms_entropy_wall"], 3),
+                    chain_host_ms=round(best["ms_chain_host"], 3),
+                    chain_host_ms_per_section=round(best["ms_chain_host"] / max(best["sections"], 1), 4),
+                    inverse_ms=round(st["ms_inverse"], 3),
+                    decode_block_ms=round(t * 1e3, 3), decode_block_GBps=round(size / t / 1e9, 3),
+                    sections=st["sections"], tiles=st["tiles"], map_entries_per_tile=round(st["map_entries"] / max(st["tiles"], 1), 2),
+                    host_syncs=st["host_syncs"], retries=st["retries"], launches=st["launches"],
+                    workspace_bytes_per_block_byte=round(st["workspace_bytes"] / size, 2))
+    with tempfile.TemporaryDirectory() as tmp:
+        src, comp = os.path.join(tmp, "in"), os.path.join(tmp, "in.bwtc")
+        data.tofile(src)
+        subprocess.run([os.path.join(ROOT, "bwtc_amd", "host", "compress"), "-m", str(file_blocks_mb), "-e", "H", src, comp],
+                       check=True, stdout=subprocess.DEVNULL)
+        line["file_blocks"] = -(-size // int(0.185 * file_blocks_mb * 1e6))
+        outs = {}
+        for route in ("", "host"):
+            dst = os.path.join(tmp, "out_" + (route or "device"))
+            line["uncompress_%s_s" % (route or "device")] = round(_uncompress(comp, dst, route, reps), 3)
+            outs[route] = open(dst, "rb").read()
+        assert outs[""] == outs["host"] == data.tobytes(), name
+    line["uncompress_speedup"] = round(line["uncompress_host_s"] / line["uncompress_device_s"], 2)
+    return line
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--mib", type=int, default=256)
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--file-mem", type=int, default=400, help="compress -m for the multi-block file (0.185 MB blocks per MB)")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    size = a.mib << 20
+    rng = np.random.default_rng(1)
+    lines = []
+    for name, gen in (("C3_text", lambda: synth.gen_text(size, 3)),
+                      ("uniform_random", lambda: rng.integers(0, 256, size, dtype=np.uint8))):
+        line = run(name, gen(), a.reps, a.file_mem)
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+
+
+if __name__ == "__main__":
+    main()
