@@ -119,6 +119,14 @@ __device__ __forceinline__ u32 decode_one(const BitPeek& bits, u64 pos, const Sm
   }
 }
 
+// no gamma code could be read at pos: true when its leading one lies past the window's end (the
+// device copy reads zeros there) and a code with that many zeros would still fit max_len, i.e. the
+// code was cut by the end rather than being too long for the section
+__device__ __forceinline__ bool gamma_cut_by_end(const BitPeek& bits, u64 pos, u64 wend, u32 max_len) {
+  const u64 a = wend - pos, w = bits.at(pos);
+  return (w ? (u64)__builtin_clzll(w) : 64ull) >= a && 2 * a + 1 <= max_len;
+}
+
 __device__ __forceinline__ u64 stream_start(const u64* d_start, u64 start) {
   if (!d_start) return start;
   const u64 h = *d_start;                         // the Huffman stream's end: the gamma stream starts at the next byte
@@ -232,9 +240,11 @@ __global__ __launch_bounds__(kDecTPB) void k_hd_decode(const u64* __restrict__ r
     u64 v;
     const u32 len = pos < wend ? decode_one<GAMMA>(bits, pos, &s, max_len, &v) : 0;
     if (!len || pos + len > wend) {
-      const bool past = pos >= wend || (len && pos + len > wend);
+      const bool past = pos >= wend || (len ? pos + len > wend : GAMMA && gamma_cut_by_end(bits, pos, wend, max_len));
       if (past && soft) return;                   // an estimated window: the host maps the stream again in full
-      set_error(&res->err, (u32)-(past ? kHdPastRecord : GAMMA ? kHdRuns : kHdNoCode));
+      // a gamma stream that outruns its window inside the record holds lengths that cannot add up to S
+      const bool record_end = !GAMMA || wend == rec_bits;
+      set_error(&res->err, (u32)-(past ? (record_end ? kHdPastRecord : kHdRuns) : GAMMA ? kHdRuns : kHdNoCode));
       return;
     }
     if (GAMMA) { run_len[idx] = (u32)v; sum += v; }
