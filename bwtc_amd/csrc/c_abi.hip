@@ -2,6 +2,7 @@
 #include "bwt_engine.hpp"
 #include "gpu_lanes.hpp"
 #include "huffman_decoder.hpp"
+#include "postprocess.hpp"
 #include "prepr_host.hpp"
 #include <new>
 #include "radix_sort.hpp"
@@ -23,6 +24,7 @@ using namespace bwtc_hip;
 struct bwtc_hip_ctx {
   BwtEngine eng;
   bwtc_hip::HDecoder* hdec = nullptr;   // 'H' decoder, made by the first decode call
+  bwtc_hip::PostProcessor* post = nullptr;   // `--prepr` postprocessor, made by the first postprocess call
 };
 struct bwtc_hip_grammar {
   bwtc::prepr::Grammar g;
@@ -95,6 +97,7 @@ int bwtc_hip_create(int device, uint32_t max_block_size, bwtc_hip_ctx** ctx_out)
 void bwtc_hip_destroy(bwtc_hip_ctx* ctx) {
   if (!ctx) return;
   bwtc_hip::hdecoder_destroy(ctx->hdec);
+  bwtc_hip::postprocessor_destroy(ctx->post);
   ctx->eng.release();
   delete ctx;
 }
@@ -341,6 +344,14 @@ int bwtc_hip_decode_block_H(bwtc_hip_ctx* ctx, const uint8_t* rec, uint64_t rec_
   HDecoder* d = hdecoder(ctx);
   if (!d) return -2;
   return huffman_decode_block(ctx->eng, *d, rec, rec_bytes, out, cap, size, consumed);
+}
+
+int bwtc_hip_decode_block_H_device(bwtc_hip_ctx* ctx, const uint8_t* rec, uint64_t rec_bytes, uint8_t* d_out, uint64_t cap,
+                                   uint32_t* size, uint64_t* consumed) {
+  if (!ctx || !rec || (!d_out && cap) || !size || !consumed) return -1;
+  HDecoder* d = hdecoder(ctx);
+  if (!d) return -2;
+  return huffman_decode_block_device(ctx->eng, *d, rec, rec_bytes, d_out, cap, size, consumed);
 }
 
 int bwtc_hip_huffman_decode_stats_get(bwtc_hip_ctx* ctx, bwtc_hip_huffman_decode_stats* out) {
@@ -994,6 +1005,45 @@ int bwtc_hip_postprocess(const bwtc_hip_grammar* g, const uint8_t* data, uint64_
   if (!bwtc::prepr::postprocess(g->g, data, static_cast<size_t>(n), &v, static_cast<size_t>(cap))) return -1;
   if (!v.empty()) std::memcpy(out, v.data(), v.size());
   *n_out = v.size();
+  return 0;
+}
+
+static PostProcessor* postprocessor(bwtc_hip_ctx* ctx) {
+  if (!ctx->post) ctx->post = postprocessor_create();
+  return ctx->post;
+}
+int bwtc_hip_postprocess_device(bwtc_hip_ctx* ctx, const bwtc_hip_grammar* g, const uint8_t* d_data, uint64_t n, uint8_t* d_out,
+                                uint64_t cap, uint64_t* n_out) {
+  if (!ctx || !g || (!d_data && n) || !d_out || !n_out) return -1;
+  PostProcessor* p = postprocessor(ctx);
+  if (!p) return -2;
+  return postprocess_device(ctx->eng, *p, g->g, d_data, n, d_out, cap, n_out);
+}
+int bwtc_hip_postprocess_block(bwtc_hip_ctx* ctx, const bwtc_hip_grammar* g, const uint8_t* data, uint64_t n, uint8_t* out,
+                               uint64_t cap, uint64_t* n_out) {
+  if (!ctx || !g || (!data && n) || !out || !n_out) return -1;
+  PostProcessor* p = postprocessor(ctx);
+  if (!p) return -2;
+  return postprocess_block(ctx->eng, *p, g->g, data, n, out, cap, n_out);
+}
+int bwtc_hip_postprocess_stats_get(bwtc_hip_ctx* ctx, bwtc_hip_postprocess_stats* out) {
+  if (!ctx || !out) return -1;
+  return postprocessor_stats(ctx->post, out);
+}
+int bwtc_hip_host_postprocess_tiles(const bwtc_hip_grammar* g, const uint8_t* data, uint64_t n, uint8_t* out, uint64_t cap,
+                                    uint64_t* n_out, uint32_t tile) {
+  if (!g || (!data && n) || !out || !n_out || tile == 0) return -1;
+  if (g->g.numberOfRules() == 0) {
+    if (n > cap) return -1;
+    if (n) std::memcpy(out, data, n);
+    *n_out = n;
+    return 0;
+  }
+  bwtc::prepr::ExpansionTable t;
+  if (!bwtc::prepr::buildExpansionTable(g->g, static_cast<size_t>(cap), &t)) return -1;
+  const int64_t total = bwtc::prepr::postprocessTilesOnHost(t, data, static_cast<size_t>(n), out, static_cast<size_t>(cap), tile);
+  if (total < 0) return -1;
+  *n_out = static_cast<uint64_t>(total);
   return 0;
 }
 

@@ -620,14 +620,25 @@ int huffman_decode(BwtEngine& e, HDecoder& d, const u8* rec, const u8* d_rec_src
   return 0;
 }
 
-int huffman_decode_block(BwtEngine& e, HDecoder& d, const u8* rec, u64 rec_bytes, u8* out, u64 cap, u32* size_out, u64* consumed_out) {
+int huffman_decode_block_device(BwtEngine& e, HDecoder& d, const u8* rec, u64 rec_bytes, u8* d_out, u64 cap, u32* size_out,
+                                u64* consumed_out) {
   u32 lf[256], n_lf = 0, size = 0;
   int rc = huffman_decode(e, d, rec, nullptr, rec_bytes, nullptr, std::min<u64>(cap, e.max_block), lf, &n_lf, &size, consumed_out);
   if (rc) return rc;
   if (size) {
-    rc = inverse_bwt_device(e, d.d_bwt, e.d_in, size, lf, n_lf);
+    rc = inverse_bwt_device(e, d.d_bwt, d_out, size, lf, n_lf);
     d.stats.ms_inverse = e.stats.ms_total;
     if (rc) return rc;
+  }
+  *size_out = size;
+  return 0;
+}
+
+int huffman_decode_block(BwtEngine& e, HDecoder& d, const u8* rec, u64 rec_bytes, u8* out, u64 cap, u32* size_out, u64* consumed_out) {
+  u32 size = 0;
+  const int rc = huffman_decode_block_device(e, d, rec, rec_bytes, e.d_in, cap, &size, consumed_out);
+  if (rc) return rc;
+  if (size) {
     HD_TRY(hipMemcpyAsync(e.h_stage, e.d_in, size, hipMemcpyDeviceToHost, e.stream));
     HD_TRY(e.wait());
     std::memcpy(out, e.h_stage, size);

@@ -30,5 +30,8 @@ int huffman_decode(BwtEngine& e, HDecoder& d, const u8* rec, const u8* d_rec_src
 // the same plus the inverse transform; out = host
 int huffman_decode_block(BwtEngine& e, HDecoder& d, const u8* rec, u64 rec_bytes, u8* out, u64 cap, u32* size_out,
                          u64* consumed_out);
+// the same with the original block left in device memory at d_out
+int huffman_decode_block_device(BwtEngine& e, HDecoder& d, const u8* rec, u64 rec_bytes, u8* d_out, u64 cap, u32* size_out,
+                                u64* consumed_out);
 
 }  // namespace bwtc_hip

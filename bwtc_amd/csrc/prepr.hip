@@ -87,27 +87,6 @@ __global__ __launch_bounds__(kPrTPB) void k_pr_heads(const u8* __restrict__ d, u
   (void)block_scan_incl_max<kPrTPB>(last, scr, &total);
   if (threadIdx.x == 0) tile_head[blockIdx.x] = total;
 }
-// exclusive running maximum over the tiles, in place (one workgroup; at most a few hundred thousand tiles)
-__global__ __launch_bounds__(1024) void k_pr_head_scan(u32* __restrict__ tile_head, u32 ntiles) {
-  __shared__ u32 scr[1024 / kWave + 1];
-  __shared__ u32 s_incl[1024];
-  __shared__ u32 carry;
-  if (threadIdx.x == 0) carry = 0;
-  __syncthreads();
-  for (u32 base = 0; base < ntiles; base += 1024u) {
-    const u32 i = base + threadIdx.x;
-    const u32 v = i < ntiles ? tile_head[i] : 0u;
-    u32 total;
-    s_incl[threadIdx.x] = block_scan_incl_max<1024>(v, scr, &total);
-    __syncthreads();
-    const u32 excl = max(carry, threadIdx.x ? s_incl[threadIdx.x - 1] : 0u);
-    if (i < ntiles) tile_head[i] = excl;
-    __syncthreads();
-    if (threadIdx.x == 0) carry = max(carry, total);
-    __syncthreads();
-  }
-}
-
 // What the thread's sixteen positions turn into.  len[k] in {0, 1, 2}, bytes b0 / b1.
 // SELF: some replaced pair has two equal bytes; run_before = where the run that reaches position j0 - 1 starts.
 template <bool SELF>

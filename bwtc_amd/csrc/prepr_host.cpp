@@ -381,29 +381,34 @@ void decideReplacements(Grammar* grammar, const uint64_t* byte_freq, const uint6
 }
 
 // ---- Postprocessor ---------------------------------------------------------------------------------
-bool postprocess(const Grammar& grammar, const byte* data, size_t n, std::vector<byte>* out, size_t cap) {
-  if (grammar.numberOfRules() == 0) {                             // Postprocessor.cpp:114-117
-    if (n > cap) return false;
-    out->insert(out->end(), data, data + n);
-    return true;
+namespace {
+
+typedef std::vector<std::vector<byte> > Expansions;
+
+// src expanded with what is known so far, appended to dst; false when dst would grow past `limit` bytes
+bool expandInto(const Grammar& grammar, const Expansions& plain, const Expansions& paired, const byte* src, size_t len,
+                std::vector<byte>* dst, size_t limit) {
+  for (size_t i = 0; i < len; ++i) {
+    const std::vector<byte>* e = &plain[src[i]];
+    if (grammar.isSpecial(src[i]) && i + 1 < len) { e = &paired[static_cast<uint32_t>(src[i]) << 8 | src[i + 1]]; ++i; }
+    if (dst->size() + e->size() > limit) return false;
+    dst->insert(dst->end(), e->begin(), e->end());
   }
-  // what every byte, and every pair that starts with a special symbol, stands for (Postprocessor.cpp:62-94)
-  std::vector<std::vector<byte> > plain(256), paired(1u << 16);
+  return true;
+}
+
+// what every byte, and every pair that starts with a special symbol, stands for (Postprocessor.cpp:62-94)
+bool buildExpansions(const Grammar& grammar, size_t cap, Expansions* plain_out, Expansions* paired_out) {
+  Expansions& plain = *plain_out;
+  Expansions& paired = *paired_out;
+  plain.assign(256, std::vector<byte>());
+  paired.assign(1u << 16, std::vector<byte>());
   for (int c = 0; c < 256; ++c) plain[c].push_back(static_cast<byte>(c));
   {
     std::vector<std::pair<uint16_t, byte> > freed;
     grammar.freedSymbols(&freed);
     for (size_t i = 0; i < freed.size(); ++i) paired[freed[i].first].push_back(freed[i].second);
   }
-  auto expand = [&](const byte* src, size_t len, std::vector<byte>* dst, size_t limit) -> bool {
-    for (size_t i = 0; i < len; ++i) {
-      const std::vector<byte>* e = &plain[src[i]];
-      if (grammar.isSpecial(src[i]) && i + 1 < len) { e = &paired[static_cast<uint32_t>(src[i]) << 8 | src[i + 1]]; ++i; }
-      if (dst->size() + e->size() > limit) return false;
-      dst->insert(dst->end(), e->begin(), e->end());
-    }
-    return true;
-  };
   // The grammar comes out of the stream: a damaged (or hostile) one can chain twenty rules whose right sides name
   // the rule before four times each -- 4^20 bytes.  No rule of a sound grammar stands for more than the block it came
   // from, and all of them together for little more than twice that (a rule is used where it saves bytes).
@@ -412,12 +417,105 @@ bool postprocess(const Grammar& grammar, const byte* data, size_t n, std::vector
   const size_t budget = 2 * cap + (static_cast<size_t>(1) << 20);
   for (size_t i = 0; i < rules.size(); ++i) {                     // in order: a right side only uses earlier variables
     std::vector<byte> full;
-    if (!expand(&rules[i].rhs[0], rules[i].rhs.size(), &full, cap)) return false;
+    if (!expandInto(grammar, plain, paired, &rules[i].rhs[0], rules[i].rhs.size(), &full, cap)) return false;
     expanded += full.size();
     if (expanded > budget) return false;
     if (rules[i].large) paired[rules[i].variable].swap(full); else plain[rules[i].variable & 0xff].swap(full);
   }
-  return expand(data, n, out, out->size() + cap);
+  return true;
+}
+
+}  // namespace
+
+bool postprocess(const Grammar& grammar, const byte* data, size_t n, std::vector<byte>* out, size_t cap) {
+  if (grammar.numberOfRules() == 0) {                             // Postprocessor.cpp:114-117
+    if (n > cap) return false;
+    out->insert(out->end(), data, data + n);
+    return true;
+  }
+  Expansions plain, paired;
+  if (!buildExpansions(grammar, cap, &plain, &paired)) return false;
+  return expandInto(grammar, plain, paired, data, n, out, out->size() + cap);
+}
+
+bool buildExpansionTable(const Grammar& grammar, size_t cap, ExpansionTable* t) {
+  Expansions plain, paired;
+  if (!buildExpansions(grammar, cap, &plain, &paired)) return false;
+  t->entry.assign(2 * static_cast<size_t>(kExpansionKeys), 0);
+  t->pool.clear();
+  t->any_special = grammar.numberOfSpecialSymbols() > 0;
+  for (int w = 0; w < 8; ++w) t->special[w] = 0;
+  for (uint32_t c = 0; c < 256; ++c) if (grammar.isSpecial(static_cast<byte>(c))) t->special[c >> 5] |= 1u << (c & 31);
+  uint64_t total = 0;
+  for (uint32_t c = 0; c < 256; ++c) total += plain[c].size();
+  for (uint32_t c = 0; c < 256; ++c)
+    if (grammar.isSpecial(static_cast<byte>(c))) for (uint32_t d = 0; d < 256; ++d) total += paired[c << 8 | d].size();
+  if (total >= (static_cast<uint64_t>(1) << 32)) return false;    // entries address the pool with 32 bits
+  t->pool.reserve(static_cast<size_t>(total));
+  auto put = [&](uint32_t key, const std::vector<byte>& e) {
+    t->entry[2 * key] = static_cast<uint32_t>(t->pool.size());
+    t->entry[2 * key + 1] = static_cast<uint32_t>(e.size());
+    t->pool.insert(t->pool.end(), e.begin(), e.end());
+  };
+  for (uint32_t c = 0; c < 256; ++c) put(c, plain[c]);
+  for (uint32_t c = 0; c < 256; ++c)                              // pairs that do not start with a special symbol: unused
+    if (grammar.isSpecial(static_cast<byte>(c))) for (uint32_t d = 0; d < 256; ++d) put(256u + (c << 8 | d), paired[c << 8 | d]);
+  return true;
+}
+
+// The device passes of postprocess.hip, tile by tile on the calling thread.
+//   heads   mark of a tile = (last position of a byte that is NOT special) + 1, 0 when it has none; the exclusive
+//           running maximum over the tiles is where the run of special bytes that reaches into a tile starts
+//   count   position i starts a token when the run of special bytes that ends at i - 1 has even length
+//   write   a tile's output range is produced in 16-byte groups of the OUTPUT; every group finds the token that
+//           covers its first byte by a search of the tile's offsets and copies from there
+int64_t postprocessTilesOnHost(const ExpansionTable& t, const byte* data, size_t n, byte* out, size_t cap, size_t tile) {
+  if (tile == 0) return -1;
+  const size_t ntiles = (n + tile - 1) / tile;
+  auto is_special = [&](byte c) { return (t.special[c >> 5] >> (c & 31)) & 1u; };
+  std::vector<uint64_t> run_start(ntiles, 0), offset(ntiles + 1, 0);
+  {
+    uint64_t carry = 0;
+    for (size_t b = 0; b < ntiles; ++b) {
+      run_start[b] = carry;
+      const size_t lo = b * tile, hi = std::min(n, lo + tile);
+      for (size_t i = hi; i > lo; --i) if (!is_special(data[i - 1])) { carry = std::max<uint64_t>(carry, i); break; }
+    }
+  }
+  struct Token { uint64_t at; uint32_t src, len; };
+  auto tokens_of = [&](size_t b, std::vector<Token>* toks) -> uint64_t {
+    const size_t lo = b * tile, hi = std::min(n, lo + tile);
+    uint64_t run = run_start[b], at = 0;
+    for (size_t i = lo; i < hi; ++i) {
+      const bool starts = ((i - run) & 1) == 0;
+      if (starts) {
+        const uint32_t key = is_special(data[i]) && i + 1 < n ? 256u + (static_cast<uint32_t>(data[i]) << 8 | data[i + 1]) : data[i];
+        const Token k = {at, t.entry[2 * key], t.entry[2 * key + 1]};
+        if (toks) toks->push_back(k);
+        at += k.len;
+      }
+      if (!is_special(data[i])) run = i + 1;
+    }
+    return at;
+  };
+  for (size_t b = 0; b < ntiles; ++b) offset[b + 1] = offset[b] + tokens_of(b, 0);
+  const uint64_t total = offset[ntiles];
+  if (total > cap) return -1;                                     // nothing has been written
+  std::vector<Token> toks;
+  for (size_t b = 0; b < ntiles; ++b) {
+    toks.clear();
+    const uint64_t size = tokens_of(b, &toks);
+    for (uint64_t x0 = 0; x0 < size; x0 += 16) {                  // one group: what a lane of the write pass does
+      size_t lo = 0, hi = toks.size();                            // the last token with at <= x0 (it covers x0)
+      while (hi - lo > 1) { const size_t mid = (lo + hi) / 2; if (toks[mid].at <= x0) lo = mid; else hi = mid; }
+      size_t k = lo;
+      for (uint64_t x = x0; x < std::min(size, x0 + 16); ++x) {
+        while (x >= toks[k].at + toks[k].len) ++k;
+        out[offset[b] + x] = t.pool[toks[k].src + (x - toks[k].at)];
+      }
+    }
+  }
+  return static_cast<int64_t>(total);
 }
 
 // ---- host twins of the GPU passes ------------------------------------------------------------------

@@ -84,6 +84,23 @@ void decideReplacements(Grammar* grammar, const uint64_t* byte_freq, const uint6
 // Postprocessor (Postprocessor.cpp:62-133): expands `data`; false when the output does not fit `cap`.
 bool postprocess(const Grammar& grammar, const byte* data, size_t n, std::vector<byte>* out, size_t cap);
 
+// What the expansion kernels (postprocess.hip) read: one flat byte pool and an (offset, length) entry for each of the
+// 256 single-byte keys [c] and each of the 65 536 pair keys [256 + (first << 8 | second)].  Only pairs that start
+// with a special symbol are filled in; a pair nobody defined has length 0, as the host's empty vector has.
+constexpr uint32_t kExpansionKeys = 256u + 65536u;
+struct ExpansionTable {
+  std::vector<uint32_t> entry;       // 2 * kExpansionKeys words: offset into the pool, length
+  std::vector<byte> pool;
+  uint32_t special[8];               // bit c: c is a special symbol
+  bool any_special;
+};
+// The rules expanded in order exactly as postprocess does, with its guard: false when one expansion exceeds `cap`,
+// all of them exceed 2 * cap + 1 MiB, or the pool does not fit 32-bit offsets.
+bool buildExpansionTable(const Grammar& grammar, size_t cap, ExpansionTable* table);
+// Host twin of the expansion kernels' passes over tiles of `tile` bytes: bytes written, or -1 when they exceed `cap`
+// (nothing written then).
+int64_t postprocessTilesOnHost(const ExpansionTable& table, const byte* data, size_t n, byte* out, size_t cap, size_t tile);
+
 // Host twins of the two GPU passes (the CPU suite, and blocks too short for a launch to pay).
 void pairStatisticsOnHost(const byte* data, size_t n, uint64_t* byte_freq, uint64_t* pair_freq);
 size_t writeReplacedOnHost(const Replacements& r, const byte* src, size_t n, byte* dst);

@@ -93,6 +93,28 @@ static __global__ __launch_bounds__(kScanTPB) void k_scan_apply(u32* __restrict_
   }
 }
 
+// Exclusive running maximum over per-tile words, in place (one workgroup; at most a few hundred thousand tiles):
+// where the run that reaches into a tile starts (prepr.hip: runs of equal bytes, postprocess.hip: runs of special bytes).
+static __global__ __launch_bounds__(1024) void k_pr_head_scan(u32* __restrict__ tile_head, u32 ntiles) {
+  __shared__ u32 scr[1024 / kWave + 1];
+  __shared__ u32 s_incl[1024];
+  __shared__ u32 carry;
+  if (threadIdx.x == 0) carry = 0;
+  __syncthreads();
+  for (u32 base = 0; base < ntiles; base += 1024u) {
+    const u32 i = base + threadIdx.x;
+    const u32 v = i < ntiles ? tile_head[i] : 0u;
+    u32 total;
+    s_incl[threadIdx.x] = block_scan_incl_max<1024>(v, scr, &total);
+    __syncthreads();
+    const u32 excl = max(carry, threadIdx.x ? s_incl[threadIdx.x - 1] : 0u);
+    if (i < ntiles) tile_head[i] = excl;
+    __syncthreads();
+    if (threadIdx.x == 0) carry = max(carry, total);
+    __syncthreads();
+  }
+}
+
 // ---- one launch: chained tiles with decoupled look-back -------------------------------------------
 // A suffix sort makes some hundred scans per block (one per radix pass, over the tile histograms),
 // each small: three launches cost more in launch boundaries and in reading the table twice than

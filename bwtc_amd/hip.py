@@ -34,6 +34,11 @@ class HuffmanDecodeStats(ctypes.Structure):
                 ("ms_entropy_wall", ctypes.c_float), ("ms_chain_host", ctypes.c_float), ("ms_inverse", ctypes.c_float)]
 
 
+class PostprocessStats(ctypes.Structure):
+    _fields_ = [("route", _u32), ("launches", _u32), ("tokens", _u64), ("pair_tokens", _u64), ("in_bytes", _u64),
+                ("out_bytes", _u64), ("pool_bytes", _u64), ("workspace_bytes", _u64), ("ms_device", ctypes.c_float)]
+
+
 class Stats(ctypes.Structure):
     _fields_ = [("n", _u32), ("rounds", _u32), ("active_sum", _u64), ("sort_pass_items", _u64),
                 ("ms_total", ctypes.c_float), ("ms_sort", ctypes.c_float),
@@ -73,6 +78,8 @@ EXPORTS = [
     "bwtc_hip_wavelet_depth_needed", "bwtc_hip_grammar_create", "bwtc_hip_grammar_destroy", "bwtc_hip_grammar_rules", "bwtc_hip_grammar_special_symbols",
     "bwtc_hip_grammar_is_special", "bwtc_hip_grammar_write", "bwtc_hip_grammar_read", "bwtc_hip_pair_replace_device",
     "bwtc_hip_precompress", "bwtc_hip_host_precompress", "bwtc_hip_postprocess",
+    "bwtc_hip_postprocess_device", "bwtc_hip_postprocess_block", "bwtc_hip_postprocess_stats_get",
+    "bwtc_hip_host_postprocess_tiles",
 ]
 
 _lib = None
@@ -178,6 +185,11 @@ def load():
     L.bwtc_hip_precompress.argtypes = [_vp, _vp, ctypes.c_char_p, _vp, _u64, ctypes.POINTER(_u64)]
     L.bwtc_hip_host_precompress.argtypes = [_vp, ctypes.c_char_p, _vp, _u64, ctypes.POINTER(_u64)]
     L.bwtc_hip_postprocess.argtypes = [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64)]
+    L.bwtc_hip_postprocess_device.argtypes = [_vp, _vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64)]
+    L.bwtc_hip_postprocess_block.argtypes = [_vp, _vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64)]
+    L.bwtc_hip_postprocess_stats_get.argtypes = [_vp, ctypes.POINTER(PostprocessStats)]
+    L.bwtc_hip_host_postprocess_tiles.argtypes = [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _u32]
+    L.bwtc_hip_decode_block_H_device.argtypes = [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u32), ctypes.POINTER(_u64)]
     L.bwtc_hip_host_huffman_lengths.restype = None
     L.bwtc_hip_host_huffman_lengths.argtypes = [_vp, _vp]
     L.bwtc_hip_host_huffman_codes.restype = None
@@ -256,6 +268,15 @@ class Grammar:
         _check(self.lib.bwtc_hip_postprocess(self.h, _ptr(data), data.size, _ptr(out), out.size, ctypes.byref(n)), "bwtc_hip_postprocess")
         return out[:n.value].copy()
 
+    def host_postprocess_tiles(self, data, max_size, tile):
+        """Host twin of the device postprocessor's passes over tiles of `tile` bytes (no device)."""
+        data = np.ascontiguousarray(data, np.uint8)
+        out = np.zeros(max(1, max_size), np.uint8)
+        n = _u64(0)
+        _check(self.lib.bwtc_hip_host_postprocess_tiles(self.h, _ptr(data), data.size, _ptr(out), max_size, ctypes.byref(n), tile),
+               "bwtc_hip_host_postprocess_tiles")
+        return out[:n.value].copy()
+
 
 class Context:
     """One GPU, one stream, one persistent workspace (bwtc_hip_ctx)."""
@@ -295,6 +316,27 @@ class Context:
         n = _u64(0)
         _check(self.lib.bwtc_hip_precompress(self.handle, grammar.h, options.encode(), _ptr(buf), buf.size, ctypes.byref(n)), "bwtc_hip_precompress")
         return buf[:n.value].copy()
+
+    def postprocess(self, grammar, data, max_size):
+        """Postprocessor::uncompress on the GPU (bwtc_hip_postprocess_block): host buffers in and out."""
+        data = np.ascontiguousarray(data, np.uint8)
+        out = np.zeros(max(1, max_size), np.uint8)
+        n = _u64(0)
+        _check(self.lib.bwtc_hip_postprocess_block(self.handle, grammar.h, _ptr(data), data.size, _ptr(out), max_size, ctypes.byref(n)),
+               "bwtc_hip_postprocess_block")
+        return out[:n.value].copy()
+
+    def postprocess_device(self, grammar, d_data_ptr, n, d_out_ptr, cap):
+        """The same on device pointers (bwtc_hip_postprocess_device): the expansion's size."""
+        n_out = _u64(0)
+        _check(self.lib.bwtc_hip_postprocess_device(self.handle, grammar.h, _vp(d_data_ptr), n, _vp(d_out_ptr), cap, ctypes.byref(n_out)),
+               "bwtc_hip_postprocess_device")
+        return int(n_out.value)
+
+    def postprocess_stats(self):
+        s = PostprocessStats()
+        _check(self.lib.bwtc_hip_postprocess_stats_get(self.handle, ctypes.byref(s)), "bwtc_hip_postprocess_stats_get")
+        return {f: getattr(s, f) for f, _ in PostprocessStats._fields_}
 
     def stats(self):
         s = Stats()
@@ -661,6 +703,15 @@ class Context:
                "bwtc_hip_decode_block_H")
         data = out[:size.value].copy()
         return (data, int(used.value)) if with_consumed else data
+
+    def decode_block_H_device(self, record, d_out_ptr, cap):
+        """decode_block_H with the original block left in device memory at d_out_ptr: returns (size, consumed)."""
+        record = np.ascontiguousarray(record, dtype=np.uint8)
+        size, used = _u32(0), _u64(0)
+        _check(self.lib.bwtc_hip_decode_block_H_device(self.handle, _ptr(record), record.size, _vp(d_out_ptr), cap,
+                                                       ctypes.byref(size), ctypes.byref(used)),
+               "bwtc_hip_decode_block_H_device")
+        return int(size.value), int(used.value)
 
     def huffman_decode_stats(self):
         s = HuffmanDecodeStats()

@@ -313,6 +313,7 @@ class InverseBWTransform {
     *block.end() = data[block.LFpowers()[0]];
     doTransform(block.begin(), (uint32)block.size() + 1, block.LFpowers());
   }
+  virtual bwtc_hip_ctx* hipContext() const { return 0; }          // the GPU context behind it, if any
 };
 
 class HipInverseBWTransform : public InverseBWTransform {
@@ -332,6 +333,7 @@ class HipInverseBWTransform : public InverseBWTransform {
                                         &block.LFpowers()[0], (uint32)block.LFpowers().size()),
              "bwtc_hip_inverse_bwt_block");
   }
+  bwtc_hip_ctx* hipContext() const { return m_ctx; }
  private:
   bwtc_hip_ctx* m_ctx;
 };
@@ -544,13 +546,44 @@ class Precompressor {
 };
 
 // preprocessors/Postprocessor.hpp
+// Precompressed blocks below this size are expanded by the host function: a chain of launches and a host read do
+// not pay there.
+static const size_t kPostprocessDeviceMin = 64u << 10;
+
+// BWTC_HIP_POSTPROCESS=host keeps every block on the host function (same bytes)
+inline bool postprocessOnHostOnly() {
+  const char* route = std::getenv("BWTC_HIP_POSTPROCESS");
+  return route && std::strcmp(route, "host") == 0;
+}
+
+// which route the precompressor blocks of a stream took (uncompress prints it under BWTC_HIP_DEBUG=1)
+struct PostprocessTally {
+  PostprocessTally() : device(0), host(0), msDevice(0.0) {}
+  void noteDevice(bwtc_hip_ctx* ctx) {
+    bwtc_hip_postprocess_stats st;
+    if (bwtc_hip_postprocess_stats_get(ctx, &st) == 0 && st.route == 1) { ++device; msDevice += st.ms_device; }
+    else ++host;
+  }
+  uint64 device, host;
+  double msDevice;
+};
+
 class Postprocessor {
  public:
   Postprocessor(bool, const Grammar& grammar) : m_grammar(grammar) {}
-  size_t uncompress(const byte* data, size_t length, OutStream* to, size_t originalSize) const {   // Postprocessor.cpp:112-133
+  // Postprocessor.cpp:112-133.  With a context (the one that ran the block's inverse transforms) the block is
+  // expanded on its GPU (bwtc_hip_postprocess_block); without one, or for a small block, by the host function.
+  size_t uncompress(const byte* data, size_t length, OutStream* to, size_t originalSize, bwtc_hip_ctx* ctx = 0,
+                    PostprocessTally* tally = 0) const {
     std::vector<byte> out(originalSize + 1);
     uint64_t n = 0;
-    hipFatal(bwtc_hip_postprocess(m_grammar.handle(), data, length, &out[0], originalSize, &n), "bwtc_hip_postprocess");
+    if (ctx && length >= kPostprocessDeviceMin && !postprocessOnHostOnly()) {
+      hipFatal(bwtc_hip_postprocess_block(ctx, m_grammar.handle(), data, length, &out[0], originalSize, &n), "bwtc_hip_postprocess_block");
+      if (tally) tally->noteDevice(ctx);
+    } else {
+      hipFatal(bwtc_hip_postprocess(m_grammar.handle(), data, length, &out[0], originalSize, &n), "bwtc_hip_postprocess");
+      if (tally) ++tally->host;
+    }
     to->writeBlock(&out[0], &out[0] + n);
     return (size_t)n;
   }

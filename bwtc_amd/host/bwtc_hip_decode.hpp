@@ -595,6 +595,10 @@ class Decompressor {
     uint32 hctxCap = 0;
     size_t decompressedSize = 0;
     std::vector<byte> buf;
+    // `--prepr` blocks of an 'H' stream stay on the device from record to original bytes: the slices are decoded side
+    // by side into dPre, expanded into dPost and downloaded once
+    uint8_t *dPre = 0, *dPost = 0;
+    uint64 dPreCap = 0, dPostCap = 0;
     for (;;) {
       const uint64 originalSize = in.readPackedInteger();           // PrecompressorBlock.cpp:97-108
       if (originalSize == 0) break;
@@ -606,7 +610,58 @@ class Decompressor {
       in.advance(grammar.readGrammar(in.here(), in.left()));
       const bool rules = grammar.numberOfRules() > 0;
       const size_t room = rules ? 2 * (size_t)originalSize + 64 : (size_t)originalSize;
-      buf.resize(room + 1);
+      if (rules && deviceH && !postprocessOnHostOnly() && originalSize < ((uint64)1 << 32)) {
+        // what the slices hold, and the largest of them (the context is sized by it, as below)
+        uint64 precompressed = 0, largest = 0;
+        { const byte* p = in.here(); size_t left = in.left();
+          for (uint64 i = 0; i < slices && left >= 6; ++i) {
+            const uint64 blockSize = hRecordBlockSize(p, left);
+            uint64 len = 0;
+            for (int k = 0; k < 6; ++k) len = (len << 8) | p[k];
+            precompressed += blockSize; largest = std::max(largest, blockSize);
+            const uint64 step = std::min<uint64>(6 + len, left);
+            p += step; left -= (size_t)step;
+          } }
+        if (precompressed >= kPostprocessDeviceMin && precompressed <= room) {
+          largest = std::min<uint64>(largest, room);
+          if (!hctx || largest > hctxCap) {
+            if (hctx) bwtc_hip_destroy(hctx);
+            hctxCap = (uint32)std::min<uint64>(std::max<uint64>(largest, 1u << 20), 0x7FFFFFF0u);
+            hipFatal(bwtc_hip_create(m_device, hctxCap, &hctx), "bwtc_hip_create");
+          }
+          if (room > dPreCap) {
+            if (dPre) bwtc_hip_free(hctx, dPre);
+            dPre = static_cast<uint8_t*>(bwtc_hip_malloc(hctx, room));
+            if (!dPre) hipFatal(-2, "bwtc_hip_malloc");
+            dPreCap = room;
+          }
+          if (originalSize + 16 > dPostCap) {
+            if (dPost) bwtc_hip_free(hctx, dPost);
+            dPost = static_cast<uint8_t*>(bwtc_hip_malloc(hctx, originalSize + 16));
+            if (!dPost) hipFatal(-2, "bwtc_hip_malloc");
+            dPostCap = originalSize + 16;
+          }
+          size_t used = 0;
+          for (uint64 i = 0; i < slices; ++i) {
+            uint32_t size = 0;
+            uint64_t consumed = 0;
+            const int rc = bwtc_hip_decode_block_H_device(hctx, in.here(), in.left(), dPre + used, room - used, &size, &consumed);
+            if (rc) { std::fprintf(stderr, "bwtc-hip: bwtc_hip_decode_block_H_device returned %d\n", rc); MemoryBitReader::fail("'H' record"); }
+            in.advance(consumed);
+            used += size;
+          }
+          uint64_t postSize = 0;
+          hipFatal(bwtc_hip_postprocess_device(hctx, grammar.handle(), dPre, used, dPost, originalSize, &postSize), "bwtc_hip_postprocess_device");
+          m_postprocess.noteDevice(hctx);
+          if (postSize != originalSize) MemoryBitReader::fail("postprocessed block size");
+          buf.resize(std::max(buf.size(), (size_t)originalSize + 1));
+          hipFatal(bwtc_hip_memcpy_to_host(hctx, &buf[0], dPost, postSize), "bwtc_hip_memcpy_to_host");
+          m_out->writeBlock(&buf[0], &buf[0] + postSize);
+          decompressedSize += postSize;
+          continue;
+        }
+      }
+      buf.resize(std::max(buf.size(), room + 1));
       size_t used = 0;
       for (uint64 i = 0; deviceH && i < slices; ++i) {
         const uint64 blockSize = std::min<uint64>(hRecordBlockSize(in.here(), in.left()), room - used);
@@ -635,7 +690,8 @@ class Decompressor {
       }
       if (rules) {
         Postprocessor postprocessor(false, grammar);               // Decompressor.cpp:82-88
-        const size_t postSize = postprocessor.uncompress(&buf[0], used, m_out, (size_t)originalSize);
+        const size_t postSize = postprocessor.uncompress(&buf[0], used, m_out, (size_t)originalSize, ibwt ? ibwt->hipContext() : 0,
+                                                         &m_postprocess);
         if (postSize != originalSize) MemoryBitReader::fail("postprocessed block size");
         decompressedSize += postSize;
         continue;
@@ -645,11 +701,13 @@ class Decompressor {
       decompressedSize += used;
     }
     delete ibwt;
-    if (hctx) bwtc_hip_destroy(hctx);
+    if (hctx) { if (dPre) bwtc_hip_free(hctx, dPre); if (dPost) bwtc_hip_free(hctx, dPost); bwtc_hip_destroy(hctx); }
     m_out->flush();
     return decompressedSize;
   }
+  const PostprocessTally& postprocessTally() const { return m_postprocess; }
  private:
+  PostprocessTally m_postprocess;
   InStream* m_in;
   OutStream* m_out;
   EntropyDecoder* m_decoder;

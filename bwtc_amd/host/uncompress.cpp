@@ -37,6 +37,10 @@ int main(int argc, char** argv) {
   bwtc::Decompressor d(new bwtc::RawInStream(in_name), new bwtc::RawOutStream(out_name), device);
   const size_t n = d.decompress(1);
   const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  const char* debug = std::getenv("BWTC_HIP_DEBUG");
+  if (debug && std::strcmp(debug, "1") == 0)
+    std::fprintf(stderr, "postprocess: device %llu host %llu ms_device %.3f\n", (unsigned long long)d.postprocessTally().device,
+                 (unsigned long long)d.postprocessTally().host, d.postprocessTally().msDevice);
   if (verbosity > 0) std::fprintf(stderr, "Decompressed size: %zu bytes, %.3f s\n", n, s);
   return 0;
 }

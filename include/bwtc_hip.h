@@ -469,6 +469,46 @@ int      bwtc_hip_host_precompress(bwtc_hip_grammar* g, const char* options, uin
 /* Postprocessor::uncompress: data (n bytes) expanded into out (cap bytes); -1 when it does not fit */
 int      bwtc_hip_postprocess(const bwtc_hip_grammar* g, const uint8_t* data, uint64_t n, uint8_t* out, uint64_t cap,
                               uint64_t* n_out);
+/* ---- Postprocessor on the device (postprocess.hip) --------------------------------------------------
+ * The grammar's expansion table is built on the host; lengths are summed per tile, the tiles' offsets come from a
+ * device scan, the bytes are written by a gather from the table's pool.  The device workspace (per-tile words,
+ * table, pool, the staging of _block) is the postprocessor's own, made by the first call and grown on demand
+ * (bwtc_hip_postprocess_stats: workspace_bytes).  Blocks of n >= 2^31 or cap >= 2^32 bytes take the host function
+ * (same bytes), as bwtc_hip_precompress does. */
+/* Postprocessor::uncompress(const byte* data, size_t length, OutStream* to, size_t originalSize)
+ * (preprocessors/Postprocessor.cpp:112-133) with the block and its expansion in device memory: d_data (n bytes) ->
+ * d_out (cap bytes; must not overlap d_data), *n_out = the expansion's size.  -1: bad arguments, or the expansion
+ * does not fit cap (nothing has been written to d_out then); -2 / -3 as everywhere. */
+int      bwtc_hip_postprocess_device(bwtc_hip_ctx* ctx, const bwtc_hip_grammar* g, const uint8_t* d_data, uint64_t n,
+                                     uint8_t* d_out, uint64_t cap, uint64_t* n_out);
+/* The same interface with host buffers, as bwtc_hip_postprocess has them: data goes up, is expanded on the device
+ * and comes down once. */
+int      bwtc_hip_postprocess_block(bwtc_hip_ctx* ctx, const bwtc_hip_grammar* g, const uint8_t* data, uint64_t n,
+                                    uint8_t* out, uint64_t cap, uint64_t* n_out);
+/* HuffmanDecoder::decodeBlock (HuffmanCoders.cpp:324-616) plus InverseBWTransform::doTransform
+ * (InverseBWT.cpp:47-51) like bwtc_hip_decode_block_H, with the original block left in DEVICE memory at d_out (cap
+ * bytes; the record still comes from the host): the slices of one precompressor block are decoded side by side into
+ * one device buffer (Decompressor.cpp:71-80) and expanded there.  Same error codes. */
+int      bwtc_hip_decode_block_H_device(bwtc_hip_ctx* ctx, const uint8_t* rec, uint64_t rec_bytes, uint8_t* d_out,
+                                        uint64_t cap, uint32_t* size, uint64_t* consumed);
+/* What the last postprocess on this context did. */
+typedef struct bwtc_hip_postprocess_stats {
+  uint32_t route;             /* 1: the device made the bytes, 2: the host function (the limits above)          */
+  uint32_t launches;          /* kernels launched                                                                */
+  uint64_t tokens;            /* tokens of the block (single bytes and pairs)                                    */
+  uint64_t pair_tokens;       /* ... of which pairs that start with a special symbol                             */
+  uint64_t in_bytes;          /* n                                                                               */
+  uint64_t out_bytes;         /* the expansion's size                                                            */
+  uint64_t pool_bytes;        /* bytes of the expansion table's pool                                             */
+  uint64_t workspace_bytes;   /* device memory the postprocessor holds                                           */
+  float    ms_device;         /* device time of the passes (event pairs on the context's stream)                 */
+} bwtc_hip_postprocess_stats;
+int      bwtc_hip_postprocess_stats_get(bwtc_hip_ctx* ctx, bwtc_hip_postprocess_stats* out);
+/* Host twin of the device passes (no device work): the same run starts, per-tile counts, offsets and the write
+ * pass's search from the output's side, over tiles of `tile` bytes on the calling thread.  Same results as
+ * bwtc_hip_postprocess. */
+int      bwtc_hip_host_postprocess_tiles(const bwtc_hip_grammar* g, const uint8_t* data, uint64_t n, uint8_t* out,
+                                         uint64_t cap, uint64_t* n_out, uint32_t tile);
 
 #ifdef __cplusplus
 }

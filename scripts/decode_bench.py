@@ -10,7 +10,13 @@ For a 256 MiB C3 text block and a 256 MiB uniform-random block, both encoded by 
   decode_block_ms decode_block_H from the host record to the host bytes (the call synchronises)
   uncompress_s    `uncompress` end to end over a file of several blocks, on the default (GPU)
                   route and under BWTC_HIP_DECODE=host (serial HuffmanDecoder + GPU inverse)
-Best of --reps runs each.  Usage: scripts/decode_bench.py [--mib 256] [--reps 3] [--out FILE]"""
+Best of --reps runs each.  Usage: scripts/decode_bench.py [--mib 256] [--reps 3] [--out FILE]
+
+With --prepr ppppp the line is that of the device postprocessor instead (a C3 text block precompressed by the
+product): precompressed size, ms_device of the expansion, its algorithmic bytes (block read + expansion written +
+the per-tile words, each once) over that time as a fraction of bwtc_hip_copy_probe, the host function's seconds
+for the same block, and `uncompress` end to end over a four-block `-e H --prepr` file on the default route, under
+BWTC_HIP_POSTPROCESS=host and under BWTC_HIP_DECODE=host, in alternating runs."""
 import argparse
 import json
 import os
@@ -44,6 +50,63 @@ def _uncompress(comp, dst, route, reps):
         env["BWTC_HIP_DECODE"] = route
     exe = os.path.join(ROOT, "bwtc_amd", "host", "uncompress")
     return _best(lambda: subprocess.run([exe, comp, dst], check=True, env=env), reps)[0]
+
+
+def run_prepr(options, data, reps):
+    size = data.size
+    line = {"workload": "C3_text_prepr_" + options, "block_bytes": size}
+    with hip.Context(0, 32 << 20) as ctx:
+        g = hip.Grammar()
+        pre = ctx.precompress(g, options, data)
+        line.update(precompressed_bytes=int(pre.size), rules=g.rules, special_symbols=g.special_symbols)
+        d_in, d_out = ctx.dmalloc(pre.size + 16), ctx.dmalloc(size + 16)
+        ctx.to_device(d_in, pre)
+        stats = []
+        for _ in range(reps + 1):                            # first call: workspace
+            assert ctx.postprocess_device(g, d_in, pre.size, d_out, size) == size
+            stats.append(ctx.postprocess_stats())
+        assert ctx.to_host(d_out, size).tobytes() == data.tobytes()
+        ctx.dfree(d_in)
+        ctx.dfree(d_out)
+        st = min(stats[1:], key=lambda x: x["ms_device"])
+        assert st["route"] == 1
+        tiles = -(-pre.size // 4096)
+        alg = pre.size + size + 2 * 4 * tiles                # run starts and offsets: one word per tile each
+        probe = ctx.copy_probe(1 << 30, 5)
+        gbps = alg / (st["ms_device"] * 1e-3) / 1e9
+        t_host, back = _best(lambda: g.postprocess(pre, size), reps)
+        assert back.tobytes() == data.tobytes()
+        line.update(ms_device=round(st["ms_device"], 3), alg_bytes=int(alg), alg_GBps=round(gbps, 1), copy_probe_GBps=round(probe, 1),
+                    fraction_of_copy_probe=round(gbps / probe, 3), host_postprocess_s=round(t_host, 3),
+                    tokens=st["tokens"], pair_tokens=st["pair_tokens"], pool_bytes=st["pool_bytes"], launches=st["launches"],
+                    workspace_bytes=st["workspace_bytes"])
+    with tempfile.TemporaryDirectory() as tmp:
+        src, comp = os.path.join(tmp, "in"), os.path.join(tmp, "in.bwtc")
+        data.tofile(src)
+        mem = int(size / 4 / 0.74 / 1e6) + 1                 # four precompressor blocks of 0.74 MB per MB
+        subprocess.run([os.path.join(ROOT, "bwtc_amd", "host", "compress"), "-m", str(mem), "-e", "H", "--prepr", options, src, comp],
+                       check=True, stdout=subprocess.DEVNULL)
+        line["file_blocks"] = -(-size // int(0.74 * mem * 1e6))
+        exe = os.path.join(ROOT, "bwtc_amd", "host", "uncompress")
+        routes = {"default": {}, "postprocess_host": {"BWTC_HIP_POSTPROCESS": "host"}, "decode_host": {"BWTC_HIP_DECODE": "host"}}
+        times = {r: [] for r in routes}
+        for _ in range(reps):                                # alternating runs
+            for r, extra in routes.items():
+                env = {k: v for k, v in os.environ.items() if k not in ("BWTC_HIP_POSTPROCESS", "BWTC_HIP_DECODE")}
+                env.update(extra)
+                dst = os.path.join(tmp, "out_" + r)
+                t = time.perf_counter()
+                subprocess.run([exe, comp, dst], check=True, env=env)
+                times[r].append(round(time.perf_counter() - t, 3))
+                assert open(dst, "rb").read() == data.tobytes(), r
+                os.remove(dst)
+    for r in routes:
+        line["uncompress_%s_s" % r] = min(times[r])
+        line["uncompress_%s_runs_s" % r] = times[r]
+    spread = max(times["postprocess_host"]) - min(times["postprocess_host"])
+    gain = min(times["postprocess_host"]) - min(times["default"])
+    line.update(postprocess_host_spread_s=round(spread, 3), default_faster_by_s=round(gain, 3), default_faster_than_spread=bool(gain > spread))
+    return line
 
 
 def run(name, data, reps, file_blocks_mb):
@@ -91,11 +154,15 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--file-mem", type=int, default=400, help="compress -m for the multi-block file (0.185 MB blocks per MB)")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--prepr", default=None, help="pre-stage options (ppppp): the device postprocessor's line instead")
     a = ap.parse_args()
     size = a.mib << 20
     rng = np.random.default_rng(1)
     lines = []
-    for name, gen in (("C3_text", lambda: synth.gen_text(size, 3)),
+    if a.prepr:
+        lines.append(run_prepr(a.prepr, synth.gen_text(size, 3), a.reps))
+        print(json.dumps(lines[0]), flush=True)
+    for name, gen in () if a.prepr else (("C3_text", lambda: synth.gen_text(size, 3)),
                       ("uniform_random", lambda: rng.integers(0, 256, size, dtype=np.uint8))):
         line = run(name, gen(), a.reps, a.file_mem)
         print(json.dumps(line), flush=True)
