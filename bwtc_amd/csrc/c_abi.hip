@@ -3,6 +3,7 @@
 #include "gpu_lanes.hpp"
 #include "huffman_decoder.hpp"
 #include "postprocess.hpp"
+#include "wavelet_rebuild.hpp"
 #include "prepr_host.hpp"
 #include <new>
 #include "radix_sort.hpp"
@@ -25,6 +26,11 @@ struct bwtc_hip_ctx {
   BwtEngine eng;
   bwtc_hip::HDecoder* hdec = nullptr;   // 'H' decoder, made by the first decode call
   bwtc_hip::PostProcessor* post = nullptr;   // `--prepr` postprocessor, made by the first postprocess call
+  bwtc_hip::WRebuild* wreb = nullptr;        // wavelet rebuild, made by the first 'B' / 'b' / 'u' decode call
+};
+struct bwtc_hip_wavelet_decoder {
+  bwtc_hip::WDecoderState* state;
+  bwtc_hip::WrForest forest;                 // of the pure host route
 };
 struct bwtc_hip_grammar {
   bwtc::prepr::Grammar g;
@@ -98,6 +104,7 @@ void bwtc_hip_destroy(bwtc_hip_ctx* ctx) {
   if (!ctx) return;
   bwtc_hip::hdecoder_destroy(ctx->hdec);
   bwtc_hip::postprocessor_destroy(ctx->post);
+  bwtc_hip::wrebuild_destroy(ctx->wreb);
   ctx->eng.release();
   delete ctx;
 }
@@ -357,6 +364,131 @@ int bwtc_hip_decode_block_H_device(bwtc_hip_ctx* ctx, const uint8_t* rec, uint64
 int bwtc_hip_huffman_decode_stats_get(bwtc_hip_ctx* ctx, bwtc_hip_huffman_decode_stats* out) {
   if (!ctx || !out) return -1;
   return hdecoder_stats(ctx->hdec, out);
+}
+
+// ---- 'B' / 'b' / 'u' decoding: host range decoder + wavelet rebuild (wavelet_rebuild.hip) ----
+static WRebuild* wrebuild(bwtc_hip_ctx* ctx) {
+  if (!ctx->wreb) ctx->wreb = wrebuild_create();
+  return ctx->wreb;
+}
+
+bwtc_hip_wavelet_decoder* bwtc_hip_wavelet_decoder_create(char coder) {
+  WDecoderState* s = wdecoder_create(coder);
+  if (!s) return nullptr;
+  bwtc_hip_wavelet_decoder* d = new (std::nothrow) bwtc_hip_wavelet_decoder();
+  if (!d) { wdecoder_destroy(s); return nullptr; }
+  d->state = s;
+  return d;
+}
+void bwtc_hip_wavelet_decoder_destroy(bwtc_hip_wavelet_decoder* d) {
+  if (!d) return;
+  wdecoder_destroy(d->state);
+  d->forest.words.drop();
+  delete d;
+}
+void bwtc_hip_wavelet_decoder_reset(bwtc_hip_wavelet_decoder* d) { if (d) wdecoder_reset(d->state); }
+
+int bwtc_hip_decode_block_W(bwtc_hip_ctx* ctx, bwtc_hip_wavelet_decoder* dec, const uint8_t* rec, uint64_t rec_bytes, uint8_t* out,
+                            uint64_t cap, uint32_t* size, uint64_t* consumed) {
+  if (!ctx || !dec || !rec || (!out && cap) || !size || !consumed) return -1;
+  WRebuild* w = wrebuild(ctx);
+  if (!w) return -2;
+  return wavelet_decode_block(ctx->eng, *w, *dec->state, rec, rec_bytes, out, cap, size, consumed);
+}
+
+int bwtc_hip_decode_block_W_device(bwtc_hip_ctx* ctx, bwtc_hip_wavelet_decoder* dec, const uint8_t* rec, uint64_t rec_bytes,
+                                   uint8_t* d_out, uint64_t cap, uint32_t* size, uint64_t* consumed) {
+  if (!ctx || !dec || !rec || (!d_out && cap) || !size || !consumed) return -1;
+  WRebuild* w = wrebuild(ctx);
+  if (!w) return -2;
+  return wavelet_decode_block_device(ctx->eng, *w, *dec->state, rec, rec_bytes, d_out, cap, size, consumed);
+}
+
+int bwtc_hip_decode_block_W_begin(bwtc_hip_ctx* ctx, bwtc_hip_wavelet_decoder* dec, const uint8_t* rec, uint64_t rec_bytes, uint64_t cap,
+                                  uint32_t slot, uint32_t* size, uint64_t* consumed) {
+  if (!ctx || !dec || !rec || slot >= kWrSlots || !size || !consumed) return -1;
+  WRebuild* w = wrebuild(ctx);
+  if (!w) return -2;
+  return wavelet_decode_begin(ctx->eng, *w, *dec->state, rec, rec_bytes, cap, slot, size, consumed);
+}
+
+int bwtc_hip_decode_block_W_end(bwtc_hip_ctx* ctx, uint32_t slot, uint8_t* out, uint64_t cap, uint32_t* size) {
+  if (!ctx || !ctx->wreb || slot >= kWrSlots || (!out && cap) || !size) return -1;
+  return wavelet_decode_end(ctx->eng, *ctx->wreb, slot, out, cap, size);
+}
+
+int bwtc_hip_decode_block_W_end_device(bwtc_hip_ctx* ctx, uint32_t slot, uint8_t* d_out, uint64_t cap, uint32_t* size) {
+  if (!ctx || !ctx->wreb || slot >= kWrSlots || (!d_out && cap) || !size) return -1;
+  return wavelet_decode_end_device(ctx->eng, *ctx->wreb, slot, d_out, cap, size);
+}
+
+int bwtc_hip_wavelet_decode_bwt_host(bwtc_hip_wavelet_decoder* dec, const uint8_t* rec, uint64_t rec_bytes, uint8_t* bwt_out,
+                                     uint64_t cap, uint32_t* lf_out, uint32_t* n_lf, uint32_t* size, uint64_t* consumed) {
+  if (!dec || !rec || (!bwt_out && cap) || !lf_out || !n_lf || !size || !consumed) return -1;
+  int rc = wavelet_range_decode(*dec->state, rec, rec_bytes, cap, dec->forest, consumed);
+  if (rc) return rc;
+  uint64_t total = 0;
+  try { rc = host_wavelet_rebuild(dec->forest.view(), bwt_out, cap, &total, 8, nullptr); }
+  catch (const std::bad_alloc&) { rc = -2; }
+  if (rc) { wdecoder_undo(dec->state); return rc; }
+  for (uint32_t i = 0; i < dec->forest.n_lf; ++i) lf_out[i] = dec->forest.lf[i];
+  *n_lf = dec->forest.n_lf;
+  *size = (uint32_t)total;
+  return 0;
+}
+
+int bwtc_hip_wavelet_decode_counts(bwtc_hip_wavelet_decoder* dec, const uint8_t* rec, uint64_t rec_bytes, uint64_t cap,
+                                   uint64_t* counts, uint64_t* consumed) {
+  if (!dec || !rec || !counts || !consumed) return -1;
+  const int rc = wavelet_range_decode(*dec->state, rec, rec_bytes, cap, dec->forest, consumed);
+  if (rc) return rc;
+  counts[0] = dec->forest.sections.size(); counts[1] = dec->forest.runs; counts[2] = dec->forest.nodes.size();
+  counts[3] = dec->forest.n_words; counts[4] = dec->forest.bytes;
+  // bits the run walks take: the host twin counts them (it writes the block into a scratch buffer)
+  try {
+    std::vector<uint8_t> scratch(dec->forest.bytes + 1);
+    uint64_t total = 0;
+    return host_wavelet_rebuild(dec->forest.view(), scratch.data(), dec->forest.bytes, &total, 8, &counts[5]);
+  } catch (const std::bad_alloc&) { return -2; }
+}
+
+int bwtc_hip_wavelet_decoder_forest(bwtc_hip_wavelet_decoder* dec, bwtc_hip_wforest* out, uint32_t* lf_out, uint32_t* n_lf) {
+  if (!dec || !out) return -1;
+  *out = dec->forest.view();
+  if (lf_out && n_lf) {
+    for (uint32_t i = 0; i < dec->forest.n_lf; ++i) lf_out[i] = dec->forest.lf[i];
+    *n_lf = dec->forest.n_lf;
+  }
+  return 0;
+}
+
+int bwtc_hip_wavelet_rebuild_device(bwtc_hip_ctx* ctx, const bwtc_hip_wforest* forest, uint8_t* d_out, uint64_t cap, uint64_t* size) {
+  if (!ctx || !forest || (!d_out && cap) || !size) return -1;
+  WRebuild* w = wrebuild(ctx);
+  if (!w) return -2;
+  return wavelet_rebuild_device(ctx->eng, *w, *forest, d_out, cap, size, nullptr);
+}
+
+int bwtc_hip_wavelet_rebuild(bwtc_hip_ctx* ctx, const bwtc_hip_wforest* forest, uint8_t* out, uint64_t cap, uint64_t* size) {
+  if (!ctx || !forest || (!out && cap) || !size) return -1;
+  WRebuild* w = wrebuild(ctx);
+  if (!w) return -2;
+  uint8_t* d_bwt = nullptr;
+  const int rc = wavelet_rebuild_device(ctx->eng, *w, *forest, nullptr, cap, size, &d_bwt);
+  if (rc) return rc;
+  if (*size) BWTC_HIP_TRY(hipMemcpy(out, d_bwt, *size, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int bwtc_hip_host_wavelet_rebuild(const bwtc_hip_wforest* forest, uint8_t* out, uint64_t cap, uint64_t* size, uint32_t line_words,
+                                  uint64_t* bit_reads) {
+  if (!forest || (!out && cap) || !size || line_words == 0) return -1;
+  return host_wavelet_rebuild(*forest, out, cap, size, line_words, bit_reads);
+}
+
+int bwtc_hip_wavelet_decode_stats_get(bwtc_hip_ctx* ctx, bwtc_hip_wavelet_decode_stats* out) {
+  if (!ctx || !out) return -1;
+  return wrebuild_stats(ctx->wreb, out);
 }
 
 int bwtc_hip_huffman_encode_device(bwtc_hip_ctx* ctx, const uint8_t* d_bwt, uint32_t size,

@@ -34,6 +34,138 @@ class HuffmanDecodeStats(ctypes.Structure):
                 ("ms_entropy_wall", ctypes.c_float), ("ms_chain_host", ctypes.c_float), ("ms_inverse", ctypes.c_float)]
 
 
+# return codes of the wavelet rebuild (bwtc_hip.h BWTC_HIP_E_W_*)
+E_W_CHILD, E_W_BITS, E_W_ESCAPE, E_W_TOTAL, E_W_CAP, E_W_DEPTH, E_W_LIMIT, E_W_FOREST = -20, -21, -22, -23, -24, -25, -26, -27
+
+
+class WaveletDecodeStats(ctypes.Structure):
+    _fields_ = [("route", _u32), ("sections", _u32), ("routed_device", _u64), ("runs", _u64), ("nodes", _u64),
+                ("words", _u64), ("bit_reads", _u64), ("launches", _u64), ("workspace_bytes", _u64),
+                ("ms_range_decode", ctypes.c_float), ("ms_rebuild", ctypes.c_float), ("ms_inverse", ctypes.c_float)]
+
+
+class WForestSection(ctypes.Structure):
+    _fields_ = [(f, _u32) for f in ("runs", "bytes", "first_node", "symbol_nodes", "n_nodes", "first_code", "n_codes",
+                                     "W", "plain_fixed")]
+
+
+class WForestNode(ctypes.Structure):
+    _fields_ = [("left", ctypes.c_int32), ("right", ctypes.c_int32), ("has_symbol", _u32), ("symbol", _u32),
+                ("bits", _u32), ("first_word", _u32)]
+
+
+class WForestCode(ctypes.Structure):
+    _fields_ = [("left", ctypes.c_int32), ("right", ctypes.c_int32), ("has_symbol", _u32), ("symbol", _u32)]
+
+
+class WForest(ctypes.Structure):
+    _fields_ = [("sections", _vp), ("n_sections", _u32), ("nodes", _vp), ("n_nodes", _u32), ("codes", _vp),
+                ("n_codes", _u32), ("words", _vp), ("n_words", _u64)]
+
+
+SECTION_DTYPE = np.dtype([(f, np.uint32) for f, _ in WForestSection._fields_])
+NODE_DTYPE = np.dtype([("left", np.int32), ("right", np.int32), ("has_symbol", np.uint32), ("symbol", np.uint32),
+                       ("bits", np.uint32), ("first_word", np.uint32)])
+CODE_DTYPE = np.dtype([("left", np.int32), ("right", np.int32), ("has_symbol", np.uint32), ("symbol", np.uint32)])
+
+
+class Forest:
+    """A flattened forest (bwtc_hip_wforest) over four numpy arrays: sections (SECTION_DTYPE), nodes (NODE_DTYPE),
+    codes (CODE_DTYPE) and words (uint64)."""
+
+    def __init__(self, sections, nodes, codes, words):
+        self.sections = np.ascontiguousarray(sections, SECTION_DTYPE)
+        self.nodes = np.ascontiguousarray(nodes, NODE_DTYPE)
+        self.codes = np.ascontiguousarray(codes, CODE_DTYPE)
+        self.words = np.ascontiguousarray(words, np.uint64)
+        self.c = WForest(_ptr(self.sections), self.sections.size, _ptr(self.nodes), self.nodes.size,
+                         _ptr(self.codes), self.codes.size, _ptr(self.words), self.words.size)
+
+    @property
+    def total(self):
+        return int(self.sections["bytes"].astype(np.uint64).sum())
+
+
+def host_wavelet_rebuild(forest, cap=None, line_words=7):
+    """Host twin of the rebuild kernels (no device): forest -> (BWT bytes, bits taken out of nodes)."""
+    cap = forest.total if cap is None else cap
+    out = np.full(cap + 64, 0xA5, np.uint8)
+    size, reads = _u64(0), _u64(0)
+    _check(load().bwtc_hip_host_wavelet_rebuild(ctypes.byref(forest.c), _ptr(out), cap, ctypes.byref(size), line_words,
+                                                ctypes.byref(reads)), "bwtc_hip_host_wavelet_rebuild")
+    if not (out[cap:] == 0xA5).all():
+        raise BwtcHipError("bytes past the capacity were modified")
+    return out[:size.value].copy(), int(reads.value)
+
+
+class WaveletDecoder:
+    """The range decoder's state of one 'B' / 'b' / 'u' stream (bwtc_hip_wavelet_decoder): decode a stream's
+    records in order through one of these."""
+
+    def __init__(self, coder="B"):
+        self.lib = load()
+        self.h = self.lib.bwtc_hip_wavelet_decoder_create(coder.encode())
+        if not self.h:
+            raise BwtcHipError("bwtc_hip_wavelet_decoder_create('%s') failed" % coder)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self.lib.bwtc_hip_wavelet_decoder_destroy(self.h)
+            self.h = None
+
+    def reset(self):
+        self.lib.bwtc_hip_wavelet_decoder_reset(self.h)
+
+    def decode_bwt_host(self, record, cap):
+        """Pure host route: record -> (BWT bytes, LF powers, bytes consumed)."""
+        record = np.ascontiguousarray(record, np.uint8)
+        bwt = np.empty(max(cap, 1), np.uint8)
+        lf = np.zeros(256, np.uint32)
+        n_lf, size, used = _u32(0), _u32(0), _u64(0)
+        _check(self.lib.bwtc_hip_wavelet_decode_bwt_host(self.h, _ptr(record), record.size, _ptr(bwt), cap, _ptr(lf),
+                                                         ctypes.byref(n_lf), ctypes.byref(size), ctypes.byref(used)),
+               "bwtc_hip_wavelet_decode_bwt_host")
+        return bwt[:size.value].copy(), lf[:n_lf.value].copy(), int(used.value)
+
+    def counts(self, record, cap):
+        """Range-decodes the record and returns its forest's counts: dict(sections, runs, nodes, words, bytes,
+        bit_reads), and the bytes consumed.  Moves the models on like any decode."""
+        record = np.ascontiguousarray(record, np.uint8)
+        c = np.zeros(6, np.uint64)
+        used = _u64(0)
+        _check(self.lib.bwtc_hip_wavelet_decode_counts(self.h, _ptr(record), record.size, cap, _ptr(c), ctypes.byref(used)),
+               "bwtc_hip_wavelet_decode_counts")
+        return dict(zip(("sections", "runs", "nodes", "words", "bytes", "bit_reads"), (int(v) for v in c))), int(used.value)
+
+
+    def forest(self):
+        """The forest of the last record decode_bwt_host / counts decoded, as the rebuild entry points take it, and
+        its LF powers.  A view into the handle: use it before the handle's next call."""
+        view = ForestView()
+        lf = np.zeros(256, np.uint32)
+        n_lf = _u32(0)
+        _check(self.lib.bwtc_hip_wavelet_decoder_forest(self.h, ctypes.byref(view.c), _ptr(lf), ctypes.byref(n_lf)),
+               "bwtc_hip_wavelet_decoder_forest")
+        view.owner = self
+        return view, lf[:n_lf.value].copy()
+
+
+class ForestView:
+    """A bwtc_hip_wforest that points into a WaveletDecoder handle (WaveletDecoder.forest)."""
+
+    def __init__(self):
+        self.c = WForest()
+        self.owner = None
+
+    @property
+    def total(self):
+        n = self.c.n_sections
+        if n == 0:
+            return 0
+        secs = np.ctypeslib.as_array(ctypes.cast(self.c.sections, ctypes.POINTER(_u32)), (n, len(WForestSection._fields_)))
+        return int(secs[:, 1].astype(np.uint64).sum())
+
+
 class PostprocessStats(ctypes.Structure):
     _fields_ = [("route", _u32), ("launches", _u32), ("tokens", _u64), ("pair_tokens", _u64), ("in_bytes", _u64),
                 ("out_bytes", _u64), ("pool_bytes", _u64), ("workspace_bytes", _u64), ("ms_device", ctypes.c_float)]
@@ -58,7 +190,8 @@ class KernelTimers(ctypes.Structure):
     _fields_ = [("scatter_launches", _u64), ("scatter_bytes", _u64), ("scatter_ms", ctypes.c_double)]
 
 
-# the C ABI's lowercase names (bwtc_hip_decode_block_H is exported too; tests/test_huffman_decode_abi.py checks it)
+# the C ABI's lowercase names (bwtc_hip_decode_block_H and bwtc_hip_decode_block_W[_device|_begin|_end|_end_device] are exported too;
+# tests/test_huffman_decode_abi.py and tests/test_wavelet_rebuild_host.py check them)
 EXPORTS = [
     "bwtc_hip_huffman_decode", "bwtc_hip_huffman_decode_device", "bwtc_hip_huffman_decode_stats_get",
     "bwtc_hip_device_count", "bwtc_hip_version", "bwtc_hip_workspace_bytes", "bwtc_hip_create",
@@ -80,6 +213,10 @@ EXPORTS = [
     "bwtc_hip_precompress", "bwtc_hip_host_precompress", "bwtc_hip_postprocess",
     "bwtc_hip_postprocess_device", "bwtc_hip_postprocess_block", "bwtc_hip_postprocess_stats_get",
     "bwtc_hip_host_postprocess_tiles",
+    "bwtc_hip_wavelet_decoder_create", "bwtc_hip_wavelet_decoder_destroy", "bwtc_hip_wavelet_decoder_reset",
+    "bwtc_hip_wavelet_decode_bwt_host",
+    "bwtc_hip_wavelet_decode_counts", "bwtc_hip_wavelet_decoder_forest", "bwtc_hip_wavelet_rebuild", "bwtc_hip_wavelet_rebuild_device",
+    "bwtc_hip_host_wavelet_rebuild", "bwtc_hip_wavelet_decode_stats_get",
 ]
 
 _lib = None
@@ -190,6 +327,25 @@ def load():
     L.bwtc_hip_postprocess_stats_get.argtypes = [_vp, ctypes.POINTER(PostprocessStats)]
     L.bwtc_hip_host_postprocess_tiles.argtypes = [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64), _u32]
     L.bwtc_hip_decode_block_H_device.argtypes = [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u32), ctypes.POINTER(_u64)]
+    L.bwtc_hip_wavelet_decoder_create.restype = _vp
+    L.bwtc_hip_wavelet_decoder_create.argtypes = [ctypes.c_char]
+    L.bwtc_hip_wavelet_decoder_destroy.restype = None
+    L.bwtc_hip_wavelet_decoder_destroy.argtypes = [_vp]
+    L.bwtc_hip_wavelet_decoder_reset.restype = None
+    L.bwtc_hip_wavelet_decoder_reset.argtypes = [_vp]
+    L.bwtc_hip_decode_block_W.argtypes = [_vp, _vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u32), ctypes.POINTER(_u64)]
+    L.bwtc_hip_decode_block_W_device.argtypes = L.bwtc_hip_decode_block_W.argtypes
+    L.bwtc_hip_decode_block_W_begin.argtypes = [_vp, _vp, _vp, _u64, _u64, _u32, ctypes.POINTER(_u32), ctypes.POINTER(_u64)]
+    L.bwtc_hip_decode_block_W_end.argtypes = [_vp, _u32, _vp, _u64, ctypes.POINTER(_u32)]
+    L.bwtc_hip_decode_block_W_end_device.argtypes = L.bwtc_hip_decode_block_W_end.argtypes
+    L.bwtc_hip_wavelet_decode_bwt_host.argtypes = [_vp, _vp, _u64, _vp, _u64, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
+                                                   ctypes.POINTER(_u64)]
+    L.bwtc_hip_wavelet_decode_counts.argtypes = [_vp, _vp, _u64, _u64, _vp, ctypes.POINTER(_u64)]
+    L.bwtc_hip_wavelet_decoder_forest.argtypes = [_vp, ctypes.POINTER(WForest), _vp, ctypes.POINTER(_u32)]
+    L.bwtc_hip_wavelet_rebuild.argtypes = [_vp, ctypes.POINTER(WForest), _vp, _u64, ctypes.POINTER(_u64)]
+    L.bwtc_hip_wavelet_rebuild_device.argtypes = L.bwtc_hip_wavelet_rebuild.argtypes
+    L.bwtc_hip_host_wavelet_rebuild.argtypes = [ctypes.POINTER(WForest), _vp, _u64, ctypes.POINTER(_u64), _u32, ctypes.POINTER(_u64)]
+    L.bwtc_hip_wavelet_decode_stats_get.argtypes = [_vp, ctypes.POINTER(WaveletDecodeStats)]
     L.bwtc_hip_host_huffman_lengths.restype = None
     L.bwtc_hip_host_huffman_lengths.argtypes = [_vp, _vp]
     L.bwtc_hip_host_huffman_codes.restype = None
@@ -718,6 +874,73 @@ class Context:
         _check(self.lib.bwtc_hip_huffman_decode_stats_get(self.handle, ctypes.byref(s)),
                "bwtc_hip_huffman_decode_stats_get")
         return {f: getattr(s, f) for f, _ in HuffmanDecodeStats._fields_}
+
+    def decode_block_W(self, decoder, record, cap=None, with_consumed=False):
+        """Range decode (host) + wavelet rebuild + inverse BWT (device) of one 'B' / 'b' / 'u' record: returns the
+        original block (and the bytes consumed when with_consumed).  decoder: the stream's WaveletDecoder."""
+        record = np.ascontiguousarray(record, dtype=np.uint8)
+        cap = self.max_block_size if cap is None else cap
+        out = np.empty(max(cap, 1), np.uint8)
+        size, used = _u32(0), _u64(0)
+        _check(self.lib.bwtc_hip_decode_block_W(self.handle, decoder.h, _ptr(record), record.size, _ptr(out), cap,
+                                                ctypes.byref(size), ctypes.byref(used)),
+               "bwtc_hip_decode_block_W")
+        data = out[:size.value].copy()
+        return (data, int(used.value)) if with_consumed else data
+
+    def decode_block_W_device(self, decoder, record, d_out_ptr, cap):
+        """decode_block_W with the original block left in device memory at d_out_ptr: returns (size, consumed)."""
+        record = np.ascontiguousarray(record, dtype=np.uint8)
+        size, used = _u32(0), _u64(0)
+        _check(self.lib.bwtc_hip_decode_block_W_device(self.handle, decoder.h, _ptr(record), record.size, _vp(d_out_ptr), cap,
+                                                       ctypes.byref(size), ctypes.byref(used)),
+               "bwtc_hip_decode_block_W_device")
+        return int(size.value), int(used.value)
+
+    def decode_block_W_begin(self, decoder, record, cap, slot):
+        """The host half of decode_block_W into forest slot `slot` (0 / 1): returns (block bytes, consumed)."""
+        record = np.ascontiguousarray(record, dtype=np.uint8)
+        size, used = _u32(0), _u64(0)
+        _check(self.lib.bwtc_hip_decode_block_W_begin(self.handle, decoder.h, _ptr(record), record.size, cap, slot,
+                                                      ctypes.byref(size), ctypes.byref(used)),
+               "bwtc_hip_decode_block_W_begin")
+        return int(size.value), int(used.value)
+
+    def decode_block_W_end(self, slot, cap):
+        """The device half of slot `slot`: the original block."""
+        out = np.empty(max(cap, 1), np.uint8)
+        size = _u32(0)
+        _check(self.lib.bwtc_hip_decode_block_W_end(self.handle, slot, _ptr(out), cap, ctypes.byref(size)),
+               "bwtc_hip_decode_block_W_end")
+        return out[:size.value].copy()
+
+    def decode_block_W_end_device(self, slot, d_out_ptr, cap):
+        size = _u32(0)
+        _check(self.lib.bwtc_hip_decode_block_W_end_device(self.handle, slot, _vp(d_out_ptr), cap, ctypes.byref(size)),
+               "bwtc_hip_decode_block_W_end_device")
+        return int(size.value)
+
+    def wavelet_rebuild(self, forest, cap=None):
+        """Flattened forest (Forest) -> BWT bytes through the device kernels, host to host."""
+        cap = forest.total if cap is None else cap
+        out = np.full(cap + 64, 0xA5, np.uint8)
+        size = _u64(0)
+        _check(self.lib.bwtc_hip_wavelet_rebuild(self.handle, ctypes.byref(forest.c), _ptr(out), cap, ctypes.byref(size)),
+               "bwtc_hip_wavelet_rebuild")
+        return out[:size.value].copy()
+
+    def wavelet_rebuild_device(self, forest, d_out_ptr, cap):
+        """Same with the bytes left in device memory at d_out_ptr (any alignment): returns their number."""
+        size = _u64(0)
+        _check(self.lib.bwtc_hip_wavelet_rebuild_device(self.handle, ctypes.byref(forest.c), _vp(d_out_ptr), cap, ctypes.byref(size)),
+               "bwtc_hip_wavelet_rebuild_device")
+        return int(size.value)
+
+    def wavelet_decode_stats(self):
+        s = WaveletDecodeStats()
+        _check(self.lib.bwtc_hip_wavelet_decode_stats_get(self.handle, ctypes.byref(s)),
+               "bwtc_hip_wavelet_decode_stats_get")
+        return {f: getattr(s, f) for f, _ in WaveletDecodeStats._fields_}
 
     def suffix_array(self, T):
         T = np.ascontiguousarray(T, dtype=np.uint8)

@@ -9,8 +9,14 @@
 // is serial host code for the same reason plus the adaptive models.  Coders 'H', 'B', 'b', 'u'
 // and streams without precompression are accepted.
 #pragma once
+#include <chrono>
+#include <condition_variable>
 #include <cstring>
 #include <deque>
+#include <mutex>
+#include <functional>
+#include <memory>
+#include <thread>
 
 #include "bwtc_hip.hpp"
 
@@ -281,7 +287,9 @@ inline uint64 readPackedIntegerRev(MemoryBitReader& in) {           // utils::re
 
 class WaveletDecoder : public EntropyDecoder {
  public:
-  explicit WaveletDecoder(char decoder = 'B') : m_models(decoder) {}
+  explicit WaveletDecoder(char decoder = 'B') : msDecodeTree(0), msMessage(0), m_models(decoder) {}
+  // the two jobs of this decoder, summed over sections (two clock reads per section)
+  double msDecodeTree, msMessage;
   void decodeBlock(BWTBlock& block, MemoryBitReader& in, size_t capacity) {
     const uint64 compressed = in.readBits(48);                       // readBlockHeader, WaveletCoders.cpp:232-244
     const size_t start = in.position();
@@ -303,8 +311,12 @@ class WaveletDecoder : public EntropyDecoder {
       tree.readShape(in);
       in.flushBuffer();
       m_rc.start(&in);
+      const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
       tree.decodeTreeBF(rootSize, m_rc, m_models);
+      const std::chrono::steady_clock::time_point t1 = std::chrono::steady_clock::now();
       const size_t got = tree.message(dst, lengths[s]);
+      msDecodeTree += std::chrono::duration<double, std::milli>(t1 - t0).count();
+      msMessage += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
       if (got != lengths[s]) MemoryBitReader::fail("section length");
       dst += got;
       m_models.resetMain(); m_models.resetInts(); m_models.resetGaps();   // endContextBlock, :70-76
@@ -569,6 +581,86 @@ inline uint64 hRecordBlockSize(const byte* p, size_t n) {
   return total;
 }
 
+// which route the 'B' / 'b' / 'u' blocks of a stream took and what their phases cost (uncompress prints it under
+// BWTC_HIP_DEBUG=1)
+// A thread beside the caller's that runs jobs in the order given: block k's device half, download and write run here
+// while the caller range-decodes block k+1.  A job's error is kept (later jobs are then skipped) for the caller,
+// which ends the program from its own thread (check(), after a wait).
+class DecodeWorker {
+ public:
+  typedef std::function<void(DecodeWorker&)> Job;
+  DecodeWorker() : m_submitted(0), m_done(0), m_stop(false), m_rc(0), m_what(0), m_busyMs(0) {}
+  // time the jobs took so far, summed (after drain())
+  double busyMs() { std::lock_guard<std::mutex> l(m_mu); return m_busyMs; }
+  ~DecodeWorker() {
+    { std::lock_guard<std::mutex> l(m_mu); m_stop = true; }
+    m_cv.notify_all();
+    if (m_thread.joinable()) m_thread.join();
+  }
+  uint64 submit(const Job& job) {                                    // returns the job's ticket
+    std::lock_guard<std::mutex> l(m_mu);
+    m_queue.push_back(job);
+    if (!m_thread.joinable()) m_thread = std::thread([this]() { loop(); });
+    m_cv.notify_all();
+    return ++m_submitted;
+  }
+  void wait(uint64 ticket) { std::unique_lock<std::mutex> l(m_mu); m_cv.wait(l, [&]() { return m_done >= ticket; }); }
+  void drain() { std::unique_lock<std::mutex> l(m_mu); m_cv.wait(l, [&]() { return m_done >= m_submitted; }); }
+  void note(int rc, const char* what) { std::lock_guard<std::mutex> l(m_mu); if (rc && !m_rc) { m_rc = rc; m_what = what; } }
+  void check() {
+    int rc; const char* what;
+    { std::lock_guard<std::mutex> l(m_mu); rc = m_rc; what = m_what; }
+    if (!rc) return;
+    std::fprintf(stderr, "bwtc-hip: %s returned %d\n", what, rc);
+    MemoryBitReader::fail("wavelet record");
+  }
+ private:
+  void loop() {
+    std::unique_lock<std::mutex> l(m_mu);
+    for (;;) {
+      m_cv.wait(l, [&]() { return m_stop || !m_queue.empty(); });
+      if (m_queue.empty()) return;
+      Job job = m_queue.front();
+      m_queue.pop_front();
+      const bool skip = m_rc != 0;
+      l.unlock();
+      const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+      if (!skip) job(*this);
+      const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+      l.lock();
+      m_busyMs += ms;
+      ++m_done;
+      m_cv.notify_all();
+    }
+  }
+  std::thread m_thread;
+  std::mutex m_mu;
+  std::condition_variable m_cv;
+  std::deque<Job> m_queue;
+  uint64 m_submitted, m_done;
+  bool m_stop;
+  int m_rc;
+  const char* m_what;
+  double m_busyMs;
+};
+
+struct WaveletDecodeTally {
+  uint64 device, host;
+  double msRangeDecode, msRebuild, msInverse;
+  // the serial WaveletDecoder route's phases (BWTC_HIP_DECODE=host): its two jobs, the inverse with its upload and
+  // download, and the writes
+  double msHostDecodeTree, msHostMessage, msHostTransform, msHostWrite;
+  double msWorker;          // device route: what the worker thread's jobs took (device halves, downloads, writes)
+  WaveletDecodeTally() : device(0), host(0), msRangeDecode(0), msRebuild(0), msInverse(0), msHostDecodeTree(0), msHostMessage(0),
+                         msHostTransform(0), msHostWrite(0), msWorker(0) {}
+  void noteDevice(bwtc_hip_ctx* ctx) {
+    bwtc_hip_wavelet_decode_stats st;
+    if (bwtc_hip_wavelet_decode_stats_get(ctx, &st) == 0 && st.route == 1) {
+      ++device; msRangeDecode += st.ms_range_decode; msRebuild += st.ms_rebuild; msInverse += st.ms_inverse;
+    }
+  }
+};
+
 class Decompressor {
  public:
   Decompressor(InStream* in, OutStream* out, int device = 0)
@@ -590,7 +682,17 @@ class Decompressor {
     // 'H' blocks are entropy decoded and inverted on the GPU (bwtc_hip_decode_block_H) unless
     // BWTC_HIP_DECODE=host asks for the serial HuffmanDecoder + GPU inverse; same bytes either way
     const char* route = std::getenv("BWTC_HIP_DECODE");
-    const bool deviceH = coder == 'H' && !(route && std::strcmp(route, "host") == 0);
+    const bool hostRoute = route && std::strcmp(route, "host") == 0;
+    const bool deviceH = coder == 'H' && !hostRoute;
+    // 'B' / 'b' / 'u' blocks: the range decoder stays on this thread (bwtc_hip_decode_block_W_begin), the wavelet rebuild,
+    // the inverse, the download and the write run behind it on a worker thread (bwtc_hip_decode_block_W_end); BWTC_HIP_DECODE=host keeps the serial WaveletDecoder + upload + GPU inverse.  One
+    // handle decodes every block of the stream, whichever side rebuilds it: the main model's state crosses blocks.
+    const bool wavelet = coder == 'B' || coder == 'b' || coder == 'u';
+    const bool deviceW = wavelet && !hostRoute;
+    bwtc_hip_wavelet_decoder* wdec = deviceW ? bwtc_hip_wavelet_decoder_create(coder) : 0;
+    if (deviceW && !wdec) hipFatal(-2, "bwtc_hip_wavelet_decoder_create");
+    std::vector<byte> wtmp;
+    std::vector<uint32> wlf(256);
     bwtc_hip_ctx* hctx = 0;
     uint32 hctxCap = 0;
     size_t decompressedSize = 0;
@@ -599,18 +701,30 @@ class Decompressor {
     // by side into dPre, expanded into dPost and downloaded once
     uint8_t *dPre = 0, *dPost = 0;
     uint64 dPreCap = 0, dPostCap = 0;
+    // 'B' / 'b' / 'u' on the device route, one block deep: the jobs (a slice's device half; a block's expansion,
+    // download and write) run on `worker` in the order given while this thread range-decodes what comes next into the
+    // context's other forest slot, once the job that read that slot is done (slotJob).  Everything else this loop does
+    // to hctx, the buffers, the tallies or m_out waits for the worker first (drain).
+    DecodeWorker worker;
+    uint32 slot = 0;
+    uint64 slotJob[2] = {0, 0};
+    auto drain = [&]() { worker.drain(); worker.check(); };
+    auto freeSlot = [&]() { worker.wait(slotJob[slot]); worker.check(); };
+    typedef std::chrono::steady_clock Clock;
+    auto since = [](Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); };
     for (;;) {
       const uint64 originalSize = in.readPackedInteger();           // PrecompressorBlock.cpp:97-108
       if (originalSize == 0) break;
       const uint64 slices = in.readPackedInteger();
       // PrecompressorBlock::readBlockHeader reads the block's grammar here (PrecompressorBlock.cpp:97-108); a
       // grammar with rules means the slices hold the PRECOMPRESSED block, which the Postprocessor expands
-      Grammar grammar;
+      std::shared_ptr<Grammar> grammarOwner(new Grammar());            // a job may outlive this turn of the loop
+      Grammar& grammar = *grammarOwner;
       in.flushBuffer();
       in.advance(grammar.readGrammar(in.here(), in.left()));
       const bool rules = grammar.numberOfRules() > 0;
       const size_t room = rules ? 2 * (size_t)originalSize + 64 : (size_t)originalSize;
-      if (rules && deviceH && !postprocessOnHostOnly() && originalSize < ((uint64)1 << 32)) {
+      if (rules && (deviceH || deviceW) && !postprocessOnHostOnly() && originalSize < ((uint64)1 << 32)) {
         // what the slices hold, and the largest of them (the context is sized by it, as below)
         uint64 precompressed = 0, largest = 0;
         { const byte* p = in.here(); size_t left = in.left();
@@ -624,6 +738,7 @@ class Decompressor {
           } }
         if (precompressed >= kPostprocessDeviceMin && precompressed <= room) {
           largest = std::min<uint64>(largest, room);
+          if (!hctx || largest > hctxCap || room > dPreCap || originalSize + 16 > dPostCap || buf.size() < (size_t)originalSize + 1) drain();
           if (!hctx || largest > hctxCap) {
             if (hctx) bwtc_hip_destroy(hctx);
             hctxCap = (uint32)std::min<uint64>(std::max<uint64>(largest, 1u << 20), 0x7FFFFFF0u);
@@ -645,10 +760,55 @@ class Decompressor {
           for (uint64 i = 0; i < slices; ++i) {
             uint32_t size = 0;
             uint64_t consumed = 0;
+            if (deviceW) {
+              freeSlot();
+              int rc = bwtc_hip_decode_block_W_begin(hctx, wdec, in.here(), in.left(), room - used, slot, &size, &consumed);
+              if (rc == 0) {
+                uint8_t* const at = dPre + used;
+                const uint64 left = room - used;
+                const uint32 sl = slot;
+                slotJob[sl] = worker.submit([this, hctx, at, left, sl](DecodeWorker& w) {
+                  uint32_t n = 0;
+                  const int erc = bwtc_hip_decode_block_W_end_device(hctx, sl, at, left, &n);
+                  w.note(erc, "bwtc_hip_decode_block_W_end_device");
+                  if (erc == 0) m_wavelet.noteDevice(hctx);
+                });
+                slot ^= 1u;
+              } else if (rc == BWTC_HIP_E_W_LIMIT) {                // beyond the rebuild's limits: rebuilt here, inverted there
+                drain();
+                uint32_t nLF = 0;
+                wtmp.resize(std::max(wtmp.size(), room - used + 1));
+                rc = bwtc_hip_wavelet_decode_bwt_host(wdec, in.here(), in.left(), &wtmp[0], room - used, &wlf[0], &nLF, &size, &consumed);
+                if (rc == 0) rc = bwtc_hip_memcpy_to_device(hctx, dPre + used, &wtmp[0], size);
+                if (rc == 0 && size) rc = bwtc_hip_inverse_bwt_block_device(hctx, dPre + used, dPre + used, size, &wlf[0], nLF);
+                if (rc == 0) ++m_wavelet.host;
+              }
+              if (rc) { std::fprintf(stderr, "bwtc-hip: bwtc_hip_decode_block_W_begin returned %d\n", rc); MemoryBitReader::fail("wavelet record"); }
+              in.advance(consumed);
+              used += size;
+              continue;
+            }
             const int rc = bwtc_hip_decode_block_H_device(hctx, in.here(), in.left(), dPre + used, room - used, &size, &consumed);
             if (rc) { std::fprintf(stderr, "bwtc-hip: bwtc_hip_decode_block_H_device returned %d\n", rc); MemoryBitReader::fail("'H' record"); }
             in.advance(consumed);
             used += size;
+          }
+          if (deviceW) {                                             // expansion, the one download and the write: behind the slices
+            buf.resize(std::max(buf.size(), (size_t)originalSize + 1));
+            byte* const host = &buf[0];
+            worker.submit([this, hctx, grammarOwner, dPre, dPost, used, originalSize, host](DecodeWorker& w) {
+              uint64_t n = 0;
+              int erc = bwtc_hip_postprocess_device(hctx, grammarOwner->handle(), dPre, used, dPost, originalSize, &n);
+              w.note(erc, "bwtc_hip_postprocess_device");
+              if (erc) return;
+              m_postprocess.noteDevice(hctx);
+              if (n != originalSize) { w.note(-1, "postprocessed block size"); return; }
+              erc = bwtc_hip_memcpy_to_host(hctx, host, dPost, n);
+              w.note(erc, "bwtc_hip_memcpy_to_host");
+              if (erc == 0) m_out->writeBlock(host, host + n);
+            });
+            decompressedSize += originalSize;
+            continue;
           }
           uint64_t postSize = 0;
           hipFatal(bwtc_hip_postprocess_device(hctx, grammar.handle(), dPre, used, dPost, originalSize, &postSize), "bwtc_hip_postprocess_device");
@@ -661,7 +821,7 @@ class Decompressor {
           continue;
         }
       }
-      buf.resize(std::max(buf.size(), room + 1));
+      if (buf.size() < room + 1) { drain(); buf.resize(room + 1); }
       size_t used = 0;
       for (uint64 i = 0; deviceH && i < slices; ++i) {
         const uint64 blockSize = std::min<uint64>(hRecordBlockSize(in.here(), in.left()), room - used);
@@ -677,18 +837,69 @@ class Decompressor {
         in.advance(consumed);
         used += size;
       }
-      for (uint64 i = 0; !deviceH && i < slices; ++i) {
+      for (uint64 i = 0; deviceW && i < slices; ++i) {
+        const uint64 blockSize = std::min<uint64>(hRecordBlockSize(in.here(), in.left()), room - used);
+        uint32_t size = 0;
+        uint64_t consumed = 0;
+        int rc = BWTC_HIP_E_W_LIMIT;
+        if (blockSize >= kPostprocessDeviceMin && blockSize < ((uint64)1 << 31)) {
+          if (!hctx || blockSize > hctxCap) {
+            drain();
+            if (hctx) bwtc_hip_destroy(hctx);
+            hctxCap = (uint32)std::min<uint64>(std::max<uint64>(blockSize, 1u << 20), 0x7FFFFFF0u);
+            hipFatal(bwtc_hip_create(m_device, hctxCap, &hctx), "bwtc_hip_create");
+          }
+          freeSlot();
+          rc = bwtc_hip_decode_block_W_begin(hctx, wdec, in.here(), in.left(), room - used, slot, &size, &consumed);
+          if (rc == 0) {
+            byte* const at = &buf[used];
+            const uint64 left = room - used;
+            const uint32 sl = slot;
+            slotJob[sl] = worker.submit([this, hctx, at, left, sl](DecodeWorker& w) {
+              uint32_t n = 0;
+              const int erc = bwtc_hip_decode_block_W_end(hctx, sl, at, left, &n);
+              w.note(erc, "bwtc_hip_decode_block_W_end");
+              if (erc == 0) m_wavelet.noteDevice(hctx);
+            });
+            slot ^= 1u;
+          }
+        }
+        if (rc == BWTC_HIP_E_W_LIMIT) drain();
+        if (rc == BWTC_HIP_E_W_LIMIT) {                             // below the floor or beyond the limits: the host rebuilds
+          uint32_t nLF = 0;
+          rc = bwtc_hip_wavelet_decode_bwt_host(wdec, in.here(), in.left(), &buf[used], room - used, &wlf[0], &nLF, &size, &consumed);
+          if (rc == 0 && size) {
+            BWTBlock block(&buf[used], size, true);
+            block.LFpowers().assign(wlf.begin(), wlf.begin() + nLF);
+            if (!ibwt || size > ibwtCap) {
+              delete ibwt;
+              ibwtCap = (uint32)std::max<size_t>(size, 1u << 20);
+              ibwt = giveInverseTransformer(ibwtCap, m_device);
+            }
+            ibwt->doTransform(block);
+          }
+          if (rc == 0) ++m_wavelet.host;
+        }
+        if (rc) { std::fprintf(stderr, "bwtc-hip: bwtc_hip_decode_block_W_begin returned %d\n", rc); MemoryBitReader::fail("wavelet record"); }
+        in.advance(consumed);
+        used += size;
+      }
+      for (uint64 i = 0; !deviceH && !deviceW && i < slices; ++i) {
         BWTBlock block(&buf[used], 0, true);
         m_decoder->decodeBlock(block, in, room - used);
+        if (wavelet) ++m_wavelet.host;
+        const Clock::time_point tT = Clock::now();
         if (!ibwt || block.size() > ibwtCap) {
           delete ibwt;
           ibwtCap = (uint32)std::max<size_t>(block.size(), 1u << 20);
           ibwt = giveInverseTransformer(ibwtCap, m_device);
         }
         ibwt->doTransform(block);
+        if (wavelet) m_wavelet.msHostTransform += since(tT);
         used += block.size();
       }
       if (rules) {
+        drain();
         Postprocessor postprocessor(false, grammar);               // Decompressor.cpp:82-88
         const size_t postSize = postprocessor.uncompress(&buf[0], used, m_out, (size_t)originalSize, ibwt ? ibwt->hipContext() : 0,
                                                          &m_postprocess);
@@ -697,17 +908,33 @@ class Decompressor {
         continue;
       }
       if (used != originalSize) MemoryBitReader::fail("precompressor block size");
-      m_out->writeBlock(&buf[0], &buf[0] + used);
+      if (deviceW) {                                                 // the write goes behind the block's device half
+        byte* const host = &buf[0];
+        OutStream* const os = m_out;
+        worker.submit([os, host, used](DecodeWorker&) { os->writeBlock(host, host + used); });
+      } else {
+        const Clock::time_point tW = Clock::now();
+        m_out->writeBlock(&buf[0], &buf[0] + used);
+        if (wavelet) m_wavelet.msHostWrite += since(tW);
+      }
       decompressedSize += used;
     }
+    drain();
+    m_wavelet.msWorker = worker.busyMs();
+    if (WaveletDecoder* wd = dynamic_cast<WaveletDecoder*>(m_decoder)) {
+      m_wavelet.msHostDecodeTree = wd->msDecodeTree; m_wavelet.msHostMessage = wd->msMessage;
+    }
     delete ibwt;
+    bwtc_hip_wavelet_decoder_destroy(wdec);
     if (hctx) { if (dPre) bwtc_hip_free(hctx, dPre); if (dPost) bwtc_hip_free(hctx, dPost); bwtc_hip_destroy(hctx); }
     m_out->flush();
     return decompressedSize;
   }
   const PostprocessTally& postprocessTally() const { return m_postprocess; }
+  const WaveletDecodeTally& waveletTally() const { return m_wavelet; }
  private:
   PostprocessTally m_postprocess;
+  WaveletDecodeTally m_wavelet;
   InStream* m_in;
   OutStream* m_out;
   EntropyDecoder* m_decoder;

@@ -41,6 +41,16 @@ int main(int argc, char** argv) {
   if (debug && std::strcmp(debug, "1") == 0)
     std::fprintf(stderr, "postprocess: device %llu host %llu ms_device %.3f\n", (unsigned long long)d.postprocessTally().device,
                  (unsigned long long)d.postprocessTally().host, d.postprocessTally().msDevice);
+  if (debug && std::strcmp(debug, "1") == 0 && d.waveletTally().device + d.waveletTally().host > 0)
+    std::fprintf(stderr, "wavelet decode: device %llu host %llu ms_range_decode %.3f ms_rebuild %.3f ms_inverse %.3f wall_ms %.3f\n",
+                 (unsigned long long)d.waveletTally().device, (unsigned long long)d.waveletTally().host, d.waveletTally().msRangeDecode,
+                 d.waveletTally().msRebuild, d.waveletTally().msInverse, s * 1e3);
+  if (debug && std::strcmp(debug, "1") == 0 && d.waveletTally().device > 0)
+    std::fprintf(stderr, "wavelet worker: busy_ms %.3f\n", d.waveletTally().msWorker);
+  if (debug && std::strcmp(debug, "1") == 0 && d.waveletTally().msHostDecodeTree > 0)
+    std::fprintf(stderr, "wavelet host phases: ms_decode_tree %.3f ms_message %.3f ms_upload_inverse_download %.3f ms_write %.3f\n",
+                 d.waveletTally().msHostDecodeTree, d.waveletTally().msHostMessage, d.waveletTally().msHostTransform,
+                 d.waveletTally().msHostWrite);
   if (verbosity > 0) std::fprintf(stderr, "Decompressed size: %zu bytes, %.3f s\n", n, s);
   return 0;
 }

@@ -510,6 +510,128 @@ int      bwtc_hip_postprocess_stats_get(bwtc_hip_ctx* ctx, bwtc_hip_postprocess_
 int      bwtc_hip_host_postprocess_tiles(const bwtc_hip_grammar* g, const uint8_t* data, uint64_t n, uint8_t* out,
                                          uint64_t cap, uint64_t* n_out, uint32_t tile);
 
+/* ---- 'B' / 'b' / 'u' decoding: host range decoder + wavelet rebuild on the device ------------------------------- */
+
+/* Return codes of the wavelet rebuild (beside the record-level BWTC_HIP_E_* above).  Every device loop is bounded
+ * by a node's bit count, a step cap and the output's capacity: no input makes a kernel write past out + cap. */
+#define BWTC_HIP_E_W_CHILD   (-20)  /* a run's path asks for a child the tree does not have                      */
+#define BWTC_HIP_E_W_BITS    (-21)  /* a node has fewer bits than the runs that reach it                          */
+#define BWTC_HIP_E_W_ESCAPE  (-22)  /* an escape code with more than 32 leading ones                              */
+#define BWTC_HIP_E_W_TOTAL   (-23)  /* a section's run lengths do not add up to its announced bytes               */
+#define BWTC_HIP_E_W_CAP     (-24)  /* the sections' bytes go past the output's capacity                          */
+#define BWTC_HIP_E_W_DEPTH   (-25)  /* a path longer than its tree has nodes (child links that form a cycle)      */
+#define BWTC_HIP_E_W_LIMIT   (-26)  /* beyond the device route's limits (block below 2^31 bytes, words below 2^32
+                                       and below 4 x bytes + nodes): the caller takes the host route; the decoder
+                                       handle is as it was before the call                                        */
+#define BWTC_HIP_E_W_FOREST  (-27)  /* a table entry that points outside its table                                */
+
+/* A block's decoded wavelet trees, flattened: what WaveletTree::decodeTreeBF leaves, and all WaveletTree::message
+ * needs.  Child links are relative to their section's first node (-1: none). */
+typedef struct bwtc_hip_wforest_section {
+  uint32_t runs;          /* rootSize: bits of the root = runs of the section                                    */
+  uint32_t bytes;         /* the section's announced length                                                      */
+  uint32_t first_node;    /* root of the symbol tree in nodes[]                                                  */
+  uint32_t symbol_nodes;  /* nodes of the symbol tree; run-length data nodes follow                              */
+  uint32_t n_nodes;       /* all nodes of the section                                                            */
+  uint32_t first_code;    /* root of the run-length code tree in codes[]                                         */
+  uint32_t n_codes;
+  uint32_t W;             /* width parameter of the escape code, 0..15                                           */
+  uint32_t plain_fixed;   /* no length has a code of its own: every run is escape coded                          */
+} bwtc_hip_wforest_section;
+typedef struct bwtc_hip_wforest_node {
+  int32_t  left, right;
+  uint32_t has_symbol;    /* a leaf of the symbol tree                                                           */
+  uint32_t symbol;
+  uint32_t bits;          /* bits of this node                                                                   */
+  uint32_t first_word;    /* where they start in words[] (bit i of the node = bit i % 64 of word i / 64)         */
+} bwtc_hip_wforest_node;
+typedef struct bwtc_hip_wforest_code {
+  int32_t  left, right;
+  uint32_t has_symbol;
+  uint32_t symbol;        /* run length; 0 = escape                                                              */
+} bwtc_hip_wforest_code;
+typedef struct bwtc_hip_wforest {
+  const bwtc_hip_wforest_section* sections; uint32_t n_sections;
+  const bwtc_hip_wforest_node*    nodes;    uint32_t n_nodes;
+  const bwtc_hip_wforest_code*    codes;    uint32_t n_codes;
+  const uint64_t*                 words;    uint64_t n_words;
+} bwtc_hip_wforest;
+
+/* What the last wavelet decode / rebuild on this context did. */
+typedef struct bwtc_hip_wavelet_decode_stats {
+  uint32_t route;             /* 1: the device kernels made the BWT bytes                                        */
+  uint32_t sections;          /* non-empty sections                                                              */
+  uint64_t routed_device;     /* calls so far on this context whose bytes the device kernels made                */
+  uint64_t runs;
+  uint64_t nodes;
+  uint64_t words;
+  uint64_t bit_reads;         /* bits taken out of nodes by the run walks (counted on the device)                */
+  uint64_t launches;          /* kernels launched                                                                */
+  uint64_t workspace_bytes;   /* device memory the rebuild holds                                                 */
+  float    ms_range_decode;   /* host: header, shapes and the range decoder (decode_block_W only)                */
+  float    ms_rebuild;        /* device span: upload of the forest to BWT bytes                                  */
+  float    ms_inverse;        /* device time of the inverse transform (decode_block_W only)                      */
+} bwtc_hip_wavelet_decode_stats;
+int bwtc_hip_wavelet_decode_stats_get(bwtc_hip_ctx* ctx, bwtc_hip_wavelet_decode_stats* out);
+
+/* The range decoder's state (three adaptive model sets and the coder) of one stream: the main model's state carries
+ * on from block to block, so one handle decodes a stream's blocks in order.  coder: 'B', 'b' or 'u'. */
+typedef struct bwtc_hip_wavelet_decoder bwtc_hip_wavelet_decoder;
+bwtc_hip_wavelet_decoder* bwtc_hip_wavelet_decoder_create(char coder);
+void bwtc_hip_wavelet_decoder_destroy(bwtc_hip_wavelet_decoder* d);
+void bwtc_hip_wavelet_decoder_reset(bwtc_hip_wavelet_decoder* d);
+
+/* Twin of bwtc_hip_decode_block_H for the wavelet coders: record (host) -> the original block in out (host, cap
+ * bytes).  The host range-decodes the record into a flattened forest in page-locked staging, which goes up once;
+ * the device rebuilds the BWT bytes (rank directory, run walk, expansion) and inverts them with the header's LF
+ * powers.  The rebuild's workspace is its own, made by the first call and grown on demand.  cap is clipped to
+ * the context's max_block_size (BWTC_HIP_E_CAPACITY beyond).  An error of the range decoder (the record-level codes,
+ * BWTC_HIP_E_W_LIMIT) or a forest the kernels refuse (BWTC_HIP_E_W_*): any non-zero return leaves the decoder handle
+ * as it was before the call, so the caller can take another route with the same handle. */
+int bwtc_hip_decode_block_W(bwtc_hip_ctx* ctx, bwtc_hip_wavelet_decoder* dec, const uint8_t* rec, uint64_t rec_bytes,
+                            uint8_t* out, uint64_t cap, uint32_t* size, uint64_t* consumed);
+/* Same with the original block left in device memory at d_out. */
+int bwtc_hip_decode_block_W_device(bwtc_hip_ctx* ctx, bwtc_hip_wavelet_decoder* dec, const uint8_t* rec,
+                                   uint64_t rec_bytes, uint8_t* d_out, uint64_t cap, uint32_t* size, uint64_t* consumed);
+/* The same block in two halves, so that a caller's worker thread can run block k's device half while the calling
+ * thread range-decodes block k+1 (the range decoder is serial by the format; nothing else has to wait for it).
+ * _begin is the host half: header, shapes and the range decoder, into forest slot `slot` (0 or 1) of the context,
+ * page-locked; *size = the block's bytes.  It does no device work and touches no statistics, and it may run while
+ * another thread is inside _end of the OTHER slot; every other pair of calls on one context is the caller's to
+ * order.  An error leaves the decoder handle as it was.  _end / _end_device is the device half of the slot: upload,
+ * rebuild, inverse (and download through page-locked memory); by then the models have moved on, and a forest the
+ * kernels refuse ends the stream. */
+int bwtc_hip_decode_block_W_begin(bwtc_hip_ctx* ctx, bwtc_hip_wavelet_decoder* dec, const uint8_t* rec, uint64_t rec_bytes,
+                                  uint64_t cap, uint32_t slot, uint32_t* size, uint64_t* consumed);
+int bwtc_hip_decode_block_W_end(bwtc_hip_ctx* ctx, uint32_t slot, uint8_t* out, uint64_t cap, uint32_t* size);
+int bwtc_hip_decode_block_W_end_device(bwtc_hip_ctx* ctx, uint32_t slot, uint8_t* d_out, uint64_t cap, uint32_t* size);
+/* Pure host route with the same handle (no device work): record -> BWT bytes in bwt_out and the LF powers in
+ * lf_out[256].  For blocks below the device route's floor or beyond its limits. */
+int bwtc_hip_wavelet_decode_bwt_host(bwtc_hip_wavelet_decoder* dec, const uint8_t* rec, uint64_t rec_bytes,
+                                     uint8_t* bwt_out, uint64_t cap, uint32_t* lf_out, uint32_t* n_lf, uint32_t* size,
+                                     uint64_t* consumed);
+/* The record's forest alone (host; what the device route uploads): counts for tests and tools.  counts[0..5] =
+ * sections, runs, nodes, words, bytes, bits taken out of nodes (counted by the host twin of the kernels, which
+ * writes the block into a scratch buffer of its size: -2 when that cannot be had). */
+int bwtc_hip_wavelet_decode_counts(bwtc_hip_wavelet_decoder* dec, const uint8_t* rec, uint64_t rec_bytes, uint64_t cap,
+                                   uint64_t* counts, uint64_t* consumed);
+
+/* A view of the forest the handle's last bwtc_hip_wavelet_decode_bwt_host / _decode_counts call decoded (and its LF
+ * powers, lf_out[256]; both may be null): valid until the next call on the handle.  What the rebuild entry points
+ * below take, for a real record. */
+int bwtc_hip_wavelet_decoder_forest(bwtc_hip_wavelet_decoder* dec, bwtc_hip_wforest* out, uint32_t* lf_out, uint32_t* n_lf);
+
+/* Flattened forest -> BWT bytes on the device: out is host memory (rebuild) or device memory at any alignment
+ * (rebuild_device).  *size = the sections' bytes. */
+int bwtc_hip_wavelet_rebuild(bwtc_hip_ctx* ctx, const bwtc_hip_wforest* forest, uint8_t* out, uint64_t cap, uint64_t* size);
+int bwtc_hip_wavelet_rebuild_device(bwtc_hip_ctx* ctx, const bwtc_hip_wforest* forest, uint8_t* d_out, uint64_t cap,
+                                    uint64_t* size);
+/* Host twin of the kernels (no device work): the same rank-directory walk on the calling thread, with one
+ * directory entry per `line_words` words (the device uses 7).  Same bytes, same error codes; *bit_reads (may be
+ * null) = bits taken out of nodes. */
+int bwtc_hip_host_wavelet_rebuild(const bwtc_hip_wforest* forest, uint8_t* out, uint64_t cap, uint64_t* size,
+                                  uint32_t line_words, uint64_t* bit_reads);
+
 #ifdef __cplusplus
 }
 #endif
