@@ -73,7 +73,7 @@ __global__ __launch_bounds__(kInvTPB) void k_inv_lf(const u8* __restrict__ bwt, 
   for (int e = 0; e < kInvE; ++e) {
     const u32 row = wrow + e * kWave;
     const bool ok = row < n && row != eob;
-    c[e] = row < n ? inv_L(bwt, size, eob, row) : 0u;
+    c[e] = ok ? inv_L(bwt, size, eob, row) : 0u;     // not for the end-of-block row: row == eob == size is bwt[size]
     u32 below, peers;
     wave_digit_rank<8>(c[e], ok, &below, &peers);
     u32 prev = 0;

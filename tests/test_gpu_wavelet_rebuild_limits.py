@@ -60,6 +60,20 @@ def test_host_twin_agrees_on_counts(hip_ctx):
         assert hip_ctx.wavelet_decode_stats()["bit_reads"] == twin_reads == reads, name
 
 
+def test_line_count_scan_goes_from_one_launch_to_three(hip_ctx):
+    """4096 lines of 7 words are one tile of the scan over the line counts; one word more is a 4097th line."""
+    launches = []
+    for w in wforest.WORD_COUNTS:
+        sections, gap = wforest.cases()["words_%d" % w]
+        forest, runs, reads = wforest.pack(sections, gap)
+        assert forest.words.size == w
+        assert hip_ctx.wavelet_rebuild(forest).tobytes() == wforest.expand(runs).tobytes(), w
+        st = hip_ctx.wavelet_decode_stats()
+        assert st["words"] == w and st["bit_reads"] == reads, st
+        launches.append(st["launches"])
+    assert launches[0] == launches[1] and launches[2] == launches[1] + 2 and launches[3] == launches[2], launches
+
+
 def test_run_of_2_pow_31_minus_1(hip_ctx):
     n = (1 << 31) - 1
     forest, runs, reads = wforest.pack([wforest.section([(200, n)], W=15)])

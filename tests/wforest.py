@@ -119,6 +119,7 @@ def pack(sections, gap_words=0):
                 words.extend(int(x) for x in w)
                 words.extend([0xFFFFFFFFFFFFFFFF] * gap_words)      # set bits nobody owns: the ranks must not see them
             nodes.append((t.left[i], t.right[i], t.has_symbol[i], t.symbol[i], bits.size, first if bits.size else 0))
+        words.extend([0xFFFFFFFFFFFFFFFF] * sec.get("tail_words", 0))   # words no node owns, behind the section's
         for i in range(len(c.left)):
             codes.append((c.left[i], c.right[i], c.has_symbol[i], c.symbol[i]))
         runs += sec["runs"]
@@ -126,6 +127,28 @@ def pack(sections, gap_words=0):
     f = hip.Forest(np.array(secs, hip.SECTION_DTYPE), np.array(nodes, hip.NODE_DTYPE), np.array(codes, hip.CODE_DTYPE),
                    np.array(words, np.uint64))
     return f, runs, reads
+
+
+def with_words(sections, gap_words, total_words):
+    """The same sections with unused all-ones words behind the last one, total_words words in all."""
+    have = pack(sections, gap_words)[0].words.size
+    assert have <= total_words
+    return sections[:-1] + [dict(sections[-1], tail_words=total_words - have)]
+
+
+def many_sections(count, seed=7):
+    """count sections of one to three runs each, shapes rotated."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for k in range(count):
+        runs = [(int(s), int(n)) for s, n in zip(rng.integers(0, 1 + k % 5, 1 + k % 3), rng.integers(1, 50, 1 + k % 3))]
+        out.append(section(runs, W=k % 4, len_code=None if k % 2 else {1: "0", 0: "1"}))
+    return out
+
+
+LINE_SCAN_TILE = 4096   # lines one workgroup scans: one more line takes the scan of the line counts to three launches
+WORD_COUNTS = (LINE_WORDS * LINE_SCAN_TILE - 1, LINE_WORDS * LINE_SCAN_TILE, LINE_WORDS * LINE_SCAN_TILE + 1,
+               LINE_WORDS * 2 * LINE_SCAN_TILE + 1)
 
 
 def expand(runs):
@@ -160,6 +183,14 @@ def cases():
         r = [(int(s), int(v)) for s, v in zip(rng.integers(0, 2 + 50 * k, n), rng.integers(1, 40, n))]
         multi.append(section(r, W=k * 3, len_code=None if k % 2 else {1: "0", 3: "10", 0: "11"}))
     out["five_sections"] = (multi, 1)
+    for gap in (0, 2, 3, 4, 5, 6, 7):              # with gap 1 above: a node starts in every slot of a 7-word line
+        out["five_sections_gap_%d" % gap] = (multi, gap)
+    # kWrMaxSections: a wave of the walk spans up to 64 sections, the verdict uses all its 256 threads
+    out["256_sections"] = (many_sections(256), 0)
+    # the scan of the line counts around one tile of lines
+    base = out["root_of_%d_bits" % (64 * LINE_WORDS + 1)][0]
+    for w in WORD_COUNTS:
+        out["words_%d" % w] = (with_words(base, 0, w), 0)
     return out
 
 
@@ -192,6 +223,8 @@ def corrupt_cases():
     out["cycle"] = (hip.Forest(f.sections, n2, f.codes, f.words), total, hip.E_W_DEPTH)
     n3 = f.nodes.copy(); n3["left"][0] = n3.size
     out["link_outside_the_table"] = (hip.Forest(f.sections, n3, f.codes, f.words), total, hip.E_W_FOREST)
+    f257, runs257, _ = pack(many_sections(257))
+    out["257_sections"] = (f257, sum(n for _, n in runs257), hip.E_W_FOREST)
     return out
 
 
