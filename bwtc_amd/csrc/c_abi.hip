@@ -37,6 +37,7 @@ struct bwtc_hip_grammar {
 };
 namespace bwtc_hip {
 int pair_replace_device(BwtEngine& e, bwtc::prepr::Grammar& grammar, const u8* d_src, u64 n, u8* d_dst, u64* n_out, u32* replaced);
+int pair_stats_device(BwtEngine& e, const u8* d_src, u64 n, u32* host_counts);
 }
 
 template <typename K>
@@ -1073,6 +1074,14 @@ int bwtc_hip_pair_replace_device(bwtc_hip_ctx* ctx, bwtc_hip_grammar* g, const u
                                  uint8_t* d_dst, uint64_t* n_out, uint32_t* replaced) {
   if (!ctx || !g || !d_src || !d_dst || !n_out || !replaced) return -1;
   return bwtc_hip::pair_replace_device(ctx->eng, g->g, d_src, n, d_dst, n_out, replaced);
+}
+int bwtc_hip_test_pair_stats(bwtc_hip_ctx* ctx, const uint8_t* d_src, uint64_t n, uint32_t* pair_cnt, uint32_t* byte_cnt) {
+  if (!ctx || !d_src || !pair_cnt || !byte_cnt) return -1;
+  std::vector<uint32_t> counts(65536 + 256);
+  if (const int rc = bwtc_hip::pair_stats_device(ctx->eng, d_src, n, counts.data())) return rc;
+  std::memcpy(pair_cnt, counts.data(), 65536 * 4);
+  std::memcpy(byte_cnt, counts.data() + 65536, 256 * 4);
+  return 0;
 }
 int bwtc_hip_host_precompress(bwtc_hip_grammar* g, const char* options, uint8_t* block, uint64_t n, uint64_t* n_out);
 int bwtc_hip_precompress(bwtc_hip_ctx* ctx, bwtc_hip_grammar* g, const char* options, uint8_t* block, uint64_t n, uint64_t* n_out) {

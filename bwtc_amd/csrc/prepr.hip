@@ -165,26 +165,36 @@ __global__ __launch_bounds__(kPrTPB) void k_pr_emit(const u8* __restrict__ d, u6
   }
 }
 
+// ---- the statistics of one PairReplacer ---------------------------------------------------------------
+// host_counts[0 .. 65535] = the pair counters, [65536 .. 65791] = the byte counters of d_src (n bytes): the counters
+// cleared, counted and read back on the engine's stream, waited for.  The arguments are checked here for both callers.
+int pair_stats_device(BwtEngine& e, const u8* d_src, u64 n, u32* host_counts) {
+  hipStream_t st = e.stream;
+  if (n < 3 || n >= (1ull << 31)) return -1;                       // PairReplacer::analyseData asserts length > 2
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  const u32 ntiles = (u32)((n + kPrTile - 1) / kPrTile);
+  u32* d_pairs = e.d_V0;                                           // 65536 + 256 words
+  u32* d_bytes = d_pairs + 65536;
+  if ((u64)ntiles + 1 > e.cap || e.cap < (1u << 17)) return -1;
+  BWTC_HIP_TRY(hipMemsetAsync(d_pairs, 0, (65536 + 256) * 4, st));
+  hipLaunchKernelGGL(k_pair_stats, dim3(std::min<u32>(ntiles, 512u), 4), dim3(kPrTPB), 0, st, d_src, n, d_pairs, d_bytes);
+  BWTC_HIP_TRY(hipMemcpyAsync(host_counts, d_pairs, (65536 + 256) * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(e.wait());
+  return 0;
+}
+
 // ---- one PairReplacer over a device-resident text ---------------------------------------------------
 // d_src (n bytes) -> d_dst (room for 2 n): statistics on the device, the choice on the host (grammar updated),
 // the replaced text on the device.  *n_out = its length, *replaced = pairs replaced.
 int pair_replace_device(BwtEngine& e, bwtc::prepr::Grammar& grammar, const u8* d_src, u64 n, u8* d_dst, u64* n_out, u32* replaced) {
   hipStream_t st = e.stream;
-  if (n < 3 || n >= (1ull << 31)) return -1;                       // PairReplacer::analyseData asserts length > 2
-  BWTC_HIP_TRY(hipSetDevice(e.device));
+  std::vector<u32> counts(65536 + 256);
+  if (const int rc = pair_stats_device(e, d_src, n, counts.data())) return rc;
   const u32 ntiles = (u32)((n + kPrTile - 1) / kPrTile);
-  // workspace: counters, replacement table, per-tile words -- in the transform's arena (free between blocks)
-  u32* d_pairs = e.d_V0;                                           // 65536 + 256 words
-  u32* d_bytes = d_pairs + 65536;
+  // workspace: replacement table, per-tile words -- in the transform's arena (free between blocks)
   uint16_t* d_table = reinterpret_cast<uint16_t*>(e.d_V1);         // 65536 half words
   u32* d_head = e.d_G0;                                            // ntiles words each
   u32* d_count = e.d_G1;
-  if ((u64)ntiles + 1 > e.cap || e.cap < (1u << 17)) return -1;
-  BWTC_HIP_TRY(hipMemsetAsync(d_pairs, 0, (65536 + 256) * 4, st));
-  hipLaunchKernelGGL(k_pair_stats, dim3(std::min<u32>(ntiles, 512u), 4), dim3(kPrTPB), 0, st, d_src, n, d_pairs, d_bytes);
-  std::vector<u32> counts(65536 + 256);
-  BWTC_HIP_TRY(hipMemcpyAsync(counts.data(), d_pairs, counts.size() * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(e.wait());
   std::vector<uint64_t> pf(65536), bf(256);
   for (size_t i = 0; i < 65536; ++i) pf[i] = counts[i];
   for (size_t i = 0; i < 256; ++i) bf[i] = counts[65536 + i];

@@ -210,7 +210,7 @@ EXPORTS = [
     "bwtc_hip_test_sort_u32", "bwtc_hip_test_sort_u64", "bwtc_hip_test_scan_u32",
     "bwtc_hip_wavelet_depth_needed", "bwtc_hip_grammar_create", "bwtc_hip_grammar_destroy", "bwtc_hip_grammar_rules", "bwtc_hip_grammar_special_symbols",
     "bwtc_hip_grammar_is_special", "bwtc_hip_grammar_write", "bwtc_hip_grammar_read", "bwtc_hip_pair_replace_device",
-    "bwtc_hip_precompress", "bwtc_hip_host_precompress", "bwtc_hip_postprocess",
+    "bwtc_hip_test_pair_stats", "bwtc_hip_precompress", "bwtc_hip_host_precompress", "bwtc_hip_postprocess",
     "bwtc_hip_postprocess_device", "bwtc_hip_postprocess_block", "bwtc_hip_postprocess_stats_get",
     "bwtc_hip_host_postprocess_tiles",
     "bwtc_hip_wavelet_decoder_create", "bwtc_hip_wavelet_decoder_destroy", "bwtc_hip_wavelet_decoder_reset",
@@ -319,6 +319,7 @@ def load():
     L.bwtc_hip_grammar_write.argtypes = [_vp, _vp, _u64, ctypes.POINTER(_u64)]
     L.bwtc_hip_grammar_read.argtypes = [_vp, _vp, _u64, ctypes.POINTER(_u64)]
     L.bwtc_hip_pair_replace_device.argtypes = [_vp, _vp, _vp, _u64, _vp, ctypes.POINTER(_u64), ctypes.POINTER(_u32)]
+    L.bwtc_hip_test_pair_stats.argtypes = [_vp, _vp, _u64, _vp, _vp]
     L.bwtc_hip_precompress.argtypes = [_vp, _vp, ctypes.c_char_p, _vp, _u64, ctypes.POINTER(_u64)]
     L.bwtc_hip_host_precompress.argtypes = [_vp, ctypes.c_char_p, _vp, _u64, ctypes.POINTER(_u64)]
     L.bwtc_hip_postprocess.argtypes = [_vp, _vp, _u64, _vp, _u64, ctypes.POINTER(_u64)]
@@ -472,6 +473,22 @@ class Context:
         n = _u64(0)
         _check(self.lib.bwtc_hip_precompress(self.handle, grammar.h, options.encode(), _ptr(buf), buf.size, ctypes.byref(n)), "bwtc_hip_precompress")
         return buf[:n.value].copy()
+
+    def pair_replace_device(self, grammar, d_src_ptr, n, d_dst_ptr):
+        """One PairReplacer round on device pointers (bwtc_hip_pair_replace_device; d_dst: room for 2 n bytes):
+        (new length, pairs replaced)."""
+        n_out, replaced = _u64(0), _u32(0)
+        _check(self.lib.bwtc_hip_pair_replace_device(self.handle, grammar.h, _vp(d_src_ptr), n, _vp(d_dst_ptr), ctypes.byref(n_out),
+                                                     ctypes.byref(replaced)), "bwtc_hip_pair_replace_device")
+        return int(n_out.value), int(replaced.value)
+
+    def test_pair_stats(self, d_ptr, n):
+        """The statistics step of a round alone (bwtc_hip_test_pair_stats) over n device bytes at d_ptr:
+        (byte counters[256], pair counters[65536], index = first << 8 | second)."""
+        pair_cnt = np.zeros(65536, np.uint32)
+        byte_cnt = np.zeros(256, np.uint32)
+        _check(self.lib.bwtc_hip_test_pair_stats(self.handle, _vp(d_ptr), n, _ptr(pair_cnt), _ptr(byte_cnt)), "bwtc_hip_test_pair_stats")
+        return byte_cnt, pair_cnt
 
     def postprocess(self, grammar, data, max_size):
         """Postprocessor::uncompress on the GPU (bwtc_hip_postprocess_block): host buffers in and out."""

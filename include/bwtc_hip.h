@@ -459,6 +459,10 @@ int      bwtc_hip_grammar_read(bwtc_hip_grammar* g, const uint8_t* in, uint64_t 
  * *replaced = pairs replaced (0: the text is copied unchanged). */
 int      bwtc_hip_pair_replace_device(bwtc_hip_ctx* ctx, bwtc_hip_grammar* g, const uint8_t* d_src, uint64_t n,
                                       uint8_t* d_dst, uint64_t* n_out, uint32_t* replaced);
+/* Test hook: the statistics step of bwtc_hip_pair_replace_device alone (the same function: counters cleared, counted,
+ * read back) over a device-resident text: pair_cnt[first << 8 | second] (65536 words) and byte_cnt (256 words), host
+ * buffers.  -1 for n < 3 or n >= 2^31, as there. */
+int      bwtc_hip_test_pair_stats(bwtc_hip_ctx* ctx, const uint8_t* d_src, uint64_t n, uint32_t* pair_cnt, uint32_t* byte_cnt);
 /* Precompressor::precompress over a host block, in place: one round per letter of `options` ('p'), stopped by the
  * first round that does not shorten the block; *n_out = the new length.  Blocks shorter than three bytes are left
  * alone (the reference asserts length > 2). */
