@@ -62,6 +62,147 @@ static int test_sort(bwtc_hip_ctx* ctx, K* keys, uint32_t* vals, uint64_t n, int
   return 0;
 }
 
+// ---- test hooks of the radix sorts themselves (bwtc_hip_test_radix_*; DESIGN.md, "The sort hooks") ----------------
+// radix_sort_pairs / _long / _keys_segmented called directly on the engine's buffers, three-launch scans (no ScanScope),
+// no BwtEngine::sort_pairs in between.  A hook checks the sort's contract on the host before it launches anything (-1),
+// makes the "producer's" first digit plane itself, and puts 256 bytes of canary behind the last item of both buffers of
+// every ping-pong pair it hands over: a changed canary is kSortCanaryBase - (index in the order they were put).
+namespace {
+constexpr size_t kSortCanaryBytes = 256;
+constexpr int kSortCanaryBase = -20;
+struct SortCanaries {
+  u8 pat[kSortCanaryBytes];
+  u8 back[8][kSortCanaryBytes];
+  const u8* at[8];
+  int count = 0;
+  SortCanaries() { for (size_t i = 0; i < kSortCanaryBytes; ++i) pat[i] = (u8)(0xC3u ^ (i * 29u)); }
+  hipError_t put(void* buf, u64 bytes, hipStream_t st) {
+    u8* p = static_cast<u8*>(buf) + bytes;
+    at[count++] = p;
+    return hipMemcpyAsync(p, pat, kSortCanaryBytes, hipMemcpyHostToDevice, st);
+  }
+  hipError_t fetch(hipStream_t st) {
+    for (int i = 0; i < count; ++i) {
+      const hipError_t rc = hipMemcpyAsync(back[i], at[i], kSortCanaryBytes, hipMemcpyDeviceToHost, st);
+      if (rc != hipSuccess) return rc;
+    }
+    return hipSuccess;
+  }
+  int verdict() const {                                 // after the stream has been waited for
+    for (int i = 0; i < count; ++i) if (std::memcmp(back[i], pat, kSortCanaryBytes) != 0) return kSortCanaryBase - i;
+    return 0;
+  }
+};
+
+// keys: n + n_holes items in, n out; vals likewise (given values), n out (made-up values), untouched (keys only).
+// values_mode as k_radix_scatter's: 0 given, 1 positions, 2 keys only, 3 descending.  planes: 0 none, 1 both, 2 both and
+// the first pass's digits ready in the first.
+template <typename K, typename V>
+int test_radix_pairs(BwtEngine& e, K* keys, V* vals, u64 n, u64 n_holes, int bit_lo, int nbits, int values_mode, int planes) {
+  const u64 n_in = n + n_holes;
+  if (n == 0 || n_in < n || n_in + kSortCanaryBytes > e.cap) return -1;                  // (the planes are cap + 64 bytes)
+  if (bit_lo < 0 || bit_lo > nbits || nbits > 8 * (int)sizeof(K)) return -1;
+  if (values_mode < 0 || values_mode > 3 || planes < 0 || planes > 2) return -1;
+  if (values_mode != 2 && !vals) return -1;
+  // holes come with given values only; values are made up by the first pass, so there has to be one
+  if (values_mode != 0 && n_holes) return -1;
+  if (n_holes && bit_lo >= 8 * (int)sizeof(K)) return -1;                      // the compacting pass takes a digit at bit_lo
+  if ((values_mode == 1 || values_mode == 3) && (n < 2 || nbits == bit_lo)) return -1;
+  if (n_holes) {
+    u64 ones = 0;
+    for (u64 i = 0; i < n_in; ++i) ones += keys[i] == ~(K)0;
+    if (ones != n_holes) return -1;
+  }
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  hipStream_t st = e.stream;
+  K* k0 = static_cast<K*>(e.d_R1);
+  K* k1 = static_cast<K*>(e.d_R2);
+  V* v0 = reinterpret_cast<V*>(e.d_V0);
+  V* v1 = reinterpret_cast<V*>(e.d_V1);
+  const bool keys_only = values_mode == 2;
+  std::vector<u8> plane;
+  SortCanaries can;
+  // the input's buffers hold n + n_holes items, the other side never more than the n that exist
+  BWTC_HIP_TRY(hipMemcpyAsync(k0, keys, n_in * sizeof(K), hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(can.put(k0, n_in * sizeof(K), st));
+  BWTC_HIP_TRY(can.put(k1, n * sizeof(K), st));
+  if (!keys_only) {
+    if (values_mode == 0) BWTC_HIP_TRY(hipMemcpyAsync(v0, vals, n_in * sizeof(V), hipMemcpyHostToDevice, st));
+    else BWTC_HIP_TRY(hipMemsetAsync(v0, 0xA5, n_in * sizeof(V), st));          // "v0 need not be filled"
+    BWTC_HIP_TRY(can.put(v0, n_in * sizeof(V), st));
+    BWTC_HIP_TRY(can.put(v1, n * sizeof(V), st));
+  }
+  if (planes) {
+    if (planes == 2) {
+      // the first pass's digit rule: radix_digit(key, bit_lo), one byte per slot of the input
+      plane.resize(n_in);
+      for (u64 i = 0; i < n_in; ++i) plane[i] = (u8)((keys[i] >> (bit_lo < 8 * (int)sizeof(K) ? bit_lo : 0)) & 255u);
+      BWTC_HIP_TRY(hipMemcpyAsync(e.d_P0, plane.data(), n_in, hipMemcpyHostToDevice, st));
+    } else {
+      BWTC_HIP_TRY(hipMemsetAsync(e.d_P0, 0x5A, n_in, st));                     // a plane nobody may read
+    }
+    BWTC_HIP_TRY(can.put(e.d_P0, n_in, st));
+    BWTC_HIP_TRY(can.put(e.d_P1, n, st));
+  }
+  K* ks = nullptr; V* vs = nullptr;
+  radix_sort_pairs<K, V>(k0, k1, keys_only ? (V*)nullptr : v0, keys_only ? (V*)nullptr : v1, n, nbits, e.d_table, e.d_partial, st, &ks, &vs,
+                         nullptr, bit_lo, values_mode == 1, keys_only, n_holes, planes ? e.d_P0 : nullptr, planes ? e.d_P1 : nullptr,
+                         planes == 2, values_mode == 3);
+  BWTC_HIP_TRY(hipMemcpyAsync(keys, ks, n * sizeof(K), hipMemcpyDeviceToHost, st));
+  if (!keys_only) BWTC_HIP_TRY(hipMemcpyAsync(vals, vs, n * sizeof(V), hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(e.wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return can.verdict();
+}
+
+// keys, w: n items in and out; vals: n out (the first pass makes them up: item i's value is n - 1 - i).
+template <typename V, int EL>
+int test_radix_long(BwtEngine& e, u64* keys, V* vals, u32* w, u64 n, int kbits, int wbits, bool direct_w) {
+  if (n < 2 || n + kSortCanaryBytes > e.cap) return -1;                        // made-up values: there has to be a pass
+  if (kbits < 1 || kbits > 64 || wbits < 1 || wbits > 32) return -1;
+  if (wbits < 32) for (u64 i = 0; i < n; ++i) if (w[i] >> wbits) return -1;
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  hipStream_t st = e.stream;
+  u64* k0 = static_cast<u64*>(e.d_R1);
+  u64* k1 = static_cast<u64*>(e.d_R2);
+  V* v0 = reinterpret_cast<V*>(e.d_V0);
+  V* v1 = reinterpret_cast<V*>(e.d_V1);
+  // the first pass's digit rule (radix_sort_long's pass plan): w's lowest digit, or -- w shorter than a digit -- the
+  // bridge digit: w's wbits bits under the key's lowest, cut to min(8, wbits + kbits) bits
+  std::vector<u8> plane(n);
+  if (wbits >= kRadixBits) {
+    for (u64 i = 0; i < n; ++i) plane[i] = (u8)(w[i] & 255u);
+  } else {
+    const u32 dmask = (1u << std::min(kRadixBits, wbits + kbits)) - 1u;
+    for (u64 i = 0; i < n; ++i) plane[i] = (u8)((w[i] | ((u32)keys[i] << wbits)) & dmask);
+  }
+  SortCanaries can;
+  BWTC_HIP_TRY(hipMemcpyAsync(k0, keys, n * 8, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_W0, w, n * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_P0, plane.data(), n, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemsetAsync(v0, 0xA5, n * sizeof(V), st));
+  BWTC_HIP_TRY(can.put(k0, n * 8, st));
+  BWTC_HIP_TRY(can.put(k1, n * 8, st));
+  BWTC_HIP_TRY(can.put(v0, n * sizeof(V), st));
+  BWTC_HIP_TRY(can.put(v1, n * sizeof(V), st));
+  BWTC_HIP_TRY(can.put(e.d_W0, n * 4, st));
+  BWTC_HIP_TRY(can.put(e.d_W1, n * 4, st));
+  BWTC_HIP_TRY(can.put(e.d_P0, n, st));
+  BWTC_HIP_TRY(can.put(e.d_P1, n, st));
+  u64* ks = nullptr; V* vs = nullptr; u32* ws = nullptr;
+  radix_sort_long<V, EL>(k0, k1, v0, v1, e.d_W0, e.d_W1, n, kbits, wbits, e.d_table, e.d_partial, st, &ks, &vs, &ws, nullptr,
+                         e.d_P0, e.d_P1, 0, false, direct_w);
+  BWTC_HIP_TRY(hipMemcpyAsync(keys, ks, n * 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(vals, vs, n * sizeof(V), hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(w, ws, n * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(e.wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return can.verdict();
+}
+}  // namespace
+
 // how every buffer handed out by bwtc_hip_host_alloc was locked (see lockedHostAlloc)
 static std::mutex& host_allocs_mu() { static std::mutex m; return m; }
 static std::map<void*, std::pair<int, uint64_t> >& host_allocs() { static std::map<void*, std::pair<int, uint64_t> > m; return m; }
@@ -972,6 +1113,61 @@ int bwtc_hip_test_sort_u32(bwtc_hip_ctx* ctx, uint32_t* keys, uint32_t* vals, ui
 }
 int bwtc_hip_test_sort_u64(bwtc_hip_ctx* ctx, uint64_t* keys, uint32_t* vals, uint64_t n, int nbits) {
   return test_sort<u64>(ctx, keys, vals, n, nbits);
+}
+
+int bwtc_hip_test_radix_pairs(bwtc_hip_ctx* ctx, void* keys, void* vals, uint64_t n, uint64_t n_holes, int key_bytes, int val_bytes,
+                              int bit_lo, int nbits, int values_mode, int planes) {
+  if (!ctx || !keys) return -1;
+  BwtEngine& e = ctx->eng;
+  typedef unsigned short u16v;
+  if (key_bytes == 4 && val_bytes == 4) return test_radix_pairs<u32, u32>(e, static_cast<u32*>(keys), static_cast<u32*>(vals), n, n_holes, bit_lo, nbits, values_mode, planes);
+  if (key_bytes == 8 && val_bytes == 4) return test_radix_pairs<u64, u32>(e, static_cast<u64*>(keys), static_cast<u32*>(vals), n, n_holes, bit_lo, nbits, values_mode, planes);
+  if (key_bytes == 4 && val_bytes == 2) return test_radix_pairs<u32, u16v>(e, static_cast<u32*>(keys), static_cast<u16v*>(vals), n, n_holes, bit_lo, nbits, values_mode, planes);
+  if (key_bytes == 8 && val_bytes == 2) return test_radix_pairs<u64, u16v>(e, static_cast<u64*>(keys), static_cast<u16v*>(vals), n, n_holes, bit_lo, nbits, values_mode, planes);
+  return -1;
+}
+
+int bwtc_hip_test_radix_long(bwtc_hip_ctx* ctx, uint64_t* keys, void* vals, uint32_t* w, uint64_t n, int val_bytes, int items_per_thread,
+                             int kbits, int wbits, int direct_w) {
+  if (!ctx || !keys || !vals || !w) return -1;
+  BwtEngine& e = ctx->eng;
+  typedef unsigned short u16v;
+  // the three instantiations the suffix sorter makes
+  if (val_bytes == 4 && items_per_thread == 6) return test_radix_long<u32, 6>(e, keys, static_cast<u32*>(vals), w, n, kbits, wbits, direct_w != 0);
+  if (val_bytes == 2 && items_per_thread == 6) return test_radix_long<u16v, 6>(e, keys, static_cast<u16v*>(vals), w, n, kbits, wbits, direct_w != 0);
+  if (val_bytes == 2 && items_per_thread == 8) return test_radix_long<u16v, 8>(e, keys, static_cast<u16v*>(vals), w, n, kbits, wbits, direct_w != 0);
+  return -1;
+}
+
+int bwtc_hip_test_radix_segmented(bwtc_hip_ctx* ctx, uint32_t* keys, uint64_t n, int bit_lo, const uint32_t* tile_first, uint32_t nseg) {
+  if (!ctx || !keys || !tile_first) return -1;
+  BwtEngine& e = ctx->eng;
+  const u64 tile = (u64)radix_tile<u32>();
+  if (n == 0 || n % tile != 0 || n + kSortCanaryBytes > e.cap) return -1;
+  if (bit_lo < 0 || bit_lo + 2 * kRadixBits > 32) return -1;
+  if (nseg == 0 || (u64)nseg + 1 > e.cap || tile_first[0] != 0 || (u64)tile_first[nseg] != n / tile) return -1;
+  for (u32 s = 0; s < nseg; ++s) if (tile_first[s] > tile_first[s + 1]) return -1;
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  hipStream_t st = e.stream;
+  u32* k0 = static_cast<u32*>(e.d_R1);
+  u32* k1 = static_cast<u32*>(e.d_R2);
+  std::vector<u8> plane(n);                             // the first pass's digit rule: radix_digit(key, bit_lo)
+  for (u64 i = 0; i < n; ++i) plane[i] = (u8)((keys[i] >> bit_lo) & 255u);
+  SortCanaries can;
+  BWTC_HIP_TRY(hipMemcpyAsync(k0, keys, n * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_P0, plane.data(), n, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_V0, tile_first, ((u64)nseg + 1) * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(can.put(k0, n * 4, st));
+  BWTC_HIP_TRY(can.put(k1, n * 4, st));
+  BWTC_HIP_TRY(can.put(e.d_P0, n, st));
+  BWTC_HIP_TRY(can.put(e.d_P1, n, st));
+  u32* ks = nullptr;
+  radix_sort_keys_segmented(k0, k1, n, bit_lo, e.d_V0, nseg, e.d_table, e.d_partial, st, &ks, e.d_P0, e.d_P1);
+  BWTC_HIP_TRY(hipMemcpyAsync(keys, ks, n * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(e.wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return can.verdict();
 }
 
 // Test hook of the GPU lane engine (gpu_lanes.hpp): k chains of w-elements, chain j = elements [bounds[j], bounds[j+1]),

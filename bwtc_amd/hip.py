@@ -208,6 +208,7 @@ EXPORTS = [
     "bwtc_hip_wavelet_depth", "bwtc_hip_wavelet_set_depth", "bwtc_hip_numa_node", "bwtc_hip_host_cpu_slice", "bwtc_hip_set_worker_cpus", "bwtc_hip_wavelet_reset", "bwtc_hip_wavelet_start", "bwtc_hip_host_wavelet_sections", "bwtc_hip_host_wavelet_streams", "bwtc_hip_host_wavelet_streams_lanes", "bwtc_hip_host_huffman_lengths", "bwtc_hip_host_huffman_codes", "bwtc_hip_host_serialize_shape",
     "bwtc_hip_host_sections", "bwtc_hip_host_bwtblock_header", "bwtc_hip_synth", "bwtc_hip_suffix_array",
     "bwtc_hip_test_sort_u32", "bwtc_hip_test_sort_u64", "bwtc_hip_test_scan_u32",
+    "bwtc_hip_test_radix_pairs", "bwtc_hip_test_radix_long", "bwtc_hip_test_radix_segmented",
     "bwtc_hip_wavelet_depth_needed", "bwtc_hip_grammar_create", "bwtc_hip_grammar_destroy", "bwtc_hip_grammar_rules", "bwtc_hip_grammar_special_symbols",
     "bwtc_hip_grammar_is_special", "bwtc_hip_grammar_write", "bwtc_hip_grammar_read", "bwtc_hip_pair_replace_device",
     "bwtc_hip_test_pair_stats", "bwtc_hip_precompress", "bwtc_hip_host_precompress", "bwtc_hip_postprocess",
@@ -361,6 +362,9 @@ def load():
     L.bwtc_hip_test_sort_u32.argtypes = [_vp, _vp, _vp, _u64, ctypes.c_int]
     L.bwtc_hip_test_sort_u64.argtypes = [_vp, _vp, _vp, _u64, ctypes.c_int]
     L.bwtc_hip_test_scan_u32.argtypes = [_vp, _vp, _u64]
+    L.bwtc_hip_test_radix_pairs.argtypes = [_vp, _vp, _vp, _u64, _u64] + [ctypes.c_int] * 6
+    L.bwtc_hip_test_radix_long.argtypes = [_vp, _vp, _vp, _vp, _u64] + [ctypes.c_int] * 5
+    L.bwtc_hip_test_radix_segmented.argtypes = [_vp, _vp, _u64, ctypes.c_int, _vp, _u32]
     _lib = L
     return L
 
@@ -977,6 +981,52 @@ class Context:
         data = np.array(data, dtype=np.uint32, copy=True)
         _check(self.lib.bwtc_hip_test_scan_u32(self.handle, _ptr(data), data.size), "bwtc_hip_test_scan")
         return data
+
+    # radix_sort.hpp's three sorts, called directly (bwtc_hip_test_radix_*): a contract the hook refuses raises
+    # BwtcHipError with code -1, a changed canary behind a buffer with code -20 - its index
+    RADIX_VALUES = {"given": 0, "positions": 1, "keys": 2, "descending": 3}
+
+    def test_radix_pairs(self, keys, vals=None, n_holes=0, bit_lo=0, nbits=None, values="given", planes=0, vtype=np.uint32):
+        """keys (uint32 | uint64): n + n_holes slots, of which n_holes all ones.  -> (n sorted keys, their values or None).
+        values: "given" (vals, one per slot), "positions", "descending" or "keys"; planes 0 off, 1 on, 2 on with the first
+        pass's plane ready (made by the hook); vtype uint32 | uint16."""
+        keys = np.array(keys, copy=True)
+        assert keys.dtype in (np.uint32, np.uint64) and keys.ndim == 1
+        vtype = np.dtype(vtype)
+        n = keys.size - n_holes
+        mode = self.RADIX_VALUES[values]
+        if mode == 0:
+            vals = np.array(vals, dtype=vtype, copy=True)
+            assert vals.size == keys.size
+        elif mode != 2:
+            vals = np.zeros(max(n, 1), vtype)
+        else:
+            vals = None
+        nbits = 8 * keys.itemsize if nbits is None else nbits
+        _check(self.lib.bwtc_hip_test_radix_pairs(self.handle, _ptr(keys), None if vals is None else _ptr(vals), n, n_holes, keys.itemsize,
+                                                  vtype.itemsize, bit_lo, nbits, mode, planes), "bwtc_hip_test_radix_pairs")
+        return keys[:n], (None if vals is None else vals[:n])
+
+    def test_radix_long(self, keys, w, kbits, wbits, vtype=np.uint32, items_per_thread=6, direct_w=True):
+        """Long items (uint64 keys, uint32 w) -> (keys, values, w) sorted by (keys bits [0, kbits), w bits [0, wbits));
+        the values are n - 1 - (first place), cut to vtype."""
+        keys = np.array(keys, dtype=np.uint64, copy=True)
+        w = np.array(w, dtype=np.uint32, copy=True)
+        assert keys.size == w.size
+        vals = np.zeros(max(keys.size, 1), np.dtype(vtype))
+        _check(self.lib.bwtc_hip_test_radix_long(self.handle, _ptr(keys), _ptr(vals), _ptr(w), keys.size, vals.itemsize, items_per_thread,
+                                                 kbits, wbits, 1 if direct_w else 0), "bwtc_hip_test_radix_long")
+        return keys, vals[:keys.size], w
+
+    def test_radix_segmented(self, keys, bit_lo, tile_first):
+        """uint32 keys in whole tiles of 8192, segment s = tiles [tile_first[s], tile_first[s + 1]) -> every segment
+        sorted on its own by bits [bit_lo, bit_lo + 16)."""
+        keys = np.array(keys, dtype=np.uint32, copy=True)
+        tf = np.array(tile_first, dtype=np.uint32, copy=True)
+        assert tf.size >= 2
+        _check(self.lib.bwtc_hip_test_radix_segmented(self.handle, _ptr(keys), keys.size, bit_lo, _ptr(tf), tf.size - 1),
+               "bwtc_hip_test_radix_segmented")
+        return keys
 
 
 def host_cpu_slice(numa_node, rank, ranks):

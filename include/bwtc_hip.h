@@ -432,6 +432,26 @@ int bwtc_hip_suffix_array(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t length, 
 int bwtc_hip_test_sort_u32(bwtc_hip_ctx* ctx, uint32_t* keys, uint32_t* vals, uint64_t n, int nbits);
 int bwtc_hip_test_sort_u64(bwtc_hip_ctx* ctx, uint64_t* keys, uint32_t* vals, uint64_t n, int nbits);
 int bwtc_hip_test_scan_u32(bwtc_hip_ctx* ctx, uint32_t* data, uint64_t n);
+/* Unit-test hooks for the radix sorts themselves (radix_sort.hpp: radix_sort_pairs, radix_sort_long,
+ * radix_sort_keys_segmented), called directly on the context's buffers with three-launch scans; host buffers, in place.
+ * Each checks the sort's contract on the host before it launches anything (-1 otherwise), makes the producer's first
+ * digit plane itself from the keys, and guards both buffers of every ping-pong pair with 256 canary bytes behind the
+ * last item: -20 - i when canary i changed (in the order keys, values, second words, planes; two each).
+ *   _pairs: keys = n + n_holes items of key_bytes (4 | 8) in, n out; n_holes > 0: exactly that many keys are all ones
+ *     and do not exist (given values only).  Sorted bits [bit_lo, nbits), 0 <= bit_lo <= nbits <= 8 * key_bytes.
+ *     vals of val_bytes (4 | 2).  values_mode 0: given (n + n_holes in, n out), 1: item i's value is i, 3: n - 1 - i
+ *     (n out; n >= 2 and nbits > bit_lo, the first pass makes them), 2: keys only (vals unused).
+ *     planes 0: none, 1: digit planes, 2: digit planes and the first pass's digits ready in the first.
+ *   _long: items (keys[i], w[i]) ordered by (keys bits [0, kbits), w bits [0, wbits)), 1 <= kbits <= 64,
+ *     1 <= wbits <= 32, w without bits at or above wbits, n >= 2; vals (n out) are n - 1 - i of the item's first place.
+ *     (val_bytes, items_per_thread) is (4, 6), (2, 6) or (2, 8); direct_w as radix_sort_long's.
+ *   _segmented: n = whole tiles of 8192 keys; segment s is tiles [tile_first[s], tile_first[s + 1]), tile_first[0] = 0,
+ *     non-decreasing, tile_first[nseg] = n / 8192; every segment sorted on its own by bits [bit_lo, bit_lo + 16). */
+int bwtc_hip_test_radix_pairs(bwtc_hip_ctx* ctx, void* keys, void* vals, uint64_t n, uint64_t n_holes, int key_bytes, int val_bytes,
+                              int bit_lo, int nbits, int values_mode, int planes);
+int bwtc_hip_test_radix_long(bwtc_hip_ctx* ctx, uint64_t* keys, void* vals, uint32_t* w, uint64_t n, int val_bytes, int items_per_thread,
+                             int kbits, int wbits, int direct_w);
+int bwtc_hip_test_radix_segmented(bwtc_hip_ctx* ctx, uint32_t* keys, uint64_t n, int bit_lo, const uint32_t* tile_first, uint32_t nseg);
 /* Test hook: k range-coder chains over w-elements (w = bit << 15 | probability of the coded bit), chain j = elements
  * [bounds[j], bounds[j+1]), on the GPU lane engine (mode 0; BitEncoder, BitCoders.cpp:59-113, one lane per chain) or by the
  * host's scalar loop (mode 1); bytes of chain j = out[offsets[j] .. offsets[j+1]). */

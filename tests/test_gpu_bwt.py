@@ -21,10 +21,27 @@ def _load(name):
 
 # ---- primitives --------------------------------------------------------------------------
 
-@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 4095, 4096, 4097, 100000, (1 << 20) + 3, 30000001])
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 4095, 4096, 4097, 100000, (1 << 20) + 3, 30000001,
+                               # kScanRawTiles tiles of 4096 items: k_scan_apply<true> hands over to k_scan_single + k_scan_apply<false>
+                               4096 * 4096 - 1, 4096 * 4096, 4096 * 4096 + 1,
+                               pytest.param(("total", 3 * 4096 + 5), id="total_2pow32_minus_1"),
+                               pytest.param(("last", 5 * 4096), id="all_zero_but_the_last_item")])
 def test_scan(hip_ctx, n):
-    rng = np.random.default_rng(n)
-    d = rng.integers(0, 1000 if n < 4000000 else 100, n).astype(np.uint32)      # the total fits 32 bits (the scan's contract)
+    """exclusive_scan_u32 against numpy's cumsum; 4096^2 -1/0/+1 items is the kScanRawTiles switch, where k_scan_apply<true>
+    hands over to k_scan_single + k_scan_apply<false>; one total of exactly 2^32 - 1; one input that is zero but for its
+    last item (every tile total 0)."""
+    if isinstance(n, tuple):
+        kind, n = n
+        d = np.zeros(n, np.uint32)
+        if kind == "total":                     # the largest total the contract allows, spread over every tile
+            d[:] = (1 << 32) // n
+            d[-1] += (1 << 32) - 1 - int(d.sum(dtype=np.uint64))
+            assert int(d.sum(dtype=np.uint64)) == (1 << 32) - 1
+        else:                                   # every tile's total is 0 but the last's
+            d[-1] = 0xFFFFFFFF
+    else:
+        rng = np.random.default_rng(n)
+        d = rng.integers(0, 1000 if n < 4000000 else 100, n).astype(np.uint32)      # the total fits 32 bits (the scan's contract)
     got = hip_ctx.test_scan(d)
     want = np.concatenate([np.zeros(1, np.uint64), np.cumsum(d[:-1], dtype=np.uint64)]).astype(np.uint32)
     assert (got == want).all()
