@@ -1597,9 +1597,142 @@ __global__ __launch_bounds__(kWinTPB) void k_scatter_dense(u32* __restrict__ ran
   for (u32 i = threadIdx.x; i < count; i += kWinTPB) { const u64 x = s_r[i]; rank[(u32)(x >> 32)] = (u32)x; }
 }
 
+// ---------------------------------------------------------------------------------------
+// Runs.  k[s] = number of positions from s on that hold T[s] (the run ends at n at the latest).  A group whose
+// members share c^h holds exactly the suffixes with k >= h, and their order is known in closed form: the members whose
+// run is followed by something smaller (or by the end of T) first, by ascending k, then the others by descending k;
+// members equal in that come from different runs, share exactly k characters and are ordered by the rank of the
+// run's tail, rank[s + k].  So ONE round (the run step, mode 1) gives such members the second key (type, k | n - k)
+// instead of rank[s + h] + 1 -- a bit more than a rank needs -- and does not double the list's depth; every later
+// round (mode 2) looks a member with k >= h_split up at rank[s + max(h, k)] instead of rank[s + h].
+// ---------------------------------------------------------------------------------------
+struct RunKeys { const u32* k; u32 h_split; int mode; };   // mode 0: no runs in play (k is not read); 1: the run step; 2: a round after it
+__device__ __forceinline__ u32 run_offset(const RunKeys& rk, u32 s, u32 h) {
+  if (rk.mode != 2) return h;
+  const u32 kk = rk.k[s];
+  return kk >= rk.h_split ? max(h, kk) : h;
+}
+// the second key of suffix s in a round at depth h (b2: the key's bits, one more than a rank's in the run step);
+// rank == nullptr (a run step before rank[] is complete): the members without a long run keep their group
+__device__ __forceinline__ u64 run_key2(const RunKeys& rk, const u32* __restrict__ rank, const u8* __restrict__ T,
+                                        u32 s, u32 n, u32 h, int b2) {
+  if (rk.mode == 1) {
+    const u32 kk = rk.k[s];
+    if (kk >= h) {
+      const u64 e = (u64)s + kk;
+      const bool falling = e >= (u64)n || T[e] < T[s];
+      return falling ? (u64)kk : (1ull << (b2 - 1)) | (u64)(n - kk);
+    }
+  }
+  if (!rank) return 0ull;
+  const u64 t = (u64)s + run_offset(rk, s, h);
+  return t < (u64)n ? (u64)rank[t] + 1ull : 0ull;
+}
+
+// The run-length pass, three launches over tiles of kRunTile positions (256 threads x 64 consecutive bytes, 16-byte loads).
+// A position p in [1, n) is a run start when T[p] != T[p-1]; k[s] = (first run start behind s, or n) - s.
+constexpr u32 kRunTile = 16384, kRunTPB = 256, kRunNone = 0xFFFFFFFFu;
+// the 64 positions from `at` on (a multiple of 64): bit j set = position at + j starts a run
+__device__ __forceinline__ u64 run_starts(const u8* __restrict__ T, u32 at, u32 n) {
+  if (at >= n) return 0ull;
+  u32 prev = at ? T[at - 1u] : 0u;
+  u64 mask = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const u32 a = at + 16u * q;
+    if (a >= n) break;                                  // (T is padded: a 16-byte load that begins below n is the arena's)
+    const uint4 v = *reinterpret_cast<const uint4*>(T + a);
+    const u32 w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const u32 c = (w[j >> 2] >> (8 * (j & 3))) & 255u;
+      if (c != prev) mask |= 1ull << (16 * q + j);
+      prev = c;
+    }
+  }
+  if (at == 0) mask &= ~1ull;                           // position 0 starts no run: nothing lies before it
+  const u32 left = n - at;                              // positions at or past n are not the text's
+  if (left < 64u) mask &= (1ull << left) - 1ull;
+  return mask;
+}
+// launch 1: first[t] = the first run start in tile t, or none
+__global__ __launch_bounds__(kRunTPB) void k_run_tiles(const u8* __restrict__ T, u32 n, u32* __restrict__ first) {
+  __shared__ u32 s_min[kRunTPB / kWave];
+  const u32 at = blockIdx.x * kRunTile + threadIdx.x * 64u;
+  const u64 mask = run_starts(T, at, n);
+  u32 f = mask ? at + (u32)__builtin_ctzll(mask) : kRunNone;
+  for (int o = kWave / 2; o > 0; o >>= 1) f = min(f, (u32)__shfl_xor(f, o, kWave));
+  if ((threadIdx.x & (kWave - 1)) == 0) s_min[threadIdx.x / kWave] = f;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (u32 w = 1; w < kRunTPB / kWave; ++w) f = min(f, s_min[w]);
+    first[blockIdx.x] = f;
+  }
+}
+// launch 2 (one workgroup): behind[t] = the first run start in a tile after t, or n -- a right-to-left carry
+__global__ __launch_bounds__(1024) void k_run_carry(const u32* __restrict__ first, u32 tiles, u32 n, u32* __restrict__ behind) {
+  __shared__ u32 s_part[1024];
+  const u32 per = (tiles + 1023u) / 1024u;
+  const u32 lo = min(tiles, threadIdx.x * per), hi = min(tiles, lo + per);
+  u32 f = kRunNone;
+  for (u32 t = lo; t < hi; ++t) f = min(f, first[t]);
+  s_part[threadIdx.x] = f;
+  __syncthreads();
+  if (threadIdx.x == 0) {                               // exclusive suffix minimum of the 1024 parts
+    u32 run = kRunNone;
+    for (int i = 1023; i >= 0; --i) { const u32 v = s_part[i]; s_part[i] = run; run = min(run, v); }
+  }
+  __syncthreads();
+  u32 run = s_part[threadIdx.x];
+  for (u32 t = hi; t > lo; --t) {
+    behind[t - 1u] = run == kRunNone ? n : run;
+    run = min(run, first[t - 1u]);
+  }
+}
+// launch 3: k[] of the tile (coalesced 4-byte stores), and the block's longest run
+__global__ __launch_bounds__(kRunTPB) void k_run_lengths(const u8* __restrict__ T, u32 n, const u32* __restrict__ behind,
+                                                          u32* __restrict__ k, u32* __restrict__ longest) {
+  __shared__ u64 s_mask[kRunTPB];
+  __shared__ u32 s_next[kRunTPB];                      // the first run start behind the thread's 64 positions
+  __shared__ u32 s_wave[kRunTPB / kWave];
+  const u32 base = blockIdx.x * kRunTile;
+  const u32 at = base + threadIdx.x * 64u;
+  const u64 mask = run_starts(T, at, n);
+  s_mask[threadIdx.x] = mask;
+  // suffix minimum of the threads' first run starts: inside the wave by shuffles, across the four waves through LDS
+  const u32 lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  u32 incl = mask ? at + (u32)__builtin_ctzll(mask) : kRunNone;
+  for (int o = 1; o < kWave; o <<= 1) {
+    const u32 t = __shfl_down(incl, o, kWave);
+    if (lane + o < (u32)kWave) incl = min(incl, t);
+  }
+  if (lane == 0) s_wave[wave] = incl;
+  u32 excl = __shfl_down(incl, 1, kWave);
+  if (lane == kWave - 1) excl = kRunNone;
+  __syncthreads();
+  for (u32 w = wave + 1; w < kRunTPB / kWave; ++w) excl = min(excl, s_wave[w]);
+  if (excl == kRunNone) excl = behind[blockIdx.x];
+  s_next[threadIdx.x] = excl;
+  __syncthreads();
+  u32 best = 0;
+  for (u32 j = 0; j < kRunTile / kRunTPB; ++j) {
+    const u32 q = base + j * kRunTPB + threadIdx.x;     // chunk j * 4 + wave of the tile, bit `lane`
+    if (q >= n) break;
+    const u32 c = j * (kRunTPB / 64u) + wave;
+    const u64 later = lane < 63u ? s_mask[c] >> (lane + 1u) : 0ull;
+    const u32 nd = later ? q + 1u + (u32)__builtin_ctzll(later) : s_next[c];
+    const u32 kk = min(nd, n) - q;
+    k[q] = kk;
+    best = max(best, kk);
+  }
+  for (int o = kWave / 2; o > 0; o >>= 1) best = max(best, (u32)__shfl_xor(best, o, kWave));
+  if (lane == 0 && best) atomicMax(longest, best);
+}
+
 // Dense route, step 3 (after ALL of rank[] is updated): the next round's sort input, written
 // over the records.  Record p of suffix s with dense group number grp (all ones: finished)
-// becomes key = grp << b2 | rank[s+h]+1 (0 when s+h is past the end) | T[s-1] << 56 (emit),
+// becomes key = grp << b2 | rank[s+h]+1 (0 when s+h is past the end; with runs in play run_key2: the run step's
+// closed-form key, or the look-up at the member's own offset) | T[s-1] << 56 (emit),
 // value = s; finished suffixes become the all-ones key, which the sort's first pass drops.
 // The records are in window order of s and h is small against a window at the dense stage, so
 // rank[s+h] and T[s-1] are read from the window being swept, not at random.  The chunk's items
@@ -1607,7 +1740,7 @@ __global__ __launch_bounds__(kWinTPB) void k_scatter_dense(u32* __restrict__ ran
 __global__ __launch_bounds__(kWinTPB) void k_gather_dense(u64* __restrict__ rec, u32* __restrict__ val,
                                                           const u32* __restrict__ rank,
                                                           const u8* __restrict__ T, u32 m, u32 n, u32 h,
-                                                          int b2, int emit, int bin_shift) {
+                                                          int b2, int emit, int bin_shift, RunKeys rk) {
   __shared__ u32 s_cnt[256], scr[kWinTPB / kWave + 1];
   __shared__ u32 s_s[kWinTile], s_g[kWinTile];
   u32 blk;
@@ -1633,10 +1766,9 @@ __global__ __launch_bounds__(kWinTPB) void k_gather_dense(u64* __restrict__ rec,
     const u32 ss = s_s[i], gg = s_g[i];
     u64 key = ~0ull;
     if (gg != 0xFFFFFFFFu) {
-      const u64 t = (u64)ss + (u64)h;
-      const u32 r = t < (u64)n ? rank[t] + 1u : 0u;
+      const u64 r = run_key2(rk, rank, T, ss, n, h, b2);
       const u32 c = (emit && ss) ? T[ss - 1u] : 0u;
-      key = ((u64)gg << b2) | (u64)r | ((u64)c << 56);
+      key = ((u64)gg << b2) | r | ((u64)c << 56);
     }
     rec[base + i] = key;
     val[base + i] = ss;
@@ -1653,8 +1785,17 @@ __global__ __launch_bounds__(256) void k_gather_key2(const u32* __restrict__ aid
                                                      const u32* __restrict__ rank,
                                                      const u8* __restrict__ achr,
                                                      u64* __restrict__ key, u32 m, u32 n, u32 h,
-                                                     int b2) {
+                                                     int b2, RunKeys rk, const u8* __restrict__ T) {
   const u32 p0 = blockIdx.x * (256u * kSimpleE) + threadIdx.x;
+  if (rk.mode != 0) {
+    // a block with long runs (see RunKeys): the run step's keys, or the later rounds' look-ups at each member's own offset
+#pragma unroll
+    for (int e = 0; e < kSimpleE; ++e) {
+      const u32 p = p0 + e * 256u;
+      if (p < m) key[p] = ((u64)agrp[p] << b2) | run_key2(rk, rank, T, aidx[p], n, h, b2) | (achr ? (u64)achr[p] << 56 : 0ull);
+    }
+    return;
+  }
   u64 t[kSimpleE];
   u32 r[kSimpleE], g[kSimpleE];
 #pragma unroll
@@ -1678,14 +1819,21 @@ __global__ __launch_bounds__(256) void k_gather_key2(const u32* __restrict__ aid
 // suffixes equal on those characters the one that ends there comes first, shortest first.
 __global__ __launch_bounds__(256) void k_gather_text(const u32* __restrict__ aidx, const u32* __restrict__ agrp,
                                                      const u8* __restrict__ T, const u8* __restrict__ achr,
-                                                     u64* __restrict__ key, u32 m, u32 n, u32 h, u32 c) {
+                                                     u64* __restrict__ key, u32 m, u32 n, u32 h, u32 c, RunKeys rk) {
   const u32 p = blockIdx.x * 256u + threadIdx.x;
   if (p >= m) return;
   const u32 s = aidx[p];
   u64 c0, c1;
-  fin_chars(T, s + h, n, &c0, &c1);                      // s + h < 2^31: h stays small in text rounds
+  // s + h < 2^31: h stays small in text rounds; a run's member reads behind its run (RunKeys), which may be anywhere up to n:
+  // its sub-group shares its k characters and what the text rounds since the run step (at depth h_split) have compared
+  u64 at = (u64)s + h;
+  if (rk.mode == 2) {                                    // (rank[] is refined between rounds, the text is not: max(h, k) would read the same characters again)
+    const u32 kk = rk.k[s];
+    if (kk >= rk.h_split) at = (u64)s + kk + (h - rk.h_split);
+  }
+  fin_chars(T, (u32)min(at, (u64)n), n, &c0, &c1);
   const u64 chars = c0 >> (64u - 8u * c);
-  const u64 end = (u64)s + h + c;
+  const u64 end = at + c;
   const u32 over = end > (u64)n ? (u32)min((u64)c, end - (u64)n) : 0u;
   key[p] = ((u64)agrp[p] << (8u * c + 4u)) | (chars << 4) | (u64)(c - over) | (achr ? (u64)achr[p] << 56 : 0ull);
 }
@@ -1742,7 +1890,7 @@ static u64 align_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
 
 struct ArenaPlan {
   u64 off_T, off_out, off_in, off_SA, off_rank, off_R1, off_R2, off_V0, off_V1, off_G0, off_G1,
-      off_GRP, off_C0, off_C1, off_P0, off_P1, off_W0, off_W1, off_table, off_partial, off_aggA, off_aggB, off_aggC, off_agg_part, off_small, off_ent, off_comp, off_sweep, off_parkS, off_parkHP, off_hardS, off_hardHP, off_hardC, off_LP0, off_LH0, off_LH1, off_LC1, off_US, off_UR, off_pairs, off_codes, total;
+      off_GRP, off_C0, off_C1, off_P0, off_P1, off_W0, off_W1, off_table, off_partial, off_aggA, off_aggB, off_aggC, off_agg_part, off_small, off_ent, off_comp, off_sweep, off_parkS, off_parkHP, off_hardS, off_hardHP, off_hardC, off_LP0, off_LH0, off_LH1, off_LC1, off_US, off_UR, off_pairs, off_codes, off_runK, off_runF, off_runB, total;
 };
 
 static ArenaPlan plan_arena(u64 cap) {
@@ -1793,6 +1941,10 @@ static ArenaPlan plan_arena(u64 cap) {
   a.off_UR = take(lcap * 4);
   a.off_pairs = take((u64)kPairReplicas * 65536 * 4);
   a.off_codes = take((u64)kCodeRows * 256 * 4);
+  a.off_runK = take(cap * 4);            // runs: k[] of every suffix, and the run-length pass's two words per tile
+  const u64 run_tiles = (cap + kRunTile - 1) / kRunTile + 1;
+  a.off_runF = take(run_tiles * 4);
+  a.off_runB = take(run_tiles * 4);
   a.total = o;
   return a;
 }
@@ -1855,6 +2007,9 @@ int BwtEngine::init(int dev, u32 max_block_size) {
   d_UR = reinterpret_cast<u32*>(base + a.off_UR);
   d_pairs = reinterpret_cast<u32*>(base + a.off_pairs);
   d_codes = reinterpret_cast<u32*>(base + a.off_codes);
+  d_runK = reinterpret_cast<u32*>(base + a.off_runK);
+  d_runF = reinterpret_cast<u32*>(base + a.off_runF);
+  d_runB = reinterpret_cast<u32*>(base + a.off_runB);
   {
     const char* e = std::getenv("BWTC_HIP_SORT");
     use_sweep = e && std::strcmp(e, "sweep") == 0;
@@ -1896,6 +2051,7 @@ int BwtEngine::init(int dev, u32 max_block_size) {
     if (std::getenv("BWTC_HIP_FIN_WORDS")) fin_words = std::min(4, std::max(2, std::atoi(std::getenv("BWTC_HIP_FIN_WORDS"))));
     if (std::getenv("BWTC_HIP_LONG_DIRECT")) long_direct = std::getenv("BWTC_HIP_LONG_DIRECT")[0] != '0';
     if (std::getenv("BWTC_HIP_FIN_ROUNDS")) fin_rounds = std::min(4, std::max(1, std::atoi(std::getenv("BWTC_HIP_FIN_ROUNDS"))));
+    run_ranks = !(std::getenv("BWTC_HIP_RUNS") && std::getenv("BWTC_HIP_RUNS")[0] == '0');
     local_rounds = !(std::getenv("BWTC_HIP_LOCAL_ROUNDS") && std::getenv("BWTC_HIP_LOCAL_ROUNDS")[0] == '0');
     if (std::getenv("BWTC_HIP_FIN_FLOOR")) fin_floor = (u32)std::max(0, std::atoi(std::getenv("BWTC_HIP_FIN_FLOOR")));
     if (std::getenv("BWTC_HIP_TEXT_ROUNDS")) { text_rounds = std::max(0, std::atoi(std::getenv("BWTC_HIP_TEXT_ROUNDS"))); text_rounds_fixed = true; }
@@ -2163,7 +2319,7 @@ void BwtEngine::scatter_rank_pairs(u32* pairs, u32* tmp, u32 m, u32 n) {
 template <typename K, bool INIT>
 int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len, K kmask,
                          RankBuffers& rb, RrEmit re, bool emit, u64 h_next, RankResult* res, u32 split,
-                         const RrLong* lg, bool text, bool carry_in, bool raw_out) {
+                         const RrLong* lg, bool text, bool carry_in, bool raw_out, int run_mode) {
   hipStream_t st = stream;
   u32* counts = d_small + kSmallCounts;
   const u32 tiles = ceil_div(m, kRrTile);
@@ -2202,7 +2358,13 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
   const int nbits = b1 + b2;
   // a key of more than 56 bits has no room for the carried character (blocks above 256 MiB with many groups): the
   // next list then goes without, and its ranking reads T[s-1] for what it finishes
-  const bool carry_next = emit && nbits <= 56;
+  // the run step's second key takes one bit more than a rank (RunKeys); a key that would not fit 64 bits: an ordinary round
+  const bool run_now = !INIT && run_mode == 1 && nbits + 1 <= 64;
+  res->ran_run = run_now;
+  const int b2k = run_now ? b2 + 1 : b2;
+  const int kbits = run_now ? nbits + 1 : nbits;
+  const RunKeys rkeys{d_runK, run_now ? 0u : run_split, run_now ? 1 : (run_mode == 2 ? 2 : 0)};
+  const bool carry_next = emit && kbits <= 56;
   res->carry = carry_next;
   const bool dense = !text && dense_route && m_next > 0 && (u64)m_next * 2 >= m && m >= kPairsMin && !use_sweep;
   u32* sa_out = (emit && !fin_active) ? nullptr : d_SA;   // finisher route: the bridge will want the finished suffixes' slots
@@ -2262,17 +2424,18 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
     const int bin_shift = lo > 8 ? lo - 8 : 0;           // the eight bits of s below the window bits
     hipLaunchKernelGGL(k_scatter_dense, dim3(grid), dim3(kWinTPB), 0, st, d_rank, (const u64*)ws, m, bin_shift);
     hipLaunchKernelGGL(k_gather_dense, dim3(grid), dim3(kWinTPB), 0, st, ws, wv, (const u32*)d_rank,
-                       (const u8*)d_T, m, n, (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2,
-                       carry_next ? 1 : 0, bin_shift);
+                       (const u8*)d_T, m, n, (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k,
+                       carry_next ? 1 : 0, bin_shift, rkeys);
     const bool timed = n_sort_events + 2 <= kMaxSortEvents;
     if (timed) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-    sort_pairs<u64>(ws, ws_other, wv, wv_other, m_next, nbits, &res->ks, &res->vs, true, 0, (u64)(m - m_next));
+    sort_pairs<u64>(ws, ws_other, wv, wv_other, m_next, kbits, &res->ks, &res->vs, true, 0, (u64)(m - m_next));
     if (timed) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-    stats.sort_pass_items += (u64)m + (u64)m_next * (u64)std::max(0, (nbits + kRadixBits - 1) / kRadixBits - 1);
+    stats.sort_pass_items += (u64)m + (u64)m_next * (u64)std::max(0, (kbits + kRadixBits - 1) / kRadixBits - 1);
     {
-      const int P = (nbits + kRadixBits - 1) / kRadixBits;
+      const int P = (kbits + kRadixBits - 1) / kRadixBits;
       stats.alg_bytes += sort_bytes(m, 2, 12, 8, digit_planes)                         // window partition of the records
                          + (u64)m * (12 + 4) + (u64)m * (12 + 4 + 1 + 12)             // k_scatter_dense, k_gather_dense
+                         + (rkeys.mode ? (u64)m_next * (4 + (run_now ? 1 : 0)) : 0)    //   ... and k[], the byte behind the run
                          + (u64)m * (8 + 12) + (u64)m_next * 12                        // hole-dropping first pass
                          + sort_bytes(m_next, std::max(0, P - 1), 12, 8, digit_planes);
     }
@@ -2293,12 +2456,27 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
     BWTC_APPLY(0, (u32*)nullptr, (u32*)nullptr, rb.v_free);
     res->carry = emit;
     if (m_next == 0) return 0;
+    if (run_now) {
+      // the run step before rank[] is complete: the members without a long run keep their groups (key 0)
+      res->carry = carry_next;
+      hipLaunchKernelGGL(k_gather_key2, dim3(ceil_div(m_next, 256 * kSimpleE)), dim3(256), 0, st,
+                         (const u32*)rb.v_free, (const u32*)d_GRP, (const u32*)nullptr,
+                         carry_next ? (const u8*)re.achr_out : (const u8*)nullptr, recA, m_next, n,
+                         (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k, rkeys, (const u8*)d_T);
+      sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m_next, kbits, &res->ks, &res->vs, false);
+      stats.sort_pass_items += (u64)m_next * (u64)((kbits + kRadixBits - 1) / kRadixBits);
+      stats.alg_bytes += (u64)m_next * (4 + 4 + 4 + 1 + 1 + 8) + sort_bytes(m_next, (kbits + kRadixBits - 1) / kRadixBits, 12, 8, digit_planes);
+      res->text_chars = 0;
+      res->rec_other = res->ks == recA ? recB : recA;
+      res->v_other = res->vs == rb.v_free ? rb.v_keys : rb.v_free;
+      return 0;
+    }
     const int tbits = b1 + 8 * (int)res->text_chars + 4;
     hipLaunchKernelGGL(k_gather_text, dim3(ceil_div(m_next, 256)), dim3(256), 0, st, (const u32*)rb.v_free, (const u32*)d_GRP,
-                       (const u8*)d_T, emit ? (const u8*)re.achr_out : (const u8*)nullptr, recA, m_next, n, (u32)h_next, res->text_chars);
+                       (const u8*)d_T, emit ? (const u8*)re.achr_out : (const u8*)nullptr, recA, m_next, n, (u32)h_next, res->text_chars, rkeys);
     sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m_next, tbits, &res->ks, &res->vs, false);
     stats.sort_pass_items += (u64)m_next * (u64)((tbits + kRadixBits - 1) / kRadixBits);
-    stats.alg_bytes += (u64)m_next * (4 + 4 + 1 + 16 + 8) + sort_bytes(m_next, (tbits + kRadixBits - 1) / kRadixBits, 12, 8, digit_planes);
+    stats.alg_bytes += (u64)m_next * (4 + 4 + 1 + 16 + 8 + (rkeys.mode ? 4 : 0)) + sort_bytes(m_next, (tbits + kRadixBits - 1) / kRadixBits, 12, 8, digit_planes);
     stats.route |= 4u;
     res->rec_other = res->ks == recA ? recB : recA;
     res->v_other = res->vs == rb.v_free ? rb.v_keys : rb.v_free;
@@ -2316,13 +2494,13 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
   hipLaunchKernelGGL(k_gather_key2, dim3(ceil_div(m_next, 256 * kSimpleE)), dim3(256), 0, st,
                      (const u32*)rb.v_free, (const u32*)d_GRP, (const u32*)d_rank,
                      carry_next ? (const u8*)re.achr_out : (const u8*)nullptr, recA, m_next, n,
-                     (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2);
+                     (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k, rkeys, (const u8*)d_T);
   const bool timed = n_sort_events + 2 <= kMaxSortEvents;
   if (timed) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-  sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m_next, nbits, &res->ks, &res->vs, true);
+  sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m_next, kbits, &res->ks, &res->vs, true);
   if (timed) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-  stats.sort_pass_items += (u64)m_next * (u64)((nbits + kRadixBits - 1) / kRadixBits);
-  stats.alg_bytes += (u64)m_next * (4 + 4 + 4 + 1 + 8) + sort_bytes(m_next, (nbits + kRadixBits - 1) / kRadixBits, 12, 8, digit_planes);
+  stats.sort_pass_items += (u64)m_next * (u64)((kbits + kRadixBits - 1) / kRadixBits);
+  stats.alg_bytes += (u64)m_next * (4 + 4 + 4 + 1 + 8 + (rkeys.mode ? 4 + (run_now ? 1 : 0) : 0)) + sort_bytes(m_next, (kbits + kRadixBits - 1) / kRadixBits, 12, 8, digit_planes);
   res->rec_other = res->ks == recA ? recB : recA;
   res->v_other = res->vs == rb.v_free ? rb.v_keys : rb.v_free;
   return 0;
@@ -2388,6 +2566,7 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
   stats.sort_pass_items = 0;
   stats.route = 0;
   stats.finisher_entries = 0;
+  runs_built = false; run_longest = 0; run_split = 0;   // (nothing of the last block's runs)
   if (n == 0) return 0;
 
   const bool emit = em != nullptr;
@@ -2424,6 +2603,7 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
   rb.aglob_next = d_G0;
   RankResult res;
   res.finish = false;
+  res.ran_run = false;
   u64 h = (u64)plan.k;                    // the next round compares rank[s + h]
 
   // initial sort + ranking
@@ -2608,12 +2788,27 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
     u64 h = h0;
     bool keep_h = keep_first;                // the list is sorted to depth h as it stands (no doubling before the next step)
     int text_left = text_rounds_now;
+    // Runs: a list about to double may hold long runs of one byte, which doubling takes log2(length) rounds over.  k[] and
+    // the block's longest run are made here (once per block, one host wait); a run longer than the depth the first round
+    // establishes gets the run step as that round, before any text round and before rank[] is completed.
+    bool run_try = false;
+    if (run_ranks && doubling && m > 0 && run_split == 0) {
+      const int rcr = build_runs(n);
+      if (rcr) return rcr;
+      const u64 h_first = keep_first ? h0 : h0 * 2;
+      run_try = (u64)run_longest > h_first;
+      if (std::getenv("BWTC_HIP_DEBUG"))
+        std::fprintf(stderr, "runs: longest run %u, the rounds begin at depth %llu: %s\n", run_longest, (unsigned long long)h_first, run_try ? "run step" : "no run step");
+    }
     int text_extra = text_rounds_fixed ? 0 : 12;        // further ones, one at a time, while the list is short (not when BWTC_HIP_TEXT_ROUNDS says how many)
     while (m > 0 || (doubling && local_m > 0)) {
       if (h >= (u64)n * 2 + 64) return -3;   // cannot happen: every group splits by then
       ++stats.rounds;
       stats.active_sum += m;
-      const bool text = text_left > 0 && m > 0;
+      const bool run_req = run_try && m > 0;             // (the first round only)
+      run_try = false;
+      const bool text_round = text_left > 0 && m > 0;
+      const bool text = text_round || (run_req && !ranks_complete);   // the run step reads no rank[]: it does not need the completion either
       const bool raw = !text && !doubling;               // out of text rounds and not allowed to double: hand the list back
       if (std::getenv("BWTC_HIP_DEBUG")) std::fprintf(stderr, "round %u%s: h=%llu m=%u groups=%u\n", stats.rounds, text ? " (text)" : "", (unsigned long long)h, m, res.groups);
       if (!keep_h) h *= 2;
@@ -2644,14 +2839,29 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
       const u64* ks = res.ks;
       const u32* vs = res.vs;
       const bool carried = emit && res.carry;             // this list's keys hold the characters in bits 56..63
-      const int rc2 = rank_step<u64, false>(ks, vs, m, n, 0u, carried ? ((1ull << 56) - 1ull) : ~0ull, rb, re, emit, h, &res, 0u, nullptr, text || raw, carried, raw);
+      // the second keys (RunKeys::mode): the run step, a round behind one, or no runs in play
+      const int rc2 = rank_step<u64, false>(ks, vs, m, n, 0u, carried ? ((1ull << 56) - 1ull) : ~0ull, rb, re, emit, h, &res, 0u, nullptr, text || raw, carried, raw,
+                                            run_req ? 1 : run_split ? 2 : 0);
       if (rc2) return rc2;
       m = res.m;
+      const bool ran = run_req && res.ran_run;
+      if (ran) {
+        // the list is sorted to depth h still: a run's members by their closed-form keys, the others as they were (or by rank[s + h])
+        run_split = (u32)std::min<u64>(h, 0xFFFFFFFFull);
+        stats.route |= 32u;
+        keep_h = true;
+        // rank[] still incomplete: one text round behind the runs first -- a block that is one giant run ends there,
+        // without the completion of rank[] that the first doubling round costs.  Not beside a live local list: its
+        // members' ranks are local_depth deep, and the first doubling look-up must not lie deeper than that (text rounds
+        // raise h; that is why a list with a local list beside it takes none)
+        if (!ranks_complete && text_left == 0 && !text_rounds_fixed && local_m == 0) text_left = 1;
+      }
       if (raw) { *left = m; *h_left = h; return 0; }
       // the local list's doubling step beside the global list's (both read the rank[] this round's ranking step left)
       if (!text && doubling && local_m > 0) { const int rcl = local_pass(n, h, re); if (rcl) return rcl; }
-      if (text) {
-        h += res.text_chars; keep_h = true; --text_left;
+      if (text && !ran) {
+        h += res.text_chars; keep_h = true;
+        if (text_round) --text_left;
         // Out of text rounds with a short list left: a few more cost tens of microseconds each, the doubling rounds
         // cost the completion of rank[] for the whole block first (5 ms per 256 MiB, 16 ms for the 1 GiB text -- the
         // block whose text rounds ended with 10 entries still tied paid it).  Long lists (deep repeats) go on to the
@@ -2680,6 +2890,8 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
     // Groups of hundreds of members on average (a period, one text many times over) are not the finisher's: its loop
     // costs a group's size per member.  The list then goes to the rounds as it is (shallow groups apart).
     const bool giant = res.groups > 0 && (u64)res.m > (u64)res.groups * 64;
+    if (giant && std::getenv("BWTC_HIP_DEBUG"))
+      std::fprintf(stderr, "finisher: skipped, %u entries in %u groups (more than 64 members on average)\n", res.m, res.groups);
     // The shape of the passes.  The comparison loop costs a group's size per member, which is why groups above 256 members
     // are not the finisher's on a real text (most of the block is on its list).  A SHORT list -- the long keys told
     // nearly everything apart: 2.6 % of the generator's text is left -- takes windows of 2048 entries and groups of up to
@@ -2751,6 +2963,43 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
   }
   BWTC_HIP_TRY(hipGetLastError());
   BWTC_HIP_TRY(take_sticky_error());
+  return 0;
+}
+
+// k[] for every suffix of the block, and its longest run (the run-length pass: three launches behind whatever the stream holds).
+static constexpr int kSmallRun = 800;     // the block's longest run
+int BwtEngine::build_runs(u32 n) {
+  if (runs_built) return 0;
+  hipStream_t st = stream;
+  const u32 tiles = ceil_div(n, kRunTile);
+  // (BWTC_HIP_DEBUG: the pass times itself, for scripts/runs_bench.py)
+  const bool timed = std::getenv("BWTC_HIP_DEBUG") != nullptr;
+  struct Events {                                        // (destroyed on every way out)
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  } ev;
+  hipEvent_t& ev0 = ev.a;
+  hipEvent_t& ev1 = ev.b;
+  if (timed) {
+    BWTC_HIP_TRY(hipEventCreate(&ev0));
+    BWTC_HIP_TRY(hipEventCreate(&ev1));
+  }
+  BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallRun, 0, 4, st));
+  if (timed) BWTC_HIP_TRY(hipEventRecord(ev0, st));
+  hipLaunchKernelGGL(k_run_tiles, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, d_runF);
+  hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(1024), 0, st, (const u32*)d_runF, tiles, n, d_runB);
+  hipLaunchKernelGGL(k_run_lengths, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, (const u32*)d_runB, d_runK, d_small + kSmallRun);
+  if (timed) BWTC_HIP_TRY(hipEventRecord(ev1, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallRun, d_small + kSmallRun, 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(wait());
+  if (timed) {
+    float ms = 0.f;
+    BWTC_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+    std::fprintf(stderr, "runs: the run-length pass took %.4f ms for %u suffixes\n", ms, n);
+  }
+  run_longest = h_small[kSmallRun];
+  runs_built = true;
+  stats.alg_bytes += (u64)n * (1 + 1 + 4) + (u64)tiles * 16;   // T read twice, k[] written; the tiles' words written and read
   return 0;
 }
 

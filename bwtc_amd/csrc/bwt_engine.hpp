@@ -401,11 +401,13 @@ struct BwtEngine {
                   bool probe_it, int bit_lo = 0, u64 n_holes = 0, bool plane_ready = false, bool values_descend = false);
   // one ranking step of the suffix sorter (bwt_engine.hip)
   struct RankBuffers { void* rec_keys; void* rec_free; u32* v_keys; u32* v_free; u32* aglob; u32* aglob_next; };
-  struct RankResult { u32 m, groups; u64* ks; u32* vs; void* rec_other; u32* v_other; bool finish; u32 text_chars; bool carry; };
+  struct RankResult { u32 m, groups; u64* ks; u32* vs; void* rec_other; u32* v_other; bool finish; u32 text_chars; bool carry;
+                      bool ran_run; };   // ran_run: the step made the run step's keys (run_mode 1 and the key had room)
   template <typename K, bool INIT>
   int rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len, K kmask, RankBuffers& rb,
                 struct RrEmit re, bool emit, u64 h_next, RankResult* res, u32 split = 0,
-                const struct RrLong* lg = nullptr, bool text = false, bool carry_in = true, bool raw_out = false);
+                const struct RrLong* lg = nullptr, bool text = false, bool carry_in = true, bool raw_out = false,
+                int run_mode = 0);   // run_mode: RunKeys::mode of the next list's second keys
   bool dense_route = true;   // BWTC_HIP_DENSE=0: always the list-order route (random rank[s+h] gather)
   bool digit_planes = true;  // BWTC_HIP_PLANES=0: every histogram pass reads the keys
   int window_bits = 16;      // BWTC_HIP_WINDOW_BITS: rank[] is updated / read in windows of n >> window_bits suffixes
@@ -466,6 +468,14 @@ struct BwtEngine {
   int local_pass(u32 n, u64 h_global, struct RrEmit& re);
   // a raw list (suffix; head slot << 32 | slot) in (S, HP) -> a sorted list the rounds understand, in res / rb
   int dress_list(u32 n, u32 total, u32* S, u64* HP, RankBuffers& rb, RankResult* res, u32 holes = 0);
+  // runs (bwt_engine.hip, RunKeys): long runs of one byte are ranked in closed form by one round, the run step
+  bool run_ranks = true;     // BWTC_HIP_RUNS=0: no run step, k[] is not built
+  u32* d_runK = nullptr;     // k[s]: positions from s on that hold T[s]
+  u32* d_runF = nullptr; u32* d_runB = nullptr;   // the run-length pass's words per tile
+  bool runs_built = false;   // this block: k[] and the longest run are there
+  u32 run_longest = 0;       // this block's longest run
+  u32 run_split = 0;         // this block: the depth of the run step that ran (0: none)
+  int build_runs(u32 n);
   int long_grams_override = 0;   // BWTC_HIP_LONG_G2=N: N grams in the second key word
   void scatter_rank_pairs(u32* pairs, u32* tmp, u32 m, u32 n);
   int load_text(const u8* d_src, u32 ncopy, u32 n, bool reverse, u32* hist_T);

@@ -36,6 +36,10 @@ typedef struct bwtc_hip_stats {
   /* round 4: which way the block went, and the algorithmic bytes of the kernels that ran      */
   uint32_t route;             /* bit 0: long-key initial sort; bit 1: finisher settled the ties;
                                  bit 2: text rounds ran; bit 3: rank[] completed late for doubling rounds;
+                                 bit 4: the long key is the order-1 prefix code (not dense gram codes);
+                                 bit 5: a run step ran -- long runs of one byte were ranked in closed form
+                                        (BWTC_HIP_RUNS=0: never);
+                                 bit 6: the finisher's small groups doubled beside the rounds' list (local list);
                                  bit 7: a finisher list too long for its pass's shape went to the rounds */
   uint32_t finisher_entries;  /* list entries over all finisher passes                      */
   uint64_t alg_bytes;         /* compulsory bytes of the transform's kernels: every array a kernel
