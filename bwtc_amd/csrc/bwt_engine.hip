@@ -1606,7 +1606,7 @@ __global__ __launch_bounds__(kWinTPB) void k_scatter_dense(u32* __restrict__ ran
 // instead of rank[s + h] + 1 -- a bit more than a rank needs -- and does not double the list's depth; every later
 // round (mode 2) looks a member with k >= h_split up at rank[s + max(h, k)] instead of rank[s + h].
 // ---------------------------------------------------------------------------------------
-struct RunKeys { const u32* k; u32 h_split; int mode; };   // mode 0: no runs in play (k is not read); 1: the run step; 2: a round after it
+struct RunKeys { const u32* k; u32 h_split; int mode; u32 p; };   // mode 0: no runs in play (k is not read); 1: the run step; 2: a round after it; p: the period k[] was made for (1: runs)
 __device__ __forceinline__ u32 run_offset(const RunKeys& rk, u32 s, u32 h) {
   if (rk.mode != 2) return h;
   const u32 kk = rk.k[s];
@@ -1620,7 +1620,7 @@ __device__ __forceinline__ u64 run_key2(const RunKeys& rk, const u32* __restrict
     const u32 kk = rk.k[s];
     if (kk >= h) {
       const u64 e = (u64)s + kk;
-      const bool falling = e >= (u64)n || T[e] < T[s];
+      const bool falling = e >= (u64)n || T[e] < T[e - rk.p];   // (p = 1: T[e - 1] is the run's byte, T[s]; kk >= h >= p)
       return falling ? (u64)kk : (1ull << (b2 - 1)) | (u64)(n - kk);
     }
   }
@@ -1727,6 +1727,194 @@ __global__ __launch_bounds__(kRunTPB) void k_run_lengths(const u8* __restrict__ 
   }
   for (int o = kWave / 2; o > 0; o >>= 1) best = max(best, (u32)__shfl_xor(best, o, kWave));
   if (lane == 0 && best) atomicMax(longest, best);
+}
+
+// ---------------------------------------------------------------------------------------
+// Periods.  The run rule holds for every period p >= 1 (tests/periodmodel.py): position q is a break when q >= p and
+// T[q] != T[q - p]; k_p[s] = (the first break at or behind s + p, or n) - s is the number of leading characters of
+// suffix s that are p-periodic.  Once a list is sorted to a depth h >= p, a group holds members with k_p >= h only or
+// none, and those are ordered as a run's: the falling ones (the end of T, or T[s + k] < T[s + k - p]) by ascending k,
+// then the rising ones by descending k, ties by rank[s + k].  So the period step is the run step over k_p[] (which takes
+// k[]'s place in d_runK) with RunKeys::p = p.
+//
+// The period-length pass has the run-length pass's shape -- tiles of kRunTile positions, 64 per thread, 16-byte loads,
+// a right-to-left carry in one workgroup, coalesced stores -- with two differences: the break mask compares with the
+// text p bytes back, a second stream read by aligned 16-byte loads and shifted into place, and a thread works out the
+// first break at or behind x for the positions x of its tile and stores it as k_p[x - p]: nobody looks ahead into the
+// next chunks, and the tiles cover x in [p, n + p).
+// ---------------------------------------------------------------------------------------
+__device__ __forceinline__ u32 differing_bytes(u32 x) {   // bit j set = byte j of x is not zero
+  return ((x & 0x000000FFu) ? 1u : 0u) | ((x & 0x0000FF00u) ? 2u : 0u) | ((x & 0x00FF0000u) ? 4u : 0u) | ((x & 0xFF000000u) ? 8u : 0u);
+}
+// the words of T from byte `from` on (sixteen of them), out of the twenty aligned words w[] that begin at from & ~15:
+// WO whole words and bs bytes further on
+template <int WO>
+__device__ __forceinline__ u64 period_compare(const u32 (&a)[16], const u32 (&w)[20], u32 bs) {
+  u64 mask = 0;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const u64 two = ((u64)w[i + WO + 1] << 32) | (u64)w[i + WO];
+    const u32 b = (u32)(two >> (8u * bs));
+    mask |= (u64)differing_bytes(a[i] ^ b) << (4 * i);
+  }
+  return mask;
+}
+// the 64 positions from `at` on (a multiple of 64): bit j set = position at + j is a break of period p
+__device__ __forceinline__ u64 period_breaks(const u8* __restrict__ T, u32 at, u32 n, u32 p) {
+  if (at >= n || at + 64u <= p) return 0ull;
+  u64 mask = 0;
+  if (at < p) {
+    // the one chunk of the block that holds position p: nothing lies p bytes before its first positions
+    for (u32 j = p - at; j < 64u && at + j < n; ++j)
+      if (T[at + j] != T[at + j - p]) mask |= 1ull << j;
+    return mask;
+  }
+  const u32 from = at - p;                              // the second stream: T[from ...] beside T[at ...]
+  const u32 a0 = from & ~15u, sh = from & 15u;          // (sh is the same for every thread: at is a multiple of 64)
+  u32 a[16], w[20];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {                         // (T is padded: a 16-byte load that begins below n is the arena's)
+    const u32 x = at + 16u * q;
+    const uint4 v = x < n ? *reinterpret_cast<const uint4*>(T + x) : make_uint4(0u, 0u, 0u, 0u);
+    a[4 * q] = v.x; a[4 * q + 1] = v.y; a[4 * q + 2] = v.z; a[4 * q + 3] = v.w;
+  }
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {
+    const u32 x = a0 + 16u * q;
+    const uint4 v = x < n ? *reinterpret_cast<const uint4*>(T + x) : make_uint4(0u, 0u, 0u, 0u);
+    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+  }
+  const u32 bs = sh & 3u;
+  switch (sh >> 2) {
+    case 0: mask = period_compare<0>(a, w, bs); break;
+    case 1: mask = period_compare<1>(a, w, bs); break;
+    case 2: mask = period_compare<2>(a, w, bs); break;
+    default: mask = period_compare<3>(a, w, bs); break;
+  }
+  const u32 left = n - at;                              // positions at or past n are not the text's
+  if (left < 64u) mask &= (1ull << left) - 1ull;
+  return mask;
+}
+// launch 1: first[t] = the first break in tile t, or none (tiles past n included: the lengths' tiles reach n + p)
+__global__ __launch_bounds__(kRunTPB) void k_period_tiles(const u8* __restrict__ T, u32 n, u32 p, u32* __restrict__ first) {
+  __shared__ u32 s_min[kRunTPB / kWave];
+  const u32 at = blockIdx.x * kRunTile + threadIdx.x * 64u;
+  const u64 mask = period_breaks(T, at, n, p);
+  u32 f = mask ? at + (u32)__builtin_ctzll(mask) : kRunNone;
+  for (int o = kWave / 2; o > 0; o >>= 1) f = min(f, (u32)__shfl_xor(f, o, kWave));
+  if ((threadIdx.x & (kWave - 1)) == 0) s_min[threadIdx.x / kWave] = f;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (u32 w = 1; w < kRunTPB / kWave; ++w) f = min(f, s_min[w]);
+    first[blockIdx.x] = f;
+  }
+}
+// launch 2 is the runs' carry, k_run_carry: behind[t] = the first break in a tile after t, or n
+// launch 3: k_p[x - p] for the positions x of the tile (coalesced 4-byte stores), and the block's longest k_p
+__global__ __launch_bounds__(kRunTPB) void k_period_lengths(const u8* __restrict__ T, u32 n, u32 p, const u32* __restrict__ behind,
+                                                             u32* __restrict__ k, u32* __restrict__ longest) {
+  __shared__ u64 s_mask[kRunTPB];
+  __shared__ u32 s_next[kRunTPB];                      // the first break behind the thread's 64 positions
+  __shared__ u32 s_wave[kRunTPB / kWave];
+  const u32 base = blockIdx.x * kRunTile;
+  const u32 at = base + threadIdx.x * 64u;
+  const u64 mask = period_breaks(T, at, n, p);
+  s_mask[threadIdx.x] = mask;
+  const u32 lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  u32 incl = mask ? at + (u32)__builtin_ctzll(mask) : kRunNone;
+  for (int o = 1; o < kWave; o <<= 1) {
+    const u32 t = __shfl_down(incl, o, kWave);
+    if (lane + o < (u32)kWave) incl = min(incl, t);
+  }
+  if (lane == 0) s_wave[wave] = incl;
+  u32 excl = __shfl_down(incl, 1, kWave);
+  if (lane == kWave - 1) excl = kRunNone;
+  __syncthreads();
+  for (u32 w = wave + 1; w < kRunTPB / kWave; ++w) excl = min(excl, s_wave[w]);
+  if (excl == kRunNone) excl = behind[blockIdx.x];
+  s_next[threadIdx.x] = excl;
+  __syncthreads();
+  u32 best = 0;
+  for (u32 j = 0; j < kRunTile / kRunTPB; ++j) {
+    const u32 x = base + j * kRunTPB + threadIdx.x;     // chunk j * 4 + wave of the tile, bit `lane`
+    if (x < p) continue;
+    const u32 q = x - p;                                // the suffix whose periodic stretch ends at the first break from x on
+    if (q >= n) break;
+    const u32 c = j * (kRunTPB / 64u) + wave;
+    const u64 here = s_mask[c] >> lane;
+    const u32 nd = here ? x + (u32)__builtin_ctzll(here) : s_next[c];
+    const u32 kk = min(nd, n) - q;
+    if (k) k[q] = kk;                                   // (k == nullptr: a trial, for the longest stretch alone)
+    best = max(best, kk);
+  }
+  for (int o = kWave / 2; o > 0; o >>= 1) best = max(best, (u32)__shfl_xor(best, o, kWave));
+  if (lane == 0 && best) atomicMax(longest, best);
+}
+
+// The period finder: one pass over a sorted list.  Neighbouring entries of one group (equal keys under kmask) that lie
+// d positions apart, 2 <= d <= kPeriodMax, vote for d: inside a stretch of period p the members of a group lie p apart
+// and are neighbours.  A histogram in LDS per workgroup, then one global add per non-empty bin, the workgroups
+// beginning at different bins.
+constexpr u32 kVoteTPB = 256, kVoteTile = 16384, kVoteBins = kPeriodMax + 1;
+constexpr int kSmallPeriod = 802;      // d_small: the block's longest k_p; [803] the probe's flag; [804..805] the finder's winner and its votes
+constexpr u32 kPeriodMinVotes = 256;   // the winner's votes buy the period-length pass from max(this, n / 64) on (find_period)
+constexpr u64 kPeriodWorth = 8;        // a voted period's longest stretch must reach this many times max(the first round's depth, p)
+__global__ __launch_bounds__(kVoteTPB) void k_period_votes(const u64* __restrict__ ks, const u32* __restrict__ vs, u32 m, u64 kmask,
+                                                           u32* __restrict__ table) {
+  __shared__ u32 s_bin[kVoteBins];
+  for (u32 b = threadIdx.x; b < kVoteBins; b += kVoteTPB) s_bin[b] = 0;
+  __syncthreads();
+  const u32 base = blockIdx.x * kVoteTile;
+  for (u32 j = 0; j < kVoteTile / kVoteTPB; ++j) {
+    const u32 i = base + j * kVoteTPB + threadIdx.x;
+    if (i + 1u >= m) break;
+    if (((ks[i] ^ ks[i + 1u]) & kmask) != 0ull) continue;
+    const u32 a = vs[i], b = vs[i + 1u];
+    const u32 d = a > b ? a - b : b - a;
+    if (d >= 2u && d <= kPeriodMax) atomicAdd(&s_bin[d], 1u);
+  }
+  __syncthreads();
+  const u32 turn = (blockIdx.x * 67u) % kVoteBins;
+  for (u32 b = threadIdx.x; b < kVoteBins; b += kVoteTPB) {
+    u32 bb = b + turn;
+    if (bb >= kVoteBins) bb -= kVoteBins;
+    const u32 c = s_bin[bb];
+    if (c) atomicAdd(&table[bb], c);
+  }
+}
+// The probe before the pass: thread i walks the window of `span` positions from p + i * span on and stops at its first
+// break; a window without one sets the flag, and threads that find it set do not begin.
+__global__ __launch_bounds__(256) void k_period_probe(const u8* __restrict__ T, u32 n, u32 p, u32 span, u32 windows, u32* flag) {
+  const u32 i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= windows) return;
+  if (*reinterpret_cast<volatile u32*>(flag)) return;
+  const u64 x0 = (u64)p + (u64)i * span;
+  if (x0 + span > (u64)n) return;
+  const u8* a = T + x0;
+  const u8* b = a - p;
+  for (u32 j = 0; j < span; ++j)
+    if (a[j] != b[j]) return;
+  atomicOr(flag, 1u);
+}
+// (one workgroup) out[0] = the distance with the most votes (the smallest of equals), out[1] = its votes
+__global__ __launch_bounds__(1024) void k_period_winner(const u32* __restrict__ table, u32* __restrict__ out) {
+  __shared__ u64 s_best[1024];
+  u64 best = 0;
+  for (u32 b = threadIdx.x; b < kVoteBins; b += 1024u) {
+    const u64 v = ((u64)table[b] << 32) | (u64)(kVoteBins - b);
+    best = v > best ? v : best;
+  }
+  s_best[threadIdx.x] = best;
+  __syncthreads();
+  for (u32 o = 512; o > 0; o >>= 1) {
+    if (threadIdx.x < o) { const u64 v = s_best[threadIdx.x + o]; if (v > s_best[threadIdx.x]) s_best[threadIdx.x] = v; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    const u64 v = s_best[0];
+    out[0] = (v >> 32) ? kVoteBins - (u32)v : 0u;
+    out[1] = (u32)(v >> 32);
+  }
 }
 
 // Dense route, step 3 (after ALL of rank[] is updated): the next round's sort input, written
@@ -1890,7 +2078,7 @@ static u64 align_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
 
 struct ArenaPlan {
   u64 off_T, off_out, off_in, off_SA, off_rank, off_R1, off_R2, off_V0, off_V1, off_G0, off_G1,
-      off_GRP, off_C0, off_C1, off_P0, off_P1, off_W0, off_W1, off_table, off_partial, off_aggA, off_aggB, off_aggC, off_agg_part, off_small, off_ent, off_comp, off_sweep, off_parkS, off_parkHP, off_hardS, off_hardHP, off_hardC, off_LP0, off_LH0, off_LH1, off_LC1, off_US, off_UR, off_pairs, off_codes, off_runK, off_runF, off_runB, total;
+      off_GRP, off_C0, off_C1, off_P0, off_P1, off_W0, off_W1, off_table, off_partial, off_aggA, off_aggB, off_aggC, off_agg_part, off_small, off_ent, off_comp, off_sweep, off_parkS, off_parkHP, off_hardS, off_hardHP, off_hardC, off_LP0, off_LH0, off_LH1, off_LC1, off_US, off_UR, off_pairs, off_codes, off_runK, off_runF, off_runB, off_votes, total;
 };
 
 static ArenaPlan plan_arena(u64 cap) {
@@ -1945,6 +2133,7 @@ static ArenaPlan plan_arena(u64 cap) {
   const u64 run_tiles = (cap + kRunTile - 1) / kRunTile + 1;
   a.off_runF = take(run_tiles * 4);
   a.off_runB = take(run_tiles * 4);
+  a.off_votes = take((u64)kVoteBins * 4);   // periods: the finder's vote table
   a.total = o;
   return a;
 }
@@ -2010,6 +2199,7 @@ int BwtEngine::init(int dev, u32 max_block_size) {
   d_runK = reinterpret_cast<u32*>(base + a.off_runK);
   d_runF = reinterpret_cast<u32*>(base + a.off_runF);
   d_runB = reinterpret_cast<u32*>(base + a.off_runB);
+  d_votes = reinterpret_cast<u32*>(base + a.off_votes);
   {
     const char* e = std::getenv("BWTC_HIP_SORT");
     use_sweep = e && std::strcmp(e, "sweep") == 0;
@@ -2052,6 +2242,8 @@ int BwtEngine::init(int dev, u32 max_block_size) {
     if (std::getenv("BWTC_HIP_LONG_DIRECT")) long_direct = std::getenv("BWTC_HIP_LONG_DIRECT")[0] != '0';
     if (std::getenv("BWTC_HIP_FIN_ROUNDS")) fin_rounds = std::min(4, std::max(1, std::atoi(std::getenv("BWTC_HIP_FIN_ROUNDS"))));
     run_ranks = !(std::getenv("BWTC_HIP_RUNS") && std::getenv("BWTC_HIP_RUNS")[0] == '0');
+    period_ranks = !(std::getenv("BWTC_HIP_PERIODS") && std::getenv("BWTC_HIP_PERIODS")[0] == '0');
+    if (std::getenv("BWTC_HIP_PERIOD")) period_forced = (u32)std::min(std::max(std::atoi(std::getenv("BWTC_HIP_PERIOD")), 0), (int)kPeriodMax);
     local_rounds = !(std::getenv("BWTC_HIP_LOCAL_ROUNDS") && std::getenv("BWTC_HIP_LOCAL_ROUNDS")[0] == '0');
     if (std::getenv("BWTC_HIP_FIN_FLOOR")) fin_floor = (u32)std::max(0, std::atoi(std::getenv("BWTC_HIP_FIN_FLOOR")));
     if (std::getenv("BWTC_HIP_TEXT_ROUNDS")) { text_rounds = std::max(0, std::atoi(std::getenv("BWTC_HIP_TEXT_ROUNDS"))); text_rounds_fixed = true; }
@@ -2363,7 +2555,7 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
   res->ran_run = run_now;
   const int b2k = run_now ? b2 + 1 : b2;
   const int kbits = run_now ? nbits + 1 : nbits;
-  const RunKeys rkeys{d_runK, run_now ? 0u : run_split, run_now ? 1 : (run_mode == 2 ? 2 : 0)};
+  const RunKeys rkeys{d_runK, run_now ? 0u : run_split, run_now ? 1 : (run_mode == 2 ? 2 : 0), run_period};
   const bool carry_next = emit && kbits <= 56;
   res->carry = carry_next;
   const bool dense = !text && dense_route && m_next > 0 && (u64)m_next * 2 >= m && m >= kPairsMin && !use_sweep;
@@ -2567,6 +2759,7 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
   stats.route = 0;
   stats.finisher_entries = 0;
   runs_built = false; run_longest = 0; run_split = 0;   // (nothing of the last block's runs)
+  run_period = 1; period_looked = false; period_p = 0; period_longest = 0; period_votes = 0; period_step_depth = 0;   // (nor of its periods)
   if (n == 0) return 0;
 
   const bool emit = em != nullptr;
@@ -2792,22 +2985,116 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
     // the block's longest run are made here (once per block, one host wait); a run longer than the depth the first round
     // establishes gets the run step as that round, before any text round and before rank[] is completed.
     bool run_try = false;
-    if (run_ranks && doubling && m > 0 && run_split == 0) {
+    const u64 h_first = keep_first ? h0 : h0 * 2;
+    // (BWTC_HIP_PERIOD=1: the run step is the period step of period 1, whatever BWTC_HIP_RUNS says)
+    if ((run_ranks || period_forced == 1) && doubling && m > 0 && run_split == 0) {
       const int rcr = build_runs(n);
       if (rcr) return rcr;
-      const u64 h_first = keep_first ? h0 : h0 * 2;
       run_try = (u64)run_longest > h_first;
       if (std::getenv("BWTC_HIP_DEBUG"))
         std::fprintf(stderr, "runs: longest run %u, the rounds begin at depth %llu: %s\n", run_longest, (unsigned long long)h_first, run_try ? "run step" : "no run step");
+    }
+    // Periods: a list that takes doubling rounds and no run step may hold stretches of a period p > 1, which tie their
+    // suffixes for the stretch's length just as a run does.  The finder votes for p over the list as it stands (or
+    // BWTC_HIP_PERIOD names it); votes above the threshold buy the period-length pass, which puts k_p[] where k[] was.
+    // p <= the first round's depth: that round is the period step, exactly as the run step.  A deeper p: the step waits
+    // for the first doubling round whose depth reaches p (period_wait), with rank[] complete and no local list beside it.
+    bool period_try = false, period_wait = false;
+    auto say_no_step = [&]() {
+      if (std::getenv("BWTC_HIP_DEBUG"))
+        std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: no period step\n",
+                     period_p, period_votes, period_longest, (unsigned long long)h_first);
+    };
+    if (period_ranks && period_forced != 1 && doubling && m > 0 && run_split == 0 && !run_try && !period_looked) {
+      period_looked = true;
+      const int rcp = find_period(n, res.ks, res.vs, m, (emit && res.carry) ? ((1ull << 56) - 1ull) : ~0ull);
+      if (rcp) return rcp;
+      if (period_p >= 2 && !period_forced) {
+        // votes say how many members lie p apart, not for how long they tie: fixed-width records with a few free bytes
+        // each vote for their width and tie for less than two records.  Before the pass, a probe: is any aligned window
+        // of (W - p) / 2 positions free of breaks, W = kPeriodWorth x max(the first round's depth, p) being the stretch
+        // the step is worth?  A stretch of W characters holds such a window; the probe's threads stop at their first break.
+        const u64 worth = kPeriodWorth * std::max<u64>(h_first, period_p);
+        const u32 span = (u32)std::min<u64>((worth - period_p) / 2, 0x40000000ull);
+        const u64 windows = (u64)n > period_p + span ? ((u64)n - period_p) / span : 0;
+        bool found = false;
+        if (windows) {
+          BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallPeriod + 1, 0, 4, st));
+          hipLaunchKernelGGL(k_period_probe, dim3((u32)((windows + 255) / 256)), dim3(256), 0, st, (const u8*)d_T, n, period_p, span, (u32)std::min<u64>(windows, 0xFFFFFFFFull), d_small + kSmallPeriod + 1);
+          BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 1, d_small + kSmallPeriod + 1, 4, hipMemcpyDeviceToHost, st));
+          BWTC_HIP_TRY(wait());
+          found = h_small[kSmallPeriod + 1] != 0;
+          stats.alg_bytes += windows * 2;                   // (at the least: a byte of each stream per window)
+        }
+        if (!found) {
+          if (std::getenv("BWTC_HIP_DEBUG")) std::fprintf(stderr, "periods: no window of %u positions of period %u without a break: no period-length pass\n", span, period_p);
+          period_p = 0;
+        }
+      }
+      if (period_p >= 2) {
+        // (a run of one byte is a stretch of every period, and the run step's business: the block's longest run first --
+        // known already unless BWTC_HIP_RUNS=0 -- and no period step where the longest stretch is no longer than that)
+        int rcb = (run_ranks || period_forced) ? 0 : build_periods(n, 1);
+        if (rcb) return rcb;
+        const u32 longest_run = run_longest;
+        rcb = build_periods(n, period_p);
+        if (rcb) return rcb;
+        if (!period_forced && longest_run >= period_longest) period_p = 0;
+        // ... and none where the longest stretch is short of kPeriodWorth times the depth it has to pass: doubling gets
+        // through it in three rounds, and the step's own round and the passes cost as much (fixed-width records with
+        // a few free bytes per record vote for their width and tie for less than two records)
+        if (!period_forced && (u64)period_longest < kPeriodWorth * std::max<u64>(h_first, period_p)) period_p = 0;
+      }
+      if (period_p >= 2) {
+        int rcb = 0;
+        if (!period_forced && (u64)period_p > h_first && (u64)period_longest > period_p) {
+          // The winner may be a multiple of the stretches' period: a list that a sort by windows of the suffix number
+          // has been through holds a group's members in another order than by position.  A period above the first
+          // round's depth defers the step, so it is worth dividing: p / q for the winner's prime factors q, kept while
+          // the longest stretch stays as long (trial passes: the longest stretch alone, no lengths stored).
+          const u32 voted = period_p, longest_voted = period_longest;
+          u32 rest = voted;
+          for (u32 q = 2; q <= rest && period_p / q >= 2; ) {
+            if (rest % q) { ++q; continue; }
+            rest /= q;
+            rcb = build_periods(n, period_p / q, false);
+            if (rcb) return rcb;
+            if (period_longest >= longest_voted) period_p /= q;
+            else while (rest % q == 0) rest /= q;          // (the same candidate again)
+          }
+          period_longest = longest_voted;
+          if (period_p != voted) {
+            rcb = build_periods(n, period_p);
+            if (rcb) return rcb;
+          }
+        }
+        if ((u64)period_p <= h_first) period_try = (u64)period_longest > h_first;
+        else period_wait = period_longest > period_p;
+        if (period_try) { run_try = true; run_period = period_p; }
+      }
+      if (!period_wait && !period_try) say_no_step();
     }
     int text_extra = text_rounds_fixed ? 0 : 12;        // further ones, one at a time, while the list is short (not when BWTC_HIP_TEXT_ROUNDS says how many)
     while (m > 0 || (doubling && local_m > 0)) {
       if (h >= (u64)n * 2 + 64) return -3;   // cannot happen: every group splits by then
       ++stats.rounds;
       stats.active_sum += m;
-      const bool run_req = run_try && m > 0;             // (the first round only)
-      run_try = false;
       const bool text_round = text_left > 0 && m > 0;
+      bool period_req = period_try && run_try && m > 0;
+      if (period_wait && m > 0) {
+        // the deferred period step: this round, if its depth has reached p and the stretches are longer than that
+        const u64 h_round = keep_h ? h : h * 2;
+        if ((u64)period_longest <= std::max<u64>(h_round, period_p)) {
+          period_wait = false;
+          say_no_step();
+        } else if (h_round >= (u64)period_p && ranks_complete && local_m == 0 && !text_round) {
+          period_wait = false;
+          period_req = true;
+          run_period = period_p;
+        }
+      }
+      const bool run_req = (run_try && m > 0) || period_req;   // (the first round only, or the deferred period step's)
+      run_try = false;
       const bool text = text_round || (run_req && !ranks_complete);   // the run step reads no rank[]: it does not need the completion either
       const bool raw = !text && !doubling;               // out of text rounds and not allowed to double: hand the list back
       if (std::getenv("BWTC_HIP_DEBUG")) std::fprintf(stderr, "round %u%s: h=%llu m=%u groups=%u\n", stats.rounds, text ? " (text)" : "", (unsigned long long)h, m, res.groups);
@@ -2845,11 +3132,18 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
       if (rc2) return rc2;
       m = res.m;
       const bool ran = run_req && res.ran_run;
+      if (period_req && !ran) say_no_step();               // (the key had no room for the step's bit: an ordinary round)
       if (ran) {
         // the list is sorted to depth h still: a run's members by their closed-form keys, the others as they were (or by rank[s + h])
         run_split = (u32)std::min<u64>(h, 0xFFFFFFFFull);
-        stats.route |= 32u;
+        stats.route |= period_req ? 256u : 32u;
         keep_h = true;
+        if (period_req) {
+          period_step_depth = run_split;
+          if (std::getenv("BWTC_HIP_DEBUG"))
+            std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: period step at depth %u\n",
+                         period_p, period_votes, period_longest, (unsigned long long)h_first, run_split);
+        }
         // rank[] still incomplete: one text round behind the runs first -- a block that is one giant run ends there,
         // without the completion of rank[] that the first doubling round costs.  Not beside a live local list: its
         // members' ranks are local_depth deep, and the first doubling look-up must not lie deeper than that (text rounds
@@ -2869,6 +3163,7 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
         if (text_left == 0 && m > 0 && (u64)m * 4096 < (u64)n && text_extra > 0) { text_left = 1; --text_extra; }
       }
     }
+    if (period_wait) say_no_step();                        // (the rounds ended before their depth reached p)
     if (left) { *left = 0; *h_left = h; }
     return 0;
   };
@@ -3000,6 +3295,84 @@ int BwtEngine::build_runs(u32 n) {
   run_longest = h_small[kSmallRun];
   runs_built = true;
   stats.alg_bytes += (u64)n * (1 + 1 + 4) + (u64)tiles * 16;   // T read twice, k[] written; the tiles' words written and read
+  return 0;
+}
+
+// k_p[] for every suffix of the block, in k[]'s place, and its longest periodic stretch (the period-length pass: the run-
+// length pass's three launches with the text p bytes back beside the text).  p = 1 is the run-length pass itself.
+int BwtEngine::build_periods(u32 n, u32 p, bool store) {
+  if (p == 1) {
+    runs_built = false;
+    const int rc = build_runs(n);
+    period_longest = run_longest;
+    return rc;
+  }
+  // (the tiles reach n + p and their positions are 32-bit: a block within two tiles of 2^32 takes no period step)
+  if ((u64)n + p + 2ull * kRunTile > 0xFFFFFFFFull) { period_longest = 0; return 0; }
+  hipStream_t st = stream;
+  const u32 tiles = (u32)(((u64)n + p + kRunTile - 1) / kRunTile);   // the tiles cover the positions x = s + p, s < n
+  const bool timed = std::getenv("BWTC_HIP_DEBUG") != nullptr;
+  struct Events {                                        // (destroyed on every way out)
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  } ev;
+  if (timed) {
+    BWTC_HIP_TRY(hipEventCreate(&ev.a));
+    BWTC_HIP_TRY(hipEventCreate(&ev.b));
+  }
+  BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallPeriod, 0, 4, st));
+  if (timed) BWTC_HIP_TRY(hipEventRecord(ev.a, st));
+  hipLaunchKernelGGL(k_period_tiles, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, d_runF);
+  hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(1024), 0, st, (const u32*)d_runF, tiles, n, d_runB);
+  hipLaunchKernelGGL(k_period_lengths, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, store ? d_runK : (u32*)nullptr, d_small + kSmallPeriod);
+  if (timed) BWTC_HIP_TRY(hipEventRecord(ev.b, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod, d_small + kSmallPeriod, 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(wait());
+  if (timed) {
+    float ms = 0.f;
+    BWTC_HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+    std::fprintf(stderr, store ? "periods: the period-length pass took %.4f ms for %u suffixes, period %u\n"
+                               : "periods: a trial pass (no lengths stored) took %.4f ms for %u suffixes, period %u\n", ms, n, p);
+  }
+  period_longest = h_small[kSmallPeriod];
+  if (store) runs_built = false;                         // (k[] is gone from d_runK)
+  stats.alg_bytes += (u64)n * (2 + 2 + (store ? 4 : 0)) + (u64)tiles * 16;   // both streams of T read twice, k_p[] written; the tiles' words written and read
+  return 0;
+}
+
+// The block's period, into period_p (0: none worth the pass) and period_votes: BWTC_HIP_PERIOD's, or the vote's winner
+// if its votes reach the threshold -- a 64th of the block, and kPeriodMinVotes at the least.
+int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask) {
+  if (period_forced) { period_p = period_forced; period_votes = 0; return 0; }
+  if (m < 2) return 0;
+  hipStream_t st = stream;
+  const bool timed = std::getenv("BWTC_HIP_DEBUG") != nullptr;
+  struct Events {
+    hipEvent_t a = nullptr, b = nullptr;
+    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  } ev;
+  if (timed) {
+    BWTC_HIP_TRY(hipEventCreate(&ev.a));
+    BWTC_HIP_TRY(hipEventCreate(&ev.b));
+  }
+  BWTC_HIP_TRY(hipMemsetAsync(d_votes, 0, (size_t)kVoteBins * 4, st));
+  if (timed) BWTC_HIP_TRY(hipEventRecord(ev.a, st));
+  hipLaunchKernelGGL(k_period_votes, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes);
+  if (timed) BWTC_HIP_TRY(hipEventRecord(ev.b, st));
+  hipLaunchKernelGGL(k_period_winner, dim3(1), dim3(1024), 0, st, (const u32*)d_votes, d_small + kSmallPeriod + 2);
+  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 2, d_small + kSmallPeriod + 2, 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(wait());
+  if (timed) {
+    float ms = 0.f;
+    BWTC_HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+    std::fprintf(stderr, "periods: the vote kernel took %.4f ms for %u entries\n", ms, m);
+  }
+  const u32 winner = h_small[kSmallPeriod + 2];
+  period_votes = h_small[kSmallPeriod + 3];
+  const u64 need = std::max<u64>(kPeriodMinVotes, (u64)n / 64);
+  period_p = (winner >= 2 && (u64)period_votes >= need) ? winner : 0u;
+  if (!period_p && timed) std::fprintf(stderr, "periods: distance %u leads with %u votes of the %llu a pass takes\n", winner, period_votes, (unsigned long long)need);
+  stats.alg_bytes += (u64)m * (8 + 4) + (u64)kVoteBins * 8;   // the list's keys and suffixes read; the table zeroed and read
   return 0;
 }
 

@@ -1139,6 +1139,38 @@ int bwtc_hip_test_radix_long(bwtc_hip_ctx* ctx, uint64_t* keys, void* vals, uint
   return -1;
 }
 
+// The period step's last block: its period, its longest periodic stretch, the winner's votes and the depth of the step
+// (zeros where nothing was looked for, nothing was found or no step ran).
+int bwtc_hip_period_get(bwtc_hip_ctx* ctx, uint32_t* p, uint32_t* longest, uint32_t* votes, uint32_t* step_depth) {
+  if (!ctx) return -1;
+  const BwtEngine& e = ctx->eng;
+  if (p) *p = e.period_p;
+  if (longest) *longest = e.period_longest;
+  if (votes) *votes = e.period_votes;
+  if (step_depth) *step_depth = e.period_step_depth;
+  return 0;
+}
+
+// The sorter's own period-length pass (BwtEngine::build_periods: three launches; p = 1: the run-length pass) over T as
+// the sorter holds it -- loaded by load_text, padded with zero bytes -- on the context's buffers.
+int bwtc_hip_test_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest_out) {
+  if (!ctx || !T || !k_out || !longest_out) return -1;
+  BwtEngine& e = ctx->eng;
+  if (p == 0 || p > kPeriodMax || n == 0 || (u64)n > e.cap) return -1;
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_in, T, n, hipMemcpyHostToDevice, e.stream));
+  u32 hist[256];
+  int rc = e.load_text(e.d_in, n, n, false, hist);
+  if (rc) return rc;
+  rc = e.build_periods(n, p);
+  if (rc) return rc;
+  BWTC_HIP_TRY(hipMemcpyAsync(k_out, e.d_runK, (u64)n * 4, hipMemcpyDeviceToHost, e.stream));
+  BWTC_HIP_TRY(e.wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  *longest_out = e.period_longest;
+  return 0;
+}
+
 int bwtc_hip_test_radix_segmented(bwtc_hip_ctx* ctx, uint32_t* keys, uint64_t n, int bit_lo, const uint32_t* tile_first, uint32_t nseg) {
   if (!ctx || !keys || !tile_first) return -1;
   BwtEngine& e = ctx->eng;

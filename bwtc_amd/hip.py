@@ -209,6 +209,7 @@ EXPORTS = [
     "bwtc_hip_host_sections", "bwtc_hip_host_bwtblock_header", "bwtc_hip_synth", "bwtc_hip_suffix_array",
     "bwtc_hip_test_sort_u32", "bwtc_hip_test_sort_u64", "bwtc_hip_test_scan_u32",
     "bwtc_hip_test_radix_pairs", "bwtc_hip_test_radix_long", "bwtc_hip_test_radix_segmented",
+    "bwtc_hip_period_get", "bwtc_hip_test_period_lengths",
     "bwtc_hip_wavelet_depth_needed", "bwtc_hip_grammar_create", "bwtc_hip_grammar_destroy", "bwtc_hip_grammar_rules", "bwtc_hip_grammar_special_symbols",
     "bwtc_hip_grammar_is_special", "bwtc_hip_grammar_write", "bwtc_hip_grammar_read", "bwtc_hip_pair_replace_device",
     "bwtc_hip_test_pair_stats", "bwtc_hip_precompress", "bwtc_hip_host_precompress", "bwtc_hip_postprocess",
@@ -365,6 +366,8 @@ def load():
     L.bwtc_hip_test_radix_pairs.argtypes = [_vp, _vp, _vp, _u64, _u64] + [ctypes.c_int] * 6
     L.bwtc_hip_test_radix_long.argtypes = [_vp, _vp, _vp, _vp, _u64] + [ctypes.c_int] * 5
     L.bwtc_hip_test_radix_segmented.argtypes = [_vp, _vp, _u64, ctypes.c_int, _vp, _u32]
+    L.bwtc_hip_period_get.argtypes = [_vp] + [ctypes.POINTER(_u32)] * 4
+    L.bwtc_hip_test_period_lengths.argtypes = [_vp, _vp, _u32, _u32, _vp, ctypes.POINTER(_u32)]
     _lib = L
     return L
 
@@ -1027,6 +1030,26 @@ class Context:
         _check(self.lib.bwtc_hip_test_radix_segmented(self.handle, _ptr(keys), keys.size, bit_lo, _ptr(tf), tf.size - 1),
                "bwtc_hip_test_radix_segmented")
         return keys
+
+    # the suffix sorter's period step
+    def period(self):
+        """The last block's (period, longest periodic stretch, the winner's votes, depth of the period step): zeros
+        where nothing was looked for, nothing was found or no step ran (bwtc_hip_period_get)."""
+        v = [_u32(0) for _ in range(4)]
+        _check(self.lib.bwtc_hip_period_get(self.handle, *[ctypes.byref(x) for x in v]), "bwtc_hip_period_get")
+        return tuple(int(x.value) for x in v)
+
+    def test_period_lengths(self, T, p, k_out=None):
+        """The sorter's own period-length pass over T (bwtc_hip_test_period_lengths) -> (k_p[], the longest).  k_out: the
+        uint32 array to fill (left untouched where the hook refuses: BwtcHipError, code -1)."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        if k_out is None:
+            k_out = np.zeros(max(T.size, 1), np.uint32)
+        assert k_out.dtype == np.uint32 and k_out.size >= T.size
+        longest = _u32(0)
+        _check(self.lib.bwtc_hip_test_period_lengths(self.handle, _ptr(T) if T.size else None, T.size, int(p), _ptr(k_out), ctypes.byref(longest)),
+               "bwtc_hip_test_period_lengths")
+        return k_out[:T.size], int(longest.value)
 
 
 def host_cpu_slice(numa_node, rank, ranks):

@@ -40,7 +40,9 @@ typedef struct bwtc_hip_stats {
                                  bit 5: a run step ran -- long runs of one byte were ranked in closed form
                                         (BWTC_HIP_RUNS=0: never);
                                  bit 6: the finisher's small groups doubled beside the rounds' list (local list);
-                                 bit 7: a finisher list too long for its pass's shape went to the rounds */
+                                 bit 7: a finisher list too long for its pass's shape went to the rounds;
+                                 bit 8: a period step ran -- stretches of a period p > 1 were ranked in closed form
+                                        (BWTC_HIP_PERIODS=0: never; never together with bit 5) */
   uint32_t finisher_entries;  /* list entries over all finisher passes                      */
   uint64_t alg_bytes;         /* compulsory bytes of the transform's kernels: every array a kernel
                                  reads counted once, every array it writes counted once (SURVEY.md
@@ -456,6 +458,14 @@ int bwtc_hip_test_radix_pairs(bwtc_hip_ctx* ctx, void* keys, void* vals, uint64_
 int bwtc_hip_test_radix_long(bwtc_hip_ctx* ctx, uint64_t* keys, void* vals, uint32_t* w, uint64_t n, int val_bytes, int items_per_thread,
                              int kbits, int wbits, int direct_w);
 int bwtc_hip_test_radix_segmented(bwtc_hip_ctx* ctx, uint32_t* keys, uint64_t n, int bit_lo, const uint32_t* tile_first, uint32_t nseg);
+/* The period step of the context's last block: *p its period (the finder's winner above the
+ * threshold, or BWTC_HIP_PERIOD's), *longest the block's longest p-periodic stretch, *votes the winner's votes,
+ * *step_depth the depth of the period step that ran.  Zeros where nothing was looked for or found. */
+int bwtc_hip_period_get(bwtc_hip_ctx* ctx, uint32_t* p, uint32_t* longest, uint32_t* votes, uint32_t* step_depth);
+/* Test hook: the sorter's own period-length pass (three launches; p = 1: the run-length pass) over T[0..n), on the
+ * context's buffers: k_out[s] = the number of leading characters of suffix s that are p-periodic, *longest_out their
+ * maximum.  -1, before anything is launched, for p = 0, p > 4096, n = 0 or n above the context's block size. */
+int bwtc_hip_test_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest_out);
 /* Test hook: k range-coder chains over w-elements (w = bit << 15 | probability of the coded bit), chain j = elements
  * [bounds[j], bounds[j+1]), on the GPU lane engine (mode 0; BitEncoder, BitCoders.cpp:59-113, one lane per chain) or by the
  * host's scalar loop (mode 1); bytes of chain j = out[offsets[j] .. offsets[j+1]). */
