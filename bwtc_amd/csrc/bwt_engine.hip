@@ -1604,7 +1604,8 @@ __global__ __launch_bounds__(kWinTPB) void k_scatter_dense(u32* __restrict__ ran
 // members equal in that come from different runs, share exactly k characters and are ordered by the rank of the
 // run's tail, rank[s + k].  So ONE round (the run step, mode 1) gives such members the second key (type, k | n - k)
 // instead of rank[s + h] + 1 -- a bit more than a rank needs -- and does not double the list's depth; every later
-// round (mode 2) looks a member with k >= h_split up at rank[s + max(h, k)] instead of rank[s + h].
+// round (mode 2) looks a member with k >= h_split up at rank[s + max(h, k)] instead of rank[s + h].  k[] is made by the
+// stretch-length pass below, as the lengths of period 1.
 // ---------------------------------------------------------------------------------------
 struct RunKeys { const u32* k; u32 h_split; int mode; u32 p; };   // mode 0: no runs in play (k is not read); 1: the run step; 2: a round after it; p: the period k[] was made for (1: runs)
 __device__ __forceinline__ u32 run_offset(const RunKeys& rk, u32 s, u32 h) {
@@ -1629,8 +1630,23 @@ __device__ __forceinline__ u64 run_key2(const RunKeys& rk, const u32* __restrict
   return t < (u64)n ? (u64)rank[t] + 1ull : 0ull;
 }
 
-// The run-length pass, three launches over tiles of kRunTile positions (256 threads x 64 consecutive bytes, 16-byte loads).
-// A position p in [1, n) is a run start when T[p] != T[p-1]; k[s] = (first run start behind s, or n) - s.
+// ---------------------------------------------------------------------------------------
+// Periods.  The run rule holds for every period p >= 1 (tests/periodmodel.py): position q is a break when q >= p and
+// T[q] != T[q - p] (p = 1: a run start); k_p[s] = (the first break at or behind s + p, or n) - s is the number of leading
+// characters of suffix s that are p-periodic, and k_1 is the runs' k.  Once a list is sorted to a depth h >= p, a group
+// holds members with k_p >= h only or none, and those are ordered as a run's: the falling ones (the end of T, or
+// T[s + k] < T[s + k - p]) by ascending k, then the rising ones by descending k, ties by rank[s + k].  So the period step
+// is the run step over k_p[] (d_runK holds the lengths of one period at a time) with RunKeys::p = p.
+//
+// The stretch-length pass makes k_p[] for any p, runs included: three launches over tiles of kRunTile positions (256
+// threads x 64 consecutive bytes, 16-byte loads), a right-to-left carry in one workgroup, coalesced 4-byte stores.  A
+// thread works out the first break at or behind x for the positions x of its tile and stores it as k_p[x - p]: nobody
+// looks ahead into the next chunks, and the tiles cover x in [p, n + p).  The 64-bit break mask of a thread's positions
+// is made in two ways, and the kernels are templated on which: run_starts (p = 1) carries the previous byte in
+// registers and reads the text once; period_breaks (any p) compares with the text p bytes back, a second stream read
+// by aligned 16-byte loads and shifted into place.  The run instantiation also keeps its own store form, one
+// `if constexpr` in the store loop: the thread at q looks at the break bits behind q and stores k[q].
+// ---------------------------------------------------------------------------------------
 constexpr u32 kRunTile = 16384, kRunTPB = 256, kRunNone = 0xFFFFFFFFu;
 // the 64 positions from `at` on (a multiple of 64): bit j set = position at + j starts a run
 __device__ __forceinline__ u64 run_starts(const u8* __restrict__ T, u32 at, u32 n) {
@@ -1655,105 +1671,15 @@ __device__ __forceinline__ u64 run_starts(const u8* __restrict__ T, u32 at, u32 
   if (left < 64u) mask &= (1ull << left) - 1ull;
   return mask;
 }
-// launch 1: first[t] = the first run start in tile t, or none
-__global__ __launch_bounds__(kRunTPB) void k_run_tiles(const u8* __restrict__ T, u32 n, u32* __restrict__ first) {
-  __shared__ u32 s_min[kRunTPB / kWave];
-  const u32 at = blockIdx.x * kRunTile + threadIdx.x * 64u;
-  const u64 mask = run_starts(T, at, n);
-  u32 f = mask ? at + (u32)__builtin_ctzll(mask) : kRunNone;
-  for (int o = kWave / 2; o > 0; o >>= 1) f = min(f, (u32)__shfl_xor(f, o, kWave));
-  if ((threadIdx.x & (kWave - 1)) == 0) s_min[threadIdx.x / kWave] = f;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (u32 w = 1; w < kRunTPB / kWave; ++w) f = min(f, s_min[w]);
-    first[blockIdx.x] = f;
-  }
-}
-// launch 2 (one workgroup): behind[t] = the first run start in a tile after t, or n -- a right-to-left carry
-__global__ __launch_bounds__(1024) void k_run_carry(const u32* __restrict__ first, u32 tiles, u32 n, u32* __restrict__ behind) {
-  __shared__ u32 s_part[1024];
-  const u32 per = (tiles + 1023u) / 1024u;
-  const u32 lo = min(tiles, threadIdx.x * per), hi = min(tiles, lo + per);
-  u32 f = kRunNone;
-  for (u32 t = lo; t < hi; ++t) f = min(f, first[t]);
-  s_part[threadIdx.x] = f;
-  __syncthreads();
-  if (threadIdx.x == 0) {                               // exclusive suffix minimum of the 1024 parts
-    u32 run = kRunNone;
-    for (int i = 1023; i >= 0; --i) { const u32 v = s_part[i]; s_part[i] = run; run = min(run, v); }
-  }
-  __syncthreads();
-  u32 run = s_part[threadIdx.x];
-  for (u32 t = hi; t > lo; --t) {
-    behind[t - 1u] = run == kRunNone ? n : run;
-    run = min(run, first[t - 1u]);
-  }
-}
-// launch 3: k[] of the tile (coalesced 4-byte stores), and the block's longest run
-__global__ __launch_bounds__(kRunTPB) void k_run_lengths(const u8* __restrict__ T, u32 n, const u32* __restrict__ behind,
-                                                          u32* __restrict__ k, u32* __restrict__ longest) {
-  __shared__ u64 s_mask[kRunTPB];
-  __shared__ u32 s_next[kRunTPB];                      // the first run start behind the thread's 64 positions
-  __shared__ u32 s_wave[kRunTPB / kWave];
-  const u32 base = blockIdx.x * kRunTile;
-  const u32 at = base + threadIdx.x * 64u;
-  const u64 mask = run_starts(T, at, n);
-  s_mask[threadIdx.x] = mask;
-  // suffix minimum of the threads' first run starts: inside the wave by shuffles, across the four waves through LDS
-  const u32 lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  u32 incl = mask ? at + (u32)__builtin_ctzll(mask) : kRunNone;
-  for (int o = 1; o < kWave; o <<= 1) {
-    const u32 t = __shfl_down(incl, o, kWave);
-    if (lane + o < (u32)kWave) incl = min(incl, t);
-  }
-  if (lane == 0) s_wave[wave] = incl;
-  u32 excl = __shfl_down(incl, 1, kWave);
-  if (lane == kWave - 1) excl = kRunNone;
-  __syncthreads();
-  for (u32 w = wave + 1; w < kRunTPB / kWave; ++w) excl = min(excl, s_wave[w]);
-  if (excl == kRunNone) excl = behind[blockIdx.x];
-  s_next[threadIdx.x] = excl;
-  __syncthreads();
-  u32 best = 0;
-  for (u32 j = 0; j < kRunTile / kRunTPB; ++j) {
-    const u32 q = base + j * kRunTPB + threadIdx.x;     // chunk j * 4 + wave of the tile, bit `lane`
-    if (q >= n) break;
-    const u32 c = j * (kRunTPB / 64u) + wave;
-    const u64 later = lane < 63u ? s_mask[c] >> (lane + 1u) : 0ull;
-    const u32 nd = later ? q + 1u + (u32)__builtin_ctzll(later) : s_next[c];
-    const u32 kk = min(nd, n) - q;
-    k[q] = kk;
-    best = max(best, kk);
-  }
-  for (int o = kWave / 2; o > 0; o >>= 1) best = max(best, (u32)__shfl_xor(best, o, kWave));
-  if (lane == 0 && best) atomicMax(longest, best);
-}
-
-// ---------------------------------------------------------------------------------------
-// Periods.  The run rule holds for every period p >= 1 (tests/periodmodel.py): position q is a break when q >= p and
-// T[q] != T[q - p]; k_p[s] = (the first break at or behind s + p, or n) - s is the number of leading characters of
-// suffix s that are p-periodic.  Once a list is sorted to a depth h >= p, a group holds members with k_p >= h only or
-// none, and those are ordered as a run's: the falling ones (the end of T, or T[s + k] < T[s + k - p]) by ascending k,
-// then the rising ones by descending k, ties by rank[s + k].  So the period step is the run step over k_p[] (which takes
-// k[]'s place in d_runK) with RunKeys::p = p.
-//
-// The period-length pass has the run-length pass's shape -- tiles of kRunTile positions, 64 per thread, 16-byte loads,
-// a right-to-left carry in one workgroup, coalesced stores -- with two differences: the break mask compares with the
-// text p bytes back, a second stream read by aligned 16-byte loads and shifted into place, and a thread works out the
-// first break at or behind x for the positions x of its tile and stores it as k_p[x - p]: nobody looks ahead into the
-// next chunks, and the tiles cover x in [p, n + p).
-// ---------------------------------------------------------------------------------------
 __device__ __forceinline__ u32 differing_bytes(u32 x) {   // bit j set = byte j of x is not zero
   return ((x & 0x000000FFu) ? 1u : 0u) | ((x & 0x0000FF00u) ? 2u : 0u) | ((x & 0x00FF0000u) ? 4u : 0u) | ((x & 0xFF000000u) ? 8u : 0u);
 }
-// the words of T from byte `from` on (sixteen of them), out of the twenty aligned words w[] that begin at from & ~15:
-// WO whole words and bs bytes further on
-template <int WO>
+// the sixteen words of T that begin bs bytes into w[], beside the words a[]
 __device__ __forceinline__ u64 period_compare(const u32 (&a)[16], const u32 (&w)[20], u32 bs) {
   u64 mask = 0;
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
-    const u64 two = ((u64)w[i + WO + 1] << 32) | (u64)w[i + WO];
+    const u64 two = ((u64)w[i + 1] << 32) | (u64)w[i];
     const u32 b = (u32)(two >> (8u * bs));
     mask |= (u64)differing_bytes(a[i] ^ b) << (4 * i);
   }
@@ -1784,22 +1710,33 @@ __device__ __forceinline__ u64 period_breaks(const u8* __restrict__ T, u32 at, u
     const uint4 v = x < n ? *reinterpret_cast<const uint4*>(T + x) : make_uint4(0u, 0u, 0u, 0u);
     w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
   }
-  const u32 bs = sh & 3u;
-  switch (sh >> 2) {
-    case 0: mask = period_compare<0>(a, w, bs); break;
-    case 1: mask = period_compare<1>(a, w, bs); break;
-    case 2: mask = period_compare<2>(a, w, bs); break;
-    default: mask = period_compare<3>(a, w, bs); break;
+  // the second stream begins sh bytes into w[]: whole words first, by moves between registers (a switch over the word
+  // count becomes an indexed w[], which leaves the registers), then bytes
+  if (sh & 8u) {
+#pragma unroll
+    for (int i = 0; i < 18; ++i) w[i] = w[i + 2];
   }
+  if (sh & 4u) {
+#pragma unroll
+    for (int i = 0; i < 17; ++i) w[i] = w[i + 1];
+  }
+  mask = period_compare(a, w, sh & 3u);
   const u32 left = n - at;                              // positions at or past n are not the text's
   if (left < 64u) mask &= (1ull << left) - 1ull;
   return mask;
 }
+// RUN: the pass of period 1, its mask from run_starts (p is 1 then); else period_breaks'
+template <bool RUN>
+__device__ __forceinline__ u64 stretch_breaks(const u8* __restrict__ T, u32 at, u32 n, u32 p) {
+  if constexpr (RUN) return run_starts(T, at, n);
+  else return period_breaks(T, at, n, p);
+}
 // launch 1: first[t] = the first break in tile t, or none (tiles past n included: the lengths' tiles reach n + p)
-__global__ __launch_bounds__(kRunTPB) void k_period_tiles(const u8* __restrict__ T, u32 n, u32 p, u32* __restrict__ first) {
+template <bool RUN>
+__global__ __launch_bounds__(kRunTPB) void k_stretch_tiles(const u8* __restrict__ T, u32 n, u32 p, u32* __restrict__ first) {
   __shared__ u32 s_min[kRunTPB / kWave];
   const u32 at = blockIdx.x * kRunTile + threadIdx.x * 64u;
-  const u64 mask = period_breaks(T, at, n, p);
+  const u64 mask = stretch_breaks<RUN>(T, at, n, p);
   u32 f = mask ? at + (u32)__builtin_ctzll(mask) : kRunNone;
   for (int o = kWave / 2; o > 0; o >>= 1) f = min(f, (u32)__shfl_xor(f, o, kWave));
   if ((threadIdx.x & (kWave - 1)) == 0) s_min[threadIdx.x / kWave] = f;
@@ -1809,17 +1746,39 @@ __global__ __launch_bounds__(kRunTPB) void k_period_tiles(const u8* __restrict__
     first[blockIdx.x] = f;
   }
 }
-// launch 2 is the runs' carry, k_run_carry: behind[t] = the first break in a tile after t, or n
+// launch 2 (one workgroup): behind[t] = the first break in a tile after t, or n -- a right-to-left carry
+__global__ __launch_bounds__(1024) void k_run_carry(const u32* __restrict__ first, u32 tiles, u32 n, u32* __restrict__ behind) {
+  __shared__ u32 s_part[1024];
+  const u32 per = (tiles + 1023u) / 1024u;
+  const u32 lo = min(tiles, threadIdx.x * per), hi = min(tiles, lo + per);
+  u32 f = kRunNone;
+  for (u32 t = lo; t < hi; ++t) f = min(f, first[t]);
+  s_part[threadIdx.x] = f;
+  __syncthreads();
+  if (threadIdx.x == 0) {                               // exclusive suffix minimum of the 1024 parts
+    u32 run = kRunNone;
+    for (int i = 1023; i >= 0; --i) { const u32 v = s_part[i]; s_part[i] = run; run = min(run, v); }
+  }
+  __syncthreads();
+  u32 run = s_part[threadIdx.x];
+  for (u32 t = hi; t > lo; --t) {
+    behind[t - 1u] = run == kRunNone ? n : run;
+    run = min(run, first[t - 1u]);
+  }
+}
 // launch 3: k_p[x - p] for the positions x of the tile (coalesced 4-byte stores), and the block's longest k_p
-__global__ __launch_bounds__(kRunTPB) void k_period_lengths(const u8* __restrict__ T, u32 n, u32 p, const u32* __restrict__ behind,
-                                                             u32* __restrict__ k, u32* __restrict__ longest) {
+template <bool RUN>
+__global__ __launch_bounds__(kRunTPB) void k_stretch_lengths(const u8* __restrict__ T, u32 n, u32 p_any, const u32* __restrict__ behind,
+                                                              u32* __restrict__ k, u32* __restrict__ longest) {
   __shared__ u64 s_mask[kRunTPB];
   __shared__ u32 s_next[kRunTPB];                      // the first break behind the thread's 64 positions
   __shared__ u32 s_wave[kRunTPB / kWave];
+  const u32 p = RUN ? 1u : p_any;
   const u32 base = blockIdx.x * kRunTile;
   const u32 at = base + threadIdx.x * 64u;
-  const u64 mask = period_breaks(T, at, n, p);
+  const u64 mask = stretch_breaks<RUN>(T, at, n, p);
   s_mask[threadIdx.x] = mask;
+  // suffix minimum of the threads' first breaks: inside the wave by shuffles, across the four waves through LDS
   const u32 lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   u32 incl = mask ? at + (u32)__builtin_ctzll(mask) : kRunNone;
   for (int o = 1; o < kWave; o <<= 1) {
@@ -1837,12 +1796,22 @@ __global__ __launch_bounds__(kRunTPB) void k_period_lengths(const u8* __restrict
   u32 best = 0;
   for (u32 j = 0; j < kRunTile / kRunTPB; ++j) {
     const u32 x = base + j * kRunTPB + threadIdx.x;     // chunk j * 4 + wave of the tile, bit `lane`
-    if (x < p) continue;
-    const u32 q = x - p;                                // the suffix whose periodic stretch ends at the first break from x on
-    if (q >= n) break;
     const u32 c = j * (kRunTPB / 64u) + wave;
-    const u64 here = s_mask[c] >> lane;
-    const u32 nd = here ? x + (u32)__builtin_ctzll(here) : s_next[c];
+    u32 q, nd;
+    if constexpr (RUN) {
+      // (runs: the thread looks one position ahead and stores at its own -- the same k[], by stores that begin at a
+      // multiple of 1 KiB: measurably faster than the stores 4 bytes before it; the last tile of n + 1 may find nothing)
+      q = x;
+      if (q >= n) break;
+      const u64 later = lane < 63u ? s_mask[c] >> (lane + 1u) : 0ull;
+      nd = later ? q + 1u + (u32)__builtin_ctzll(later) : s_next[c];
+    } else {
+      if (x < p) continue;
+      q = x - p;                                        // the suffix whose periodic stretch ends at the first break from x on
+      if (q >= n) break;
+      const u64 here = s_mask[c] >> lane;
+      nd = here ? x + (u32)__builtin_ctzll(here) : s_next[c];
+    }
     const u32 kk = min(nd, n) - q;
     if (k) k[q] = kk;                                   // (k == nullptr: a trial, for the longest stretch alone)
     best = max(best, kk);
@@ -2555,7 +2524,7 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
   res->ran_run = run_now;
   const int b2k = run_now ? b2 + 1 : b2;
   const int kbits = run_now ? nbits + 1 : nbits;
-  const RunKeys rkeys{d_runK, run_now ? 0u : run_split, run_now ? 1 : (run_mode == 2 ? 2 : 0), run_period};
+  const RunKeys rkeys{d_runK, run_now ? 0u : step.depth, run_now ? 1 : (run_mode == 2 ? 2 : 0), step.p};
   const bool carry_next = emit && kbits <= 56;
   res->carry = carry_next;
   const bool dense = !text && dense_route && m_next > 0 && (u64)m_next * 2 >= m && m >= kPairsMin && !use_sweep;
@@ -2748,6 +2717,13 @@ int BwtEngine::plan_grams(const KeyPlan& plan, u32 n, const u8* d_lut, GramPlan*
   return 0;
 }
 
+// (the debug line of a block that looked for a period and takes no period step: decide_step and the rounds)
+static void say_no_period_step(const BwtEngine& e, u64 h_first) {
+  if (std::getenv("BWTC_HIP_DEBUG"))
+    std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: no period step\n",
+                 e.period_p, e.period_votes, e.period_longest, (unsigned long long)h_first);
+}
+
 // em != nullptr: the rankers emit the transform's bytes (see RrEmit) and the suffix array itself
 // is not stored; em == nullptr: d_SA is filled and nothing is emitted.
 int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const EmitTarget* em) {
@@ -2758,8 +2734,8 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
   stats.sort_pass_items = 0;
   stats.route = 0;
   stats.finisher_entries = 0;
-  runs_built = false; run_longest = 0; run_split = 0;   // (nothing of the last block's runs)
-  run_period = 1; period_looked = false; period_p = 0; period_longest = 0; period_votes = 0; period_step_depth = 0;   // (nor of its periods)
+  lengths_period = 0; run_longest = 0; run_longest_known = false; step = StretchStep{};   // (nothing of the last block's runs)
+  period_looked = false; period_p = 0; period_longest = 0; period_votes = 0;                // (nor of its periods)
   if (n == 0) return 0;
 
   const bool emit = em != nullptr;
@@ -2981,98 +2957,12 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
     u64 h = h0;
     bool keep_h = keep_first;                // the list is sorted to depth h as it stands (no doubling before the next step)
     int text_left = text_rounds_now;
-    // Runs: a list about to double may hold long runs of one byte, which doubling takes log2(length) rounds over.  k[] and
-    // the block's longest run are made here (once per block, one host wait); a run longer than the depth the first round
-    // establishes gets the run step as that round, before any text round and before rank[] is completed.
-    bool run_try = false;
+    // the block's closed-form step (runs, periods), decided where a list is about to double: step.when says whether it is
+    // the first round's or waits for a deeper one
     const u64 h_first = keep_first ? h0 : h0 * 2;
-    // (BWTC_HIP_PERIOD=1: the run step is the period step of period 1, whatever BWTC_HIP_RUNS says)
-    if ((run_ranks || period_forced == 1) && doubling && m > 0 && run_split == 0) {
-      const int rcr = build_runs(n);
-      if (rcr) return rcr;
-      run_try = (u64)run_longest > h_first;
-      if (std::getenv("BWTC_HIP_DEBUG"))
-        std::fprintf(stderr, "runs: longest run %u, the rounds begin at depth %llu: %s\n", run_longest, (unsigned long long)h_first, run_try ? "run step" : "no run step");
-    }
-    // Periods: a list that takes doubling rounds and no run step may hold stretches of a period p > 1, which tie their
-    // suffixes for the stretch's length just as a run does.  The finder votes for p over the list as it stands (or
-    // BWTC_HIP_PERIOD names it); votes above the threshold buy the period-length pass, which puts k_p[] where k[] was.
-    // p <= the first round's depth: that round is the period step, exactly as the run step.  A deeper p: the step waits
-    // for the first doubling round whose depth reaches p (period_wait), with rank[] complete and no local list beside it.
-    bool period_try = false, period_wait = false;
-    auto say_no_step = [&]() {
-      if (std::getenv("BWTC_HIP_DEBUG"))
-        std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: no period step\n",
-                     period_p, period_votes, period_longest, (unsigned long long)h_first);
-    };
-    if (period_ranks && period_forced != 1 && doubling && m > 0 && run_split == 0 && !run_try && !period_looked) {
-      period_looked = true;
-      const int rcp = find_period(n, res.ks, res.vs, m, (emit && res.carry) ? ((1ull << 56) - 1ull) : ~0ull);
-      if (rcp) return rcp;
-      if (period_p >= 2 && !period_forced) {
-        // votes say how many members lie p apart, not for how long they tie: fixed-width records with a few free bytes
-        // each vote for their width and tie for less than two records.  Before the pass, a probe: is any aligned window
-        // of (W - p) / 2 positions free of breaks, W = kPeriodWorth x max(the first round's depth, p) being the stretch
-        // the step is worth?  A stretch of W characters holds such a window; the probe's threads stop at their first break.
-        const u64 worth = kPeriodWorth * std::max<u64>(h_first, period_p);
-        const u32 span = (u32)std::min<u64>((worth - period_p) / 2, 0x40000000ull);
-        const u64 windows = (u64)n > period_p + span ? ((u64)n - period_p) / span : 0;
-        bool found = false;
-        if (windows) {
-          BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallPeriod + 1, 0, 4, st));
-          hipLaunchKernelGGL(k_period_probe, dim3((u32)((windows + 255) / 256)), dim3(256), 0, st, (const u8*)d_T, n, period_p, span, (u32)std::min<u64>(windows, 0xFFFFFFFFull), d_small + kSmallPeriod + 1);
-          BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 1, d_small + kSmallPeriod + 1, 4, hipMemcpyDeviceToHost, st));
-          BWTC_HIP_TRY(wait());
-          found = h_small[kSmallPeriod + 1] != 0;
-          stats.alg_bytes += windows * 2;                   // (at the least: a byte of each stream per window)
-        }
-        if (!found) {
-          if (std::getenv("BWTC_HIP_DEBUG")) std::fprintf(stderr, "periods: no window of %u positions of period %u without a break: no period-length pass\n", span, period_p);
-          period_p = 0;
-        }
-      }
-      if (period_p >= 2) {
-        // (a run of one byte is a stretch of every period, and the run step's business: the block's longest run first --
-        // known already unless BWTC_HIP_RUNS=0 -- and no period step where the longest stretch is no longer than that)
-        int rcb = (run_ranks || period_forced) ? 0 : build_periods(n, 1);
-        if (rcb) return rcb;
-        const u32 longest_run = run_longest;
-        rcb = build_periods(n, period_p);
-        if (rcb) return rcb;
-        if (!period_forced && longest_run >= period_longest) period_p = 0;
-        // ... and none where the longest stretch is short of kPeriodWorth times the depth it has to pass: doubling gets
-        // through it in three rounds, and the step's own round and the passes cost as much (fixed-width records with
-        // a few free bytes per record vote for their width and tie for less than two records)
-        if (!period_forced && (u64)period_longest < kPeriodWorth * std::max<u64>(h_first, period_p)) period_p = 0;
-      }
-      if (period_p >= 2) {
-        int rcb = 0;
-        if (!period_forced && (u64)period_p > h_first && (u64)period_longest > period_p) {
-          // The winner may be a multiple of the stretches' period: a list that a sort by windows of the suffix number
-          // has been through holds a group's members in another order than by position.  A period above the first
-          // round's depth defers the step, so it is worth dividing: p / q for the winner's prime factors q, kept while
-          // the longest stretch stays as long (trial passes: the longest stretch alone, no lengths stored).
-          const u32 voted = period_p, longest_voted = period_longest;
-          u32 rest = voted;
-          for (u32 q = 2; q <= rest && period_p / q >= 2; ) {
-            if (rest % q) { ++q; continue; }
-            rest /= q;
-            rcb = build_periods(n, period_p / q, false);
-            if (rcb) return rcb;
-            if (period_longest >= longest_voted) period_p /= q;
-            else while (rest % q == 0) rest /= q;          // (the same candidate again)
-          }
-          period_longest = longest_voted;
-          if (period_p != voted) {
-            rcb = build_periods(n, period_p);
-            if (rcb) return rcb;
-          }
-        }
-        if ((u64)period_p <= h_first) period_try = (u64)period_longest > h_first;
-        else period_wait = period_longest > period_p;
-        if (period_try) { run_try = true; run_period = period_p; }
-      }
-      if (!period_wait && !period_try) say_no_step();
+    if (doubling && m > 0) {
+      const int rcs = decide_step(n, m, h_first, res.ks, res.vs, (emit && res.carry) ? ((1ull << 56) - 1ull) : ~0ull);
+      if (rcs) return rcs;
     }
     int text_extra = text_rounds_fixed ? 0 : 12;        // further ones, one at a time, while the list is short (not when BWTC_HIP_TEXT_ROUNDS says how many)
     while (m > 0 || (doubling && local_m > 0)) {
@@ -3080,21 +2970,22 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
       ++stats.rounds;
       stats.active_sum += m;
       const bool text_round = text_left > 0 && m > 0;
-      bool period_req = period_try && run_try && m > 0;
-      if (period_wait && m > 0) {
+      bool run_req = false;                               // is the step this round's?  (the first round only, or the deferred period step's)
+      if (step.when == StretchStep::kThisRound) {
+        run_req = m > 0;
+        step.when = StretchStep::kNone;
+      } else if (step.when == StretchStep::kWaiting && m > 0) {
         // the deferred period step: this round, if its depth has reached p and the stretches are longer than that
         const u64 h_round = keep_h ? h : h * 2;
-        if ((u64)period_longest <= std::max<u64>(h_round, period_p)) {
-          period_wait = false;
-          say_no_step();
-        } else if (h_round >= (u64)period_p && ranks_complete && local_m == 0 && !text_round) {
-          period_wait = false;
-          period_req = true;
-          run_period = period_p;
+        if ((u64)period_longest <= std::max<u64>(h_round, step.p)) {
+          step.when = StretchStep::kNone;
+          say_no_period_step(*this, h_first);
+        } else if (h_round >= (u64)step.p && ranks_complete && local_m == 0 && !text_round) {
+          step.when = StretchStep::kNone;
+          run_req = true;
         }
       }
-      const bool run_req = (run_try && m > 0) || period_req;   // (the first round only, or the deferred period step's)
-      run_try = false;
+      const bool period_req = run_req && step.p >= 2;
       const bool text = text_round || (run_req && !ranks_complete);   // the run step reads no rank[]: it does not need the completion either
       const bool raw = !text && !doubling;               // out of text rounds and not allowed to double: hand the list back
       if (std::getenv("BWTC_HIP_DEBUG")) std::fprintf(stderr, "round %u%s: h=%llu m=%u groups=%u\n", stats.rounds, text ? " (text)" : "", (unsigned long long)h, m, res.groups);
@@ -3128,22 +3019,19 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
       const bool carried = emit && res.carry;             // this list's keys hold the characters in bits 56..63
       // the second keys (RunKeys::mode): the run step, a round behind one, or no runs in play
       const int rc2 = rank_step<u64, false>(ks, vs, m, n, 0u, carried ? ((1ull << 56) - 1ull) : ~0ull, rb, re, emit, h, &res, 0u, nullptr, text || raw, carried, raw,
-                                            run_req ? 1 : run_split ? 2 : 0);
+                                            run_req ? 1 : step.depth ? 2 : 0);
       if (rc2) return rc2;
       m = res.m;
       const bool ran = run_req && res.ran_run;
-      if (period_req && !ran) say_no_step();               // (the key had no room for the step's bit: an ordinary round)
+      if (period_req && !ran) say_no_period_step(*this, h_first);   // (the key had no room for the step's bit: an ordinary round)
       if (ran) {
         // the list is sorted to depth h still: a run's members by their closed-form keys, the others as they were (or by rank[s + h])
-        run_split = (u32)std::min<u64>(h, 0xFFFFFFFFull);
+        step.depth = (u32)std::min<u64>(h, 0xFFFFFFFFull);
         stats.route |= period_req ? 256u : 32u;
         keep_h = true;
-        if (period_req) {
-          period_step_depth = run_split;
-          if (std::getenv("BWTC_HIP_DEBUG"))
-            std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: period step at depth %u\n",
-                         period_p, period_votes, period_longest, (unsigned long long)h_first, run_split);
-        }
+        if (period_req && std::getenv("BWTC_HIP_DEBUG"))
+          std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: period step at depth %u\n",
+                       period_p, period_votes, period_longest, (unsigned long long)h_first, step.depth);
         // rank[] still incomplete: one text round behind the runs first -- a block that is one giant run ends there,
         // without the completion of rank[] that the first doubling round costs.  Not beside a live local list: its
         // members' ranks are local_depth deep, and the first doubling look-up must not lie deeper than that (text rounds
@@ -3163,7 +3051,10 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
         if (text_left == 0 && m > 0 && (u64)m * 4096 < (u64)n && text_extra > 0) { text_left = 1; --text_extra; }
       }
     }
-    if (period_wait) say_no_step();                        // (the rounds ended before their depth reached p)
+    if (step.when == StretchStep::kWaiting) {              // (the rounds ended before their depth reached p)
+      step.when = StretchStep::kNone;
+      say_no_period_step(*this, h_first);
+    }
     if (left) { *left = 0; *h_left = h; }
     return 0;
   };
@@ -3261,82 +3152,156 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
   return 0;
 }
 
-// k[] for every suffix of the block, and its longest run (the run-length pass: three launches behind whatever the stream holds).
-static constexpr int kSmallRun = 800;     // the block's longest run
-int BwtEngine::build_runs(u32 n) {
-  if (runs_built) return 0;
+// BWTC_HIP_DEBUG (read at the call: tests and scripts switch it on a live context): a pass times itself between two
+// events, for scripts/runs_bench.py and scripts/periods_bench.py.  The events are destroyed on every way out.
+namespace {
+struct PassTimer {
+  const bool on = std::getenv("BWTC_HIP_DEBUG") != nullptr;
+  hipStream_t st;
+  hipEvent_t a = nullptr, b = nullptr;
+  explicit PassTimer(hipStream_t s) : st(s) {}
+  ~PassTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  hipError_t start() {
+    if (!on) return hipSuccess;
+    hipError_t e = hipEventCreate(&a);
+    if (e == hipSuccess) e = hipEventCreate(&b);
+    return e == hipSuccess ? hipEventRecord(a, st) : e;
+  }
+  hipError_t stop() { return on ? hipEventRecord(b, st) : hipSuccess; }
+  hipError_t ms(float* out) { return hipEventElapsedTime(out, a, b); }   // (behind a wait for the stream)
+};
+}  // namespace
+
+// The stretch-length pass (three launches behind whatever the stream holds, one host wait): k_p[] for every suffix of
+// the block into d_runK, unless this is a trial, and the block's longest stretch of period p.  p = 1 is the run-length
+// pass: the text read once per launch, and the block's longest run is known from then on.
+static constexpr int kSmallStretch = 800;   // d_small: the word a pass reads back
+int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest) {
+  // (the tiles reach n + p and their positions are 32-bit: a block within two tiles of 2^32 takes no step)
+  if ((u64)n + p + 2ull * kRunTile > 0xFFFFFFFFull) { *longest = 0; return 0; }
   hipStream_t st = stream;
-  const u32 tiles = ceil_div(n, kRunTile);
-  // (BWTC_HIP_DEBUG: the pass times itself, for scripts/runs_bench.py)
-  const bool timed = std::getenv("BWTC_HIP_DEBUG") != nullptr;
-  struct Events {                                        // (destroyed on every way out)
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  } ev;
-  hipEvent_t& ev0 = ev.a;
-  hipEvent_t& ev1 = ev.b;
-  if (timed) {
-    BWTC_HIP_TRY(hipEventCreate(&ev0));
-    BWTC_HIP_TRY(hipEventCreate(&ev1));
+  const u32 tiles = (u32)(((u64)n + p + kRunTile - 1) / kRunTile);   // the tiles cover the positions x = s + p, s < n
+  u32* k = store ? d_runK : nullptr;
+  PassTimer timer(st);
+  BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallStretch, 0, 4, st));
+  BWTC_HIP_TRY(timer.start());
+  if (p == 1) {
+    hipLaunchKernelGGL(k_stretch_tiles<true>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, d_runF);
+    hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(1024), 0, st, (const u32*)d_runF, tiles, n, d_runB);
+    hipLaunchKernelGGL(k_stretch_lengths<true>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch);
+  } else {
+    hipLaunchKernelGGL(k_stretch_tiles<false>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, d_runF);
+    hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(1024), 0, st, (const u32*)d_runF, tiles, n, d_runB);
+    hipLaunchKernelGGL(k_stretch_lengths<false>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch);
   }
-  BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallRun, 0, 4, st));
-  if (timed) BWTC_HIP_TRY(hipEventRecord(ev0, st));
-  hipLaunchKernelGGL(k_run_tiles, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, d_runF);
-  hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(1024), 0, st, (const u32*)d_runF, tiles, n, d_runB);
-  hipLaunchKernelGGL(k_run_lengths, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, (const u32*)d_runB, d_runK, d_small + kSmallRun);
-  if (timed) BWTC_HIP_TRY(hipEventRecord(ev1, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallRun, d_small + kSmallRun, 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(timer.stop());
+  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallStretch, d_small + kSmallStretch, 4, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(wait());
-  if (timed) {
+  if (timer.on) {
     float ms = 0.f;
-    BWTC_HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-    std::fprintf(stderr, "runs: the run-length pass took %.4f ms for %u suffixes\n", ms, n);
+    BWTC_HIP_TRY(timer.ms(&ms));
+    if (p == 1 && store) std::fprintf(stderr, "runs: the run-length pass took %.4f ms for %u suffixes\n", ms, n);
+    else std::fprintf(stderr, store ? "periods: the period-length pass took %.4f ms for %u suffixes, period %u\n"
+                                    : "periods: a trial pass (no lengths stored) took %.4f ms for %u suffixes, period %u\n", ms, n, p);
   }
-  run_longest = h_small[kSmallRun];
-  runs_built = true;
-  stats.alg_bytes += (u64)n * (1 + 1 + 4) + (u64)tiles * 16;   // T read twice, k[] written; the tiles' words written and read
+  *longest = h_small[kSmallStretch];
+  if (store) lengths_period = p;
+  if (p == 1) { run_longest = *longest; run_longest_known = true; }
+  // T read twice (p > 1: both streams of it), the lengths written; the tiles' words written and read
+  stats.alg_bytes += (u64)n * ((p == 1 ? 1 + 1 : 2 + 2) + (store ? 4 : 0)) + (u64)tiles * 16;
   return 0;
 }
 
-// k_p[] for every suffix of the block, in k[]'s place, and its longest periodic stretch (the period-length pass: the run-
-// length pass's three launches with the text p bytes back beside the text).  p = 1 is the run-length pass itself.
-int BwtEngine::build_periods(u32 n, u32 p, bool store) {
-  if (p == 1) {
-    runs_built = false;
-    const int rc = build_runs(n);
-    period_longest = run_longest;
-    return rc;
-  }
-  // (the tiles reach n + p and their positions are 32-bit: a block within two tiles of 2^32 takes no period step)
-  if ((u64)n + p + 2ull * kRunTile > 0xFFFFFFFFull) { period_longest = 0; return 0; }
+// The block's closed-form step, into `step`, for a list of m > 0 entries that is about to double and whose first round
+// establishes depth h_first.  Nothing where a step has run already: one step per block.
+int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask) {
+  if (step.depth != 0) return 0;
   hipStream_t st = stream;
-  const u32 tiles = (u32)(((u64)n + p + kRunTile - 1) / kRunTile);   // the tiles cover the positions x = s + p, s < n
-  const bool timed = std::getenv("BWTC_HIP_DEBUG") != nullptr;
-  struct Events {                                        // (destroyed on every way out)
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  } ev;
-  if (timed) {
-    BWTC_HIP_TRY(hipEventCreate(&ev.a));
-    BWTC_HIP_TRY(hipEventCreate(&ev.b));
+  // Runs: the list may hold long runs of one byte, which doubling takes log2(length) rounds over.  k[] and the block's
+  // longest run are made here (once per block, one host wait); a run longer than the depth the first round establishes
+  // gets the run step as that round, before any text round and before rank[] is completed.
+  // (BWTC_HIP_PERIOD=1: the run step is the period step of period 1, whatever BWTC_HIP_RUNS says)
+  if (run_ranks || period_forced == 1) {
+    if (lengths_period != 1) {
+      const int rcr = stretch_lengths(n, 1, true, &run_longest);
+      if (rcr) return rcr;
+    }
+    if ((u64)run_longest > h_first) step = StretchStep{1, StretchStep::kThisRound, 0};
+    if (std::getenv("BWTC_HIP_DEBUG"))
+      std::fprintf(stderr, "runs: longest run %u, the rounds begin at depth %llu: %s\n", run_longest, (unsigned long long)h_first,
+                   step.when == StretchStep::kThisRound ? "run step" : "no run step");
   }
-  BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallPeriod, 0, 4, st));
-  if (timed) BWTC_HIP_TRY(hipEventRecord(ev.a, st));
-  hipLaunchKernelGGL(k_period_tiles, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, d_runF);
-  hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(1024), 0, st, (const u32*)d_runF, tiles, n, d_runB);
-  hipLaunchKernelGGL(k_period_lengths, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, store ? d_runK : (u32*)nullptr, d_small + kSmallPeriod);
-  if (timed) BWTC_HIP_TRY(hipEventRecord(ev.b, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod, d_small + kSmallPeriod, 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(wait());
-  if (timed) {
-    float ms = 0.f;
-    BWTC_HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-    std::fprintf(stderr, store ? "periods: the period-length pass took %.4f ms for %u suffixes, period %u\n"
-                               : "periods: a trial pass (no lengths stored) took %.4f ms for %u suffixes, period %u\n", ms, n, p);
+  // Periods: a list that takes doubling rounds and no run step may hold stretches of a period p > 1, which tie their
+  // suffixes for the stretch's length just as a run does.  The finder votes for p over the list as it stands (or
+  // BWTC_HIP_PERIOD names it); votes above the threshold buy the period-length pass, which puts k_p[] where k[] was.
+  // p <= the first round's depth: that round is the period step, exactly as the run step.  A deeper p: the step waits
+  // for the first doubling round whose depth reaches p (kWaiting), with rank[] complete and no local list beside it.
+  if (!period_ranks || period_forced == 1 || step.when != StretchStep::kNone || period_looked) return 0;
+  period_looked = true;
+  const int rcp = find_period(n, ks, vs, m, kmask);
+  if (rcp) return rcp;
+  if (period_p >= 2 && !period_forced) {
+    // votes say how many members lie p apart, not for how long they tie: fixed-width records with a few free bytes
+    // each vote for their width and tie for less than two records.  Before the pass, a probe: is any aligned window
+    // of (W - p) / 2 positions free of breaks, W = kPeriodWorth x max(the first round's depth, p) being the stretch
+    // the step is worth?  A stretch of W characters holds such a window; the probe's threads stop at their first break.
+    const u64 worth = kPeriodWorth * std::max<u64>(h_first, period_p);
+    const u32 span = (u32)std::min<u64>((worth - period_p) / 2, 0x40000000ull);
+    const u64 windows = (u64)n > period_p + span ? ((u64)n - period_p) / span : 0;
+    bool found = false;
+    if (windows) {
+      BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallPeriod + 1, 0, 4, st));
+      hipLaunchKernelGGL(k_period_probe, dim3((u32)((windows + 255) / 256)), dim3(256), 0, st, (const u8*)d_T, n, period_p, span, (u32)std::min<u64>(windows, 0xFFFFFFFFull), d_small + kSmallPeriod + 1);
+      BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 1, d_small + kSmallPeriod + 1, 4, hipMemcpyDeviceToHost, st));
+      BWTC_HIP_TRY(wait());
+      found = h_small[kSmallPeriod + 1] != 0;
+      stats.alg_bytes += windows * 2;                   // (at the least: a byte of each stream per window)
+    }
+    if (!found) {
+      if (std::getenv("BWTC_HIP_DEBUG")) std::fprintf(stderr, "periods: no window of %u positions of period %u without a break: no period-length pass\n", span, period_p);
+      period_p = 0;
+    }
   }
-  period_longest = h_small[kSmallPeriod];
-  if (store) runs_built = false;                         // (k[] is gone from d_runK)
-  stats.alg_bytes += (u64)n * (2 + 2 + (store ? 4 : 0)) + (u64)tiles * 16;   // both streams of T read twice, k_p[] written; the tiles' words written and read
+  if (period_p >= 2) {
+    // (a run of one byte is a stretch of every period, and the run step's business: the block's longest run first --
+    // known already unless BWTC_HIP_RUNS=0, where a trial pass of period 1 finds it -- and no period step where the
+    // longest stretch is no longer than that)
+    int rcb = (period_forced || run_longest_known) ? 0 : stretch_lengths(n, 1, false, &run_longest);
+    if (rcb) return rcb;
+    rcb = stretch_lengths(n, period_p, true, &period_longest);
+    if (rcb) return rcb;
+    if (!period_forced && run_longest >= period_longest) period_p = 0;
+    // ... and none where the longest stretch is short of kPeriodWorth times the depth it has to pass: doubling gets
+    // through it in three rounds, and the step's own round and the passes cost as much (fixed-width records with
+    // a few free bytes per record vote for their width and tie for less than two records)
+    if (!period_forced && (u64)period_longest < kPeriodWorth * std::max<u64>(h_first, period_p)) period_p = 0;
+  }
+  if (period_p >= 2) {
+    if (!period_forced && (u64)period_p > h_first && (u64)period_longest > period_p) {
+      // The winner may be a multiple of the stretches' period: a list that a sort by windows of the suffix number
+      // has been through holds a group's members in another order than by position.  A period above the first
+      // round's depth defers the step, so it is worth dividing: p / q for the winner's prime factors q, kept while
+      // the longest stretch stays as long (trial passes: the longest stretch alone, no lengths stored).
+      const u32 voted = period_p, longest_voted = period_longest;
+      u32 rest = voted;
+      for (u32 q = 2; q <= rest && period_p / q >= 2; ) {
+        if (rest % q) { ++q; continue; }
+        rest /= q;
+        const int rcb = stretch_lengths(n, period_p / q, false, &period_longest);
+        if (rcb) return rcb;
+        if (period_longest >= longest_voted) period_p /= q;
+        else while (rest % q == 0) rest /= q;          // (the same candidate again)
+      }
+      period_longest = longest_voted;
+      if (period_p != voted) {
+        const int rcb = stretch_lengths(n, period_p, true, &period_longest);
+        if (rcb) return rcb;
+      }
+    }
+    if ((u64)period_p <= h_first) { if ((u64)period_longest > h_first) step = StretchStep{period_p, StretchStep::kThisRound, 0}; }
+    else if (period_longest > period_p) step = StretchStep{period_p, StretchStep::kWaiting, 0};
+  }
+  if (step.when == StretchStep::kNone) say_no_period_step(*this, h_first);
   return 0;
 }
 
@@ -3346,25 +3311,18 @@ int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask
   if (period_forced) { period_p = period_forced; period_votes = 0; return 0; }
   if (m < 2) return 0;
   hipStream_t st = stream;
-  const bool timed = std::getenv("BWTC_HIP_DEBUG") != nullptr;
-  struct Events {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  } ev;
-  if (timed) {
-    BWTC_HIP_TRY(hipEventCreate(&ev.a));
-    BWTC_HIP_TRY(hipEventCreate(&ev.b));
-  }
+  PassTimer timer(st);
+  const bool timed = timer.on;
   BWTC_HIP_TRY(hipMemsetAsync(d_votes, 0, (size_t)kVoteBins * 4, st));
-  if (timed) BWTC_HIP_TRY(hipEventRecord(ev.a, st));
+  BWTC_HIP_TRY(timer.start());
   hipLaunchKernelGGL(k_period_votes, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes);
-  if (timed) BWTC_HIP_TRY(hipEventRecord(ev.b, st));
+  BWTC_HIP_TRY(timer.stop());
   hipLaunchKernelGGL(k_period_winner, dim3(1), dim3(1024), 0, st, (const u32*)d_votes, d_small + kSmallPeriod + 2);
   BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 2, d_small + kSmallPeriod + 2, 8, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(wait());
   if (timed) {
     float ms = 0.f;
-    BWTC_HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+    BWTC_HIP_TRY(timer.ms(&ms));
     std::fprintf(stderr, "periods: the vote kernel took %.4f ms for %u entries\n", ms, m);
   }
   const u32 winner = h_small[kSmallPeriod + 2];

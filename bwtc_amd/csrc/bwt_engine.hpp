@@ -469,24 +469,23 @@ struct BwtEngine {
   int local_pass(u32 n, u64 h_global, struct RrEmit& re);
   // a raw list (suffix; head slot << 32 | slot) in (S, HP) -> a sorted list the rounds understand, in res / rb
   int dress_list(u32 n, u32 total, u32* S, u64* HP, RankBuffers& rb, RankResult* res, u32 holes = 0);
-  // runs (bwt_engine.hip, RunKeys): long runs of one byte are ranked in closed form by one round, the run step
-  bool run_ranks = true;     // BWTC_HIP_RUNS=0: no run step; k[] is built only to tell a run from a voted period (run_rounds)
-  u32* d_runK = nullptr;     // k[s]: positions from s on that hold T[s]
-  u32* d_runF = nullptr; u32* d_runB = nullptr;   // the run-length pass's words per tile
-  bool runs_built = false;   // this block: k[] and the longest run are there
-  u32 run_longest = 0;       // this block's longest run
-  u32 run_split = 0;         // this block: the depth of the run step that ran (0: none)
-  int build_runs(u32 n);
-  // periods (bwt_engine.hip, "Periods"): stretches of a period p > 1 are ranked in closed form by one round, the period
-  // step -- the run step over k_p[], which takes k[]'s place in d_runK.  One closed-form step per block.
+  // runs and periods (bwt_engine.hip, "Runs" / "Periods"): long runs of one byte (period 1) and stretches of a period p > 1
+  // are ranked in closed form by one round, the step.  One step per block, over the one length array d_runK.
+  bool run_ranks = true;     // BWTC_HIP_RUNS=0: no run step; the longest run is found only to tell a run from a voted period (decide_step)
   bool period_ranks = true;  // BWTC_HIP_PERIODS=0: no votes, no period-length pass, no period step
   u32 period_forced = 0;     // BWTC_HIP_PERIOD=p: that period, no votes (1: the run path)
+  u32* d_runK = nullptr;     // k_p[s]: the leading characters of suffix s that are p-periodic (p = 1: the positions from s on that hold T[s])
+  u32* d_runF = nullptr; u32* d_runB = nullptr;   // the stretch-length pass's words per tile
   u32* d_votes = nullptr;    // the finder's table: votes per distance 0 ... kPeriodMax
-  u32 run_period = 1;        // this block: the period d_runK's lengths were made for when a step is asked for (RunKeys::p)
-  bool period_looked = false;// this block: a period has been looked for (once per block)
-  u32 period_p = 0, period_longest = 0, period_votes = 0, period_step_depth = 0;   // what bwtc_hip_period_get reports
+  u32 lengths_period = 0;    // this block: the period d_runK's lengths were made for (0: none yet)
+  u32 run_longest = 0; bool run_longest_known = false;   // this block's longest run, once a pass of period 1 has found it (made at most once per block)
+  // this block's step: its period (1: the run step), when it is due (kWaiting: the first doubling round whose depth reaches p), the depth it ran at (0: it has not)
+  struct StretchStep { u32 p = 0; enum When { kNone, kThisRound, kWaiting } when = kNone; u32 depth = 0; } step;
+  bool period_looked = false;   // this block: a period has been looked for (once per block)
+  u32 period_p = 0, period_longest = 0, period_votes = 0;   // the candidate period, its longest stretch, its votes: with the period step's depth, what bwtc_hip_period_get reports
+  int stretch_lengths(u32 n, u32 p, bool store, u32* longest);   // store == false: the longest stretch alone (a trial)
   int find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask);
-  int build_periods(u32 n, u32 p, bool store = true);   // store == false: the longest stretch alone (a trial)
+  int decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask);   // -> step
   int long_grams_override = 0;   // BWTC_HIP_LONG_G2=N: N grams in the second key word
   void scatter_rank_pairs(u32* pairs, u32* tmp, u32 m, u32 n);
   int load_text(const u8* d_src, u32 ncopy, u32 n, bool reverse, u32* hist_T);

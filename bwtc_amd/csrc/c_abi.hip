@@ -1147,11 +1147,11 @@ int bwtc_hip_period_get(bwtc_hip_ctx* ctx, uint32_t* p, uint32_t* longest, uint3
   if (p) *p = e.period_p;
   if (longest) *longest = e.period_longest;
   if (votes) *votes = e.period_votes;
-  if (step_depth) *step_depth = e.period_step_depth;
+  if (step_depth) *step_depth = e.step.p >= 2 ? e.step.depth : 0;
   return 0;
 }
 
-// The sorter's own period-length pass (BwtEngine::build_periods: three launches; p = 1: the run-length pass) over T as
+// The sorter's own stretch-length pass (BwtEngine::stretch_lengths: three launches; p = 1: the run-length pass) over T as
 // the sorter holds it -- loaded by load_text, padded with zero bytes -- on the context's buffers.
 int bwtc_hip_test_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest_out) {
   if (!ctx || !T || !k_out || !longest_out) return -1;
@@ -1162,12 +1162,11 @@ int bwtc_hip_test_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n
   u32 hist[256];
   int rc = e.load_text(e.d_in, n, n, false, hist);
   if (rc) return rc;
-  rc = e.build_periods(n, p);
+  rc = e.stretch_lengths(n, p, true, longest_out);
   if (rc) return rc;
   BWTC_HIP_TRY(hipMemcpyAsync(k_out, e.d_runK, (u64)n * 4, hipMemcpyDeviceToHost, e.stream));
   BWTC_HIP_TRY(e.wait());
   BWTC_HIP_TRY(hipGetLastError());
-  *longest_out = e.period_longest;
   return 0;
 }
 
