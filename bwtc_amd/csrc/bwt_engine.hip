@@ -2724,6 +2724,44 @@ static void say_no_period_step(const BwtEngine& e, u64 h_first) {
                  e.period_p, e.period_votes, e.period_longest, (unsigned long long)h_first);
 }
 
+// The code-key stage as suffix_sort launches it (and, kernel by kernel, BwtEngine::test_code_stage).  The key word's
+// layout: the key's upper code_bits - 32 bits, 13 upper bits of the suffix number (split items), the predecessor's
+// code, the level.  parts: 1 the sampled pair counts, 2 the code table, 4 the keys.
+static CodeKey code_key_layout(const u32* codes, int code_bits, int split_now) {
+  const int key_bits = code_bits - 32, hi_bits = split_now ? 13 : 0;
+  CodeKey ck;
+  ck.codes = codes; ck.kbits = code_bits; ck.hi_shift = key_bits; ck.chr_shift = key_bits + hi_bits; ck.lvl_shift = ck.chr_shift + 8;
+  return ck;
+}
+static u32 code_sample_tiles(u32 n) { return std::min<u32>(ceil_div(n, kPairTile), 512u); }
+static int launch_code_stage(BwtEngine& e, u32 parts, u32 n, const u8* d_lut, u32 sigma, u64* ka, u8* key_plane, int split_now,
+                             const CodeKey& ck) {
+  hipStream_t st = e.stream;
+  if (parts & 1u) {
+    BWTC_HIP_TRY(hipMemsetAsync(e.d_pairs, 0, (size_t)kPairReplicas * 65536 * 4, st));
+    hipLaunchKernelGGL(k_pair_counts, dim3(code_sample_tiles(n)), dim3(256), 0, st, (const u8*)e.d_T, d_lut, n, e.d_pairs);
+  }
+  if (parts & 2u)
+    hipLaunchKernelGGL(k_code_build, dim3(kCodeRows), dim3(256), 0, st, (const u32*)e.d_pairs, sigma, e.d_codes, e.d_small + kSmallError);
+  if (parts & 4u)
+    hipLaunchKernelGGL(k_make_keys_code, dim3(ceil_div(n, 1024)), dim3(256), 0, st, (const u8*)e.d_T, d_lut, ka, e.d_W0, n, key_plane, split_now, ck);
+  return 0;
+}
+
+int BwtEngine::test_code_stage(u32 parts, u32 n, const u32* hist, bool lone_sentinel, int kbits, bool split, u8* lut, u32* sigma) {
+  if (parts & 1u) {
+    const KeyPlan plan = plan_keys(hist, n, lone_sentinel, true);
+    std::memcpy(lut, plan.lut, 256);
+    *sigma = plan.sigma;
+  }
+  std::memcpy(h_small + kSmallLut, lut, 256);
+  BWTC_HIP_TRY(hipMemcpyAsync(d_small + kSmallLut, h_small + kSmallLut, 256, hipMemcpyHostToDevice, stream));
+  const int split_now = split ? 1 : 0;
+  const CodeKey ck = code_key_layout(d_codes, kbits, split_now);
+  return launch_code_stage(*this, parts, n, reinterpret_cast<const u8*>(d_small + kSmallLut), *sigma, static_cast<u64*>(d_R1), d_P0,
+                           split_now, ck);
+}
+
 // em != nullptr: the rankers emit the transform's bytes (see RrEmit) and the suffix array itself
 // is not stored; em == nullptr: d_SA is filled and nothing is emitted.
 int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const EmitTarget* em) {
@@ -2825,16 +2863,12 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
       split_now = (split_index && n <= (1u << 29)) ? 1 : 0;
       key_bits = code_bits - 32;                        // the key word's share; the second word takes 32
       w_bits = 32;
-      const int hi_bits = split_now ? 13 : 0;
-      CodeKey ck;
-      ck.codes = d_codes; ck.kbits = code_bits; ck.hi_shift = key_bits; ck.chr_shift = key_bits + hi_bits; ck.lvl_shift = ck.chr_shift + 8;
+      const CodeKey ck = code_key_layout(d_codes, code_bits, split_now);
       rc = upload_inverse_lut();
       if (rc) return rc;
-      BWTC_HIP_TRY(hipMemsetAsync(d_pairs, 0, (size_t)kPairReplicas * 65536 * 4, st));
-      const u32 sample_tiles = std::min<u32>(ceil_div(n, kPairTile), 512u);
-      hipLaunchKernelGGL(k_pair_counts, dim3(sample_tiles), dim3(256), 0, st, (const u8*)d_T, d_lut, n, d_pairs);
-      hipLaunchKernelGGL(k_code_build, dim3(kCodeRows), dim3(256), 0, st, (const u32*)d_pairs, plan.sigma, d_codes, d_small + kSmallError);
-      hipLaunchKernelGGL(k_make_keys_code, dim3(ceil_div(n, 1024)), dim3(256), 0, st, (const u8*)d_T, d_lut, ka, d_W0, n, key_plane, split_now, ck);
+      const u32 sample_tiles = code_sample_tiles(n);
+      rc = launch_code_stage(*this, 7u, n, d_lut, plan.sigma, ka, key_plane, split_now, ck);
+      if (rc) return rc;
       lg.hi_shift = ck.hi_shift; lg.chr_shift = ck.chr_shift; lg.chr_mask = 0xFFu; lg.lvl_shift = ck.lvl_shift;
       lk.w = d_W0;
       short_len = 0;                                    // every item has its own (rr_masks)

@@ -489,6 +489,10 @@ struct BwtEngine {
   int long_grams_override = 0;   // BWTC_HIP_LONG_G2=N: N grams in the second key word
   void scatter_rank_pairs(u32* pairs, u32* tmp, u32 m, u32 n);
   int load_text(const u8* d_src, u32 ncopy, u32 n, bool reverse, u32* hist_T);
+  // Test hook (bwtc_hip_test_code_*): the code-key stage's kernels with suffix_sort's launch shapes and key layout, on
+  // d_T as load_text left it and d_pairs / d_codes / d_R1 / d_W0 / d_P0.  parts: 1 the pair counts, 2 the table, 4 the
+  // keys.  With part 1 the dense codes come from plan_keys(hist) and go out in lut / *sigma; without it they come in.
+  int test_code_stage(u32 parts, u32 n, const u32* hist, bool lone_sentinel, int kbits, bool split, u8* lut, u32* sigma);
   // Device-resident block transform: d_src (size bytes) -> d_dst (size bytes).
   // raw=false: block semantics (reverse, sentinel, EOB patch).  raw=true: d_src already is
   // T (size = length), position pidx keeps its input byte.

@@ -1170,6 +1170,146 @@ int bwtc_hip_test_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n
   return 0;
 }
 
+// ---- test hooks of the code-key stage (bwtc_hip_test_code_*; DESIGN.md, "The code-key hooks") --------------------
+// k_pair_counts, k_code_build and k_make_keys_code through BwtEngine::test_code_stage: suffix_sort's launch shapes and
+// key layout, T loaded by load_text, the context's own d_pairs / d_codes / d_R1 / d_W0 / d_P0.  Contracts are checked on
+// the host before anything is launched (-1); canaries sit behind the keys, the second words, the plane and the table.
+namespace {
+constexpr u32 kCodeTableWords = 257u * 256u;
+constexpr u32 kCodeErrorWord = 522;                    // kSmallError
+
+bool code_shape_ok(const BwtEngine& e, const uint8_t* T, uint32_t n, int code_bits, int split) {
+  if (!T || n == 0 || (u64)n + kSortCanaryBytes > e.cap) return false;
+  if (code_bits < 40 || code_bits > 72) return false;
+  return !(split && n > (1u << 29));
+}
+
+// every row prefix free over `sigma` symbols, lengths 1 .. 26, no bits above a codeword's length
+bool code_table_ok(const uint32_t* table, uint32_t sigma) {
+  for (u32 row = 0; row < 257u; ++row) {
+    const uint32_t* r = table + (size_t)row * 256u;
+    for (u32 s = 0; s < sigma; ++s) {
+      const u32 ls = r[s] >> 27, bs = r[s] & 0x7FFFFFFu;
+      if (ls < 1u || ls > 26u || (bs >> ls)) return false;
+      for (u32 t = 0; t < s; ++t) {
+        const u32 lt = r[t] >> 27, bt = r[t] & 0x7FFFFFFu;
+        if (ls <= lt ? (bt >> (lt - ls)) == bs : (bs >> (ls - lt)) == bt) return false;
+      }
+    }
+  }
+  return true;
+}
+
+// loads T, guards and poisons the key maker's outputs
+int code_prepare(BwtEngine& e, const uint8_t* T, uint32_t n, u32* hist, SortCanaries& can) {
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  hipStream_t st = e.stream;
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_in, T, n, hipMemcpyHostToDevice, st));
+  const int rc = e.load_text(e.d_in, n, n, false, hist);
+  if (rc) return rc;
+  BWTC_HIP_TRY(hipMemsetAsync(e.d_R1, 0xA5, (u64)n * 8, st));
+  BWTC_HIP_TRY(hipMemsetAsync(e.d_W0, 0xA5, (u64)n * 4, st));
+  BWTC_HIP_TRY(hipMemsetAsync(e.d_P0, 0xA5, n, st));
+  BWTC_HIP_TRY(can.put(e.d_R1, (u64)n * 8, st));
+  BWTC_HIP_TRY(can.put(e.d_W0, (u64)n * 4, st));
+  BWTC_HIP_TRY(can.put(e.d_P0, n, st));
+  return 0;
+}
+
+int code_fetch_keys(BwtEngine& e, uint32_t n, uint64_t* keys, uint32_t* w, uint8_t* plane) {
+  hipStream_t st = e.stream;
+  if (keys) BWTC_HIP_TRY(hipMemcpyAsync(keys, e.d_R1, (u64)n * 8, hipMemcpyDeviceToHost, st));
+  if (w) BWTC_HIP_TRY(hipMemcpyAsync(w, e.d_W0, (u64)n * 4, hipMemcpyDeviceToHost, st));
+  if (plane) BWTC_HIP_TRY(hipMemcpyAsync(plane, e.d_P0, n, hipMemcpyDeviceToHost, st));
+  return 0;
+}
+}  // namespace
+
+int bwtc_hip_test_code_stage(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, int lone_sentinel, int code_bits, int split, uint8_t* lut_out,
+                             uint32_t* sigma_out, uint32_t* counts_out, uint32_t* table_out, uint32_t* err_out, uint64_t* keys, uint32_t* w,
+                             uint8_t* plane) {
+  if (!ctx || !lut_out || !sigma_out || !counts_out || !table_out || !err_out) return -1;
+  BwtEngine& e = ctx->eng;
+  if (!code_shape_ok(e, T, n, code_bits, split)) return -1;
+  if (lone_sentinel && (T[n - 1] != 0 || std::memchr(T, 0, n - 1))) return -1;   // the only zero byte is the terminator
+  hipStream_t st = e.stream;
+  SortCanaries can;
+  u32 hist[256];
+  int rc = code_prepare(e, T, n, hist, can);
+  if (rc) return rc;
+  BWTC_HIP_TRY(can.put(e.d_codes, (u64)kCodeTableWords * 4, st));
+  rc = e.test_code_stage(7u, n, hist, lone_sentinel != 0, code_bits, split != 0, lut_out, sigma_out);
+  if (rc) return rc;
+  std::vector<u32> replicas((size_t)8 * 65536);
+  BWTC_HIP_TRY(hipMemcpyAsync(replicas.data(), e.d_pairs, replicas.size() * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(table_out, e.d_codes, (u64)kCodeTableWords * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.h_small + kCodeErrorWord, e.d_small + kCodeErrorWord, 4, hipMemcpyDeviceToHost, st));
+  rc = code_fetch_keys(e, n, keys, w, plane);
+  if (rc) return rc;
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(e.wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  for (u32 i = 0; i < 65536u; ++i) {
+    u32 sum = 0;
+    for (u32 r = 0; r < 8u; ++r) sum += replicas[(size_t)r * 65536u + i];
+    counts_out[i] = sum;
+  }
+  *err_out = e.h_small[kCodeErrorWord];
+  return can.verdict();
+}
+
+int bwtc_hip_test_code_table(bwtc_hip_ctx* ctx, const uint32_t* counts, uint32_t sigma, uint32_t* table_out, uint32_t* err_out) {
+  if (!ctx || !counts || !table_out || !err_out || sigma < 1 || sigma > 256) return -1;
+  BwtEngine& e = ctx->eng;
+  u64 total = 0;
+  for (u32 i = 0; i < 65536u; ++i) total += counts[i];
+  if (total > (1ull << 21)) return -1;                  // the product's sample: at most 512 tiles of 4096 pairs
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  hipStream_t st = e.stream;
+  SortCanaries can;
+  BWTC_HIP_TRY(hipMemsetAsync(e.d_pairs, 0, (size_t)8 * 65536 * 4, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_pairs, counts, 65536 * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemsetAsync(e.d_small + kCodeErrorWord, 0, 4, st));
+  BWTC_HIP_TRY(hipMemsetAsync(e.d_codes, 0xA5, (u64)kCodeTableWords * 4, st));
+  BWTC_HIP_TRY(can.put(e.d_codes, (u64)kCodeTableWords * 4, st));
+  u8 lut[256] = {0};
+  const int rc = e.test_code_stage(2u, 0, nullptr, false, 72, false, lut, &sigma);
+  if (rc) return rc;
+  BWTC_HIP_TRY(hipMemcpyAsync(table_out, e.d_codes, (u64)kCodeTableWords * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.h_small + kCodeErrorWord, e.d_small + kCodeErrorWord, 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(e.wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  *err_out = e.h_small[kCodeErrorWord];
+  return can.verdict();
+}
+
+int bwtc_hip_test_code_keys(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, int code_bits, int split, const uint8_t* lut, uint32_t sigma,
+                            const uint32_t* table, uint64_t* keys, uint32_t* w, uint8_t* plane) {
+  if (!ctx || !lut || !table || !keys || !w || !plane || sigma < 1 || sigma > 256) return -1;
+  BwtEngine& e = ctx->eng;
+  if (!code_shape_ok(e, T, n, code_bits, split)) return -1;
+  if (lut[0] >= sigma) return -1;                       // the padding behind T
+  for (u32 i = 0; i < n; ++i) if (lut[T[i]] >= sigma) return -1;
+  if (!code_table_ok(table, sigma)) return -1;
+  hipStream_t st = e.stream;
+  SortCanaries can;
+  u32 hist[256];
+  int rc = code_prepare(e, T, n, hist, can);
+  if (rc) return rc;
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_codes, table, (u64)kCodeTableWords * 4, hipMemcpyHostToDevice, st));
+  u8 lut_in[256];
+  std::memcpy(lut_in, lut, 256);
+  rc = e.test_code_stage(4u, n, nullptr, false, code_bits, split != 0, lut_in, &sigma);
+  if (rc) return rc;
+  rc = code_fetch_keys(e, n, keys, w, plane);
+  if (rc) return rc;
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(e.wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return can.verdict();
+}
+
 int bwtc_hip_test_radix_segmented(bwtc_hip_ctx* ctx, uint32_t* keys, uint64_t n, int bit_lo, const uint32_t* tile_first, uint32_t nseg) {
   if (!ctx || !keys || !tile_first) return -1;
   BwtEngine& e = ctx->eng;

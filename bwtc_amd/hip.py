@@ -210,6 +210,7 @@ EXPORTS = [
     "bwtc_hip_test_sort_u32", "bwtc_hip_test_sort_u64", "bwtc_hip_test_scan_u32",
     "bwtc_hip_test_radix_pairs", "bwtc_hip_test_radix_long", "bwtc_hip_test_radix_segmented",
     "bwtc_hip_period_get", "bwtc_hip_test_period_lengths",
+    "bwtc_hip_test_code_stage", "bwtc_hip_test_code_table", "bwtc_hip_test_code_keys",
     "bwtc_hip_wavelet_depth_needed", "bwtc_hip_grammar_create", "bwtc_hip_grammar_destroy", "bwtc_hip_grammar_rules", "bwtc_hip_grammar_special_symbols",
     "bwtc_hip_grammar_is_special", "bwtc_hip_grammar_write", "bwtc_hip_grammar_read", "bwtc_hip_pair_replace_device",
     "bwtc_hip_test_pair_stats", "bwtc_hip_precompress", "bwtc_hip_host_precompress", "bwtc_hip_postprocess",
@@ -368,6 +369,10 @@ def load():
     L.bwtc_hip_test_radix_segmented.argtypes = [_vp, _vp, _u64, ctypes.c_int, _vp, _u32]
     L.bwtc_hip_period_get.argtypes = [_vp] + [ctypes.POINTER(_u32)] * 4
     L.bwtc_hip_test_period_lengths.argtypes = [_vp, _vp, _u32, _u32, _vp, ctypes.POINTER(_u32)]
+    L.bwtc_hip_test_code_stage.argtypes = [_vp, _vp, _u32, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_u32), _vp, _vp,
+                                           ctypes.POINTER(_u32), _vp, _vp, _vp]
+    L.bwtc_hip_test_code_table.argtypes = [_vp, _vp, _u32, _vp, ctypes.POINTER(_u32)]
+    L.bwtc_hip_test_code_keys.argtypes = [_vp, _vp, _u32, ctypes.c_int, ctypes.c_int, _vp, _u32, _vp, _vp, _vp, _vp]
     _lib = L
     return L
 
@@ -1050,6 +1055,44 @@ class Context:
         _check(self.lib.bwtc_hip_test_period_lengths(self.handle, _ptr(T) if T.size else None, T.size, int(p), _ptr(k_out), ctypes.byref(longest)),
                "bwtc_hip_test_period_lengths")
         return k_out[:T.size], int(longest.value)
+
+    # the suffix sorter's code-key stage, kernel by kernel (bwtc_hip_test_code_*): a
+    # contract the hook refuses raises BwtcHipError with code -1, a changed canary with code -20 - its index
+    def test_code_stage(self, T, lone_sentinel, code_bits=72, split=True, want_keys=True):
+        """The whole stage over T as the sorter holds it -> dict(lut, sigma, counts (256 x 256, summed over the replicas),
+        table (257 x 256), err, and -- want_keys -- keys, w, plane, slot j for suffix n - 1 - j)."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        n = T.size
+        lut, counts, table = np.zeros(256, np.uint8), np.zeros((256, 256), np.uint32), np.zeros((257, 256), np.uint32)
+        sigma, err = _u32(0), _u32(0)
+        keys = np.zeros(n, np.uint64) if want_keys else None
+        w = np.zeros(n, np.uint32) if want_keys else None
+        plane = np.zeros(n, np.uint8) if want_keys else None
+        opt = lambda a: _ptr(a) if a is not None and a.size else None
+        _check(self.lib.bwtc_hip_test_code_stage(self.handle, opt(T), n, 1 if lone_sentinel else 0, int(code_bits), 1 if split else 0, _ptr(lut),
+                                                 ctypes.byref(sigma), _ptr(counts), _ptr(table), ctypes.byref(err), opt(keys), opt(w), opt(plane)),
+               "bwtc_hip_test_code_stage")
+        return dict(lut=lut, sigma=int(sigma.value), counts=counts, table=table, err=int(err.value), keys=keys, w=w, plane=plane)
+
+    def test_code_table(self, counts, sigma):
+        """k_code_build alone over one replica's 256 x 256 counts -> (table (257 x 256), the error word)."""
+        counts = np.ascontiguousarray(counts, dtype=np.uint32)
+        assert counts.size == 65536
+        table, err = np.zeros((257, 256), np.uint32), _u32(0)
+        _check(self.lib.bwtc_hip_test_code_table(self.handle, _ptr(counts), int(sigma), _ptr(table), ctypes.byref(err)), "bwtc_hip_test_code_table")
+        return table, int(err.value)
+
+    def test_code_keys(self, T, lut, sigma, table, code_bits=72, split=True):
+        """k_make_keys_code alone with the caller's dense codes and table -> (keys, w, plane)."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        lut = np.ascontiguousarray(lut, dtype=np.uint8)
+        table = np.ascontiguousarray(table, dtype=np.uint32)
+        assert lut.size == 256 and table.size == 257 * 256
+        n = T.size
+        keys, w, plane = np.zeros(max(n, 1), np.uint64), np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint8)
+        _check(self.lib.bwtc_hip_test_code_keys(self.handle, _ptr(T) if n else None, n, int(code_bits), 1 if split else 0, _ptr(lut), int(sigma),
+                                                _ptr(table), _ptr(keys), _ptr(w), _ptr(plane)), "bwtc_hip_test_code_keys")
+        return keys[:n], w[:n], plane[:n]
 
 
 def host_cpu_slice(numa_node, rank, ranks):

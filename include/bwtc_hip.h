@@ -466,6 +466,25 @@ int bwtc_hip_period_get(bwtc_hip_ctx* ctx, uint32_t* p, uint32_t* longest, uint3
  * context's buffers: k_out[s] = the number of leading characters of suffix s that are p-periodic, *longest_out their
  * maximum.  -1, before anything is launched, for p = 0, p > 4096, n = 0 or n above the context's block size. */
 int bwtc_hip_test_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest_out);
+/* Test hooks of the suffix sorter's code-key stage: k_pair_counts, k_code_build and
+ * k_make_keys_code with suffix_sort's launch shapes and key layout (hi_shift = code_bits - 32, 13 upper bits of the suffix
+ * number when split, then the predecessor's code, then the level), over T[0..n) as the sorter holds it (loaded by
+ * load_text, zero padded), on the context's own buffers.  -1, before anything is launched, for n = 0, n + 256 above the
+ * context's block size, code_bits outside 40..72, split with n > 2^29, and each hook's own contract; -20 - i when canary
+ * i changed (keys, second words, plane, table).  A table is 257 rows of 256 entries, length << 27 | bits.
+ *   _stage: the whole stage.  lone_sentinel: T[n-1] is T's only zero byte (-1 otherwise).  Out: the dense codes lut[256]
+ *     and *sigma of plan_keys, the 65536 pair counts summed over the replicas, the table, the sort's error word, and
+ *     (each may be null) keys, w and plane, n each, slot j for suffix n - 1 - j. */
+int bwtc_hip_test_code_stage(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, int lone_sentinel, int code_bits, int split, uint8_t* lut_out,
+                             uint32_t* sigma_out, uint32_t* counts_out, uint32_t* table_out, uint32_t* err_out, uint64_t* keys, uint32_t* w,
+                             uint8_t* plane);
+/*   _table: k_code_build alone over one replica's 65536 counts (the others zero): sigma in 1..256, the counts sum to at
+ *     most 2^21 (the product's sample; -1 otherwise).  Out: the table and the error word. */
+int bwtc_hip_test_code_table(bwtc_hip_ctx* ctx, const uint32_t* counts, uint32_t sigma, uint32_t* table_out, uint32_t* err_out);
+/*   _keys: k_make_keys_code alone with the caller's lut[256], sigma and table: every byte of T and the padding's zero map
+ *     below sigma, every row is prefix free over sigma symbols with lengths 1..26 (-1 otherwise).  Out: keys, w, plane. */
+int bwtc_hip_test_code_keys(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, int code_bits, int split, const uint8_t* lut, uint32_t sigma,
+                            const uint32_t* table, uint64_t* keys, uint32_t* w, uint8_t* plane);
 /* Test hook: k range-coder chains over w-elements (w = bit << 15 | probability of the coded bit), chain j = elements
  * [bounds[j], bounds[j+1]), on the GPU lane engine (mode 0; BitEncoder, BitCoders.cpp:59-113, one lane per chain) or by the
  * host's scalar loop (mode 1); bytes of chain j = out[offsets[j] .. offsets[j+1]). */
