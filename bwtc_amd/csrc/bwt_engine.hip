@@ -3395,6 +3395,34 @@ static bool fin_room(const FinRegions& rg, u32 stride, u32 group, u64 lcap, FinO
   return at <= lcap;
 }
 
+// One k_finish launch over list a's regions rg, in this block's shape (fin_window_blk / fin_group_blk): the passes'
+// (rk == nullptr: fin_words words of characters, or fin_rounds rounds of two), the local list's steps (rk: ranks), and,
+// launch by launch, the test hooks' (BwtEngine::test_finish_pass).
+static void launch_finish(BwtEngine& e, FinList a, const FinRegions& rg, u32 n, FinList b, const FinOut& ob, u32* ncnt, u32* hardS, u64* hardHP,
+                          unsigned short* hardC, u32* hard_count, FinShallow shal, const RrEmit& re, const FinRank* rk) {
+  hipStream_t st = e.stream;
+  const int window = e.fin_window_blk, group = e.fin_group_blk, fin_words = e.fin_words, fin_rounds = e.fin_rounds;
+  const u32 grid = rg.wfirst[rg.nreg];
+#define BWTC_FINISH_W(G, E, NW) hipLaunchKernelGGL((k_finish<G, E, NW>), dim3(grid), dim3(kFinTPB), 0, st, a, rg, (const u8*)e.d_T, n, \
+                                             b, ob, ncnt, hardS, hardHP, hardC, hard_count, shal, e.d_SA, re)
+#define BWTC_FINISH_R(G, E, NR) hipLaunchKernelGGL((k_finish<G, E, 2, false, NR>), dim3(grid), dim3(kFinTPB), 0, st, a, rg, (const u8*)e.d_T, n, \
+                                             b, ob, ncnt, hardS, hardHP, hardC, hard_count, shal, e.d_SA, re)
+#define BWTC_LOCAL(G, E) hipLaunchKernelGGL((k_finish<G, E, 2, true>), dim3(grid), dim3(kFinTPB), 0, st, a, rg, (const u8*)e.d_T, n, \
+                                            b, ob, ncnt, hardS, hardHP, hardC, hard_count, shal, e.d_SA, re, *rk)
+#define BWTC_FINISH(G, E) do { if (rk) BWTC_LOCAL(G, E); \
+                               else if (fin_words >= 4) BWTC_FINISH_W(G, E, 4); else if (fin_words == 3) BWTC_FINISH_W(G, E, 3); \
+                               else if (fin_rounds >= 4) BWTC_FINISH_R(G, E, 4); else if (fin_rounds == 3) BWTC_FINISH_R(G, E, 3); \
+                               else if (fin_rounds == 2) BWTC_FINISH_R(G, E, 2); else BWTC_FINISH_W(G, E, 2); } while (0)
+  if (window <= 1024) { if (group <= 256) BWTC_FINISH(256, kFinE1); else BWTC_FINISH(512, kFinE1); }
+  else if (group <= 256) BWTC_FINISH(256, kFinE2);
+  else if (group <= 512) BWTC_FINISH(512, kFinE2);
+  else BWTC_FINISH(1024, kFinE2);
+#undef BWTC_FINISH
+#undef BWTC_LOCAL
+#undef BWTC_FINISH_W
+#undef BWTC_FINISH_R
+}
+
 int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, FinShallow shal, FinOutcome* fo, bool keep_local, int max_passes) {
   hipStream_t st = stream;
   u32* cnt = d_small + kSmallFin;      // [1] hard list, [2] its smallest depth; [3] smallest depth of what waits for the rounds; [4] shallow list, [5] its smallest depth
@@ -3430,21 +3458,7 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
     // (three aligned words) per owned entry, a byte and a suffix per finished one, an entry per member that stays
     stats.alg_bytes += (u64)m * (14 * 4 / 3 + (pass_chars + 8) + 5);
     BWTC_HIP_TRY(hipMemsetAsync(ncnt, 0, (kFinRegions + 1) * 4, st));
-    const u32 grid = rg.wfirst[rg.nreg];
-#define BWTC_FINISH_W(G, E, NW) hipLaunchKernelGGL((k_finish<G, E, NW>), dim3(grid), dim3(kFinTPB), 0, st, a, rg, (const u8*)d_T, n, \
-                                             b, ob, ncnt, d_parkS + park0, d_parkHP + park0, d_hardC, cnt + 1, shal, d_SA, re)
-#define BWTC_FINISH_R(G, E, NR) hipLaunchKernelGGL((k_finish<G, E, 2, false, NR>), dim3(grid), dim3(kFinTPB), 0, st, a, rg, (const u8*)d_T, n, \
-                                             b, ob, ncnt, d_parkS + park0, d_parkHP + park0, d_hardC, cnt + 1, shal, d_SA, re)
-#define BWTC_FINISH(G, E) do { if (fin_words >= 4) BWTC_FINISH_W(G, E, 4); else if (fin_words == 3) BWTC_FINISH_W(G, E, 3); \
-                               else if (fin_rounds >= 4) BWTC_FINISH_R(G, E, 4); else if (fin_rounds == 3) BWTC_FINISH_R(G, E, 3); \
-                               else if (fin_rounds == 2) BWTC_FINISH_R(G, E, 2); else BWTC_FINISH_W(G, E, 2); } while (0)
-    if (window <= 1024) { if (group <= 256) BWTC_FINISH(256, kFinE1); else BWTC_FINISH(512, kFinE1); }
-    else if (group <= 256) BWTC_FINISH(256, kFinE2);
-    else if (group <= 512) BWTC_FINISH(512, kFinE2);
-    else BWTC_FINISH(1024, kFinE2);
-#undef BWTC_FINISH
-#undef BWTC_FINISH_W
-#undef BWTC_FINISH_R
+    launch_finish(*this, a, rg, n, b, ob, ncnt, d_parkS + park0, d_parkHP + park0, d_hardC, cnt + 1, shal, re, nullptr);
     BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin, cnt, 24, hipMemcpyDeviceToHost, st));
     BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFinNext, ncnt, (kFinRegions + 1) * 4, hipMemcpyDeviceToHost, st));
     BWTC_HIP_TRY(wait());
@@ -3572,18 +3586,12 @@ int BwtEngine::local_pass(u32 n, u64 h_global, RrEmit& re) {
   const u32 stride = (u32)(window - group);
   BWTC_HIP_TRY(hipMemsetAsync(ncnt, 0, kFinRegions * 4, st));
   BWTC_HIP_TRY(hipMemsetAsync(cnt + 1, 0, 4, st));
-  const u32 grid = local_rg.wfirst[local_rg.nreg];
   FinOut ob;
   if (!fin_room(local_rg, stride, (u32)group, cap + cap / 128 + 65536, &ob)) return -3;   // (finisher_passes keeps such lists off this route)
   FinShallow none{d_parkS, d_parkHP, cnt + 4, 0u};
   FinRank rk{d_rank, (u32)at, (u32)at2, d_US, d_UR};
-#define BWTC_LOCAL(G, E) hipLaunchKernelGGL((k_finish<G, E, 2, true>), dim3(grid), dim3(kFinTPB), 0, st, local_list(local_home), local_rg, (const u8*)d_T, n, \
-                                            local_list(1 - local_home), ob, ncnt, d_parkS, d_parkHP, d_LC1 /* never written: no group is too large */, cnt + 1, none, d_SA, re, rk)
-  if (window <= 1024) { if (group <= 256) BWTC_LOCAL(256, kFinE1); else BWTC_LOCAL(512, kFinE1); }
-  else if (group <= 256) BWTC_LOCAL(256, kFinE2);
-  else if (group <= 512) BWTC_LOCAL(512, kFinE2);
-  else BWTC_LOCAL(1024, kFinE2);
-#undef BWTC_LOCAL
+  launch_finish(*this, local_list(local_home), local_rg, n, local_list(1 - local_home), ob, ncnt, d_parkS, d_parkHP,
+                d_LC1 /* never written: no group is too large */, cnt + 1, none, re, &rk);
   BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 1, cnt + 1, 4, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFinNext, ncnt, kFinRegions * 4, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(wait());
@@ -3613,6 +3621,255 @@ int BwtEngine::local_pass(u32 n, u64 h_global, RrEmit& re) {
   local_home = 1 - local_home;
   local_depth = (u32)std::min<u64>(at2 + delta, 0xFFFFFFF0ull);
   return 0;
+}
+
+// ---- test hook: one k_finish launch ("The finisher hooks") -------------------------------------------
+// What k_finish assumes of its list, checked on the host: a list that breaks it makes the kernel store past its arrays.
+static bool fin_test_list_ok(const FinPassTest& t, u64 cap, u64 lcap, FinRegions* rg, FinOut* ob, u32* m_out, u32* span_out, u64* room_out) {
+  const u32 n = t.n;
+  if (n < 1u || (u64)n + TestCanaries::kBytes > cap) return false;
+  if (!((t.window == 1024 && (t.group == 256 || t.group == 512)) || (t.window == 2048 && (t.group == 256 || t.group == 512 || t.group == 1024)))) return false;
+  if (t.words < 2 || t.words > 4 || t.rounds < 1 || t.rounds > 4 || (t.words != 2 && t.rounds != 1)) return false;
+  if (t.ranks && (t.words != 2 || t.rounds != 1)) return false;
+  if (t.nreg < 1u || t.nreg > kFinRegions) return false;
+  if (t.lf_n > 256u || (t.lf_n > 1u && (t.lf_x != n / t.lf_n || t.lf_x < 1u))) return false;
+  if (t.out_n != n && t.out_n + 1u != n) return false;
+  const u32 stride = (u32)(t.window - t.group);
+  std::memset(rg, 0, sizeof *rg);
+  rg->nreg = t.nreg;
+  u64 m = 0, end = 0;
+  for (u32 r = 0; r < t.nreg; ++r) {
+    if ((u64)t.ebase[r] < end) return false;                           // ascending, disjoint
+    end = (u64)t.ebase[r] + t.ecount[r];
+    if (end + 128u > lcap) return false;                               // (and room for the canary behind the 16-bit array)
+    rg->ebase[r] = t.ebase[r]; rg->ecount[r] = t.ecount[r];
+    rg->wfirst[r + 1] = rg->wfirst[r] + ceil_div(t.ecount[r], stride);
+    m += t.ecount[r];
+  }
+  if (m < 1u || m > n) return false;
+  if (!fin_room(*rg, stride, (u32)t.group, lcap, ob)) return false;
+  const u32 grid = rg->wfirst[rg->nreg];
+  const u64 room = (u64)grid * stride + (u64)ceil_div(grid, kFinChunk) * (u32)t.group;     // where fin_room's last region ends
+  if (room + 128u > lcap || room > t.next_cap) return false;
+  std::vector<u8> seen_s(n, 0), seen_p(n, 0);
+  for (u32 r = 0; r < t.nreg; ++r) {
+    u32 run = 0;                                                       // members of the current group so far
+    for (u32 i = t.ebase[r]; i < t.ebase[r] + t.ecount[r]; ++i) {
+      const u32 s = t.S[i], p = t.P[i], h = t.H[i];
+      if (s >= n || p >= n || seen_s[s] || seen_p[p]) return false;
+      seen_s[s] = 1; seen_p[p] = 1;                                    // (distinct P: no head in two runs or two regions)
+      const bool cont = run > 0 && t.H[i - 1] == h;
+      if (cont) {
+        if (p != h + run || (t.C[i] >> 8) != (t.C[i - 1] >> 8)) return false;
+        ++run;
+      } else {
+        if (t.ranks && run > 0 && run < 2u) return false;
+        if (p != h) return false;
+        run = 1;
+      }
+      if (t.ranks && run > (u32)t.group) return false;
+    }
+    if (t.ranks && t.ecount[r] && run < 2u) return false;
+  }
+  if (t.ranks) {
+    if (!t.rank || t.at < 1u || (t.at2 != 0u && t.at2 <= t.at)) return false;
+    if (t.at2 && (u64)t.at2 + (t.at2 - t.at) >= 0xFFFFFFF0ull) return false;
+    for (u32 i = 0; i < n; ++i) if (t.rank[i] >= n) return false;
+  }
+  *m_out = (u32)m; *span_out = (u32)end; *room_out = room;
+  return true;
+}
+
+// the emissions of a hooked launch: SA, out, pidx, last_char and lf[] poisoned, and the RrEmit that points at them
+static hipError_t fin_test_emit_begin(BwtEngine& e, u32 n, u32 out_n, u32 lf_n, u32 lf_x, RrEmit* re) {
+  hipStream_t st = e.stream;
+  hipError_t rc = hipMemsetAsync(e.d_SA, 0xA5, (u64)n * 4, st);
+  if (rc == hipSuccess) rc = hipMemsetAsync(e.d_out, 0xA5, n, st);
+  if (rc == hipSuccess) rc = hipMemsetAsync(e.d_small + kSmallLf, 0xA5, 256 * 4, st);
+  if (rc == hipSuccess) rc = hipMemsetAsync(e.d_small + kSmallPidx, 0xA5, 4, st);
+  if (rc == hipSuccess) rc = hipMemsetAsync(e.d_small + kSmallLastChar, 0xA5, 4, st);
+  std::memset(re, 0, sizeof *re);
+  re->out = e.d_out; re->out_n = out_n; re->last_char = e.d_small + kSmallLastChar; re->pidx = e.d_small + kSmallPidx; re->T = e.d_T;
+  re->lf = e.d_small + kSmallLf; re->lf_n = lf_n; re->lf_x = lf_x; re->lf_inv = lf_x > 1u ? (u32)((1ull << 32) / lf_x) : 0u;
+  return rc;
+}
+static hipError_t fin_test_emit_fetch(BwtEngine& e, u32 n, u32* SA, u8* out, u32* small, u32* lf) {
+  hipStream_t st = e.stream;
+  hipError_t rc = hipMemcpyAsync(SA, e.d_SA, (u64)n * 4, hipMemcpyDeviceToHost, st);
+  if (rc == hipSuccess) rc = hipMemcpyAsync(out, e.d_out, n, hipMemcpyDeviceToHost, st);
+  if (rc == hipSuccess) rc = hipMemcpyAsync(small, e.d_small + kSmallPidx, 4, hipMemcpyDeviceToHost, st);
+  if (rc == hipSuccess) rc = hipMemcpyAsync(small + 1, e.d_small + kSmallLastChar, 4, hipMemcpyDeviceToHost, st);
+  if (rc == hipSuccess) rc = hipMemcpyAsync(lf, e.d_small + kSmallLf, 256 * 4, hipMemcpyDeviceToHost, st);
+  return rc;
+}
+
+// The finisher's knobs while a hook runs: the shape from the hook's arguments, fin_max_passes at its default of eight
+// (whatever BWTC_HIP_FIN_PASSES said when the context was made), all put back when the hook returns.  What a hook
+// leaves changed besides -- parked, park_holes, passes_done, local_upd, stats -- is this block's state, which the next
+// transform resets before it reads it (suffix_sort).
+struct FinKnobScope {
+  BwtEngine& e;
+  const int window, group, words, rounds, max_passes; const u32 floor;
+  FinKnobScope(BwtEngine& eng, int w, int g, int nw, int nr, u32 fl)
+      : e(eng), window(eng.fin_window_blk), group(eng.fin_group_blk), words(eng.fin_words), rounds(eng.fin_rounds),
+        max_passes(eng.fin_max_passes), floor(eng.fin_floor) {
+    e.fin_window_blk = w; e.fin_group_blk = g; e.fin_words = nw; e.fin_rounds = nr; e.fin_floor = fl; e.fin_max_passes = 8;
+  }
+  ~FinKnobScope() {
+    e.fin_window_blk = window; e.fin_group_blk = group; e.fin_words = words; e.fin_rounds = rounds; e.fin_floor = floor;
+    e.fin_max_passes = max_passes;
+  }
+};
+
+int BwtEngine::test_finish_pass(FinPassTest& t) {
+  const u64 lcap = cap + cap / 128 + 65536;
+  FinRegions rg; FinOut ob;
+  u32 m = 0, span = 0; u64 room = 0;
+  if (!fin_test_list_ok(t, cap, lcap, &rg, &ob, &m, &span, &room)) return -1;
+  hipStream_t st = stream;
+  const u32 n = t.n;
+  FinKnobScope knobs(*this, t.window, t.group, t.words, t.rounds, t.floor);
+  // the lists' homes: the passes' own arrays, the local list's two homes in RANK mode
+  const FinList a = t.ranks ? local_list(0) : FinList{d_V0, d_G0, d_GRP, reinterpret_cast<unsigned short*>(d_C0)};
+  const FinList b = t.ranks ? local_list(1) : FinList{d_W0, d_W1, d_G1, reinterpret_cast<unsigned short*>(d_C1)};
+  unsigned short* hardC = t.ranks ? d_LC1 : d_hardC;
+  u32* cnt = d_small + kSmallFin;
+  u32* ncnt = d_small + kSmallFinNext;
+  const FinShallow shal = t.ranks ? FinShallow{d_parkS, d_parkHP, cnt + 4, 0u} : FinShallow{d_V1, static_cast<u64*>(d_R2), cnt + 4, fin_floor};
+  TestCanaries can;
+  BWTC_HIP_TRY(hipMemcpyAsync(a.S, t.S, (u64)span * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(a.P, t.P, (u64)span * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(a.H, t.H, (u64)span * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(a.C, t.C, (u64)span * 2, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(can.put(a.S, (u64)span * 4, st)); BWTC_HIP_TRY(can.put(a.P, (u64)span * 4, st));
+  BWTC_HIP_TRY(can.put(a.H, (u64)span * 4, st)); BWTC_HIP_TRY(can.put(a.C, (u64)span * 2, st));
+  BWTC_HIP_TRY(hipMemsetAsync(b.S, 0xA5, room * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(b.P, 0xA5, room * 4, st));
+  BWTC_HIP_TRY(hipMemsetAsync(b.H, 0xA5, room * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(b.C, 0xA5, room * 2, st));
+  BWTC_HIP_TRY(can.put(b.S, room * 4, st)); BWTC_HIP_TRY(can.put(b.P, room * 4, st));
+  BWTC_HIP_TRY(can.put(b.H, room * 4, st)); BWTC_HIP_TRY(can.put(b.C, room * 2, st));
+  BWTC_HIP_TRY(hipMemsetAsync(d_parkS, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(d_parkHP, 0xA5, (u64)m * 8, st));
+  BWTC_HIP_TRY(can.put(d_parkS, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(d_parkHP, (u64)m * 8, st));
+  if (t.ranks) {
+    BWTC_HIP_TRY(hipMemcpyAsync(d_rank, t.rank, (u64)n * 4, hipMemcpyHostToDevice, st));
+    BWTC_HIP_TRY(hipMemsetAsync(d_US, 0xFF, (u64)span * 4, st));       // kFinNone: a place no member notes is no update
+    BWTC_HIP_TRY(hipMemsetAsync(d_UR, 0xA5, (u64)span * 4, st));
+    BWTC_HIP_TRY(can.put(d_US, (u64)span * 4, st)); BWTC_HIP_TRY(can.put(d_UR, (u64)span * 4, st));
+  } else {
+    BWTC_HIP_TRY(hipMemsetAsync(d_hardC, 0xA5, (u64)m * 2, st));
+    BWTC_HIP_TRY(can.put(d_hardC, (u64)m * 2, st));
+    BWTC_HIP_TRY(hipMemsetAsync(shal.S, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(shal.HP, 0xA5, (u64)m * 8, st));
+    BWTC_HIP_TRY(can.put(shal.S, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(shal.HP, (u64)m * 8, st));
+  }
+  h_small[kSmallFin + 1] = 0; h_small[kSmallFin + 2] = 0xFFFFFFFFu; h_small[kSmallFin + 4] = 0; h_small[kSmallFin + 5] = 0xFFFFFFFFu;
+  BWTC_HIP_TRY(hipMemcpyAsync(cnt + 1, h_small + kSmallFin + 1, 8, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(cnt + 4, h_small + kSmallFin + 4, 8, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemsetAsync(ncnt, 0, (kFinRegions + 1) * 4, st));
+  RrEmit re;
+  BWTC_HIP_TRY(fin_test_emit_begin(*this, n, t.out_n, t.lf_n, t.lf_x, &re));
+  const FinRank rk{d_rank, t.at, t.at2, d_US, d_UR};
+  launch_finish(*this, a, rg, n, b, ob, ncnt, d_parkS, d_parkHP, hardC, cnt + 1, shal, re, t.ranks ? &rk : nullptr);
+  if (t.ranks) {
+    local_upd = rg; local_pending = true;
+    const int rcu = local_updates();
+    if (rcu) return rcu;
+    BWTC_HIP_TRY(hipMemcpyAsync(t.rank, d_rank, (u64)n * 4, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(hipMemcpyAsync(t.us, d_US, (u64)span * 4, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(hipMemcpyAsync(t.ur, d_UR, (u64)span * 4, hipMemcpyDeviceToHost, st));
+  } else {
+    BWTC_HIP_TRY(hipMemcpyAsync(t.hC, d_hardC, (u64)m * 2, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(hipMemcpyAsync(t.sS, shal.S, (u64)m * 4, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(hipMemcpyAsync(t.sHP, shal.HP, (u64)m * 8, hipMemcpyDeviceToHost, st));
+  }
+  BWTC_HIP_TRY(hipMemcpyAsync(t.hS, d_parkS, (u64)m * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.hHP, d_parkHP, (u64)m * 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.nS, b.S, room * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.nP, b.P, room * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.nH, b.H, room * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.nC, b.C, room * 2, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.next_count, ncnt, (kFinRegions + 1) * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.hard_count, cnt + 1, 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.shal_count, cnt + 4, 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(fin_test_emit_fetch(*this, n, t.SA, t.out, t.small, t.lf));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  for (u32 r = 0; r < kFinRegions; ++r) t.next_base[r] = ob.base[r];
+  return can.verdict();
+}
+
+int BwtEngine::test_finisher(bwtc_hip_fin_run& t) {
+  const u64 lcap = cap + cap / 128 + 65536;
+  // the list's contracts are one pass's, over one region from entry 0
+  const u32 ebase = 0, ecount = t.m;
+  FinPassTest one;
+  std::memset(&one, 0, sizeof one);
+  one.n = t.n; one.nreg = 1; one.ebase = &ebase; one.ecount = &ecount; one.S = t.S; one.P = t.P; one.H = t.H; one.C = t.C;
+  one.window = t.window; one.group = t.group; one.words = t.words; one.rounds = t.rounds;
+  one.floor = t.floor; one.out_n = t.out_n; one.lf_n = t.lf_n; one.lf_x = t.lf_x; one.next_cap = 0xFFFFFFFFu;
+  FinRegions rg; FinOut ob;
+  u32 m = 0, span = 0; u64 room = 0;
+  if (t.max_passes < 0 || !fin_test_list_ok(one, cap, lcap, &rg, &ob, &m, &span, &room)) return -1;
+  // a later pass reads up to 16 regions, each with a last window that is not full: 16 strides (and a chunk's group) more
+  room += 16ull * (u32)(t.window - t.group) + 2ull * (u32)t.group;
+  if (room + 128u > lcap) return -1;
+  hipStream_t st = stream;
+  const u32 n = t.n;
+  FinKnobScope knobs(*this, t.window, t.group, t.words, t.rounds, t.floor);
+  const FinList a{d_V0, d_G0, d_GRP, reinterpret_cast<unsigned short*>(d_C0)};
+  const FinList b{d_W0, d_W1, d_G1, reinterpret_cast<unsigned short*>(d_C1)};
+  u32* cnt = d_small + kSmallFin;
+  const FinShallow shal{d_V1, static_cast<u64*>(d_R2), cnt + 4, fin_floor};
+  const FinList home = local_list(0);
+  TestCanaries can;
+  // both lists take a pass's output in turn: never more than the first pass's room, the longest list's
+  const FinList ab[2] = {a, b};
+  for (int i = 0; i < 2; ++i) {
+    BWTC_HIP_TRY(hipMemsetAsync(ab[i].S, 0xA5, room * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(ab[i].P, 0xA5, room * 4, st));
+    BWTC_HIP_TRY(hipMemsetAsync(ab[i].H, 0xA5, room * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(ab[i].C, 0xA5, room * 2, st));
+    BWTC_HIP_TRY(can.put(ab[i].S, room * 4, st)); BWTC_HIP_TRY(can.put(ab[i].P, room * 4, st));
+    BWTC_HIP_TRY(can.put(ab[i].H, room * 4, st)); BWTC_HIP_TRY(can.put(ab[i].C, room * 2, st));
+  }
+  BWTC_HIP_TRY(hipMemcpyAsync(a.S, t.S, (u64)m * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(a.P, t.P, (u64)m * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(a.H, t.H, (u64)m * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(a.C, t.C, (u64)m * 2, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemsetAsync(d_parkS, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(d_parkHP, 0xA5, (u64)m * 8, st));
+  BWTC_HIP_TRY(can.put(d_parkS, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(d_parkHP, (u64)m * 8, st));
+  BWTC_HIP_TRY(hipMemsetAsync(shal.S, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(shal.HP, 0xA5, (u64)m * 8, st));
+  BWTC_HIP_TRY(can.put(shal.S, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(shal.HP, (u64)m * 8, st));
+  BWTC_HIP_TRY(hipMemsetAsync(home.S, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(home.P, 0xA5, (u64)m * 4, st));
+  BWTC_HIP_TRY(hipMemsetAsync(home.H, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(home.C, 0xA5, (u64)m * 2, st));   // (d_hardC: the passes' dead output, then the local list's characters)
+  BWTC_HIP_TRY(can.put(home.S, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(home.P, (u64)m * 4, st));
+  BWTC_HIP_TRY(can.put(home.H, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(home.C, (u64)m * 2, st));
+  RrEmit re;
+  BWTC_HIP_TRY(fin_test_emit_begin(*this, n, t.out_n, t.lf_n, t.lf_x, &re));
+  // as suffix_sort leaves things before the passes
+  h_small[kSmallFin + 3] = 0xFFFFFFFFu; h_small[kSmallFin + 4] = 0; h_small[kSmallFin + 5] = 0xFFFFFFFFu; h_small[kSmallFin + 6] = 0xFFFFFFFFu;
+  BWTC_HIP_TRY(hipMemcpyAsync(cnt + 3, h_small + kSmallFin + 3, 16, hipMemcpyHostToDevice, st));
+  parked = 0; park_holes = 0; local_m = 0; local_pending = false; stats.route = 0;
+  FinOutcome fo;
+  const int rc = finisher_passes(n, m, a, b, re, shal, &fo, t.keep_local != 0, t.max_passes);
+  if (rc) return rc;
+  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 3, cnt + 3, 12, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(wait());
+  if (parked > m || h_small[kSmallFin + 4] > m || fo.local > m) return -3;
+  t.outcome[0] = fo.hard; t.outcome[1] = fo.hard_depth; t.outcome[2] = fo.left; t.outcome[3] = fo.local;
+  t.info[0] = (u32)passes_done; t.info[1] = stats.route; t.info[2] = parked; t.info[3] = park_holes;
+  t.info[4] = h_small[kSmallFin + 4]; t.info[5] = h_small[kSmallFin + 5]; t.info[6] = h_small[kSmallFin + 3]; t.info[7] = fo.local ? local_depth : 0u;
+  BWTC_HIP_TRY(hipMemcpyAsync(t.pS, d_parkS, (u64)parked * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.pHP, d_parkHP, (u64)parked * 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.sS, shal.S, (u64)t.info[4] * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.sHP, shal.HP, (u64)t.info[4] * 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.lS, home.S, (u64)fo.local * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.lP, home.P, (u64)fo.local * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.lH, home.H, (u64)fo.local * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.lC, home.C, (u64)fo.local * 2, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(fin_test_emit_fetch(*this, n, t.SA, t.out, t.small, t.lf));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  local_m = 0;                                     // (no local list is left behind for a transform to find)
+  return can.verdict();
 }
 
 // A raw list becomes a list the rounds understand: sorted by slot (groups contiguous, a positional slot

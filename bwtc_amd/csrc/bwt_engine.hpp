@@ -30,6 +30,7 @@
 #include <memory>
 #include <utility>
 #include <cstdlib>
+#include <cstring>
 #include <functional>
 #include <vector>
 
@@ -44,6 +45,37 @@ struct FinOutcome { u32 hard = 0, hard_depth = 0xFFFFFFFFu, left = 0, local = 0;
 constexpr u32 kFinRegions = 16;
 constexpr u32 kPeriodMax = 4096;   // the longest period the period step looks for (bwt_engine.hip, "Periods")
 struct FinRegions { u32 nreg; u32 wfirst[kFinRegions + 1]; u32 ebase[kFinRegions]; u32 ecount[kFinRegions]; };   // a finisher run: entries of groups too large (and their smallest depth), entries its last pass left tied
+
+// 256 bytes of canary behind the last item a test hook's kernels may write (c_abi.hip, BwtEngine::test_finish_pass): a
+// changed canary is kBase - (index in the order they were put).
+struct TestCanaries {
+  static constexpr size_t kBytes = 256;
+  static constexpr int kBase = -20, kMax = 16;
+  u8 pat[kBytes];
+  u8 back[kMax][kBytes];
+  const u8* at[kMax];
+  int count = 0;
+  TestCanaries() { for (size_t i = 0; i < kBytes; ++i) pat[i] = (u8)(0xC3u ^ (i * 29u)); }
+  hipError_t put(void* buf, u64 bytes, hipStream_t st) {
+    if (count >= kMax) return hipErrorInvalidValue;     // (no room to remember another one: the hook fails, nothing is guarded less)
+    u8* p = static_cast<u8*>(buf) + bytes;
+    at[count++] = p;
+    return hipMemcpyAsync(p, pat, kBytes, hipMemcpyHostToDevice, st);
+  }
+  hipError_t fetch(hipStream_t st) {
+    for (int i = 0; i < count; ++i) {
+      const hipError_t rc = hipMemcpyAsync(back[i], at[i], kBytes, hipMemcpyDeviceToHost, st);
+      if (rc != hipSuccess) return rc;
+    }
+    return hipSuccess;
+  }
+  int verdict() const {                                 // after the stream has been waited for
+    for (int i = 0; i < count; ++i) if (std::memcmp(back[i], pat, kBytes) != 0) return kBase - i;
+    return 0;
+  }
+};
+
+typedef bwtc_hip_fin_pass FinPassTest;   // one k_finish launch for the test hooks (bwtc_hip.h; BwtEngine::test_finish_pass)
 
 // ---- device side of the 'B' block pipeline (host side: wavelet_pipeline.hpp) ----------------
 // Page-locked host bytes: the packed streams are copied from the device straight into the
@@ -467,6 +499,10 @@ struct BwtEngine {
   struct FinList local_list(int home) const;
   int local_updates();
   int local_pass(u32 n, u64 h_global, struct RrEmit& re);
+  // Test hook: one k_finish launch (chars or RANK) through the launch code of finisher_passes / local_pass, on d_T as
+  // load_text left it.  -1: the list breaks a contract of k_finish (nothing is launched); -20 - i: a canary changed.
+  int test_finish_pass(FinPassTest& t);
+  int test_finisher(bwtc_hip_fin_run& t);   // the same for the driver, finisher_passes, over a one-region list
   // a raw list (suffix; head slot << 32 | slot) in (S, HP) -> a sorted list the rounds understand, in res / rb
   int dress_list(u32 n, u32 total, u32* S, u64* HP, RankBuffers& rb, RankResult* res, u32 holes = 0);
   // runs and periods (bwt_engine.hip, "Runs" / "Periods"): long runs of one byte (period 1) and stretches of a period p > 1

@@ -66,33 +66,10 @@ static int test_sort(bwtc_hip_ctx* ctx, K* keys, uint32_t* vals, uint64_t n, int
 // radix_sort_pairs / _long / _keys_segmented called directly on the engine's buffers, three-launch scans (no ScanScope),
 // no BwtEngine::sort_pairs in between.  A hook checks the sort's contract on the host before it launches anything (-1),
 // makes the "producer's" first digit plane itself, and puts 256 bytes of canary behind the last item of both buffers of
-// every ping-pong pair it hands over: a changed canary is kSortCanaryBase - (index in the order they were put).
+// every ping-pong pair it hands over: a changed canary is -20 - (index in the order they were put).
 namespace {
-constexpr size_t kSortCanaryBytes = 256;
-constexpr int kSortCanaryBase = -20;
-struct SortCanaries {
-  u8 pat[kSortCanaryBytes];
-  u8 back[8][kSortCanaryBytes];
-  const u8* at[8];
-  int count = 0;
-  SortCanaries() { for (size_t i = 0; i < kSortCanaryBytes; ++i) pat[i] = (u8)(0xC3u ^ (i * 29u)); }
-  hipError_t put(void* buf, u64 bytes, hipStream_t st) {
-    u8* p = static_cast<u8*>(buf) + bytes;
-    at[count++] = p;
-    return hipMemcpyAsync(p, pat, kSortCanaryBytes, hipMemcpyHostToDevice, st);
-  }
-  hipError_t fetch(hipStream_t st) {
-    for (int i = 0; i < count; ++i) {
-      const hipError_t rc = hipMemcpyAsync(back[i], at[i], kSortCanaryBytes, hipMemcpyDeviceToHost, st);
-      if (rc != hipSuccess) return rc;
-    }
-    return hipSuccess;
-  }
-  int verdict() const {                                 // after the stream has been waited for
-    for (int i = 0; i < count; ++i) if (std::memcmp(back[i], pat, kSortCanaryBytes) != 0) return kSortCanaryBase - i;
-    return 0;
-  }
-};
+constexpr size_t kSortCanaryBytes = TestCanaries::kBytes;
+typedef TestCanaries SortCanaries;                    // (bwt_engine.hpp; shared with the finisher's hook)
 
 // keys: n + n_holes items in, n out; vals likewise (given values), n out (made-up values), untouched (keys only).
 // values_mode as k_radix_scatter's: 0 given, 1 positions, 2 keys only, 3 descending.  planes: 0 none, 1 both, 2 both and
@@ -1308,6 +1285,40 @@ int bwtc_hip_test_code_keys(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, int
   BWTC_HIP_TRY(e.wait());
   BWTC_HIP_TRY(hipGetLastError());
   return can.verdict();
+}
+
+// ---- test hooks of the finisher (bwtc_hip_test_finish_pass / _local_pass; DESIGN.md, "The finisher hooks") -------
+// One k_finish launch through BwtEngine::test_finish_pass, which checks the list's contracts on the host, guards every
+// array the kernel may write with canaries and shares its launch code with finisher_passes / local_pass.
+static int test_fin_pass(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_fin_pass* p, int ranks) {
+  if (!ctx || !T || !p) return -1;
+  if (!p->ebase || !p->ecount || !p->S || !p->P || !p->H || !p->C || !p->nS || !p->nP || !p->nH || !p->nC || !p->next_base || !p->next_count ||
+      !p->hS || !p->hHP || !p->hard_count || !p->shal_count || !p->SA || !p->out || !p->small || !p->lf) return -1;
+  if (ranks ? (!p->rank || !p->us || !p->ur) : (!p->hC || !p->sS || !p->sHP)) return -1;
+  BwtEngine& e = ctx->eng;
+  if (p->n == 0 || (u64)p->n + kSortCanaryBytes > e.cap) return -1;
+  p->ranks = ranks;
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_in, T, p->n, hipMemcpyHostToDevice, e.stream));
+  u32 hist[256];
+  const int rc = e.load_text(e.d_in, p->n, p->n, false, hist);
+  if (rc) return rc;
+  return e.test_finish_pass(*p);
+}
+int bwtc_hip_test_finish_pass(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_fin_pass* pass) { return test_fin_pass(ctx, T, pass, 0); }
+int bwtc_hip_test_local_pass(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_fin_pass* pass) { return test_fin_pass(ctx, T, pass, 1); }
+int bwtc_hip_test_finisher(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_fin_run* p) {
+  if (!ctx || !T || !p) return -1;
+  if (!p->S || !p->P || !p->H || !p->C || !p->outcome || !p->info || !p->pS || !p->pHP || !p->sS || !p->sHP || !p->lS || !p->lP || !p->lH || !p->lC ||
+      !p->SA || !p->out || !p->small || !p->lf) return -1;
+  BwtEngine& e = ctx->eng;
+  if (p->n == 0 || (u64)p->n + kSortCanaryBytes > e.cap) return -1;
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_in, T, p->n, hipMemcpyHostToDevice, e.stream));
+  u32 hist[256];
+  const int rc = e.load_text(e.d_in, p->n, p->n, false, hist);
+  if (rc) return rc;
+  return e.test_finisher(*p);
 }
 
 int bwtc_hip_test_radix_segmented(bwtc_hip_ctx* ctx, uint32_t* keys, uint64_t n, int bit_lo, const uint32_t* tile_first, uint32_t nseg) {

@@ -186,6 +186,26 @@ class WaveletRouteCounts(ctypes.Structure):
 REJECT_FLAGS, REJECT_COUNT, REJECT_SCAN, REJECT_STATE, REJECT_TEST = 1, 2, 4, 8, 16
 
 
+class FinPass(ctypes.Structure):
+    """bwtc_hip_fin_pass (include/bwtc_hip.h): one k_finish launch of the finisher's test hooks."""
+    _fields_ = [("n", _u32), ("nreg", _u32), ("ebase", _vp), ("ecount", _vp), ("S", _vp), ("P", _vp), ("H", _vp), ("C", _vp),
+                ("window", ctypes.c_int), ("group", ctypes.c_int), ("words", ctypes.c_int), ("rounds", ctypes.c_int),
+                ("floor", _u32), ("out_n", _u32), ("lf_n", _u32), ("lf_x", _u32), ("ranks", ctypes.c_int),
+                ("rank", _vp), ("at", _u32), ("at2", _u32), ("us", _vp), ("ur", _vp), ("next_cap", _u32),
+                ("nS", _vp), ("nP", _vp), ("nH", _vp), ("nC", _vp), ("next_base", _vp), ("next_count", _vp),
+                ("hS", _vp), ("hHP", _vp), ("hC", _vp), ("hard_count", _vp), ("sS", _vp), ("sHP", _vp), ("shal_count", _vp),
+                ("SA", _vp), ("out", _vp), ("small", _vp), ("lf", _vp)]
+
+
+class FinRun(ctypes.Structure):
+    """bwtc_hip_fin_run (include/bwtc_hip.h): the finisher's driver over a one-region list."""
+    _fields_ = [("n", _u32), ("m", _u32), ("S", _vp), ("P", _vp), ("H", _vp), ("C", _vp),
+                ("window", ctypes.c_int), ("group", ctypes.c_int), ("words", ctypes.c_int), ("rounds", ctypes.c_int),
+                ("floor", _u32), ("out_n", _u32), ("lf_n", _u32), ("lf_x", _u32), ("keep_local", ctypes.c_int), ("max_passes", ctypes.c_int),
+                ("outcome", _vp), ("info", _vp), ("pS", _vp), ("pHP", _vp), ("sS", _vp), ("sHP", _vp),
+                ("lS", _vp), ("lP", _vp), ("lH", _vp), ("lC", _vp), ("SA", _vp), ("out", _vp), ("small", _vp), ("lf", _vp)]
+
+
 class KernelTimers(ctypes.Structure):
     _fields_ = [("scatter_launches", _u64), ("scatter_bytes", _u64), ("scatter_ms", ctypes.c_double)]
 
@@ -211,6 +231,7 @@ EXPORTS = [
     "bwtc_hip_test_radix_pairs", "bwtc_hip_test_radix_long", "bwtc_hip_test_radix_segmented",
     "bwtc_hip_period_get", "bwtc_hip_test_period_lengths",
     "bwtc_hip_test_code_stage", "bwtc_hip_test_code_table", "bwtc_hip_test_code_keys",
+    "bwtc_hip_test_finish_pass", "bwtc_hip_test_local_pass", "bwtc_hip_test_finisher",
     "bwtc_hip_wavelet_depth_needed", "bwtc_hip_grammar_create", "bwtc_hip_grammar_destroy", "bwtc_hip_grammar_rules", "bwtc_hip_grammar_special_symbols",
     "bwtc_hip_grammar_is_special", "bwtc_hip_grammar_write", "bwtc_hip_grammar_read", "bwtc_hip_pair_replace_device",
     "bwtc_hip_test_pair_stats", "bwtc_hip_precompress", "bwtc_hip_host_precompress", "bwtc_hip_postprocess",
@@ -373,6 +394,9 @@ def load():
                                            ctypes.POINTER(_u32), _vp, _vp, _vp]
     L.bwtc_hip_test_code_table.argtypes = [_vp, _vp, _u32, _vp, ctypes.POINTER(_u32)]
     L.bwtc_hip_test_code_keys.argtypes = [_vp, _vp, _u32, ctypes.c_int, ctypes.c_int, _vp, _u32, _vp, _vp, _vp, _vp]
+    L.bwtc_hip_test_finish_pass.argtypes = [_vp, _vp, ctypes.POINTER(FinPass)]
+    L.bwtc_hip_test_local_pass.argtypes = [_vp, _vp, ctypes.POINTER(FinPass)]
+    L.bwtc_hip_test_finisher.argtypes = [_vp, _vp, ctypes.POINTER(FinRun)]
     _lib = L
     return L
 
@@ -1093,6 +1117,84 @@ class Context:
         _check(self.lib.bwtc_hip_test_code_keys(self.handle, _ptr(T) if n else None, n, int(code_bits), 1 if split else 0, _ptr(lut), int(sigma),
                                                 _ptr(table), _ptr(keys), _ptr(w), _ptr(plane)), "bwtc_hip_test_code_keys")
         return keys[:n], w[:n], plane[:n]
+
+    # the suffix sorter's finisher, launch by launch (bwtc_hip_test_finish_pass / _local_pass)
+    def test_finish_pass(self, T, regions, S, P, H, C, window=1024, group=256, words=2, rounds=1, floor=12, out_n=None, lf_n=0,
+                         rank=None, at=0, at2=0):
+        """One k_finish launch over the list (S, P, H, C) in `regions` [(ebase, ecount), ...] of T as the sorter holds it;
+        rank given: k_finish<RANK> with (rank, at, at2), then k_rank_updates.  -> dict: next (S, P, H, C arrays), next_base[16],
+        next_count[17], hard / shallow (S, HP[, C]) cut to their counts, hard_count[2], shal_count[2], SA, out, pidx,
+        last_char, lf[256] and, with ranks, us, ur, rank."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        n = T.size
+        S, P, H = (np.ascontiguousarray(a, dtype=np.uint32) for a in (S, P, H))
+        C = np.ascontiguousarray(C, dtype=np.uint16)
+        ebase = np.array([r[0] for r in regions], np.uint32)
+        ecount = np.array([r[1] for r in regions], np.uint32)
+        span = int(max([0] + [b + c for b, c in regions]))
+        assert S.size >= span and P.size >= span and H.size >= span and C.size >= span
+        m = int(ecount.sum())
+        stride = max(1, window - group)                      # (a shape the hook refuses still gets its arrays)
+        grid = sum(-(-int(c) // stride) for c in ecount)
+        room = grid * stride + -(-grid // 64) * group
+        ranks = rank is not None
+        p = FinPass()
+        p.n, p.nreg, p.ebase, p.ecount = n, len(regions), _ptr(ebase), _ptr(ecount)
+        p.S, p.P, p.H, p.C = _ptr(S), _ptr(P), _ptr(H), _ptr(C)
+        p.window, p.group, p.words, p.rounds = int(window), int(group), int(words), int(rounds)
+        p.floor, p.out_n, p.lf_n = int(floor), int(n if out_n is None else out_n), int(lf_n)
+        p.lf_x = n // lf_n if lf_n > 1 else 0
+        keep = dict(nS=np.zeros(room + 1, np.uint32), nP=np.zeros(room + 1, np.uint32), nH=np.zeros(room + 1, np.uint32), nC=np.zeros(room + 1, np.uint16),
+                    next_base=np.zeros(16, np.uint32), next_count=np.zeros(17, np.uint32),
+                    hS=np.zeros(m + 1, np.uint32), hHP=np.zeros(m + 1, np.uint64), hC=np.zeros(m + 1, np.uint16), hard_count=np.zeros(2, np.uint32),
+                    sS=np.zeros(m + 1, np.uint32), sHP=np.zeros(m + 1, np.uint64), shal_count=np.zeros(2, np.uint32),
+                    SA=np.zeros(n + 1, np.uint32), out=np.zeros(n + 1, np.uint8), small=np.zeros(2, np.uint32), lf=np.zeros(256, np.uint32))
+        if ranks:
+            keep.update(rank=np.array(rank, dtype=np.uint32), us=np.zeros(span + 1, np.uint32), ur=np.zeros(span + 1, np.uint32))
+            assert keep["rank"].size == n
+            p.at, p.at2 = int(at), int(at2)
+        for k, a in keep.items():
+            setattr(p, k, _ptr(a))
+        p.next_cap = room
+        fn = self.lib.bwtc_hip_test_local_pass if ranks else self.lib.bwtc_hip_test_finish_pass
+        _check(fn(self.handle, _ptr(T) if n else None, ctypes.byref(p)), "bwtc_hip_test_local_pass" if ranks else "bwtc_hip_test_finish_pass")
+        hc, sc = int(keep["hard_count"][0]), int(keep["shal_count"][0])
+        res = dict(next=(keep["nS"][:room], keep["nP"][:room], keep["nH"][:room], keep["nC"][:room]), next_base=keep["next_base"],
+                   next_count=keep["next_count"], hard=(keep["hS"][:hc], keep["hHP"][:hc], keep["hC"][:hc]), hard_count=keep["hard_count"],
+                   shallow=(keep["sS"][:sc], keep["sHP"][:sc]), shal_count=keep["shal_count"], SA=keep["SA"][:n], out=keep["out"][:n],
+                   pidx=int(keep["small"][0]), last_char=int(keep["small"][1]), lf=keep["lf"])
+        if ranks:
+            res.update(us=keep["us"][:span], ur=keep["ur"][:span], rank=keep["rank"])
+        return res
+
+    def test_finisher(self, T, S, P, H, C, window=1024, group=256, words=2, rounds=3, floor=12, keep_local=True, max_passes=8, out_n=None, lf_n=0):
+        """finisher_passes over the one-region list (S, P, H, C) -> dict: hard, hard_depth, left, local (FinOutcome),
+        passes_done, route, parked, park_holes, shallow_depth, wait_depth, local_depth, park / shallow (S, HP) and the local
+        list (S, P, H, C) cut to their counts, SA, out, pidx, last_char, lf[256]."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        n = T.size
+        S, P, H = (np.ascontiguousarray(a, dtype=np.uint32) for a in (S, P, H))
+        C = np.ascontiguousarray(C, dtype=np.uint16)
+        m = S.size
+        assert P.size == m and H.size == m and C.size == m
+        p = FinRun()
+        p.n, p.m, p.S, p.P, p.H, p.C = n, m, _ptr(S), _ptr(P), _ptr(H), _ptr(C)
+        p.window, p.group, p.words, p.rounds = int(window), int(group), int(words), int(rounds)
+        p.floor, p.out_n, p.lf_n = int(floor), int(n if out_n is None else out_n), int(lf_n)
+        p.lf_x = n // lf_n if lf_n > 1 else 0
+        p.keep_local, p.max_passes = 1 if keep_local else 0, int(max_passes)
+        keep = dict(outcome=np.zeros(4, np.uint32), info=np.zeros(8, np.uint32), pS=np.zeros(m + 1, np.uint32), pHP=np.zeros(m + 1, np.uint64),
+                    sS=np.zeros(m + 1, np.uint32), sHP=np.zeros(m + 1, np.uint64), lS=np.zeros(m + 1, np.uint32), lP=np.zeros(m + 1, np.uint32),
+                    lH=np.zeros(m + 1, np.uint32), lC=np.zeros(m + 1, np.uint16), SA=np.zeros(n + 1, np.uint32), out=np.zeros(n + 1, np.uint8),
+                    small=np.zeros(2, np.uint32), lf=np.zeros(256, np.uint32))
+        for k, a in keep.items():
+            setattr(p, k, _ptr(a))
+        _check(self.lib.bwtc_hip_test_finisher(self.handle, _ptr(T) if n else None, ctypes.byref(p)), "bwtc_hip_test_finisher")
+        o, i = [int(v) for v in keep["outcome"]], [int(v) for v in keep["info"]]
+        return dict(hard=o[0], hard_depth=o[1], left=o[2], local=o[3], passes_done=i[0], route=i[1], parked=i[2], park_holes=i[3], shallow=i[4],
+                    shallow_depth=i[5], wait_depth=i[6], local_depth=i[7], park=(keep["pS"][:i[2]], keep["pHP"][:i[2]]),
+                    shal=(keep["sS"][:i[4]], keep["sHP"][:i[4]]), local_list=(keep["lS"][:o[3]], keep["lP"][:o[3]], keep["lH"][:o[3]], keep["lC"][:o[3]]),
+                    SA=keep["SA"][:n], out=keep["out"][:n], pidx=int(keep["small"][0]), last_char=int(keep["small"][1]), lf=keep["lf"])
 
 
 def host_cpu_slice(numa_node, rank, ranks):

@@ -485,6 +485,64 @@ int bwtc_hip_test_code_table(bwtc_hip_ctx* ctx, const uint32_t* counts, uint32_t
  *     below sigma, every row is prefix free over sigma symbols with lengths 1..26 (-1 otherwise).  Out: keys, w, plane. */
 int bwtc_hip_test_code_keys(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, int code_bits, int split, const uint8_t* lut, uint32_t sigma,
                             const uint32_t* table, uint64_t* keys, uint32_t* w, uint8_t* plane);
+/* Test hooks of the suffix sorter's finisher: ONE k_finish launch through the launch code of
+ * finisher_passes / local_pass, over T[0..n) as the sorter holds it (loaded by load_text, zero padded), on the context's
+ * own buffers.  All pointers are the caller's arrays.  The shape is set from the arguments (and restored): no
+ * environment variable takes part.
+ *   in:  the list (S suffix, P slot, H slot of the group's head, C predecessor byte | depth << 8) in nreg <= 16 regions
+ *        [ebase[r], ebase[r] + ecount[r]) of arrays of `span` entries (where the last region ends); window / group 1024 /
+ *        256 | 512 or 2048 / 256 | 512 | 1024; words 2, 3, 4; rounds 1..4 (1 unless words is 2); floor; out_n (n or
+ *        n - 1); lf_n <= 256 and lf_x (n / lf_n where lf_n > 1).
+ *   out: the next list in arrays of next_cap entries (at least the room the pass needs: workgroups x (window - group) +
+ *        ceil(workgroups / 64) x group), region r at next_base[r] with next_count[r] entries, next_count[16] its groups;
+ *        the hard list (hS, hHP = head << 32 | slot, hC) and the shallow list (sS, sHP), arrays of as many entries as
+ *        the list has, with {entries, smallest depth} in hard_count[2] / shal_count[2]; SA[n], out[n], small = {pidx,
+ *        last_char}, lf[256], all poisoned with 0xA5 bytes first.
+ *   _local_pass (ranks != 0): k_finish<RANK> with rank[n], at, at2, then k_rank_updates over the regions read.  Out: the
+ *        next list, the notes us / ur (span entries; us filled with all ones first), rank[] after the updates, the
+ *        emissions; hC, sS, sHP are not used.
+ * -1, before anything is launched, unless 1 <= n, n + 256 <= the context's capacity, 1 <= entries <= n, the regions
+ * ascend, do not overlap and end (as does the room) 128 entries below capacity + capacity / 128 + 65536, every S < n and P
+ * < n is distinct, a group is a maximal run of equal H inside a region whose j-th entry has P = H + j and whose members
+ * carry one depth; with ranks also: every group has 2..group members, rank[] < n, 1 <= at, at2 = 0 or at2 > at, at2 +
+ * (at2 - at) < 0xFFFFFFF0.  -20 - i when canary i changed (behind S, P, H, C of the list and of the next list, hS, hHP,
+ * then hC, sS, sHP or us, ur). */
+typedef struct bwtc_hip_fin_pass {
+  uint32_t n, nreg;
+  const uint32_t* ebase; const uint32_t* ecount;
+  const uint32_t *S, *P, *H; const uint16_t* C;
+  int window, group, words, rounds;
+  uint32_t floor, out_n, lf_n, lf_x;
+  int ranks;
+  uint32_t* rank; uint32_t at, at2;
+  uint32_t *us, *ur;
+  uint32_t next_cap;
+  uint32_t *nS, *nP, *nH; uint16_t* nC;
+  uint32_t* next_base; uint32_t* next_count;
+  uint32_t* hS; uint64_t* hHP; uint16_t* hC; uint32_t* hard_count;
+  uint32_t* sS; uint64_t* sHP; uint32_t* shal_count;
+  uint32_t* SA; uint8_t* out; uint32_t* small; uint32_t* lf;
+} bwtc_hip_fin_pass;
+int bwtc_hip_test_finish_pass(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_fin_pass* pass);
+int bwtc_hip_test_local_pass(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_fin_pass* pass);
+/*   _finisher: the driver finisher_passes(n, m, a, b, re, shal, &fo, keep_local, max_passes) over a list of m entries in
+ *        one region, under the same contracts.  Out: outcome = {hard, hard_depth, left, local} (FinOutcome), info =
+ *        {passes_done, stats.route, parked, park_holes, shallow entries, their smallest depth, the smallest depth of what
+ *        waits for the rounds, local_depth}; the parked raw list (pS, pHP: `parked` entries, holes -- all ones --
+ *        included), the shallow raw list (sS, sHP), the local list after k_list_copy (lS, lP, lH, lC: `local` entries),
+ *        arrays of m entries each; SA[n], out[n], small = {pidx, last_char}, lf[256], poisoned first. */
+typedef struct bwtc_hip_fin_run {
+  uint32_t n, m;
+  const uint32_t *S, *P, *H; const uint16_t* C;
+  int window, group, words, rounds;
+  uint32_t floor, out_n, lf_n, lf_x;
+  int keep_local, max_passes;
+  uint32_t* outcome; uint32_t* info;
+  uint32_t* pS; uint64_t* pHP; uint32_t* sS; uint64_t* sHP;
+  uint32_t *lS, *lP, *lH; uint16_t* lC;
+  uint32_t* SA; uint8_t* out; uint32_t* small; uint32_t* lf;
+} bwtc_hip_fin_run;
+int bwtc_hip_test_finisher(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_fin_run* run);
 /* Test hook: k range-coder chains over w-elements (w = bit << 15 | probability of the coded bit), chain j = elements
  * [bounds[j], bounds[j+1]), on the GPU lane engine (mode 0; BitEncoder, BitCoders.cpp:59-113, one lane per chain) or by the
  * host's scalar loop (mode 1); bytes of chain j = out[offsets[j] .. offsets[j+1]). */
