@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <chrono>
+#include <climits>
 #include <ctime>
 #include <sys/prctl.h>
 
@@ -2043,6 +2044,16 @@ __global__ void k_finalize(u8* __restrict__ out, const u8* __restrict__ T,
 // ---------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------
+// The switches: off is a value that begins with '0'; a number is clamped to [lo, hi], stored only when the switch is set (-> true).
+static bool env_off(const char* name) { const char* v = std::getenv(name); return v && v[0] == '0'; }
+static bool env_is(const char* name, const char* value) { const char* v = std::getenv(name); return v && std::strcmp(v, value) == 0; }
+static bool env_int(const char* name, int* dst, int lo = INT_MIN, int hi = INT_MAX) {
+  const char* v = std::getenv(name);
+  if (v) *dst = std::min(hi, std::max(lo, std::atoi(v)));
+  return v != nullptr;
+}
+static inline bool debug_on() { return std::getenv("BWTC_HIP_DEBUG") != nullptr; }
+
 static u64 align_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
 
 struct ArenaPlan {
@@ -2169,60 +2180,45 @@ int BwtEngine::init(int dev, u32 max_block_size) {
   d_runF = reinterpret_cast<u32*>(base + a.off_runF);
   d_runB = reinterpret_cast<u32*>(base + a.off_runB);
   d_votes = reinterpret_cast<u32*>(base + a.off_votes);
-  {
-    const char* e = std::getenv("BWTC_HIP_SORT");
-    use_sweep = e && std::strcmp(e, "sweep") == 0;
-    const char* w = std::getenv("BWTC_HIP_WAVELET");
-    wavelet_on_host = w && std::strcmp(w, "host") == 0;
-    const char* gmv = std::getenv("BWTC_HIP_MODELS");
-    device_models = !(gmv && std::strcmp(gmv, "host") == 0);
-    models_side_stream = !(std::getenv("BWTC_HIP_MODELS_STREAM") && std::getenv("BWTC_HIP_MODELS_STREAM")[0] == '0');
-    const char* d = std::getenv("BWTC_HIP_WAVELET_DEPTH");
-    if (d && std::atoi(d) > 0) max_inflight = (unsigned)std::atoi(d);
-    dense_route = !(std::getenv("BWTC_HIP_DENSE") && std::getenv("BWTC_HIP_DENSE")[0] == '0');
-    no_emit = std::getenv("BWTC_HIP_NO_EMIT") != nullptr;
-    if (std::getenv("BWTC_HIP_WINDOW_BITS") && std::atoi(std::getenv("BWTC_HIP_WINDOW_BITS")) > 0)
-      window_bits = std::min(24, std::atoi(std::getenv("BWTC_HIP_WINDOW_BITS")));
-    digit_planes = !(std::getenv("BWTC_HIP_PLANES") && std::getenv("BWTC_HIP_PLANES")[0] == '0');
-    split_index = !(std::getenv("BWTC_HIP_SPLIT_INDEX") && std::getenv("BWTC_HIP_SPLIT_INDEX")[0] == '0');
-    if (const char* gr = std::getenv("BWTC_HIP_GRAMS")) {       // 0: base-sigma keys only; N > 0: N grams per key
-      gram_keys = gr[0] != '0';
-      gram_count_override = std::atoi(gr);
-    }
-    long_keys = !(std::getenv("BWTC_HIP_LONG") && std::getenv("BWTC_HIP_LONG")[0] == '0');
-    if (std::getenv("BWTC_HIP_LONG_G2")) long_grams_override = std::atoi(std::getenv("BWTC_HIP_LONG_G2"));
-    if (std::getenv("BWTC_HIP_FIN_GROUP")) fin_max_group = std::atoi(std::getenv("BWTC_HIP_FIN_GROUP"));
-    if (std::getenv("BWTC_HIP_FIN_WINDOW")) fin_window = std::atoi(std::getenv("BWTC_HIP_FIN_WINDOW"));
-    fin_shape_fixed = std::getenv("BWTC_HIP_FIN_GROUP") || std::getenv("BWTC_HIP_FIN_WINDOW");
-    fin_wide_short = !(std::getenv("BWTC_HIP_FIN_WIDE") && std::getenv("BWTC_HIP_FIN_WIDE")[0] == '0');
-    fin_window = fin_window >= 2048 ? 2048 : 1024;
-    fin_max_group = fin_max_group >= 1024 ? 1024 : fin_max_group >= 512 ? 512 : 256;
-    if (fin_max_group >= fin_window) fin_max_group = fin_window / 2;
-    code_keys = !(std::getenv("BWTC_HIP_KEYS") && std::strcmp(std::getenv("BWTC_HIP_KEYS"), "grams") == 0);
-    if (std::getenv("BWTC_HIP_CODE_BITS")) code_bits = std::min(72, std::max(40, std::atoi(std::getenv("BWTC_HIP_CODE_BITS"))));
-    finisher = !(std::getenv("BWTC_HIP_FINISHER") && std::getenv("BWTC_HIP_FINISHER")[0] == '0');
-    gm_partition_lines = std::getenv("BWTC_HIP_GM_PARTITION") && std::strcmp(std::getenv("BWTC_HIP_GM_PARTITION"), "lines") == 0;
-    wt_segmented = !(std::getenv("BWTC_HIP_SEG_STEPS") && std::getenv("BWTC_HIP_SEG_STEPS")[0] == '0');
-    gram_min_n = kGramMinN;
-    if (std::getenv("BWTC_HIP_GRAM_MIN_N")) gram_min_n = (u32)std::max(64, std::atoi(std::getenv("BWTC_HIP_GRAM_MIN_N")));   // tests: small blocks through the gram / long-key routes
-    if (std::getenv("BWTC_HIP_LONG_E")) long_items_per_thread = std::atoi(std::getenv("BWTC_HIP_LONG_E")) == 6 ? 6 : 8;
-    if (std::getenv("BWTC_HIP_FIN_PASSES")) fin_max_passes = std::max(0, std::atoi(std::getenv("BWTC_HIP_FIN_PASSES")));
-    if (std::getenv("BWTC_HIP_FIN_WORDS")) fin_words = std::min(4, std::max(2, std::atoi(std::getenv("BWTC_HIP_FIN_WORDS"))));
-    if (std::getenv("BWTC_HIP_LONG_DIRECT")) long_direct = std::getenv("BWTC_HIP_LONG_DIRECT")[0] != '0';
-    if (std::getenv("BWTC_HIP_FIN_ROUNDS")) fin_rounds = std::min(4, std::max(1, std::atoi(std::getenv("BWTC_HIP_FIN_ROUNDS"))));
-    run_ranks = !(std::getenv("BWTC_HIP_RUNS") && std::getenv("BWTC_HIP_RUNS")[0] == '0');
-    period_ranks = !(std::getenv("BWTC_HIP_PERIODS") && std::getenv("BWTC_HIP_PERIODS")[0] == '0');
-    if (std::getenv("BWTC_HIP_PERIOD")) period_forced = (u32)std::min(std::max(std::atoi(std::getenv("BWTC_HIP_PERIOD")), 0), (int)kPeriodMax);
-    local_rounds = !(std::getenv("BWTC_HIP_LOCAL_ROUNDS") && std::getenv("BWTC_HIP_LOCAL_ROUNDS")[0] == '0');
-    if (std::getenv("BWTC_HIP_FIN_FLOOR")) fin_floor = (u32)std::max(0, std::atoi(std::getenv("BWTC_HIP_FIN_FLOOR")));
-    if (std::getenv("BWTC_HIP_TEXT_ROUNDS")) { text_rounds = std::max(0, std::atoi(std::getenv("BWTC_HIP_TEXT_ROUNDS"))); text_rounds_fixed = true; }
-    const char* hg = std::getenv("BWTC_HIP_HUGE_MI");
-    if (hg && std::atoi(hg) > 0) huge_group_elements = (u64)std::atoi(hg) << 20;
-  }
+  use_sweep = env_is("BWTC_HIP_SORT", "sweep");
+  wavelet_on_host = env_is("BWTC_HIP_WAVELET", "host");
+  device_models = !env_is("BWTC_HIP_MODELS", "host"); models_side_stream = !env_off("BWTC_HIP_MODELS_STREAM");
+  int v = 0;
+  if (env_int("BWTC_HIP_WAVELET_DEPTH", &v) && v > 0) max_inflight = (unsigned)v;
+  dense_route = !env_off("BWTC_HIP_DENSE");
+  no_emit = std::getenv("BWTC_HIP_NO_EMIT") != nullptr;
+  if (env_int("BWTC_HIP_WINDOW_BITS", &v) && v > 0) window_bits = std::min(24, v);
+  digit_planes = !env_off("BWTC_HIP_PLANES"); split_index = !env_off("BWTC_HIP_SPLIT_INDEX");
+  if (env_int("BWTC_HIP_GRAMS", &gram_count_override)) gram_keys = !env_off("BWTC_HIP_GRAMS");   // 0: base-sigma keys only; N > 0: N grams per key
+  long_keys = !env_off("BWTC_HIP_LONG");
+  env_int("BWTC_HIP_LONG_G2", &long_grams_override);
+  const bool group_given = env_int("BWTC_HIP_FIN_GROUP", &fin_max_group), window_given = env_int("BWTC_HIP_FIN_WINDOW", &fin_window);
+  fin_shape_fixed = group_given || window_given;
+  fin_wide_short = !env_off("BWTC_HIP_FIN_WIDE");
+  fin_window = fin_window >= 2048 ? 2048 : 1024;
+  fin_max_group = fin_max_group >= 1024 ? 1024 : fin_max_group >= 512 ? 512 : 256;
+  if (fin_max_group >= fin_window) fin_max_group = fin_window / 2;
+  code_keys = !env_is("BWTC_HIP_KEYS", "grams");
+  env_int("BWTC_HIP_CODE_BITS", &code_bits, 40, 72);
+  finisher = !env_off("BWTC_HIP_FINISHER");
+  gm_partition_lines = env_is("BWTC_HIP_GM_PARTITION", "lines");
+  wt_segmented = !env_off("BWTC_HIP_SEG_STEPS");
+  gram_min_n = kGramMinN;
+  if (env_int("BWTC_HIP_GRAM_MIN_N", &v, 64)) gram_min_n = (u32)v;   // tests: small blocks through the gram / long-key routes
+  if (env_int("BWTC_HIP_LONG_E", &v)) long_items_per_thread = v == 6 ? 6 : 8;
+  env_int("BWTC_HIP_FIN_PASSES", &fin_max_passes, 0); env_int("BWTC_HIP_FIN_WORDS", &fin_words, 2, 4);
+  long_direct = !env_off("BWTC_HIP_LONG_DIRECT");
+  env_int("BWTC_HIP_FIN_ROUNDS", &fin_rounds, 1, 4);
+  run_ranks = !env_off("BWTC_HIP_RUNS"); period_ranks = !env_off("BWTC_HIP_PERIODS");
+  if (env_int("BWTC_HIP_PERIOD", &v, 0, (int)kPeriodMax)) period_forced = (u32)v;
+  local_rounds = !env_off("BWTC_HIP_LOCAL_ROUNDS");
+  if (env_int("BWTC_HIP_FIN_FLOOR", &v, 0)) fin_floor = (u32)v;
+  text_rounds_fixed = env_int("BWTC_HIP_TEXT_ROUNDS", &text_rounds, 0);
+  if (env_int("BWTC_HIP_HUGE_MI", &v) && v > 0) huge_group_elements = (u64)v << 20;
   // Opt-in (BWTC_HIP_SCAN=chained): measured on MI355X the single-launch scan is SLOWER for the
   // sorter's tables (63 us against 25 + 11 + 6 us for 8.4 M words: 2048 tiles are too few to hide
   // the look-back hops), so the three-launch form stays the default.
-  if (std::getenv("BWTC_HIP_SCAN") && std::strcmp(std::getenv("BWTC_HIP_SCAN"), "chained") == 0) {
+  if (env_is("BWTC_HIP_SCAN", "chained")) {
     scan_chain.cap_tiles = (u32)(cap / kScanTile + 4096);
     BWTC_HIP_TRY(hipMalloc(reinterpret_cast<void**>(&scan_chain.status), ((u64)scan_chain.cap_tiles + 1) * 8));
     BWTC_HIP_TRY(hipMemset(scan_chain.status, 0, ((u64)scan_chain.cap_tiles + 1) * 8));
@@ -2235,10 +2231,7 @@ int BwtEngine::init(int dev, u32 max_block_size) {
   BWTC_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_small), 1024 * 4, hipHostMallocDefault));
   BWTC_HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_stage), cap + 32, hipHostMallocDefault));
   BWTC_HIP_TRY(hipEventCreateWithFlags(&ev_wait, hipEventBlockingSync | hipEventDisableTiming));
-  {
-    const char* m = std::getenv("BWTC_HIP_SYNC");
-    wait_mode = m && std::strcmp(m, "spin") == 0 ? 1 : m && std::strcmp(m, "block") == 0 ? 2 : 0;
-  }
+  wait_mode = env_is("BWTC_HIP_SYNC", "spin") ? 1 : env_is("BWTC_HIP_SYNC", "block") ? 2 : 0;
   BWTC_HIP_TRY(hipEventCreate(&ev_begin));
   BWTC_HIP_TRY(hipEventCreate(&ev_end));
   for (int i = 0; i < kMaxSortEvents; ++i) BWTC_HIP_TRY(hipEventCreate(&ev_sort[i]));
@@ -2524,12 +2517,12 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
   res->ran_run = run_now;
   const int b2k = run_now ? b2 + 1 : b2;
   const int kbits = run_now ? nbits + 1 : nbits;
-  const RunKeys rkeys{d_runK, run_now ? 0u : step.depth, run_now ? 1 : (run_mode == 2 ? 2 : 0), step.p};
+  const RunKeys rkeys{d_runK, run_now ? 0u : blk.step.depth, run_now ? 1 : (run_mode == 2 ? 2 : 0), blk.step.p};
   const bool carry_next = emit && kbits <= 56;
   res->carry = carry_next;
   const bool dense = !text && dense_route && m_next > 0 && (u64)m_next * 2 >= m && m >= kPairsMin && !use_sweep;
-  u32* sa_out = (emit && !fin_active) ? nullptr : d_SA;   // finisher route: the bridge will want the finished suffixes' slots
-  u32* rank_arg = (text && !ranks_live) ? nullptr : d_rank;   // text rounds before rank[] is completed: neither complete nor needed; after: kept exact
+  u32* sa_out = (emit && !blk.fin_active) ? nullptr : d_SA;   // finisher route: the bridge will want the finished suffixes' slots
+  u32* rank_arg = (text && !blk.ranks_live) ? nullptr : d_rank;   // text rounds before rank[] is completed: neither complete nor needed; after: kept exact
   // Long items of which at most half is still tied (a 256 MiB text block: 21 %, a 1 GiB one: 37 %): the finisher
   // settles the rest by direct comparison (suffix_sort); rank[] is not written at all.  Above that the list is
   // dominated by long repeats and the doubling rounds are the better tool.
@@ -2538,7 +2531,7 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
   res->finish = lng && emit && finisher;
   if (res->finish) {
     sa_out = d_SA;
-    fin_active = true;
+    blk.fin_active = true;
     if constexpr (kCanSplit) {
       if (split)
         hipLaunchKernelGGL((k_rerank_apply<K, INIT, 3, 3, true, true>), dim3(tiles), dim3(kRrTPB), 0, st, ks, vs,
@@ -2708,7 +2701,7 @@ int BwtEngine::plan_grams(const KeyPlan& plan, u32 n, const u8* d_lut, GramPlan*
   const int base_passes = (plan.bits + kRadixBits - 1) / kRadixBits;
   // fewer passes for at least as many characters, or the same passes for more
   const bool better = (g * G >= plan.k && passes < base_passes) || (g * G > plan.k && passes <= base_passes);
-  if (std::getenv("BWTC_HIP_DEBUG"))
+  if (debug_on())
     std::fprintf(stderr, "grams: sigma=%u g=%d universe=%llu present=%u bits=%d G=%d (%d chars, %d passes) vs base %d chars, %d passes -> %s\n",
                  plan.sigma, g, (unsigned long long)U, distinct, b, G, g * G, passes, plan.k, base_passes,
                  better || gram_count_override > 0 ? "grams" : "base");
@@ -2719,9 +2712,9 @@ int BwtEngine::plan_grams(const KeyPlan& plan, u32 n, const u8* d_lut, GramPlan*
 
 // (the debug line of a block that looked for a period and takes no period step: decide_step and the rounds)
 static void say_no_period_step(const BwtEngine& e, u64 h_first) {
-  if (std::getenv("BWTC_HIP_DEBUG"))
+  if (debug_on())
     std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: no period step\n",
-                 e.period_p, e.period_votes, e.period_longest, (unsigned long long)h_first);
+                 e.blk.period_p, e.blk.period_votes, e.blk.period_longest, (unsigned long long)h_first);
 }
 
 // The code-key stage as suffix_sort launches it (and, kernel by kernel, BwtEngine::test_code_stage).  The key word's
@@ -2762,425 +2755,434 @@ int BwtEngine::test_code_stage(u32 parts, u32 n, const u32* hist, bool lone_sent
                            split_now, ck);
 }
 
-// em != nullptr: the rankers emit the transform's bytes (see RrEmit) and the suffix array itself
-// is not stored; em == nullptr: d_SA is filled and nothing is emitted.
-int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const EmitTarget* em) {
-  hipStream_t st = stream;
-  n_sort_events = 0;
-  stats.rounds = 0;
-  stats.active_sum = 0;
-  stats.sort_pass_items = 0;
-  stats.route = 0;
-  stats.finisher_entries = 0;
-  lengths_period = 0; run_longest = 0; run_longest_known = false; step = StretchStep{};   // (nothing of the last block's runs)
-  period_looked = false; period_p = 0; period_longest = 0; period_votes = 0;                // (nor of its periods)
-  if (n == 0) return 0;
+// A block's list between suffix_sort's stages: what the last ranking step left (res), the arrays the next one takes (rb),
+// the emitter with the spare plane of carried characters, and whether rank[] is complete.
+struct SortList { u32 n; bool emit; BwtEngine::RankBuffers rb; RrEmit re; BwtEngine::RankResult res; u8* achr_other; bool ranks_complete; };
+// What the stages of the initial sort share: the block, its key plan and where the key makers write.
+struct InitialSort {
+  u32 n; const u32* hist; bool lone_sentinel; const KeyPlan& plan; const u8* d_lut;
+  u8* key_plane;       // the key makers leave the first pass's digits
+  bool implied_idx;    // slot j holds suffix n-1-j: the sort's first pass can make that up instead of reading it
+  u32* idx_out;
+};
+static const LongKey kNoLongKey{nullptr, 0, -1, 0, 48, 0, 0};   // one key word: no second one, the suffix number's upper bits from bit 48
+static constexpr int kCodeTableFull = -1000;   // initial_long -> suffix_sort, and no further: the block is sorted again, with gram keys
 
-  const bool emit = em != nullptr;
-  const KeyPlan plan = plan_keys(hist, n, lone_sentinel, gram_min_n < kGramMinN);   // (the tests' small blocks: 64-bit keys whatever the entropy says)
-  std::memcpy(h_small + kSmallLut, plan.lut, 256);
-  BWTC_HIP_TRY(hipMemcpyAsync(d_small + kSmallLut, h_small + kSmallLut, 256, hipMemcpyHostToDevice, st));
-  const u8* d_lut = reinterpret_cast<const u8*>(d_small + kSmallLut);
-  int key_bits = plan.bits;
-  // suffixes of length <= k are finished by the initial ranking (a suffix of length exactly
-  // k is a proper prefix of every other suffix with the same key)
-  u32 short_len = (u32)plan.k;
+// the sorted keys and values reach the ranking step: the arrays the sort ended in, and their partners as free space
+static void hand_over(const BwtEngine& e, BwtEngine::RankBuffers& rb, void* ks, void* ka, void* kb, u32* vs) {
+  rb.rec_keys = ks; rb.rec_free = ks == ka ? kb : ka;
+  rb.v_keys = vs; rb.v_free = vs == e.d_V0 ? e.d_V1 : e.d_V0;
+}
 
-  RrEmit re;
-  re.out = emit ? em->out : nullptr;
-  re.out_n = emit ? em->out_n : 0u;
-  re.last_char = d_small + kSmallLastChar;
-  re.pidx = d_small + kSmallPidx;
-  re.T = d_T;
-  re.achr_out = d_C0;
-  re.rec_plane = nullptr;
-  re.rec_shift = 0;
-  re.inv_lut = reinterpret_cast<const u8*>(d_small + kSmallInv);
-  re.lf = d_small + kSmallLf; re.lf_n = 0; re.lf_x = 0; re.lf_inv = 0;
-  if (emit && em->n_lf > 1 && n / em->n_lf >= 1) {
-    re.lf_n = em->n_lf; re.lf_x = n / em->n_lf; re.lf_inv = re.lf_x > 1 ? (u32)((1ull << 32) / re.lf_x) : 0u;
+// the passes of an initial sort over keys of key_bits bits, and what they and the key maker move
+static void count_initial_sort(BwtEngine& e, u32 n, int key_bits, bool wide) {
+  const int passes = (key_bits + kRadixBits - 1) / kRadixBits;
+  e.stats.sort_pass_items += (u64)n * (u64)passes;
+  // items of (u64, u32 or u16 + upper bits in the key) / (u32, u32)
+  if (key_bits) e.stats.alg_bytes += (u64)n * (1 + (u64)(wide ? 8 : 4) + 1) + sort_bytes(n, passes, wide ? 12 : 8, wide ? 8 : 4, e.digit_planes);
+}
+
+// k characters as a base-sigma number
+template <typename K>
+static void launch_make_keys(BwtEngine& e, const InitialSort& in, K* ka, int split) {
+  K top = 1;
+  for (int t = 1; t < in.plan.k; ++t) top *= in.plan.sigma;
+  hipLaunchKernelGGL(k_make_keys<K>, dim3(ceil_div(in.n, 1024)), dim3(256), 0, e.stream, e.d_T, in.d_lut, ka,
+                     in.idx_out, in.n, in.plan.k, in.plan.sigma, top, in.key_plane, split);
+}
+
+// dense gram codes; lk.w: with a second word (the long keys, whose values the sort's first pass makes up: no idx_out)
+static void launch_gram_keys(BwtEngine& e, const InitialSort& in, const BwtEngine::GramPlan& gp, u64* ka, int split, const LongKey& lk) {
+  hipLaunchKernelGGL(k_make_keys_gram, dim3(ceil_div(in.n, 1024)), dim3(256), 0, e.stream, e.d_T, in.d_lut, (const uint4*)e.d_rank, ka,
+                     lk.w ? (u32*)nullptr : in.idx_out, in.n, gp.g, gp.G, gp.b, in.plan.sigma, gp.top, in.key_plane, split, lk);
+}
+
+// the long-key sort in one of its shapes: whole suffix numbers, or their 16-bit lower halves in tiles of E items per thread
+template <typename V, int E>
+static u32* sort_long_as(BwtEngine& e, u64* ka, u64* kb, u32 n, int key_bits, int w_bits, u64** ks, u32** ws) {
+  V* vs = nullptr;
+  radix_sort_long<V, E>(ka, kb, reinterpret_cast<V*>(e.d_V0), reinterpret_cast<V*>(e.d_V1), e.d_W0, e.d_W1, n, key_bits, w_bits, e.d_table,
+                        e.d_partial, e.stream, ks, &vs, ws, &e.probe, e.d_P0, e.d_P1, 0, false, e.long_direct);
+  return reinterpret_cast<u32*>(vs);
+}
+
+// dense code -> byte, for the rankers that emit from the long keys' character codes (RrEmit::inv_lut)
+static hipError_t upload_inverse_lut(BwtEngine& e, const InitialSort& in) {
+  u8* inv = reinterpret_cast<u8*>(e.h_small + kSmallInv);
+  std::memset(inv, 0, 256);
+  for (int c = 255; c >= 0; --c) if (in.hist[c] && !(c == 0 && in.lone_sentinel)) inv[in.plan.lut[c]] = (u8)c;
+  return hipMemcpyAsync(e.d_small + kSmallInv, inv, 256, hipMemcpyHostToDevice, e.stream);
+}
+
+// The 32-bit keys.  Suffixes of length <= k are finished by the initial ranking (a suffix of length exactly
+// k is a proper prefix of every other suffix with the same key): short_len, here and in the 64-bit plans.
+int BwtEngine::initial_keys32(const InitialSort& in, SortList& L, u64 h) {
+  u32* ka = static_cast<u32*>(d_R1); u32* kb = ka + cap;
+  launch_make_keys<u32>(*this, in, ka, 0);
+  u32* ks = nullptr; u32* vs = nullptr;
+  sort_pairs<u32>(ka, kb, d_V0, d_V1, in.n, in.plan.bits, &ks, &vs, true, 0, 0, in.key_plane != nullptr, in.implied_idx);
+  BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], stream));
+  hand_over(*this, L.rb, d_R1, d_R1, d_R2, vs);         // both 32-bit key arrays live in R1
+  const int rc = rank_step<u32, true>(ks, vs, in.n, in.n, (u32)in.plan.k, ~0u, L.rb, L.re, L.emit, h, &L.res);
+  if (rc) return rc;
+  count_initial_sort(*this, in.n, in.plan.bits, false);
+  return 0;
+}
+
+// The 64-bit plans: long keys where the block can take them (initial_long), else one key word (initial_keys64).
+int BwtEngine::initial_wide(const InitialSort& in, bool allow_code_keys, SortList& L, u64* h) {
+  const u32 n = in.n;
+  const bool long_ok = long_keys && in.implied_idx && L.emit && in.key_plane && n >= gram_min_n;
+  const bool coded = long_ok && code_keys && finisher && allow_code_keys;   // (the code keys take no gram plan)
+  GramPlan gp;
+  if (!coded) { const int rc = plan_grams(in.plan, n, in.d_lut, &gp); if (rc) return rc; }
+  int key_bits = in.plan.bits;
+  u32 short_len = (u32)in.plan.k;
+  if (gp.G > 0) { key_bits = gp.b * gp.G; short_len = (u32)(gp.g * gp.G); *h = (u64)short_len; }
+  // Keys of at most 48 bits leave room for the upper bits of the suffix number: the passes of
+  // the initial sort then carry (u64 key, u16 low half) = 10 bytes per item instead of 12.
+  const int split = (split_index && in.implied_idx && key_bits <= 48 && n <= (1u << 29)) ? 1 : 0;
+  if (coded || (long_ok && gp.G > 0)) {
+    bool ranked = false;
+    const int rc = initial_long(in, gp, key_bits, split, coded, L, h, &ranked);
+    if (rc || ranked) return rc;
   }
-  bridged = false;
-  lf_noted = false;
-  fin_active = false;
-  u8* achr_other = d_C1;
+  return initial_keys64(in, gp, key_bits, short_len, split, L, *h);
+}
 
-  RankBuffers rb;
-  rb.aglob = nullptr;
-  rb.aglob_next = d_G0;
-  RankResult res;
-  res.finish = false;
-  res.ran_run = false;
-  u64 h = (u64)plan.k;                    // the next round compares rank[s + h]
-
-  // initial sort + ranking
-  BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-  int rc = 0;
-  u8* key_plane = digit_planes && !use_sweep ? d_P0 : nullptr;     // the key makers leave the first pass's digits
-  // slot j holds suffix n-1-j: the sort's first pass can make that up instead of reading it
-  const bool implied_idx = !use_sweep && n > 1;
-  u32* idx_out = implied_idx ? nullptr : d_V0;
-  if (plan.wide) {
-    u64* ka = static_cast<u64*>(d_R1);
-    u64* kb = static_cast<u64*>(d_R2);
-    GramPlan gp;
-    const bool code_route = code_keys && finisher && !code_failed && long_keys && implied_idx && emit && key_plane && n >= gram_min_n;
-    if (!code_route) {
-      rc = plan_grams(plan, n, d_lut, &gp);
-      if (rc) return rc;
-    }
-    if (gp.G > 0) {
-      key_bits = gp.b * gp.G;
-      short_len = (u32)(gp.g * gp.G);
-      h = (u64)short_len;
-    }
-    // Keys of at most 48 bits leave room for the upper bits of the suffix number: the passes of
-    // the initial sort then carry (u64 key, u16 low half) = 10 bytes per item instead of 12.
-    const int split = (split_index && implied_idx && key_bits <= 48 && n <= (1u << 29)) ? 1 : 0;
-    // Long keys: the sort also orders by a second key word and the items carry their predecessor character's code, so
-    // that the ranking behind the ONE long sort can emit the transform's bytes and the finisher takes what is tied.
-    // Two makers: the order-1 prefix code (k_make_keys_code, the default) and dense gram codes (round 4, BWTC_HIP_KEYS=grams).
-    LongKey lk;
-    lk.w = nullptr; lk.G2 = 0; lk.first_r = -1; lk.first_mask = 0; lk.hi_shift = 48; lk.chr_shift = 0; lk.chr_mask = 0;
-    const bool long_ok = long_keys && implied_idx && emit && key_plane && n >= gram_min_n;
-    const bool coded = long_ok && code_keys && finisher && !code_failed;
-    auto upload_inverse_lut = [&]() -> int {
-      u8 inv[256];
-      std::memset(inv, 0, sizeof inv);
-      for (int c = 255; c >= 0; --c) if (hist[c] && !(c == 0 && lone_sentinel)) inv[plan.lut[c]] = (u8)c;
-      std::memcpy(h_small + kSmallInv, inv, 256);
-      BWTC_HIP_TRY(hipMemcpyAsync(d_small + kSmallInv, h_small + kSmallInv, 256, hipMemcpyHostToDevice, st));
-      return 0;
-    };
-    // (without the split -- blocks above 512 MiB, gram keys above 48 bits -- the items carry whole 32-bit suffix numbers:
-    // 16 bytes instead of 14, and the key only needs room for the character)
-    int w_bits = 0;
-    RrLong lg;
-    lg.w = nullptr; lg.wmask = ~0u; lg.hi_shift = 0; lg.chr_shift = 0; lg.chr_mask = 0; lg.lvl_shift = -1; lg.depth = 0;
-    int split_now = split;
-    if (coded) {
-      // the block's order-1 statistics from a sample of its character pairs, the alphabetic codes, the keys
-      split_now = (split_index && n <= (1u << 29)) ? 1 : 0;
-      key_bits = code_bits - 32;                        // the key word's share; the second word takes 32
-      w_bits = 32;
-      const CodeKey ck = code_key_layout(d_codes, code_bits, split_now);
-      rc = upload_inverse_lut();
-      if (rc) return rc;
-      const u32 sample_tiles = code_sample_tiles(n);
-      rc = launch_code_stage(*this, 7u, n, d_lut, plan.sigma, ka, key_plane, split_now, ck);
-      if (rc) return rc;
-      lg.hi_shift = ck.hi_shift; lg.chr_shift = ck.chr_shift; lg.chr_mask = 0xFFu; lg.lvl_shift = ck.lvl_shift;
-      lk.w = d_W0;
-      short_len = 0;                                    // every item has its own (rr_masks)
-      h = 1;
-      stats.alg_bytes += (u64)sample_tiles * kPairTile + (u64)kPairReplicas * 65536 * 8;
-      if (std::getenv("BWTC_HIP_DEBUG"))
-        std::fprintf(stderr, "code keys: %d + %d bits, sigma %u, %u sampled tiles, character code at bit %d, level at bit %d\n",
-                     key_bits, w_bits, plan.sigma, sample_tiles, ck.chr_shift, ck.lvl_shift);
-    } else if (long_ok && gp.G > 0) {
-      const int cb = std::max(1, bit_width_u64(plan.sigma - 1));
-      int G2 = std::min(32 / gp.b, (64 - gp.g * gp.G) / gp.g);
-      G2 = std::min(G2, long_grams_override > 0 ? long_grams_override : 2);
-      const int hi_bits = split ? 13 : 0;
-      if (G2 >= 1 && key_bits + hi_bits + cb <= 64) {
-        lk.w = d_W0; lk.G2 = G2; lk.hi_shift = key_bits; lk.chr_shift = key_bits + hi_bits; lk.chr_mask = (1u << cb) - 1u;
-        rc = upload_inverse_lut();
-        if (rc) return rc;
-        w_bits = gp.b * lk.G2;
-        if (w_bits < kRadixBits) { lk.first_r = w_bits; lk.first_mask = (1u << std::min(kRadixBits, w_bits + key_bits)) - 1u; }
-        short_len = (u32)(gp.g * (gp.G + lk.G2));
-        h = (u64)short_len;
-        hipLaunchKernelGGL(k_make_keys_gram, dim3(ceil_div(n, 1024)), dim3(256), 0, st, d_T, d_lut,
-                           (const uint4*)d_rank, ka, (u32*)nullptr, n, gp.g, gp.G, gp.b, plan.sigma, gp.top, key_plane, split, lk);
-        lg.hi_shift = lk.hi_shift; lg.chr_shift = lk.chr_shift; lg.chr_mask = lk.chr_mask; lg.lvl_shift = -1; lg.depth = short_len;
-        if (std::getenv("BWTC_HIP_DEBUG"))
-          std::fprintf(stderr, "long keys: %d + %d bits, %d + %d grams of %d characters, character code at bit %d\n",
-                       key_bits, w_bits, gp.G, lk.G2, gp.g, lk.chr_shift);
-      }
-    }
-    if (lk.w) {
-      u64* ks = nullptr; unsigned short* vs16 = nullptr; u32* ws = nullptr;
-      u32* vs32 = nullptr;
-      if (!split_now)
-        radix_sort_long<u32, 6>(ka, kb, d_V0, d_V1, d_W0, d_W1, n, key_bits, w_bits, d_table, d_partial, stream, &ks, &vs32, &ws, &probe, d_P0, d_P1, 0, false, long_direct);
-      else if (long_items_per_thread == 6)
-        radix_sort_long<unsigned short, 6>(ka, kb, reinterpret_cast<unsigned short*>(d_V0), reinterpret_cast<unsigned short*>(d_V1),
-                                           d_W0, d_W1, n, key_bits, w_bits, d_table, d_partial, stream, &ks, &vs16, &ws, &probe, d_P0, d_P1, 0, false, long_direct);
-      else
-        radix_sort_long<unsigned short, 8>(ka, kb, reinterpret_cast<unsigned short*>(d_V0), reinterpret_cast<unsigned short*>(d_V1),
-                                           d_W0, d_W1, n, key_bits, w_bits, d_table, d_partial, stream, &ks, &vs16, &ws, &probe, d_P0, d_P1, 0, false, long_direct);
-      BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-      u32* vs = split_now ? reinterpret_cast<u32*>(vs16) : vs32;
-      rb.rec_keys = ks; rb.rec_free = ks == ka ? kb : ka;
-      rb.v_keys = vs; rb.v_free = vs == d_V0 ? d_V1 : d_V0;
-      lg.w = ws; lg.wmask = w_bits >= 32 ? ~0u : (1u << w_bits) - 1u;
-      rc = rank_step<u64, true>(ks, vs, n, n, short_len, (1ull << key_bits) - 1ull, rb, re, emit, h, &res, (u32)split_now, &lg);
-      if (rc == -3 && coded && (h_small[kSmallError] & 2u)) {
-        // a codeword came out longer than the table's fields hold (k_code_build): nothing has been emitted yet --
-        // this block again, with gram keys
-        if (std::getenv("BWTC_HIP_DEBUG")) std::fprintf(stderr, "code keys: a codeword above %u bits, the block takes gram keys\n", kCodeMaxLen);
-        BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallError, 0, 4, st));
-        code_failed = true;
-        rc = suffix_sort(n, hist, lone_sentinel, em);
-        code_failed = false;
-        return rc;
-      }
-      if (rc) return rc;
-      const int long_passes = (key_bits + w_bits + kRadixBits - 1) / kRadixBits;
-      stats.sort_pass_items += (u64)n * (u64)long_passes;
-      stats.alg_bytes += (u64)n * (1 + 12 + 1)               // the key maker: T read, key + second word + first plane written (the values are made up by the first pass)
-                         + sort_bytes(n, long_passes, split_now ? 14 : 16, 8, true);
-      stats.route |= coded ? 17u : 1u;
-      key_bits = 0;                                      // counted
-    } else if (gp.G > 0) {
-      hipLaunchKernelGGL(k_make_keys_gram, dim3(ceil_div(n, 1024)), dim3(256), 0, st, d_T, d_lut,
-                         (const uint4*)d_rank, ka, idx_out, n, gp.g, gp.G, gp.b, plan.sigma, gp.top, key_plane, split, lk);
-    } else {
-      u64 top = 1;
-      for (int t = 1; t < plan.k; ++t) top *= plan.sigma;
-      hipLaunchKernelGGL(k_make_keys<u64>, dim3(ceil_div(n, 1024)), dim3(256), 0, st, d_T, d_lut, ka,
-                         idx_out, n, plan.k, plan.sigma, top, key_plane, split);
-    }
-    u64* ks = nullptr; u32* vs = nullptr;
-    if (lk.w) {
-      // sorted and ranked above
-    } else if (split) {
-      unsigned short* vs16 = nullptr;
-      radix_sort_pairs<u64, unsigned short>(ka, kb, reinterpret_cast<unsigned short*>(d_V0), reinterpret_cast<unsigned short*>(d_V1),
-                                            n, key_bits, d_table, d_partial, stream, &ks, &vs16, &probe, 0, false, false, 0,
-                                            digit_planes ? d_P0 : nullptr, digit_planes ? d_P1 : nullptr,
-                                            key_plane != nullptr, true);
-      vs = reinterpret_cast<u32*>(vs16);
-    } else {
-      sort_pairs<u64>(ka, kb, d_V0, d_V1, n, key_bits, &ks, &vs, true, 0, 0, key_plane != nullptr, implied_idx);
-    }
-    if (!lk.w) {
-      BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-      rb.rec_keys = ks; rb.rec_free = ks == ka ? kb : ka;
-      rb.v_keys = vs; rb.v_free = vs == d_V0 ? d_V1 : d_V0;
-      rc = rank_step<u64, true>(ks, vs, n, n, short_len, split ? ((1ull << 48) - 1ull) : ~0ull, rb, re, emit, h, &res, (u32)split);
-    }
+// One key word: dense gram codes (gp.G > 0) or k characters as a base-sigma number.
+int BwtEngine::initial_keys64(const InitialSort& in, const GramPlan& gp, int key_bits, u32 short_len, int split, SortList& L, u64 h) {
+  const u32 n = in.n;
+  u64* ka = static_cast<u64*>(d_R1); u64* kb = static_cast<u64*>(d_R2);
+  if (gp.G > 0) launch_gram_keys(*this, in, gp, ka, split, kNoLongKey);
+  else launch_make_keys<u64>(*this, in, ka, split);
+  u64* ks = nullptr; u32* vs = nullptr;
+  if (split) {
+    unsigned short* vs16 = nullptr;
+    radix_sort_pairs<u64, unsigned short>(ka, kb, reinterpret_cast<unsigned short*>(d_V0), reinterpret_cast<unsigned short*>(d_V1),
+                                          n, key_bits, d_table, d_partial, stream, &ks, &vs16, &probe, 0, false, false, 0,
+                                          digit_planes ? d_P0 : nullptr, digit_planes ? d_P1 : nullptr, in.key_plane != nullptr, true);
+    vs = reinterpret_cast<u32*>(vs16);
   } else {
-    u32* ka = static_cast<u32*>(d_R1);
-    u32* kb = ka + cap;
-    u32 top = 1;
-    for (int t = 1; t < plan.k; ++t) top *= plan.sigma;
-    hipLaunchKernelGGL(k_make_keys<u32>, dim3(ceil_div(n, 1024)), dim3(256), 0, st, d_T, d_lut, ka,
-                       idx_out, n, plan.k, plan.sigma, top, key_plane, 0);
-    u32* ks = nullptr; u32* vs = nullptr;
-    sort_pairs<u32>(ka, kb, d_V0, d_V1, n, key_bits, &ks, &vs, true, 0, 0, key_plane != nullptr, implied_idx);
-    BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-    rb.rec_keys = d_R1; rb.rec_free = d_R2;             // both 32-bit key arrays live in R1
-    rb.v_keys = vs; rb.v_free = vs == d_V0 ? d_V1 : d_V0;
-    rc = rank_step<u32, true>(ks, vs, n, n, short_len, ~0u, rb, re, emit, h, &res);
+    sort_pairs<u64>(ka, kb, d_V0, d_V1, n, key_bits, &ks, &vs, true, 0, 0, in.key_plane != nullptr, in.implied_idx);
+  }
+  BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], stream));
+  hand_over(*this, L.rb, ks, ka, kb, vs);
+  const int rc = rank_step<u64, true>(ks, vs, n, n, short_len, split ? ((1ull << 48) - 1ull) : ~0ull, L.rb, L.re, L.emit, h, &L.res, (u32)split);
+  if (rc) return rc;
+  count_initial_sort(*this, n, key_bits, true);
+  return 0;
+}
+
+// Long keys: the sort also orders by a second key word and the items carry their predecessor character's code, so
+// that the ranking behind the ONE long sort can emit the transform's bytes and the finisher takes what is tied.
+// Two makers: the order-1 prefix code (k_make_keys_code, the default) and dense gram codes (round 4, BWTC_HIP_KEYS=grams).
+// *ranked stays false where the gram codes leave no room for a second word: nothing was launched, the block takes one
+// key word.  kCodeTableFull: see below.
+int BwtEngine::initial_long(const InitialSort& in, const GramPlan& gp, int key_bits, int split, bool coded, SortList& L, u64* h, bool* ranked) {
+  hipStream_t st = stream;
+  const u32 n = in.n;
+  u64* ka = static_cast<u64*>(d_R1); u64* kb = static_cast<u64*>(d_R2);
+  // (without the split -- blocks above 512 MiB, gram keys above 48 bits -- the items carry whole 32-bit suffix numbers:
+  // 16 bytes instead of 14, and the key only needs room for the character)
+  int w_bits = 0, split_now = split;
+  u32 short_len = 0;
+  RrLong lg{nullptr, ~0u, 0, 0, 0, -1, 0};
+  if (coded) {
+    // the block's order-1 statistics from a sample of its character pairs, the alphabetic codes, the keys
+    split_now = (split_index && n <= (1u << 29)) ? 1 : 0;
+    key_bits = code_bits - 32;                        // the key word's share; the second word takes 32
+    w_bits = 32;
+    const CodeKey ck = code_key_layout(d_codes, code_bits, split_now);
+    BWTC_HIP_TRY(upload_inverse_lut(*this, in));
+    const u32 sample_tiles = code_sample_tiles(n);
+    const int rc = launch_code_stage(*this, 7u, n, in.d_lut, in.plan.sigma, ka, in.key_plane, split_now, ck);
+    if (rc) return rc;
+    lg.hi_shift = ck.hi_shift; lg.chr_shift = ck.chr_shift; lg.chr_mask = 0xFFu; lg.lvl_shift = ck.lvl_shift;
+    short_len = 0;                                    // every item has its own (rr_masks)
+    *h = 1;
+    stats.alg_bytes += (u64)sample_tiles * kPairTile + (u64)kPairReplicas * 65536 * 8;
+    if (debug_on())
+      std::fprintf(stderr, "code keys: %d + %d bits, sigma %u, %u sampled tiles, character code at bit %d, level at bit %d\n",
+                   key_bits, w_bits, in.plan.sigma, sample_tiles, ck.chr_shift, ck.lvl_shift);
+  } else {
+    const int cb = std::max(1, bit_width_u64(in.plan.sigma - 1));
+    int G2 = std::min(32 / gp.b, (64 - gp.g * gp.G) / gp.g);
+    G2 = std::min(G2, long_grams_override > 0 ? long_grams_override : 2);
+    const int hi_bits = split ? 13 : 0;
+    if (G2 < 1 || key_bits + hi_bits + cb > 64) return 0;
+    LongKey lk = kNoLongKey;
+    lk.w = d_W0; lk.G2 = G2; lk.hi_shift = key_bits; lk.chr_shift = key_bits + hi_bits; lk.chr_mask = (1u << cb) - 1u;
+    BWTC_HIP_TRY(upload_inverse_lut(*this, in));
+    w_bits = gp.b * lk.G2;
+    if (w_bits < kRadixBits) { lk.first_r = w_bits; lk.first_mask = (1u << std::min(kRadixBits, w_bits + key_bits)) - 1u; }
+    short_len = (u32)(gp.g * (gp.G + lk.G2));
+    *h = (u64)short_len;
+    launch_gram_keys(*this, in, gp, ka, split, lk);
+    lg.hi_shift = lk.hi_shift; lg.chr_shift = lk.chr_shift; lg.chr_mask = lk.chr_mask; lg.lvl_shift = -1; lg.depth = short_len;
+    if (debug_on())
+      std::fprintf(stderr, "long keys: %d + %d bits, %d + %d grams of %d characters, character code at bit %d\n",
+                   key_bits, w_bits, gp.G, lk.G2, gp.g, lk.chr_shift);
+  }
+  u64* ks = nullptr; u32* ws = nullptr;
+  u32* vs = !split_now ? sort_long_as<u32, 6>(*this, ka, kb, n, key_bits, w_bits, &ks, &ws)
+            : long_items_per_thread == 6 ? sort_long_as<unsigned short, 6>(*this, ka, kb, n, key_bits, w_bits, &ks, &ws)
+                                         : sort_long_as<unsigned short, 8>(*this, ka, kb, n, key_bits, w_bits, &ks, &ws);
+  BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
+  hand_over(*this, L.rb, ks, ka, kb, vs);
+  lg.w = ws; lg.wmask = w_bits >= 32 ? ~0u : (1u << w_bits) - 1u;
+  const int rc = rank_step<u64, true>(ks, vs, n, n, short_len, (1ull << key_bits) - 1ull, L.rb, L.re, L.emit, *h, &L.res, (u32)split_now, &lg);
+  if (rc == -3 && coded && (h_small[kSmallError] & 2u)) {
+    // a codeword came out longer than the table's fields hold (k_code_build): nothing has been emitted yet --
+    // this block again, with gram keys (suffix_sort, allow_code_keys == false)
+    if (debug_on()) std::fprintf(stderr, "code keys: a codeword above %u bits, the block takes gram keys\n", kCodeMaxLen);
+    BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallError, 0, 4, st));
+    return kCodeTableFull;
   }
   if (rc) return rc;
-  stats.sort_pass_items += (u64)n * (u64)((key_bits + kRadixBits - 1) / kRadixBits);
-  if (key_bits) {
-    const int item = plan.wide ? 12 : 8;                  // (u64, u32 or u16 + upper bits in the key) / (u32, u32)
-    stats.alg_bytes += (u64)n * (1 + (u64)(plan.wide ? 8 : 4) + 1) + sort_bytes(n, (key_bits + kRadixBits - 1) / kRadixBits, item, plan.wide ? 8 : 4, digit_planes);
-  }
+  const int long_passes = (key_bits + w_bits + kRadixBits - 1) / kRadixBits;
+  stats.sort_pass_items += (u64)n * (u64)long_passes;
+  stats.alg_bytes += (u64)n * (1 + 12 + 1)               // the key maker: T read, key + second word + first plane written (the values are made up by the first pass)
+                     + sort_bytes(n, long_passes, split_now ? 14 : 16, 8, true);
+  stats.route |= coded ? 17u : 1u;
+  *ranked = true;
+  return 0;
+}
 
-  bool ranks_complete = true;
-  // The rounds over the sorted list in res / rb, from depth h0 until nothing is tied.  text_rounds_now: rounds that compare
-  // the text itself first (finisher route: rank[] is not complete, and completing it costs an ISA scatter of the whole block).
-  // doubling == false: text rounds only; what they leave tied comes back raw in (rb.v_free, rb.aglob_next, d_GRP) --
-  // suffix, slot, head slot -- *left entries at depth *h_left.
-  u32 shallow_depth = 0xFFFFFFFFu;
-  auto run_rounds = [&](u32 m, u64 h0, int text_rounds_now, bool keep_first, bool doubling, u32* left, u64* h_left) -> int {
-    u64 h = h0;
-    bool keep_h = keep_first;                // the list is sorted to depth h as it stands (no doubling before the next step)
-    int text_left = text_rounds_now;
-    // the block's closed-form step (runs, periods), decided where a list is about to double: step.when says whether it is
-    // the first round's or waits for a deeper one
-    const u64 h_first = keep_first ? h0 : h0 * 2;
-    if (doubling && m > 0) {
-      const int rcs = decide_step(n, m, h_first, res.ks, res.vs, (emit && res.carry) ? ((1ull << 56) - 1ull) : ~0ull);
-      if (rcs) return rcs;
-    }
-    int text_extra = text_rounds_fixed ? 0 : 12;        // further ones, one at a time, while the list is short (not when BWTC_HIP_TEXT_ROUNDS says how many)
-    while (m > 0 || (doubling && local_m > 0)) {
-      if (h >= (u64)n * 2 + 64) return -3;   // cannot happen: every group splits by then
-      ++stats.rounds;
-      stats.active_sum += m;
-      const bool text_round = text_left > 0 && m > 0;
-      bool run_req = false;                               // is the step this round's?  (the first round only, or the deferred period step's)
-      if (step.when == StretchStep::kThisRound) {
-        run_req = m > 0;
-        step.when = StretchStep::kNone;
-      } else if (step.when == StretchStep::kWaiting && m > 0) {
-        // the deferred period step: this round, if its depth has reached p and the stretches are longer than that
-        const u64 h_round = keep_h ? h : h * 2;
-        if ((u64)period_longest <= std::max<u64>(h_round, step.p)) {
-          step.when = StretchStep::kNone;
-          say_no_period_step(*this, h_first);
-        } else if (h_round >= (u64)step.p && ranks_complete && local_m == 0 && !text_round) {
-          step.when = StretchStep::kNone;
-          run_req = true;
-        }
-      }
-      const bool period_req = run_req && step.p >= 2;
-      const bool text = text_round || (run_req && !ranks_complete);   // the run step reads no rank[]: it does not need the completion either
-      const bool raw = !text && !doubling;               // out of text rounds and not allowed to double: hand the list back
-      if (std::getenv("BWTC_HIP_DEBUG")) std::fprintf(stderr, "round %u%s: h=%llu m=%u groups=%u\n", stats.rounds, text ? " (text)" : "", (unsigned long long)h, m, res.groups);
-      if (!keep_h) h *= 2;
-      keep_h = false;
-      if (!text && !raw && !ranks_complete) {
-        // the doubling rounds start here: rank[] for everybody first (the finished from SA; the list's own
-        // ranks come from the ranking step below, before anything reads them; a parked list's are its groups' heads)
-        complete_ranks(n, res.vs, rb.aglob_next, m, res.rec_other == d_R2 ? (res.ks == (u64*)d_R1 ? (void*)d_W0 : d_R1) : d_R2, res.rec_other);
-        ranks_complete = true;
-        ranks_live = true;
-        bridged = true;
-        stats.route |= 8u;
-        stats.alg_bytes += (u64)n * (4 + 8);                // k_bridge_pairs_all (the partition and scatter count themselves)
-      }
-      // what the local list's last pass noted reaches rank[] now: before this round's look-ups, after the last round's
-      if (!text && !raw) { const int rcu = local_updates(); if (rcu) return rcu; }
-      if (m == 0) {                                       // only the local list is left
-        const int rcl = local_pass(n, 0, re);
-        if (rcl) return rcl;
-        continue;
-      }
-      // the list just sorted: positions are the active list's, aglob gives their global slots
-      rb.aglob = rb.aglob_next;
-      rb.aglob_next = rb.aglob == d_G0 ? d_G1 : d_G0;
-      { u8* t = re.achr_out; re.achr_out = achr_other; achr_other = t; }
-      rb.rec_keys = res.ks; rb.rec_free = res.rec_other;
-      rb.v_keys = res.vs; rb.v_free = res.v_other;
-      const u64* ks = res.ks;
-      const u32* vs = res.vs;
-      const bool carried = emit && res.carry;             // this list's keys hold the characters in bits 56..63
-      // the second keys (RunKeys::mode): the run step, a round behind one, or no runs in play
-      const int rc2 = rank_step<u64, false>(ks, vs, m, n, 0u, carried ? ((1ull << 56) - 1ull) : ~0ull, rb, re, emit, h, &res, 0u, nullptr, text || raw, carried, raw,
-                                            run_req ? 1 : step.depth ? 2 : 0);
-      if (rc2) return rc2;
-      m = res.m;
-      const bool ran = run_req && res.ran_run;
-      if (period_req && !ran) say_no_period_step(*this, h_first);   // (the key had no room for the step's bit: an ordinary round)
-      if (ran) {
-        // the list is sorted to depth h still: a run's members by their closed-form keys, the others as they were (or by rank[s + h])
-        step.depth = (u32)std::min<u64>(h, 0xFFFFFFFFull);
-        stats.route |= period_req ? 256u : 32u;
-        keep_h = true;
-        if (period_req && std::getenv("BWTC_HIP_DEBUG"))
-          std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: period step at depth %u\n",
-                       period_p, period_votes, period_longest, (unsigned long long)h_first, step.depth);
-        // rank[] still incomplete: one text round behind the runs first -- a block that is one giant run ends there,
-        // without the completion of rank[] that the first doubling round costs.  Not beside a live local list: its
-        // members' ranks are local_depth deep, and the first doubling look-up must not lie deeper than that (text rounds
-        // raise h; that is why a list with a local list beside it takes none)
-        if (!ranks_complete && text_left == 0 && !text_rounds_fixed && local_m == 0) text_left = 1;
-      }
-      if (raw) { *left = m; *h_left = h; return 0; }
-      // the local list's doubling step beside the global list's (both read the rank[] this round's ranking step left)
-      if (!text && doubling && local_m > 0) { const int rcl = local_pass(n, h, re); if (rcl) return rcl; }
-      if (text && !ran) {
-        h += res.text_chars; keep_h = true;
-        if (text_round) --text_left;
-        // Out of text rounds with a short list left: a few more cost tens of microseconds each, the doubling rounds
-        // cost the completion of rank[] for the whole block first (5 ms per 256 MiB, 16 ms for the 1 GiB text -- the
-        // block whose text rounds ended with 10 entries still tied paid it).  Long lists (deep repeats) go on to the
-        // doubling rounds as before: their depth doubles there and only creeps here.
-        if (text_left == 0 && m > 0 && (u64)m * 4096 < (u64)n && text_extra > 0) { text_left = 1; --text_extra; }
-      }
-    }
-    if (step.when == StretchStep::kWaiting) {              // (the rounds ended before their depth reached p)
-      step.when = StretchStep::kNone;
-      say_no_period_step(*this, h_first);
-    }
-    if (left) { *left = 0; *h_left = h; }
-    return 0;
-  };
-  ranks_live = false;
-  parked = 0; park_holes = 0;
-  local_m = 0; local_pending = false;
-  if (res.finish) {
-    if (re.lf_n == 0 && em->n_lf > 1) return -3;
-    lf_noted = true;                       // every suffix that becomes final notes its LF power (lf_note), in every route
-    ranks_complete = false;
-    u32* cnt = d_small + kSmallFin;
-    h_small[kSmallFin + 3] = 0xFFFFFFFFu; h_small[kSmallFin + 4] = 0; h_small[kSmallFin + 5] = 0xFFFFFFFFu; h_small[kSmallFin + 6] = 0xFFFFFFFFu;
-    BWTC_HIP_TRY(hipMemcpyAsync(cnt + 3, h_small + kSmallFin + 3, 16, hipMemcpyHostToDevice, st));
-    // the ranking's list through the finisher
-    FinList la{rb.v_free, rb.aglob_next, d_GRP, reinterpret_cast<unsigned short*>(re.achr_out)};
-    FinList lb{d_W0, d_W1, rb.aglob_next == d_G0 ? d_G1 : d_G0, reinterpret_cast<unsigned short*>(re.achr_out == d_C0 ? d_C1 : d_C0)};
-    FinShallow shal{rb.v_keys, static_cast<u64*>(rb.rec_free), cnt + 4, fin_floor};
-    FinOutcome fo;
-    // Groups of hundreds of members on average (a period, one text many times over) are not the finisher's: its loop
-    // costs a group's size per member.  The list then goes to the rounds as it is (shallow groups apart).
-    const bool giant = res.groups > 0 && (u64)res.m > (u64)res.groups * 64;
-    if (giant && std::getenv("BWTC_HIP_DEBUG"))
-      std::fprintf(stderr, "finisher: skipped, %u entries in %u groups (more than 64 members on average)\n", res.m, res.groups);
-    // The shape of the passes.  The comparison loop costs a group's size per member, which is why groups above 256 members
-    // are not the finisher's on a real text (most of the block is on its list).  A SHORT list -- the long keys told
-    // nearly everything apart: 2.6 % of the generator's text is left -- takes windows of 2048 entries and groups of up to
-    // 1024 members instead: the few large groups (tokens repeated: 19 K entries of 7 M) are settled with the others and
-    // no hard list is left for the text rounds, whose five rounds of tiny launches cost more than the whole pass
-    // (256 MiB: 21.9 -> 21.3 ms).  Bounded: the wide shape costs at most 0.45 ns per entry more (measured on a real
-    // text, where every group is large), n / 24 entries at most.
-    fin_window_blk = fin_window; fin_group_blk = fin_max_group;
-    // One pass only in that shape: what three rounds of sixteen characters leave tied in a short list is deep repeats
-    // (copies of a long piece), the rounds' business -- further passes over groups of hundreds of members cost their size
-    // per member and settle nothing (300 copies of a 10 KB piece in the generator's text: 32.6 ms with three passes, 30.0
-    // in the narrow shape, where such groups are hard at once).
-    bool wide = false;
-    if (!fin_shape_fixed && fin_wide_short && !giant && (u64)res.m * 24 <= (u64)n) { fin_window_blk = 2048; fin_group_blk = 1024; wide = true; }
-    rc = finisher_passes(n, res.m, la, lb, re, shal, &fo, local_rounds, giant ? 0 : wide ? std::min(1, fin_max_passes) : fin_max_passes);
-    if (rc) return rc;
-    const u32 shallow = h_small[kSmallFin + 4];
-    const u64 h_sh = h_small[kSmallFin + 5];
-    // text rounds -- a global sort per six characters -- are for what is left of a text; a long list is deep repeats,
-    // which only doubling gets through
-    auto text_for = [&](u32 m) { return ((u64)m * 16 < (u64)n || text_rounds_fixed) ? text_rounds : 0; };
-    if (shallow) {
-      // The few hard groups of little depth first, on their own: text rounds only (rank[] must not go live while
-      // finisher passes are still to come); what they leave tied joins the waiting list, at the depth they reached.
-      rc = dress_list(n, shallow, rb.v_keys, static_cast<u64*>(rb.rec_free), rb, &res);
-      if (rc) return rc;
-      u32 left = 0; u64 h_left = 0;
-      rc = run_rounds(shallow, std::max<u64>(1, h_sh), std::max(text_rounds, 3), true, false, &left, &h_left);
-      if (rc) return rc;
-      if (left) {
-        if ((u64)parked + left > cap) return -3;
-        hipLaunchKernelGGL(k_raw_to_park, dim3(ceil_div(left, 256)), dim3(256), 0, st, (const u32*)rb.v_free, (const u32*)rb.aglob_next,
-                           (const u32*)d_GRP, left, d_parkS, d_parkHP, parked);
-        parked += left;
-        shallow_depth = (u32)std::min<u64>(h_left, 0xFFFFFFFFull);
-        if (std::getenv("BWTC_HIP_DEBUG")) std::fprintf(stderr, "shallow groups: %u entries still tied at depth %llu join the waiting list\n", left, (unsigned long long)h_left);
-      }
-    }
-    const u32 hard = fo.hard, hard_depth = fo.hard_depth;
-    if (parked || local_m) {
-      BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 3, cnt + 3, 4, hipMemcpyDeviceToHost, st));
-      BWTC_HIP_TRY(wait());
-      u64 h_pk = std::min<u64>(std::min<u64>(h_small[kSmallFin + 3], hard ? hard_depth : 0xFFFFFFFFu), shallow_depth);
-      if (local_m) h_pk = std::min<u64>(h_pk, local_depth);       // every rank is at least as deep as the rounds' first look-up
-      const u32 total = parked;
-      if (std::getenv("BWTC_HIP_DEBUG"))
-        std::fprintf(stderr, "finisher: %u entries (%u of groups too large) go on to the rounds at depth %llu; %u entries of small groups double beside them from depth %u\n",
-                     total, hard, (unsigned long long)h_pk, local_m, local_m ? local_depth : 0u);
-      if (total) {
-        BWTC_HIP_TRY(hipMemcpyAsync(d_V0, d_parkS, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
-        BWTC_HIP_TRY(hipMemcpyAsync(d_R1, d_parkHP, (size_t)total * 8, hipMemcpyDeviceToDevice, st));
-        parked = 0;                        // (the list is in the rounds' hands now: complete_ranks takes it from them)
-        rc = dress_list(n, total, d_V0, static_cast<u64*>(d_R1), rb, &res, park_holes);
-        if (rc) return rc;
-      } else {
-        // no global list: the rounds still want free regions to complete rank[] in
-        res.m = 0; res.groups = 0;
-        res.ks = reinterpret_cast<u64*>(d_W0); res.rec_other = d_R1;
-        res.vs = d_V0; res.v_other = d_V1;
-        rb.aglob_next = d_G0;
-      }
-      const u32 listed = total ? res.m : 0u;             // (the waiting list without its holes)
-      rc = run_rounds(listed, std::max<u64>(1, h_pk), local_m ? 0 : text_for(listed), true, true, nullptr, nullptr);
-      if (rc) return rc;
-    }
-  } else {
-    rc = run_rounds(res.m, h, 0, false, true, nullptr, nullptr);
-    if (rc) return rc;
+// Is the block's step this round's?  The first round's (decide_step) is; the deferred period step waits for the round
+// whose depth h_round has reached p, as long as the stretches are longer than that.
+bool BwtEngine::step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool text_round) {
+  StretchStep& step = blk.step;
+  if (step.when == StretchStep::kThisRound) { step.when = StretchStep::kNone; return m > 0; }
+  if (step.when != StretchStep::kWaiting || m == 0) return false;
+  if ((u64)blk.period_longest <= std::max<u64>(h_round, step.p)) {
+    step.when = StretchStep::kNone;
+    say_no_period_step(*this, h_first);
+  } else if (h_round >= (u64)step.p && L.ranks_complete && blk.local_m == 0 && !text_round) {
+    step.when = StretchStep::kNone;
+    return true;
   }
+  return false;
+}
+
+// The rounds over the sorted list in L.res / L.rb, from depth h0 until nothing is tied.  text_rounds_now: rounds that compare
+// the text itself first (finisher route: rank[] is not complete, and completing it costs an ISA scatter of the whole block).
+// doubling == false: text rounds only; what they leave tied comes back raw in (rb.v_free, rb.aglob_next, d_GRP) --
+// suffix, slot, head slot -- *left entries at depth *h_left.
+int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool keep_first, bool doubling, u32* left, u64* h_left) {
+  const u32 n = L.n;
+  RankBuffers& rb = L.rb;
+  RankResult& res = L.res;
+  RrEmit& re = L.re;
+  StretchStep& step = blk.step;
+  u64 h = h0;
+  bool keep_h = keep_first;                // the list is sorted to depth h as it stands (no doubling before the next step)
+  int text_left = text_rounds_now;
+  // the block's closed-form step (runs, periods), decided where a list is about to double: step.when says whether it is
+  // the first round's or waits for a deeper one
+  const u64 h_first = keep_first ? h0 : h0 * 2;
+  if (doubling && m > 0) {
+    const int rcs = decide_step(n, m, h_first, res.ks, res.vs, (L.emit && res.carry) ? ((1ull << 56) - 1ull) : ~0ull);
+    if (rcs) return rcs;
+  }
+  int text_extra = text_rounds_fixed ? 0 : 12;        // further ones, one at a time, while the list is short (not when BWTC_HIP_TEXT_ROUNDS says how many)
+  while (m > 0 || (doubling && blk.local_m > 0)) {
+    if (h >= (u64)n * 2 + 64) return -3;   // cannot happen: every group splits by then
+    ++stats.rounds;
+    stats.active_sum += m;
+    const bool text_round = text_left > 0 && m > 0;
+    const bool run_req = step_due(L, m, keep_h ? h : h * 2, h_first, text_round);
+    const bool period_req = run_req && step.p >= 2;
+    const bool text = text_round || (run_req && !L.ranks_complete);   // the run step reads no rank[]: it does not need the completion either
+    const bool raw = !text && !doubling;               // out of text rounds and not allowed to double: hand the list back
+    if (debug_on()) std::fprintf(stderr, "round %u%s: h=%llu m=%u groups=%u\n", stats.rounds, text ? " (text)" : "", (unsigned long long)h, m, res.groups);
+    if (!keep_h) h *= 2;
+    keep_h = false;
+    if (!text && !raw && !L.ranks_complete) {
+      // the doubling rounds start here: rank[] for everybody first (the finished from SA; the list's own
+      // ranks come from the ranking step below, before anything reads them; a parked list's are its groups' heads)
+      complete_ranks(n, res.vs, rb.aglob_next, m, res.rec_other == d_R2 ? (res.ks == (u64*)d_R1 ? (void*)d_W0 : d_R1) : d_R2, res.rec_other);
+      L.ranks_complete = true;
+      blk.ranks_live = true;
+      stats.route |= 8u;
+      stats.alg_bytes += (u64)n * (4 + 8);                // k_bridge_pairs_all (the partition and scatter count themselves)
+    }
+    // what the local list's last pass noted reaches rank[] now: before this round's look-ups, after the last round's
+    if (!text && !raw) { const int rcu = local_updates(); if (rcu) return rcu; }
+    if (m == 0) { const int rcl = local_pass(n, 0, re); if (rcl) return rcl; continue; }   // only the local list is left
+    // the list just sorted: positions are the active list's, aglob gives their global slots
+    rb.aglob = rb.aglob_next;
+    rb.aglob_next = rb.aglob == d_G0 ? d_G1 : d_G0;
+    std::swap(re.achr_out, L.achr_other);
+    rb.rec_keys = res.ks; rb.rec_free = res.rec_other;
+    rb.v_keys = res.vs; rb.v_free = res.v_other;
+    const u64* ks = res.ks; const u32* vs = res.vs;
+    const bool carried = L.emit && res.carry;           // this list's keys hold the characters in bits 56..63
+    // the second keys (RunKeys::mode): the run step, a round behind one, or no runs in play
+    const int rc2 = rank_step<u64, false>(ks, vs, m, n, 0u, carried ? ((1ull << 56) - 1ull) : ~0ull, rb, re, L.emit, h, &res, 0u, nullptr, text || raw, carried, raw,
+                                          run_req ? 1 : step.depth ? 2 : 0);
+    if (rc2) return rc2;
+    m = res.m;
+    const bool ran = run_req && res.ran_run;
+    if (period_req && !ran) say_no_period_step(*this, h_first);   // (the key had no room for the step's bit: an ordinary round)
+    if (ran) {
+      // the list is sorted to depth h still: a run's members by their closed-form keys, the others as they were (or by rank[s + h])
+      step.depth = (u32)std::min<u64>(h, 0xFFFFFFFFull);
+      stats.route |= period_req ? 256u : 32u;
+      keep_h = true;
+      if (period_req && debug_on())
+        std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: period step at depth %u\n",
+                     blk.period_p, blk.period_votes, blk.period_longest, (unsigned long long)h_first, step.depth);
+      // rank[] still incomplete: one text round behind the runs first -- a block that is one giant run ends there,
+      // without the completion of rank[] that the first doubling round costs.  Not beside a live local list: its
+      // members' ranks are local_depth deep, and the first doubling look-up must not lie deeper than that (text rounds
+      // raise h; that is why a list with a local list beside it takes none)
+      if (!L.ranks_complete && text_left == 0 && !text_rounds_fixed && blk.local_m == 0) text_left = 1;
+    }
+    if (raw) { *left = m; *h_left = h; return 0; }
+    // the local list's doubling step beside the global list's (both read the rank[] this round's ranking step left)
+    if (!text && doubling && blk.local_m > 0) { const int rcl = local_pass(n, h, re); if (rcl) return rcl; }
+    if (text && !ran) {
+      h += res.text_chars; keep_h = true;
+      if (text_round) --text_left;
+      // Out of text rounds with a short list left: a few more cost tens of microseconds each, the doubling rounds
+      // cost the completion of rank[] for the whole block first (5 ms per 256 MiB, 16 ms for the 1 GiB text -- the
+      // block whose text rounds ended with 10 entries still tied paid it).  Long lists (deep repeats) go on to the
+      // doubling rounds as before: their depth doubles there and only creeps here.
+      if (text_left == 0 && m > 0 && (u64)m * 4096 < (u64)n && text_extra > 0) { text_left = 1; --text_extra; }
+    }
+  }
+  if (step.when == StretchStep::kWaiting) {              // (the rounds ended before their depth reached p)
+    step.when = StretchStep::kNone;
+    say_no_period_step(*this, h_first);
+  }
+  if (left) { *left = 0; *h_left = h; }
+  return 0;
+}
+
+// The finisher's start: its counter words, and the two homes its lists alternate between.  The first list's suffixes lie
+// in S (the ranking's free value array; d_V0 in the test hooks), its slots in d_G0, its characters in d_C0, where the
+// initial ranking leaves them.
+hipError_t BwtEngine::finisher_begin(u32* S, FinList* a, FinList* b) {
+  *a = FinList{S, d_G0, d_GRP, reinterpret_cast<unsigned short*>(d_C0)};
+  *b = FinList{d_W0, d_W1, d_G1, reinterpret_cast<unsigned short*>(d_C1)};
+  h_small[kSmallFin + 3] = 0xFFFFFFFFu; h_small[kSmallFin + 4] = 0; h_small[kSmallFin + 5] = 0xFFFFFFFFu; h_small[kSmallFin + 6] = 0xFFFFFFFFu;
+  return hipMemcpyAsync(d_small + kSmallFin + 3, h_small + kSmallFin + 3, 16, hipMemcpyHostToDevice, stream);
+}
+
+// The finisher route: the long-key ranking's list through the finisher's passes; the shallow list's rounds, what they
+// and the passes leave waiting (parked), the local list, and the rounds that end the block.
+int BwtEngine::finisher_route(SortList& L, u32 n_lf) {
+  hipStream_t st = stream;
+  const u32 n = L.n;
+  RankBuffers& rb = L.rb;
+  RankResult& res = L.res;
+  if (L.re.lf_n == 0 && n_lf > 1) return -3;
+  blk.lf_noted = true;                     // every suffix that becomes final notes its LF power (lf_note), in every route
+  L.ranks_complete = false;
+  u32* cnt = d_small + kSmallFin;
+  FinList la, lb;
+  BWTC_HIP_TRY(finisher_begin(rb.v_free, &la, &lb));
+  FinShallow shal{rb.v_keys, static_cast<u64*>(rb.rec_free), cnt + 4, fin_floor};
+  FinOutcome fo;
+  // Groups of hundreds of members on average (a period, one text many times over) are not the finisher's: its loop
+  // costs a group's size per member.  The list then goes to the rounds as it is (shallow groups apart).
+  const bool giant = res.groups > 0 && (u64)res.m > (u64)res.groups * 64;
+  if (giant && debug_on())
+    std::fprintf(stderr, "finisher: skipped, %u entries in %u groups (more than 64 members on average)\n", res.m, res.groups);
+  // The shape of the passes.  The comparison loop costs a group's size per member, which is why groups above 256 members
+  // are not the finisher's on a real text (most of the block is on its list).  A SHORT list -- the long keys told
+  // nearly everything apart: 2.6 % of the generator's text is left -- takes windows of 2048 entries and groups of up to
+  // 1024 members instead: the few large groups (tokens repeated: 19 K entries of 7 M) are settled with the others and
+  // no hard list is left for the text rounds, whose five rounds of tiny launches cost more than the whole pass
+  // (256 MiB: 21.9 -> 21.3 ms).  Bounded: the wide shape costs at most 0.45 ns per entry more (measured on a real
+  // text, where every group is large), n / 24 entries at most.
+  blk.fin_window_blk = fin_window; blk.fin_group_blk = fin_max_group;
+  // One pass only in that shape: what three rounds of sixteen characters leave tied in a short list is deep repeats
+  // (copies of a long piece), the rounds' business -- further passes over groups of hundreds of members cost their size
+  // per member and settle nothing (300 copies of a 10 KB piece in the generator's text: 32.6 ms with three passes, 30.0
+  // in the narrow shape, where such groups are hard at once).
+  bool wide = false;
+  if (!fin_shape_fixed && fin_wide_short && !giant && (u64)res.m * 24 <= (u64)n) { blk.fin_window_blk = 2048; blk.fin_group_blk = 1024; wide = true; }
+  int rc = finisher_passes(n, res.m, la, lb, L.re, shal, &fo, local_rounds, giant ? 0 : wide ? std::min(1, fin_max_passes) : fin_max_passes);
+  if (rc) return rc;
+  const u32 shallow = h_small[kSmallFin + 4];
+  const u64 h_sh = h_small[kSmallFin + 5];
+  u32 shallow_depth = 0xFFFFFFFFu;
+  if (shallow) {
+    // The few hard groups of little depth first, on their own: text rounds only (rank[] must not go live while
+    // finisher passes are still to come); what they leave tied joins the waiting list, at the depth they reached.
+    rc = dress_list(n, shallow, rb.v_keys, static_cast<u64*>(rb.rec_free), rb, &res);
+    if (rc) return rc;
+    u32 left = 0; u64 h_left = 0;
+    rc = run_rounds(L, shallow, std::max<u64>(1, h_sh), std::max(text_rounds, 3), true, false, &left, &h_left);
+    if (rc) return rc;
+    if (left) {
+      if ((u64)blk.parked + left > cap) return -3;
+      hipLaunchKernelGGL(k_raw_to_park, dim3(ceil_div(left, 256)), dim3(256), 0, st, (const u32*)rb.v_free, (const u32*)rb.aglob_next,
+                         (const u32*)d_GRP, left, d_parkS, d_parkHP, blk.parked);
+      blk.parked += left;
+      shallow_depth = (u32)std::min<u64>(h_left, 0xFFFFFFFFull);
+      if (debug_on()) std::fprintf(stderr, "shallow groups: %u entries still tied at depth %llu join the waiting list\n", left, (unsigned long long)h_left);
+    }
+  }
+  if (!blk.parked && !blk.local_m) return 0;
+  const u32 hard = fo.hard, hard_depth = fo.hard_depth;
+  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 3, cnt + 3, 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(wait());
+  u64 h_pk = std::min<u64>(std::min<u64>(h_small[kSmallFin + 3], hard ? hard_depth : 0xFFFFFFFFu), shallow_depth);
+  if (blk.local_m) h_pk = std::min<u64>(h_pk, blk.local_depth);   // every rank is at least as deep as the rounds' first look-up
+  const u32 total = blk.parked;
+  if (debug_on())
+    std::fprintf(stderr, "finisher: %u entries (%u of groups too large) go on to the rounds at depth %llu; %u entries of small groups double beside them from depth %u\n",
+                 total, hard, (unsigned long long)h_pk, blk.local_m, blk.local_m ? blk.local_depth : 0u);
+  if (total) {
+    BWTC_HIP_TRY(hipMemcpyAsync(d_V0, d_parkS, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
+    BWTC_HIP_TRY(hipMemcpyAsync(d_R1, d_parkHP, (size_t)total * 8, hipMemcpyDeviceToDevice, st));
+    blk.parked = 0;                        // (the list is in the rounds' hands now: complete_ranks takes it from them)
+    rc = dress_list(n, total, d_V0, static_cast<u64*>(d_R1), rb, &res, blk.park_holes);
+    if (rc) return rc;
+  } else {
+    // no global list: the rounds still want free regions to complete rank[] in
+    res.m = 0; res.groups = 0;
+    res.ks = reinterpret_cast<u64*>(d_W0); res.rec_other = d_R1;
+    res.vs = d_V0; res.v_other = d_V1;
+    rb.aglob_next = d_G0;
+  }
+  const u32 listed = total ? res.m : 0u;               // (the waiting list without its holes)
+  // text rounds -- a global sort per six characters -- are for what is left of a text; a long list is deep repeats,
+  // which only doubling gets through
+  const int text_now = (!blk.local_m && ((u64)listed * 16 < (u64)n || text_rounds_fixed)) ? text_rounds : 0;
+  return run_rounds(L, listed, std::max<u64>(1, h_pk), text_now, true, true, nullptr, nullptr);
+}
+
+// The driver: the block's state and key plan, the initial sort and ranking, then the finisher route or the rounds.
+int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const EmitTarget* em, bool allow_code_keys) {
+  n_sort_events = 0;
+  stats.rounds = 0; stats.active_sum = 0; stats.sort_pass_items = 0; stats.route = 0; stats.finisher_entries = 0;
+  blk = BlockSort{};                       // (nothing of the last block's; what bwtc_hip_period_get reports lived until here)
+  if (n == 0) return 0;
+
+  const KeyPlan plan = plan_keys(hist, n, lone_sentinel, gram_min_n < kGramMinN);   // (the tests' small blocks: 64-bit keys whatever the entropy says)
+  std::memcpy(h_small + kSmallLut, plan.lut, 256);
+  BWTC_HIP_TRY(hipMemcpyAsync(d_small + kSmallLut, h_small + kSmallLut, 256, hipMemcpyHostToDevice, stream));
+  const bool implied_idx = !use_sweep && n > 1;
+  const InitialSort in{n, hist, lone_sentinel, plan, reinterpret_cast<const u8*>(d_small + kSmallLut),
+                       digit_planes && !use_sweep ? d_P0 : nullptr, implied_idx, implied_idx ? nullptr : d_V0};
+  RrEmit re{em ? em->out : nullptr, em ? em->out_n : 0u, d_small + kSmallLastChar, d_small + kSmallPidx, d_T, d_C0, nullptr, 0,
+            reinterpret_cast<const u8*>(d_small + kSmallInv), d_small + kSmallLf, 0, 0, 0};
+  if (em && em->n_lf > 1 && n / em->n_lf >= 1) {
+    re.lf_n = em->n_lf; re.lf_x = n / em->n_lf; re.lf_inv = re.lf_x > 1 ? (u32)((1ull << 32) / re.lf_x) : 0u;
+  }
+  SortList L{n, em != nullptr, RankBuffers{nullptr, nullptr, nullptr, nullptr, nullptr, d_G0}, re, RankResult{}, d_C1, true};
+  u64 h = (u64)plan.k;                     // the next round compares rank[s + h]
+
+  BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], stream));
+  int rc = plan.wide ? initial_wide(in, allow_code_keys, L, &h) : initial_keys32(in, L, h);
+  if (rc == kCodeTableFull) return suffix_sort(n, hist, lone_sentinel, em, false);
+  if (rc) return rc;
+  rc = L.res.finish ? finisher_route(L, em->n_lf) : run_rounds(L, L.res.m, h, 0, false, true, nullptr, nullptr);
+  if (rc) return rc;
   BWTC_HIP_TRY(hipGetLastError());
   BWTC_HIP_TRY(take_sticky_error());
   return 0;
@@ -3190,7 +3192,7 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
 // events, for scripts/runs_bench.py and scripts/periods_bench.py.  The events are destroyed on every way out.
 namespace {
 struct PassTimer {
-  const bool on = std::getenv("BWTC_HIP_DEBUG") != nullptr;
+  const bool on = debug_on();
   hipStream_t st;
   hipEvent_t a = nullptr, b = nullptr;
   explicit PassTimer(hipStream_t s) : st(s) {}
@@ -3239,8 +3241,8 @@ int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest) {
                                     : "periods: a trial pass (no lengths stored) took %.4f ms for %u suffixes, period %u\n", ms, n, p);
   }
   *longest = h_small[kSmallStretch];
-  if (store) lengths_period = p;
-  if (p == 1) { run_longest = *longest; run_longest_known = true; }
+  if (store) blk.lengths_period = p;
+  if (p == 1) { blk.run_longest = *longest; blk.run_longest_known = true; }
   // T read twice (p > 1: both streams of it), the lengths written; the tiles' words written and read
   stats.alg_bytes += (u64)n * ((p == 1 ? 1 + 1 : 2 + 2) + (store ? 4 : 0)) + (u64)tiles * 16;
   return 0;
@@ -3249,100 +3251,100 @@ int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest) {
 // The block's closed-form step, into `step`, for a list of m > 0 entries that is about to double and whose first round
 // establishes depth h_first.  Nothing where a step has run already: one step per block.
 int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask) {
-  if (step.depth != 0) return 0;
+  if (blk.step.depth != 0) return 0;
   hipStream_t st = stream;
   // Runs: the list may hold long runs of one byte, which doubling takes log2(length) rounds over.  k[] and the block's
   // longest run are made here (once per block, one host wait); a run longer than the depth the first round establishes
   // gets the run step as that round, before any text round and before rank[] is completed.
   // (BWTC_HIP_PERIOD=1: the run step is the period step of period 1, whatever BWTC_HIP_RUNS says)
   if (run_ranks || period_forced == 1) {
-    if (lengths_period != 1) {
-      const int rcr = stretch_lengths(n, 1, true, &run_longest);
+    if (blk.lengths_period != 1) {
+      const int rcr = stretch_lengths(n, 1, true, &blk.run_longest);
       if (rcr) return rcr;
     }
-    if ((u64)run_longest > h_first) step = StretchStep{1, StretchStep::kThisRound, 0};
-    if (std::getenv("BWTC_HIP_DEBUG"))
-      std::fprintf(stderr, "runs: longest run %u, the rounds begin at depth %llu: %s\n", run_longest, (unsigned long long)h_first,
-                   step.when == StretchStep::kThisRound ? "run step" : "no run step");
+    if ((u64)blk.run_longest > h_first) blk.step = StretchStep{1, StretchStep::kThisRound, 0};
+    if (debug_on())
+      std::fprintf(stderr, "runs: longest run %u, the rounds begin at depth %llu: %s\n", blk.run_longest, (unsigned long long)h_first,
+                   blk.step.when == StretchStep::kThisRound ? "run step" : "no run step");
   }
   // Periods: a list that takes doubling rounds and no run step may hold stretches of a period p > 1, which tie their
   // suffixes for the stretch's length just as a run does.  The finder votes for p over the list as it stands (or
   // BWTC_HIP_PERIOD names it); votes above the threshold buy the period-length pass, which puts k_p[] where k[] was.
   // p <= the first round's depth: that round is the period step, exactly as the run step.  A deeper p: the step waits
   // for the first doubling round whose depth reaches p (kWaiting), with rank[] complete and no local list beside it.
-  if (!period_ranks || period_forced == 1 || step.when != StretchStep::kNone || period_looked) return 0;
-  period_looked = true;
+  if (!period_ranks || period_forced == 1 || blk.step.when != StretchStep::kNone || blk.period_looked) return 0;
+  blk.period_looked = true;
   const int rcp = find_period(n, ks, vs, m, kmask);
   if (rcp) return rcp;
-  if (period_p >= 2 && !period_forced) {
+  if (blk.period_p >= 2 && !period_forced) {
     // votes say how many members lie p apart, not for how long they tie: fixed-width records with a few free bytes
     // each vote for their width and tie for less than two records.  Before the pass, a probe: is any aligned window
     // of (W - p) / 2 positions free of breaks, W = kPeriodWorth x max(the first round's depth, p) being the stretch
     // the step is worth?  A stretch of W characters holds such a window; the probe's threads stop at their first break.
-    const u64 worth = kPeriodWorth * std::max<u64>(h_first, period_p);
-    const u32 span = (u32)std::min<u64>((worth - period_p) / 2, 0x40000000ull);
-    const u64 windows = (u64)n > period_p + span ? ((u64)n - period_p) / span : 0;
+    const u64 worth = kPeriodWorth * std::max<u64>(h_first, blk.period_p);
+    const u32 span = (u32)std::min<u64>((worth - blk.period_p) / 2, 0x40000000ull);
+    const u64 windows = (u64)n > blk.period_p + span ? ((u64)n - blk.period_p) / span : 0;
     bool found = false;
     if (windows) {
       BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallPeriod + 1, 0, 4, st));
-      hipLaunchKernelGGL(k_period_probe, dim3((u32)((windows + 255) / 256)), dim3(256), 0, st, (const u8*)d_T, n, period_p, span, (u32)std::min<u64>(windows, 0xFFFFFFFFull), d_small + kSmallPeriod + 1);
+      hipLaunchKernelGGL(k_period_probe, dim3((u32)((windows + 255) / 256)), dim3(256), 0, st, (const u8*)d_T, n, blk.period_p, span, (u32)std::min<u64>(windows, 0xFFFFFFFFull), d_small + kSmallPeriod + 1);
       BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 1, d_small + kSmallPeriod + 1, 4, hipMemcpyDeviceToHost, st));
       BWTC_HIP_TRY(wait());
       found = h_small[kSmallPeriod + 1] != 0;
       stats.alg_bytes += windows * 2;                   // (at the least: a byte of each stream per window)
     }
     if (!found) {
-      if (std::getenv("BWTC_HIP_DEBUG")) std::fprintf(stderr, "periods: no window of %u positions of period %u without a break: no period-length pass\n", span, period_p);
-      period_p = 0;
+      if (debug_on()) std::fprintf(stderr, "periods: no window of %u positions of period %u without a break: no period-length pass\n", span, blk.period_p);
+      blk.period_p = 0;
     }
   }
-  if (period_p >= 2) {
+  if (blk.period_p >= 2) {
     // (a run of one byte is a stretch of every period, and the run step's business: the block's longest run first --
     // known already unless BWTC_HIP_RUNS=0, where a trial pass of period 1 finds it -- and no period step where the
     // longest stretch is no longer than that)
-    int rcb = (period_forced || run_longest_known) ? 0 : stretch_lengths(n, 1, false, &run_longest);
+    int rcb = (period_forced || blk.run_longest_known) ? 0 : stretch_lengths(n, 1, false, &blk.run_longest);
     if (rcb) return rcb;
-    rcb = stretch_lengths(n, period_p, true, &period_longest);
+    rcb = stretch_lengths(n, blk.period_p, true, &blk.period_longest);
     if (rcb) return rcb;
-    if (!period_forced && run_longest >= period_longest) period_p = 0;
+    if (!period_forced && blk.run_longest >= blk.period_longest) blk.period_p = 0;
     // ... and none where the longest stretch is short of kPeriodWorth times the depth it has to pass: doubling gets
     // through it in three rounds, and the step's own round and the passes cost as much (fixed-width records with
     // a few free bytes per record vote for their width and tie for less than two records)
-    if (!period_forced && (u64)period_longest < kPeriodWorth * std::max<u64>(h_first, period_p)) period_p = 0;
+    if (!period_forced && (u64)blk.period_longest < kPeriodWorth * std::max<u64>(h_first, blk.period_p)) blk.period_p = 0;
   }
-  if (period_p >= 2) {
-    if (!period_forced && (u64)period_p > h_first && (u64)period_longest > period_p) {
+  if (blk.period_p >= 2) {
+    if (!period_forced && (u64)blk.period_p > h_first && (u64)blk.period_longest > blk.period_p) {
       // The winner may be a multiple of the stretches' period: a list that a sort by windows of the suffix number
       // has been through holds a group's members in another order than by position.  A period above the first
       // round's depth defers the step, so it is worth dividing: p / q for the winner's prime factors q, kept while
       // the longest stretch stays as long (trial passes: the longest stretch alone, no lengths stored).
-      const u32 voted = period_p, longest_voted = period_longest;
+      const u32 voted = blk.period_p, longest_voted = blk.period_longest;
       u32 rest = voted;
-      for (u32 q = 2; q <= rest && period_p / q >= 2; ) {
+      for (u32 q = 2; q <= rest && blk.period_p / q >= 2; ) {
         if (rest % q) { ++q; continue; }
         rest /= q;
-        const int rcb = stretch_lengths(n, period_p / q, false, &period_longest);
+        const int rcb = stretch_lengths(n, blk.period_p / q, false, &blk.period_longest);
         if (rcb) return rcb;
-        if (period_longest >= longest_voted) period_p /= q;
+        if (blk.period_longest >= longest_voted) blk.period_p /= q;
         else while (rest % q == 0) rest /= q;          // (the same candidate again)
       }
-      period_longest = longest_voted;
-      if (period_p != voted) {
-        const int rcb = stretch_lengths(n, period_p, true, &period_longest);
+      blk.period_longest = longest_voted;
+      if (blk.period_p != voted) {
+        const int rcb = stretch_lengths(n, blk.period_p, true, &blk.period_longest);
         if (rcb) return rcb;
       }
     }
-    if ((u64)period_p <= h_first) { if ((u64)period_longest > h_first) step = StretchStep{period_p, StretchStep::kThisRound, 0}; }
-    else if (period_longest > period_p) step = StretchStep{period_p, StretchStep::kWaiting, 0};
+    if ((u64)blk.period_p <= h_first) { if ((u64)blk.period_longest > h_first) blk.step = StretchStep{blk.period_p, StretchStep::kThisRound, 0}; }
+    else if (blk.period_longest > blk.period_p) blk.step = StretchStep{blk.period_p, StretchStep::kWaiting, 0};
   }
-  if (step.when == StretchStep::kNone) say_no_period_step(*this, h_first);
+  if (blk.step.when == StretchStep::kNone) say_no_period_step(*this, h_first);
   return 0;
 }
 
 // The block's period, into period_p (0: none worth the pass) and period_votes: BWTC_HIP_PERIOD's, or the vote's winner
 // if its votes reach the threshold -- a 64th of the block, and kPeriodMinVotes at the least.
 int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask) {
-  if (period_forced) { period_p = period_forced; period_votes = 0; return 0; }
+  if (period_forced) { blk.period_p = period_forced; blk.period_votes = 0; return 0; }
   if (m < 2) return 0;
   hipStream_t st = stream;
   PassTimer timer(st);
@@ -3360,10 +3362,10 @@ int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask
     std::fprintf(stderr, "periods: the vote kernel took %.4f ms for %u entries\n", ms, m);
   }
   const u32 winner = h_small[kSmallPeriod + 2];
-  period_votes = h_small[kSmallPeriod + 3];
+  blk.period_votes = h_small[kSmallPeriod + 3];
   const u64 need = std::max<u64>(kPeriodMinVotes, (u64)n / 64);
-  period_p = (winner >= 2 && (u64)period_votes >= need) ? winner : 0u;
-  if (!period_p && timed) std::fprintf(stderr, "periods: distance %u leads with %u votes of the %llu a pass takes\n", winner, period_votes, (unsigned long long)need);
+  blk.period_p = (winner >= 2 && (u64)blk.period_votes >= need) ? winner : 0u;
+  if (!blk.period_p && timed) std::fprintf(stderr, "periods: distance %u leads with %u votes of the %llu a pass takes\n", winner, blk.period_votes, (unsigned long long)need);
   stats.alg_bytes += (u64)m * (8 + 4) + (u64)kVoteBins * 8;   // the list's keys and suffixes read; the table zeroed and read
   return 0;
 }
@@ -3401,7 +3403,7 @@ static bool fin_room(const FinRegions& rg, u32 stride, u32 group, u64 lcap, FinO
 static void launch_finish(BwtEngine& e, FinList a, const FinRegions& rg, u32 n, FinList b, const FinOut& ob, u32* ncnt, u32* hardS, u64* hardHP,
                           unsigned short* hardC, u32* hard_count, FinShallow shal, const RrEmit& re, const FinRank* rk) {
   hipStream_t st = e.stream;
-  const int window = e.fin_window_blk, group = e.fin_group_blk, fin_words = e.fin_words, fin_rounds = e.fin_rounds;
+  const int window = e.blk.fin_window_blk, group = e.blk.fin_group_blk, fin_words = e.fin_words, fin_rounds = e.fin_rounds;
   const u32 grid = rg.wfirst[rg.nreg];
 #define BWTC_FINISH_W(G, E, NW) hipLaunchKernelGGL((k_finish<G, E, NW>), dim3(grid), dim3(kFinTPB), 0, st, a, rg, (const u8*)e.d_T, n, \
                                              b, ob, ncnt, hardS, hardHP, hardC, hard_count, shal, e.d_SA, re)
@@ -3430,9 +3432,9 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
   h_small[kSmallFin] = 0; h_small[kSmallFin + 1] = 0; h_small[kSmallFin + 2] = 0xFFFFFFFFu;
   BWTC_HIP_TRY(hipMemcpyAsync(cnt, h_small + kSmallFin, 12, hipMemcpyHostToDevice, st));
   u32 hard = 0;
-  passes_done = 0;
-  const u32 park0 = parked;            // the groups too large for a window join the waiting list from here
-  const int window = fin_window_blk, group = fin_group_blk;
+  blk.passes_done = 0;
+  const u32 park0 = blk.parked;            // the groups too large for a window join the waiting list from here
+  const int window = blk.fin_window_blk, group = blk.fin_group_blk;
   const u32 stride = (u32)(window - group);
   FinRegions rg;
   std::memset(&rg, 0, sizeof rg);
@@ -3446,7 +3448,7 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
     FinOut ob;
     if (!fin_room(rg, stride, (u32)group, lcap, &ob)) {
       stats.route |= 128u;
-      if (std::getenv("BWTC_HIP_DEBUG"))
+      if (debug_on())
         std::fprintf(stderr, "finisher pass %d: %u entries would not fit the lists in this shape (%d / %d); on to the rounds\n", it, m, window, group);
       break;
     }
@@ -3481,18 +3483,18 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
       rg = nx;
       m = total;
     }
-    if (std::getenv("BWTC_HIP_DEBUG"))
+    if (debug_on())
       std::fprintf(stderr, "finisher pass %d: %u entries -> %u still tied; %u hard (depth from %u), %u shallow (from %u)\n", it, m_was, m,
                    h_small[kSmallFin + 1], h_small[kSmallFin + 2], h_small[kSmallFin + 4], h_small[kSmallFin + 5]);
     hard = h_small[kSmallFin + 1];
     std::swap(a, b);
-    passes_done = it + 1;
+    blk.passes_done = it + 1;
     if (m < 4096u) break;                                                          // a handful: they join the waiting list (a pass of their own is a launch and a host wait for nothing)
     if (it >= 1 && (u64)m * 5 > (u64)m_was * 3 && (u64)m * 64 > (u64)n) break;     // deep repeats: on to the rounds
     if (it >= 2 && (u64)m * 4 > (u64)m_was * 3) break;                             // a list that hardly shrinks any more: the rounds double, this creeps
   }
-  parked += hard;
-  if ((u64)parked > cap) return -3;
+  blk.parked += hard;
+  if ((u64)blk.parked > cap) return -3;
   // (a pass has run: no group above the bound is left in the list; and its groups are small -- the comparison loop costs a
   // group's size per member: a block that is one text 256 times over has groups of 256 throughout and is the global rounds')
   // (the local list's steps leave up to kFinRegions regions of it: room for that many more windows)
@@ -3501,7 +3503,7 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
   worst.nreg = 1; worst.wfirst[1] = ceil_div(m, stride) + kFinRegions;
   FinOut unused;
   const bool local_fits = fin_room(worst, stride, (u32)group, lcap, &unused);
-  const bool want_local = m && keep_local && passes_done >= 1 && (u64)m * 64 >= (u64)n && (u64)groups_left * 24 >= (u64)m;
+  const bool want_local = m && keep_local && blk.passes_done >= 1 && (u64)m * 64 >= (u64)n && (u64)groups_left * 24 >= (u64)m;
   if (want_local && !local_fits) stats.route |= 128u;
   if (want_local && local_fits) {
     // deep repeats in small groups: the doubling rounds take them group by group (local_pass), not through the global sort
@@ -3515,12 +3517,12 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
     }
     BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 6, cnt + 6, 4, hipMemcpyDeviceToHost, st));
     BWTC_HIP_TRY(wait());
-    local_depth = h_small[kSmallFin + 6];
+    blk.local_depth = h_small[kSmallFin + 6];
     // its smallest depth: every member has taken the same passes, from a level's depth
-    local_m = m;
-    std::memset(&local_rg, 0, sizeof local_rg);
-    local_rg.nreg = 1; local_rg.wfirst[1] = ceil_div(m, stride); local_rg.ecount[0] = m;
-    local_home = 0;
+    blk.local_m = m;
+    std::memset(&blk.local_rg, 0, sizeof blk.local_rg);
+    blk.local_rg.nreg = 1; blk.local_rg.wfirst[1] = ceil_div(m, stride); blk.local_rg.ecount[0] = m;
+    blk.local_home = 0;
     fo->left = 0;
     fo->hard = hard;
     fo->hard_depth = h_small[kSmallFin + 2];
@@ -3529,20 +3531,20 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
   }
   if (m) {
     // what the last pass left tied waits for the rounds
-    if ((u64)parked + m > cap) return -3;
+    if ((u64)blk.parked + m > cap) return -3;
     for (u32 r = 0; r < rg.nreg; ++r) {
       if (!rg.ecount[r]) continue;
       FinList part{a.S + rg.ebase[r], a.P + rg.ebase[r], a.H + rg.ebase[r], a.C + rg.ebase[r]};
-      hipLaunchKernelGGL(k_fin_to_hard, dim3(ceil_div(rg.ecount[r], 256)), dim3(256), 0, st, part, rg.ecount[r], d_parkS, d_parkHP, parked, cnt + 3,
-                         passes_done ? FinShallow{shal.S, shal.HP, shal.count, 0u} : shal);
-      parked += rg.ecount[r];
+      hipLaunchKernelGGL(k_fin_to_hard, dim3(ceil_div(rg.ecount[r], 256)), dim3(256), 0, st, part, rg.ecount[r], d_parkS, d_parkHP, blk.parked, cnt + 3,
+                         blk.passes_done ? FinShallow{shal.S, shal.HP, shal.count, 0u} : shal);
+      blk.parked += rg.ecount[r];
     }
-    if (!passes_done) {
+    if (!blk.passes_done) {
       // a list no pass has looked at: its shallow entries went to the shallow list and left holes behind
       const u32 before = h_small[kSmallFin + 4];
       BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 4, cnt + 4, 8, hipMemcpyDeviceToHost, st));
       BWTC_HIP_TRY(wait());
-      park_holes += h_small[kSmallFin + 4] - before;
+      blk.park_holes += h_small[kSmallFin + 4] - before;
     }
   }
   fo->hard = hard;
@@ -3560,13 +3562,13 @@ FinList BwtEngine::local_list(int home) const {
   return FinList{reinterpret_cast<u32*>(d_hardHP), reinterpret_cast<u32*>(d_hardHP) + lcap, d_LH1, d_LC1};
 }
 int BwtEngine::local_updates() {
-  if (!local_pending) return 0;
+  if (!blk.local_pending) return 0;
   hipStream_t st = stream;
-  for (u32 r = 0; r < local_upd.nreg; ++r)
-    if (local_upd.ecount[r])
-      hipLaunchKernelGGL(k_rank_updates, dim3(ceil_div(local_upd.ecount[r], 1024)), dim3(256), 0, st, (const u32*)d_US, (const u32*)d_UR,
-                         local_upd.ebase[r], local_upd.ecount[r], d_rank);
-  local_pending = false;
+  for (u32 r = 0; r < blk.local_upd.nreg; ++r)
+    if (blk.local_upd.ecount[r])
+      hipLaunchKernelGGL(k_rank_updates, dim3(ceil_div(blk.local_upd.ecount[r], 1024)), dim3(256), 0, st, (const u32*)d_US, (const u32*)d_UR,
+                         blk.local_upd.ebase[r], blk.local_upd.ecount[r], d_rank);
+  blk.local_pending = false;
   return 0;
 }
 // One doubling step of the local list.  h_global: the depth the global list's groups are sorted to (0: there is no
@@ -3575,33 +3577,33 @@ int BwtEngine::local_updates() {
 // (two of its steps and more) sits the round out.
 int BwtEngine::local_pass(u32 n, u64 h_global, RrEmit& re) {
   hipStream_t st = stream;
-  if (local_m == 0) return 0;
-  if (h_global && (u64)local_depth >= 2 * h_global) return 0;
-  const u64 delta = h_global ? std::min<u64>(h_global, local_depth) : local_depth;
-  const u64 at = local_depth, at2 = (u64)local_depth + delta;
+  if (blk.local_m == 0) return 0;
+  if (h_global && (u64)blk.local_depth >= 2 * h_global) return 0;
+  const u64 delta = h_global ? std::min<u64>(h_global, blk.local_depth) : blk.local_depth;
+  const u64 at = blk.local_depth, at2 = (u64)blk.local_depth + delta;
   if (at2 + delta > 0xFFFFFFF0ull) return -3;
   u32* cnt = d_small + kSmallFin;
   u32* ncnt = d_small + kSmallFinNext;
-  const int window = fin_window_blk, group = fin_group_blk;   // the local list's groups are as large as the finisher's passes left them
+  const int window = blk.fin_window_blk, group = blk.fin_group_blk;   // the local list's groups are as large as the finisher's passes left them
   const u32 stride = (u32)(window - group);
   BWTC_HIP_TRY(hipMemsetAsync(ncnt, 0, kFinRegions * 4, st));
   BWTC_HIP_TRY(hipMemsetAsync(cnt + 1, 0, 4, st));
   FinOut ob;
-  if (!fin_room(local_rg, stride, (u32)group, cap + cap / 128 + 65536, &ob)) return -3;   // (finisher_passes keeps such lists off this route)
+  if (!fin_room(blk.local_rg, stride, (u32)group, cap + cap / 128 + 65536, &ob)) return -3;   // (finisher_passes keeps such lists off this route)
   FinShallow none{d_parkS, d_parkHP, cnt + 4, 0u};
   FinRank rk{d_rank, (u32)at, (u32)at2, d_US, d_UR};
-  launch_finish(*this, local_list(local_home), local_rg, n, local_list(1 - local_home), ob, ncnt, d_parkS, d_parkHP,
+  launch_finish(*this, local_list(blk.local_home), blk.local_rg, n, local_list(1 - blk.local_home), ob, ncnt, d_parkS, d_parkHP,
                 d_LC1 /* never written: no group is too large */, cnt + 1, none, re, &rk);
   BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 1, cnt + 1, 4, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFinNext, ncnt, kFinRegions * 4, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(wait());
   if (h_small[kSmallFin + 1]) return -3;                  // a group above the finisher's bound in a list that has none
-  stats.finisher_entries += local_m;
-  stats.active_sum += local_m;
+  stats.finisher_entries += blk.local_m;
+  stats.active_sum += blk.local_m;
   stats.route |= 64u;
-  stats.alg_bytes += (u64)local_m * (14 * 4 / 3 + 8 + 8 + 5 + 8 + 4);
-  local_upd = local_rg;
-  local_pending = true;
+  stats.alg_bytes += (u64)blk.local_m * (14 * 4 / 3 + 8 + 8 + 5 + 8 + 4);
+  blk.local_upd = blk.local_rg;
+  blk.local_pending = true;
   FinRegions nx;
   std::memset(&nx, 0, sizeof nx);
   u32 total = 0;
@@ -3614,12 +3616,12 @@ int BwtEngine::local_pass(u32 n, u64 h_global, RrEmit& re) {
     total += c;
   }
   if (nx.nreg == 0) nx.nreg = 1;
-  if (std::getenv("BWTC_HIP_DEBUG"))
-    std::fprintf(stderr, "local pass: %u entries at depth %u (+ 2 x %llu) -> %u still tied\n", local_m, local_depth, (unsigned long long)delta, total);
-  local_rg = nx;
-  local_m = total;
-  local_home = 1 - local_home;
-  local_depth = (u32)std::min<u64>(at2 + delta, 0xFFFFFFF0ull);
+  if (debug_on())
+    std::fprintf(stderr, "local pass: %u entries at depth %u (+ 2 x %llu) -> %u still tied\n", blk.local_m, blk.local_depth, (unsigned long long)delta, total);
+  blk.local_rg = nx;
+  blk.local_m = total;
+  blk.local_home = 1 - blk.local_home;
+  blk.local_depth = (u32)std::min<u64>(at2 + delta, 0xFFFFFFF0ull);
   return 0;
 }
 
@@ -3703,22 +3705,18 @@ static hipError_t fin_test_emit_fetch(BwtEngine& e, u32 n, u32* SA, u8* out, u32
   return rc;
 }
 
-// The finisher's knobs while a hook runs: the shape from the hook's arguments, fin_max_passes at its default of eight
-// (whatever BWTC_HIP_FIN_PASSES said when the context was made), all put back when the hook returns.  What a hook
-// leaves changed besides -- parked, park_holes, passes_done, local_upd, stats -- is this block's state, which the next
-// transform resets before it reads it (suffix_sort).
+// The finisher's knobs while a hook runs: the passes' shape from the hook's arguments (block state, like everything else
+// a hook leaves changed in blk: the next transform begins with a new BlockSort), and the context's switches -- words,
+// rounds, floor, and fin_max_passes at its default of eight whatever BWTC_HIP_FIN_PASSES said when the context was
+// made -- which are put back when the hook returns.
 struct FinKnobScope {
   BwtEngine& e;
-  const int window, group, words, rounds, max_passes; const u32 floor;
+  const int words, rounds, max_passes; const u32 floor;
   FinKnobScope(BwtEngine& eng, int w, int g, int nw, int nr, u32 fl)
-      : e(eng), window(eng.fin_window_blk), group(eng.fin_group_blk), words(eng.fin_words), rounds(eng.fin_rounds),
-        max_passes(eng.fin_max_passes), floor(eng.fin_floor) {
-    e.fin_window_blk = w; e.fin_group_blk = g; e.fin_words = nw; e.fin_rounds = nr; e.fin_floor = fl; e.fin_max_passes = 8;
+      : e(eng), words(eng.fin_words), rounds(eng.fin_rounds), max_passes(eng.fin_max_passes), floor(eng.fin_floor) {
+    e.blk.fin_window_blk = w; e.blk.fin_group_blk = g; e.fin_words = nw; e.fin_rounds = nr; e.fin_floor = fl; e.fin_max_passes = 8;
   }
-  ~FinKnobScope() {
-    e.fin_window_blk = window; e.fin_group_blk = group; e.fin_words = words; e.fin_rounds = rounds; e.fin_floor = floor;
-    e.fin_max_passes = max_passes;
-  }
+  ~FinKnobScope() { e.fin_words = words; e.fin_rounds = rounds; e.fin_floor = floor; e.fin_max_passes = max_passes; }
 };
 
 int BwtEngine::test_finish_pass(FinPassTest& t) {
@@ -3730,8 +3728,9 @@ int BwtEngine::test_finish_pass(FinPassTest& t) {
   const u32 n = t.n;
   FinKnobScope knobs(*this, t.window, t.group, t.words, t.rounds, t.floor);
   // the lists' homes: the passes' own arrays, the local list's two homes in RANK mode
-  const FinList a = t.ranks ? local_list(0) : FinList{d_V0, d_G0, d_GRP, reinterpret_cast<unsigned short*>(d_C0)};
-  const FinList b = t.ranks ? local_list(1) : FinList{d_W0, d_W1, d_G1, reinterpret_cast<unsigned short*>(d_C1)};
+  FinList a, b;
+  BWTC_HIP_TRY(finisher_begin(d_V0, &a, &b));           // (and the shallow list's counter words)
+  if (t.ranks) { a = local_list(0); b = local_list(1); }
   unsigned short* hardC = t.ranks ? d_LC1 : d_hardC;
   u32* cnt = d_small + kSmallFin;
   u32* ncnt = d_small + kSmallFinNext;
@@ -3760,16 +3759,15 @@ int BwtEngine::test_finish_pass(FinPassTest& t) {
     BWTC_HIP_TRY(hipMemsetAsync(shal.S, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(shal.HP, 0xA5, (u64)m * 8, st));
     BWTC_HIP_TRY(can.put(shal.S, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(shal.HP, (u64)m * 8, st));
   }
-  h_small[kSmallFin + 1] = 0; h_small[kSmallFin + 2] = 0xFFFFFFFFu; h_small[kSmallFin + 4] = 0; h_small[kSmallFin + 5] = 0xFFFFFFFFu;
+  h_small[kSmallFin + 1] = 0; h_small[kSmallFin + 2] = 0xFFFFFFFFu;
   BWTC_HIP_TRY(hipMemcpyAsync(cnt + 1, h_small + kSmallFin + 1, 8, hipMemcpyHostToDevice, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(cnt + 4, h_small + kSmallFin + 4, 8, hipMemcpyHostToDevice, st));
   BWTC_HIP_TRY(hipMemsetAsync(ncnt, 0, (kFinRegions + 1) * 4, st));
   RrEmit re;
   BWTC_HIP_TRY(fin_test_emit_begin(*this, n, t.out_n, t.lf_n, t.lf_x, &re));
   const FinRank rk{d_rank, t.at, t.at2, d_US, d_UR};
   launch_finish(*this, a, rg, n, b, ob, ncnt, d_parkS, d_parkHP, hardC, cnt + 1, shal, re, t.ranks ? &rk : nullptr);
   if (t.ranks) {
-    local_upd = rg; local_pending = true;
+    blk.local_upd = rg; blk.local_pending = true;
     const int rcu = local_updates();
     if (rcu) return rcu;
     BWTC_HIP_TRY(hipMemcpyAsync(t.rank, d_rank, (u64)n * 4, hipMemcpyDeviceToHost, st));
@@ -3814,9 +3812,11 @@ int BwtEngine::test_finisher(bwtc_hip_fin_run& t) {
   if (room + 128u > lcap) return -1;
   hipStream_t st = stream;
   const u32 n = t.n;
+  blk = BlockSort{};                               // a block of its own
+  stats.route = 0;
   FinKnobScope knobs(*this, t.window, t.group, t.words, t.rounds, t.floor);
-  const FinList a{d_V0, d_G0, d_GRP, reinterpret_cast<unsigned short*>(d_C0)};
-  const FinList b{d_W0, d_W1, d_G1, reinterpret_cast<unsigned short*>(d_C1)};
+  FinList a, b;
+  BWTC_HIP_TRY(finisher_begin(d_V0, &a, &b));
   u32* cnt = d_small + kSmallFin;
   const FinShallow shal{d_V1, static_cast<u64*>(d_R2), cnt + 4, fin_floor};
   const FinList home = local_list(0);
@@ -3843,21 +3843,17 @@ int BwtEngine::test_finisher(bwtc_hip_fin_run& t) {
   BWTC_HIP_TRY(can.put(home.H, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(home.C, (u64)m * 2, st));
   RrEmit re;
   BWTC_HIP_TRY(fin_test_emit_begin(*this, n, t.out_n, t.lf_n, t.lf_x, &re));
-  // as suffix_sort leaves things before the passes
-  h_small[kSmallFin + 3] = 0xFFFFFFFFu; h_small[kSmallFin + 4] = 0; h_small[kSmallFin + 5] = 0xFFFFFFFFu; h_small[kSmallFin + 6] = 0xFFFFFFFFu;
-  BWTC_HIP_TRY(hipMemcpyAsync(cnt + 3, h_small + kSmallFin + 3, 16, hipMemcpyHostToDevice, st));
-  parked = 0; park_holes = 0; local_m = 0; local_pending = false; stats.route = 0;
   FinOutcome fo;
   const int rc = finisher_passes(n, m, a, b, re, shal, &fo, t.keep_local != 0, t.max_passes);
   if (rc) return rc;
   BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 3, cnt + 3, 12, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(wait());
-  if (parked > m || h_small[kSmallFin + 4] > m || fo.local > m) return -3;
+  if (blk.parked > m || h_small[kSmallFin + 4] > m || fo.local > m) return -3;
   t.outcome[0] = fo.hard; t.outcome[1] = fo.hard_depth; t.outcome[2] = fo.left; t.outcome[3] = fo.local;
-  t.info[0] = (u32)passes_done; t.info[1] = stats.route; t.info[2] = parked; t.info[3] = park_holes;
-  t.info[4] = h_small[kSmallFin + 4]; t.info[5] = h_small[kSmallFin + 5]; t.info[6] = h_small[kSmallFin + 3]; t.info[7] = fo.local ? local_depth : 0u;
-  BWTC_HIP_TRY(hipMemcpyAsync(t.pS, d_parkS, (u64)parked * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.pHP, d_parkHP, (u64)parked * 8, hipMemcpyDeviceToHost, st));
+  t.info[0] = (u32)blk.passes_done; t.info[1] = stats.route; t.info[2] = blk.parked; t.info[3] = blk.park_holes;
+  t.info[4] = h_small[kSmallFin + 4]; t.info[5] = h_small[kSmallFin + 5]; t.info[6] = h_small[kSmallFin + 3]; t.info[7] = fo.local ? blk.local_depth : 0u;
+  BWTC_HIP_TRY(hipMemcpyAsync(t.pS, d_parkS, (u64)blk.parked * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.pHP, d_parkHP, (u64)blk.parked * 8, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(hipMemcpyAsync(t.sS, shal.S, (u64)t.info[4] * 4, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(hipMemcpyAsync(t.sHP, shal.HP, (u64)t.info[4] * 8, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(hipMemcpyAsync(t.lS, home.S, (u64)fo.local * 4, hipMemcpyDeviceToHost, st));
@@ -3868,7 +3864,6 @@ int BwtEngine::test_finisher(bwtc_hip_fin_run& t) {
   BWTC_HIP_TRY(can.fetch(st));
   BWTC_HIP_TRY(wait());
   BWTC_HIP_TRY(hipGetLastError());
-  local_m = 0;                                     // (no local list is left behind for a transform to find)
   return can.verdict();
 }
 
@@ -3899,13 +3894,13 @@ void BwtEngine::complete_ranks(u32 n, const u32* list_sfx, const u32* list_slot,
   u32* pairs = static_cast<u32*>(pairs_region);
   hipLaunchKernelGGL(k_bridge_pairs_all, dim3(ceil_div(n, 1024)), dim3(256), 0, st, (const u32*)d_SA, n, pairs, pairs + cap);
   if (m) hipLaunchKernelGGL(k_bridge_pairs_fix, dim3(ceil_div(m, 256)), dim3(256), 0, st, list_sfx, list_slot, m, pairs, pairs + cap);
-  for (u32 r = 0; local_m && r < local_rg.nreg; ++r) {
-    if (!local_rg.ecount[r]) continue;
-    const FinList h = local_list(local_home);
-    FinList part{h.S + local_rg.ebase[r], h.P + local_rg.ebase[r], h.H + local_rg.ebase[r], h.C + local_rg.ebase[r]};
-    hipLaunchKernelGGL(k_bridge_pairs_fix_list, dim3(ceil_div(local_rg.ecount[r], 256)), dim3(256), 0, st, part, local_rg.ecount[r], pairs, pairs + cap);
+  for (u32 r = 0; blk.local_m && r < blk.local_rg.nreg; ++r) {
+    if (!blk.local_rg.ecount[r]) continue;
+    const FinList h = local_list(blk.local_home);
+    FinList part{h.S + blk.local_rg.ebase[r], h.P + blk.local_rg.ebase[r], h.H + blk.local_rg.ebase[r], h.C + blk.local_rg.ebase[r]};
+    hipLaunchKernelGGL(k_bridge_pairs_fix_list, dim3(ceil_div(blk.local_rg.ecount[r], 256)), dim3(256), 0, st, part, blk.local_rg.ecount[r], pairs, pairs + cap);
   }
-  if (parked) hipLaunchKernelGGL(k_bridge_pairs_fix_parked, dim3(ceil_div(parked, 256)), dim3(256), 0, st, (const u32*)d_parkS, (const u64*)d_parkHP, parked, pairs, pairs + cap);
+  if (blk.parked) hipLaunchKernelGGL(k_bridge_pairs_fix_parked, dim3(ceil_div(blk.parked, 256)), dim3(256), 0, st, (const u32*)d_parkS, (const u64*)d_parkHP, blk.parked, pairs, pairs + cap);
   scatter_rank_pairs(pairs, static_cast<u32*>(tmp_region), n, n);
 }
 
@@ -3949,20 +3944,14 @@ int BwtEngine::transform(const u8* d_src, u8* d_dst, u32 size, bool raw, u32* lf
   // Larger blocks (a round's key then needs the character's bits): suffix array + gather.
   // The transform's bytes leave from the ranking kernels (a list whose keys have no room for the carried
   // character -- more than 56 bits, only possible above 256 MiB -- reads T[s-1] for what it finishes).
-  const bool emit = !no_emit;
-  if (emit) {
-    EmitTarget em;
-    em.out = d_dst;
-    em.out_n = raw ? n : size;
-    em.n_lf = n_lf;
-    rc = suffix_sort(n, hist_T, h_small[kSmallFreqs] == 0, &em);
-    if (rc) return rc;
+  const EmitTarget em{d_dst, raw ? n : size, n_lf};
+  rc = suffix_sort(n, hist_T, h_small[kSmallFreqs] == 0, no_emit ? nullptr : &em);
+  if (rc) return rc;
+  if (!no_emit) {
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, st, d_dst, d_T, d_rank,
                        d_small + kSmallLf, n_lf, n, d_small + kSmallPidx, raw ? 1 : 0,
-                       d_small + kSmallLastChar, lf_noted ? 1 : 0);
+                       d_small + kSmallLastChar, blk.lf_noted ? 1 : 0);
   } else {
-    rc = suffix_sort(n, hist_T, h_small[kSmallFreqs] == 0, nullptr);
-    if (rc) return rc;
     hipLaunchKernelGGL(k_bwt_gather, dim3(ceil_div(ceil_div(n, 4), 256)), dim3(256), 0, st, d_SA,
                        d_T, d_out, n, d_small + kSmallPidx);
     hipLaunchKernelGGL(k_finalize, dim3(1), dim3(256), 0, st, d_out, d_T, d_rank,

@@ -40,6 +40,8 @@ struct RrEmit;
 struct RrLong;
 struct FinList;
 struct FinShallow;
+struct InitialSort;
+struct SortList;
 struct FinOutcome { u32 hard = 0, hard_depth = 0xFFFFFFFFu, left = 0, local = 0; };
 // A finisher list lives in up to kFinRegions regions of its arrays (bwt_engine.hip, k_finish)
 constexpr u32 kFinRegions = 16;
@@ -425,13 +427,32 @@ struct BwtEngine {
   // hist = byte histogram of d_T[0..n-1] (drives the width of the initial sort key).
   // em != nullptr: instead of storing the suffix array the ranking kernels write the
   // transform's bytes, out[slot] = T[SA[slot]-1] for slot < out_n, as suffixes become final
-  // (blocks for which can_carry() holds only; see k_rerank_apply).
+  // (blocks for which can_carry() holds only; see k_rerank_apply).  allow_code_keys == false: the block's second go, with gram keys.
   struct EmitTarget { u8* out; u32 out_n; u32 n_lf; };
-  int suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const EmitTarget* em = nullptr);
+  int suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const EmitTarget* em = nullptr, bool allow_code_keys = true);
+  // This block's state: suffix_sort begins a block by assigning BlockSort{} (so does test_finisher), and nothing else resets it.
+  struct StretchStep { u32 p = 0; enum When { kNone, kThisRound, kWaiting } when = kNone; u32 depth = 0; };
+  struct BlockSort {
+    u32 parked = 0;            // entries waiting in d_parkS / d_parkHP
+    u32 park_holes = 0;        //   of which empty (all ones: they sort to the list's end)
+    bool ranks_live = false;   // rank[] has been completed (every ranking step keeps it exact from then on)
+    bool fin_active = false;   // the block takes the finisher route: finished suffixes also go to d_SA
+    bool lf_noted = false;     // the LF powers were noted as suffixes became final (rank[] is not complete)
+    // the passes' shape (finisher_passes and local_pass must agree: the local list's groups are as large as the passes left them):
+    int fin_window_blk = 1024, fin_group_blk = 256;   // set by finisher_route before the passes, by FinKnobScope for a test hook
+    // the local list (deep repeats in small groups, doubled group by group beside the global list: bwt_engine.hip, local_pass)
+    u32 local_m = 0, local_depth = 0; int local_home = 0, passes_done = 0; bool local_pending = false;
+    FinRegions local_rg = {}, local_upd = {};   // where the local list lives now; where the last pass's notes lie
+    u32 lengths_period = 0;    // the period d_runK's lengths were made for (0: none yet)
+    u32 run_longest = 0; bool run_longest_known = false;   // the longest run, once a pass of period 1 has found it (made at most once per block)
+    StretchStep step;          // its period (1: the run step), when it is due (kWaiting: the first doubling round whose depth reaches p), the depth it ran at (0: it has not)
+    bool period_looked = false;   // a period has been looked for (once per block)
+    // the candidate period, its longest stretch, its votes: with the step's depth, what bwtc_hip_period_get reports until the next block begins
+    u32 period_p = 0, period_longest = 0, period_votes = 0;
+  } blk;
   // radix sort front door: picks the chained single-read passes or the classic ones
   template <typename K>
-  void sort_pairs(K* k0, K* k1, u32* v0, u32* v1, u64 n, int nbits, K** ks, u32** vs,
-                  bool probe_it, int bit_lo = 0, u64 n_holes = 0, bool plane_ready = false, bool values_descend = false);
+  void sort_pairs(K* k0, K* k1, u32* v0, u32* v1, u64 n, int nbits, K** ks, u32** vs, bool probe_it, int bit_lo = 0, u64 n_holes = 0, bool plane_ready = false, bool values_descend = false);
   // one ranking step of the suffix sorter (bwt_engine.hip)
   struct RankBuffers { void* rec_keys; void* rec_free; u32* v_keys; u32* v_free; u32* aglob; u32* aglob_next; };
   struct RankResult { u32 m, groups; u64* ks; u32* vs; void* rec_other; u32* v_other; bool finish; u32 text_chars; bool carry;
@@ -449,23 +470,28 @@ struct BwtEngine {
   int gram_count_override = 0;
   struct GramPlan { int g = 0, G = 0, b = 0; u32 top = 0; };
   int plan_grams(const KeyPlan& plan, u32 n, const u8* d_lut, GramPlan* gp);
+  // suffix_sort's stages (bwt_engine.hip): the initial sort and ranking by key plan, the rounds, the finisher route
+  int initial_keys32(const InitialSort& in, SortList& L, u64 h);
+  int initial_wide(const InitialSort& in, bool allow_code_keys, SortList& L, u64* h);
+  int initial_keys64(const InitialSort& in, const GramPlan& gp, int key_bits, u32 short_len, int split, SortList& L, u64 h);
+  int initial_long(const InitialSort& in, const GramPlan& gp, int key_bits, int split, bool coded, SortList& L, u64* h, bool* ranked);
+  int run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool keep_first, bool doubling, u32* left, u64* h_left);
+  bool step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool text_round);
+  int finisher_route(SortList& L, u32 n_lf);
+  hipError_t finisher_begin(u32* S, FinList* a, FinList* b);
   bool no_emit = false;      // BWTC_HIP_NO_EMIT: suffix array + gather even for blocks that could carry
   bool long_keys = true;     // BWTC_HIP_LONG=0: never the long-key initial sort
   int long_items_per_thread = 8;   // BWTC_HIP_LONG_E=6: tiles of 3072 items (three workgroups per CU instead of two)
   u32 gram_min_n = 1u << 22; // blocks below this keep the plain base-sigma key (BWTC_HIP_GRAM_MIN_N: tests)
-  bool code_failed = false;  // this block's code table could not be built: it is sorted again with gram keys
   bool code_keys = true;     // BWTC_HIP_KEYS=grams: the long key is made of dense gram codes (round 4) instead of the order-1 prefix code
   int code_bits = 72;        // BWTC_HIP_CODE_BITS=N (40..72): bits of a code key (the low 32 in the second word)
   u32* d_pairs = nullptr;    // code keys: sampled character-pair counts (kPairReplicas x 65536 words), and the code table (257 x 256 words)
   u32* d_codes = nullptr;
   u32* d_parkS = nullptr;    // finisher route: the hard list (suffix; head slot << 32 | slot) while the shallow list takes its rounds
   u64* d_parkHP = nullptr;
-  u32 parked = 0;            // this block: entries waiting there
-  u32 park_holes = 0;        //   of which empty (all ones: they sort to the list's end)
   u32* d_hardS = nullptr;    // finisher route: the groups too large for a window (suffix; head slot << 32 | slot; character | depth << 8), until their code round
   u64* d_hardHP = nullptr;
   unsigned short* d_hardC = nullptr;
-  bool ranks_live = false;   // this block: rank[] has been completed (every ranking step keeps it exact from then on)
   u32 fin_floor = 12;        // BWTC_HIP_FIN_FLOOR: hard groups that share fewer characters take their rounds first, on their own
   bool finisher = true;      // BWTC_HIP_FINISHER=0: after the long-key sort straight into the doubling rounds
   int fin_window = 1024;     // BWTC_HIP_FIN_WINDOW=2048: entries a finisher workgroup sorts
@@ -474,16 +500,11 @@ struct BwtEngine {
   bool fin_shape_fixed = false;  // either of the two was given: every block takes that shape
   bool fin_wide_short = true;    // BWTC_HIP_FIN_WIDE=0: a short list (the long keys left at most n / 24 suffixes tied) keeps the default shape;
                                  // else it takes windows of 2048 entries and groups of up to 1024 members, and no hard list is left for the rounds
-  int fin_window_blk = 1024;     // this block's shape (finisher_passes and local_pass must agree: the local list's groups are as large as the passes left them)
-  int fin_group_blk = 256;
   bool long_direct = true;   // BWTC_HIP_LONG_DIRECT=0: every pass of the long-key sort takes its histogram from a digit plane (else: the second word's passes read the words)
   int fin_rounds = 3;        // BWTC_HIP_FIN_ROUNDS=1..4 (with two words): rounds of fin_words words a finisher pass makes (the members a round leaves tied are compared again inside the workgroup)
   int fin_max_passes = 8;    // BWTC_HIP_FIN_PASSES: finisher passes at most before what is still tied takes the doubling rounds
   int text_rounds = 6;       // BWTC_HIP_TEXT_ROUNDS: rounds that compare the text itself before rank[] is completed for doubling
   bool text_rounds_fixed = false;
-  bool fin_active = false;   // this block takes the finisher route: finished suffixes also go to d_SA
-  bool bridged = false;      // this block: the finisher handed its rest to the doubling rounds (rank[] is complete)
-  bool lf_noted = false;     // this block: the LF powers were noted as suffixes became final (rank[] is not complete)
   void complete_ranks(u32 n, const u32* list_sfx, const u32* list_slot, u32 m, void* pairs_region, void* tmp_region);
   // finisher passes over list a (m entries, one region; b: spare list arrays): groups too large for a window go to
   // d_hardS / d_hardHP / d_hardC, shallow ones to shal, what the last pass leaves tied is appended to d_parkS / d_parkHP (`parked`)
@@ -492,10 +513,6 @@ struct BwtEngine {
   bool local_rounds = true;  // BWTC_HIP_LOCAL_ROUNDS=0: what the finisher's passes leave joins the waiting list, as in round 4
   u32* d_LP0 = nullptr; u32* d_LH0 = nullptr; u32* d_LH1 = nullptr; unsigned short* d_LC1 = nullptr;
   u32* d_US = nullptr; u32* d_UR = nullptr;          // k_finish<RANK>'s notes: suffix (or none), its new rank, by list position
-  u32 local_m = 0, local_depth = 0;
-  int local_home = 0, passes_done = 0;
-  bool local_pending = false;
-  FinRegions local_rg, local_upd;                    // where the local list lives now; where the last pass's notes lie
   struct FinList local_list(int home) const;
   int local_updates();
   int local_pass(u32 n, u64 h_global, struct RrEmit& re);
@@ -513,12 +530,6 @@ struct BwtEngine {
   u32* d_runK = nullptr;     // k_p[s]: the leading characters of suffix s that are p-periodic (p = 1: the positions from s on that hold T[s])
   u32* d_runF = nullptr; u32* d_runB = nullptr;   // the stretch-length pass's words per tile
   u32* d_votes = nullptr;    // the finder's table: votes per distance 0 ... kPeriodMax
-  u32 lengths_period = 0;    // this block: the period d_runK's lengths were made for (0: none yet)
-  u32 run_longest = 0; bool run_longest_known = false;   // this block's longest run, once a pass of period 1 has found it (made at most once per block)
-  // this block's step: its period (1: the run step), when it is due (kWaiting: the first doubling round whose depth reaches p), the depth it ran at (0: it has not)
-  struct StretchStep { u32 p = 0; enum When { kNone, kThisRound, kWaiting } when = kNone; u32 depth = 0; } step;
-  bool period_looked = false;   // this block: a period has been looked for (once per block)
-  u32 period_p = 0, period_longest = 0, period_votes = 0;   // the candidate period, its longest stretch, its votes: with the period step's depth, what bwtc_hip_period_get reports
   int stretch_lengths(u32 n, u32 p, bool store, u32* longest);   // store == false: the longest stretch alone (a trial)
   int find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask);
   int decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask);   // -> step

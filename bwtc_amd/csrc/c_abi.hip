@@ -1121,10 +1121,10 @@ int bwtc_hip_test_radix_long(bwtc_hip_ctx* ctx, uint64_t* keys, void* vals, uint
 int bwtc_hip_period_get(bwtc_hip_ctx* ctx, uint32_t* p, uint32_t* longest, uint32_t* votes, uint32_t* step_depth) {
   if (!ctx) return -1;
   const BwtEngine& e = ctx->eng;
-  if (p) *p = e.period_p;
-  if (longest) *longest = e.period_longest;
-  if (votes) *votes = e.period_votes;
-  if (step_depth) *step_depth = e.step.p >= 2 ? e.step.depth : 0;
+  if (p) *p = e.blk.period_p;
+  if (longest) *longest = e.blk.period_longest;
+  if (votes) *votes = e.blk.period_votes;
+  if (step_depth) *step_depth = e.blk.step.p >= 2 ? e.blk.step.depth : 0;
   return 0;
 }
 

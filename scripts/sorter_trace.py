@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""What the suffix sorter does with a fixed list of small blocks, on one GPU: one JSON line per case, no times.
+
+A line holds the case's name and switch set, the block's size and starting points, SHA-256 of the transformed bytes, the
+LF powers, pidx (LF[0]), stats.rounds / route / active_sum / sort_pass_items / finisher_entries / alg_bytes and what
+bwtc_hip_period_get says.  Two builds of the library whose traces are equal line for line sorted these blocks by the
+same routes, with the same launch-independent counters, to the same bytes: the check of a change to the sorter's host
+code that is meant to change nothing.
+
+The blocks come from the tests' own builders (tests/test_gpu_bwt.py, test_gpu_run_ranks.py, test_gpu_period_step.py,
+periodcases.py), at 4 MiB at most.  A switch is read when a context is made: every switch set gets a context of its
+own, one at a time.  The tool itself asserts that the cases between them set every route bit it names in WANT_BITS, and
+that a block without the long keys (route bit 0 clear) was seen on a 64-bit key plan and on the 32-bit one -- equal
+traces over cases that all took one route would say little.
+
+Usage: scripts/sorter_trace.py [--out FILE]     (BWTC_HIP_LIB=<another build's libbwtc_hip.so> traces that build)"""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+import periodcases as pc                  # noqa: E402
+import test_gpu_bwt as tb                 # noqa: E402
+import test_gpu_period_step as tp         # noqa: E402
+import test_gpu_run_ranks as tr           # noqa: E402
+from bwtc_amd import hip, synth           # noqa: E402
+
+SMALL = "BWTC_HIP_GRAM_MIN_N=64"          # as the tests do: small blocks through the gram / long-key routes (and a 64-bit key plan)
+# Route bit 7 (a finisher pass's lists would not fit) is not wanted: it takes a list of more than 8 Mi entries in a
+# context made for exactly the block (m / 64 > cap / 128 + 65536), which no block of 4 MiB has.
+# test_wide_finisher_shape_on_blocks_that_are_mostly_tied covers it at 16 MiB.
+WANT_BITS = (0, 1, 2, 3, 4, 5, 6, 8)
+# The vote count of bwtc_hip_period_get is printed as null for these: the finder counts neighbours of one group in a
+# list whose order inside a group the finisher's atomic appends decide, and on the block with the planted run of three
+# rare symbols one build's count differs from run to run by a few votes in 2900 (threshold: 256).  Nothing else does.
+VOTES_VARY = ("structured_5",)
+
+
+def switch_rows():
+    """The rows of test_sorter_feature_switches_agree, from its parametrize mark."""
+    for mark in tb.test_sorter_feature_switches_agree.pytestmark:
+        if mark.name == "parametrize":
+            return list(mark.args[1])
+    raise SystemExit("test_sorter_feature_switches_agree has lost its rows")
+
+
+def cases():
+    """(name, switch set, plan, builder, starting points); plan: "wide" / "32" where the key plan is known by
+    construction (BWTC_HIP_GRAM_MIN_N below its default forces 64-bit keys; random bytes and four letters at these sizes
+    have too much entropy in four / sixteen characters for them), else None."""
+    out = []
+    # the structured blocks, one of each shape (block 5 with the exotic run) per switch set of the test
+    for extra in tb.STRUCTURED_EXTRAS:
+        def structured(it, extra=extra):
+            rng = np.random.default_rng(1234 + len(extra))
+            for i in range(it + 1):
+                d = tb._structured_block(rng, i)[0]
+                rng.choice([1, 2, 8, 256])              # (the test draws the block's starting points here)
+            return d
+        for it in (1, 2, 3, 4, 5, 6):
+            out.append(("structured_%d" % it, ",".join(x for x in (SMALL, extra) if x), None, lambda it=it, f=structured: f(it), (1, 2, 8, 256)[it % 4]))
+    out.append(("deep_repeats", "", None, lambda: tb._deep_repeat_block(4 << 20), 8))
+    for shape in ("", "BWTC_HIP_FIN_WINDOW=2048,BWTC_HIP_FIN_GROUP=1024"):
+        for i, name in enumerate(("repeated_lines", "four_copies")):
+            out.append(("mostly_tied_" + name, shape, None, lambda i=i: tb._mostly_tied_blocks(4 << 20)[i][1], 8))
+    for extra in ("", "BWTC_HIP_LONG=0"):
+        sw = ",".join(x for x in (SMALL, extra) if x)
+        out.append(("run_2pow18", sw, "wide", lambda: tr._long_block(30, "run_2pow18"), 1))
+        out.append(("runs_200x300", sw, "wide", lambda: tr._long_block(200, "runs_200x300"), 2))
+        out.append(("period_7_stretch", sw, "wide", lambda: tp._long_block(30), 8))
+    out.append(("period_3_first_round", "", None, lambda: pc.stretch(3, 1 << 18), 8))
+    out.append(("period_257_deferred", "", None, lambda: pc.stretch(257, 1 << 18), 8))
+    out.append(("random_bytes", "", "32", lambda: np.random.default_rng(3).integers(0, 256, 300000).astype(np.uint8), 8))
+    out.append(("four_letters", "", "32", lambda: synth.gen_dna(1 << 20, 2), 8))
+    blocks = {}
+    for i, row in enumerate(switch_rows()):
+        def one(i=i):
+            if not blocks:
+                blocks["all"] = tb._switch_blocks(4 << 20)
+            return blocks["all"][i % 3]
+        out.append(("switch_row_%s" % ("text", "zeros", "repeats")[i % 3], row, None, one, 7))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    sink = open(args.out, "w") if args.out else sys.stdout
+    by_switch = {}
+    for c in cases():
+        by_switch.setdefault(c[1], []).append(c)
+    touched = set(x.split("=")[0] for sw in by_switch for x in sw.split(",") if x)
+    union, clear = 0, set()
+    for sw, group in by_switch.items():
+        for name in touched:
+            os.environ.pop(name, None)
+        for one in sw.split(","):
+            if one:
+                name, value = one.split("=")
+                os.environ[name] = value
+        built = [(c, np.ascontiguousarray(c[3](), dtype=np.uint8)) for c in group]
+        assert all(d.size <= 4 << 20 for _, d in built)
+        with hip.Context(0, max(d.size for _, d in built)) as ctx:
+            for (name, _, plan, _, sp), d in built:
+                bwt, lf, _ = ctx.bwt_block(d, sp)
+                st = ctx.stats()
+                union |= st.route
+                if not st.route & 1 and plan:
+                    clear.add(plan)
+                line = {"case": name, "switches": sw, "bytes": int(d.size), "starting_points": sp,
+                        "sha256": hashlib.sha256(bwt.tobytes()).hexdigest(), "lf": [int(x) for x in lf], "pidx": int(lf[0]),
+                        "rounds": st.rounds, "route": st.route, "active_sum": st.active_sum, "sort_pass_items": st.sort_pass_items,
+                        "finisher_entries": st.finisher_entries, "alg_bytes": st.alg_bytes, "period_get": list(ctx.period())}
+                if name in VOTES_VARY:
+                    line["period_get"][2] = None
+                sink.write(json.dumps(line) + "\n")
+                sink.flush()
+    missing = [b for b in WANT_BITS if not union >> b & 1]
+    assert not missing, "route bits never set: %s (union %#x)" % (missing, union)
+    assert clear == {"wide", "32"}, "no block without the long keys on the key plans %s" % sorted({"wide", "32"} - clear)
+    print("sorter_trace: %d cases, route bits %#x" % (sum(len(g) for g in by_switch.values()), union), file=sys.stderr)
+
+
+if __name__ == "__main__":
+    main()

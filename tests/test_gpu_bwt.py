@@ -359,6 +359,18 @@ def test_chained_sort_variant(oracle, monkeypatch):
 _SWITCH_INPUTS = []
 
 
+def _switch_blocks(size):
+    """A text block, the same with zero bytes, and the same with repeats of every length up to 200 KB (deep ties behind
+    the long keys: hard groups, text rounds, the bridge)."""
+    text = synth.gen_text(size, 21)
+    zeros = text.copy()
+    zeros[zeros == 101] = 0
+    rep = text.copy()
+    rep[size // 2:size // 2 + 200000] = rep[:200000]
+    rep[size * 5 // 6:size * 5 // 6 + 3000] = rep[1000:4000]
+    return text, zeros, rep
+
+
 @pytest.mark.parametrize("switch", ["BWTC_HIP_GRAMS=0", "BWTC_HIP_GRAMS=4", "BWTC_HIP_SPLIT_INDEX=0", "BWTC_HIP_PLANES=0",
                                     "BWTC_HIP_DENSE=0", "BWTC_HIP_NO_EMIT=1", "BWTC_HIP_WINDOW_BITS=12", "BWTC_HIP_SCAN=chained",
                                     # round 4: the long-key route's pieces, each switched off or cut short so that the
@@ -395,14 +407,7 @@ def test_sorter_feature_switches_agree(oracle, monkeypatch, switch):
         monkeypatch.setenv(name, value)
     size = 6 << 20
     if not _SWITCH_INPUTS:                                    # the inputs and the reference's answers, once for all switches
-        text = synth.gen_text(size, 21)
-        zeros = text.copy()
-        zeros[zeros == 101] = 0
-        # text with repeats of every length up to 200 KB (deep ties behind the long keys: hard groups, text rounds, the bridge)
-        rep = text.copy()
-        rep[3 << 20:(3 << 20) + 200000] = rep[:200000]
-        rep[5 << 20:(5 << 20) + 3000] = rep[1000:4000]
-        for d in (text, zeros, rep):
+        for d in _switch_blocks(size):
             _SWITCH_INPUTS.append((d, oracle.oracle_bwt_block(d, 7)))
     with hip.Context(0, size) as ctx:
         for d, b in _SWITCH_INPUTS:
@@ -455,9 +460,49 @@ def test_device_pointers_unaligned_and_aliased(hip_ctx, oracle):
         hip_ctx.dfree(out)
 
 
-@pytest.mark.parametrize("extra", ["", "BWTC_HIP_FIN_PASSES=1", "BWTC_HIP_TEXT_ROUNDS=1", "BWTC_HIP_FIN_PASSES=0,BWTC_HIP_TEXT_ROUNDS=0",
-                                   "BWTC_HIP_KEYS=grams", "BWTC_HIP_FIN_FLOOR=48", "BWTC_HIP_CODE_BITS=48", "BWTC_HIP_FIN_ROUNDS=1",
-                                   "BWTC_HIP_FIN_ROUNDS=2,BWTC_HIP_FIN_PASSES=1"])
+STRUCTURED_EXTRAS = ["", "BWTC_HIP_FIN_PASSES=1", "BWTC_HIP_TEXT_ROUNDS=1", "BWTC_HIP_FIN_PASSES=0,BWTC_HIP_TEXT_ROUNDS=0",
+                     "BWTC_HIP_KEYS=grams", "BWTC_HIP_FIN_FLOOR=48", "BWTC_HIP_CODE_BITS=48", "BWTC_HIP_FIN_ROUNDS=1",
+                     "BWTC_HIP_FIN_ROUNDS=2,BWTC_HIP_FIN_PASSES=1"]
+
+
+def _structured_block(rng, it):
+    """Block `it` of the structured blocks, from rng as it stands: (block, shape, sigma)."""
+    n = int(rng.integers(300, 400000))
+    # alphabets of a generated text (18-64 symbols) and of a real one (150-230: round 5's code keys exist for those)
+    sigma = int(rng.integers(18, 64)) if it % 4 else int(rng.integers(150, 231))
+    alphabet = rng.choice(np.arange(1 if it % 3 else 0, 256), sigma, replace=False).astype(np.uint8)
+    words = [alphabet[rng.integers(0, sigma, int(rng.integers(1, 9)))] for _ in range(int(rng.integers(5, 200)))]
+    d = np.concatenate([words[int(i)] for i in rng.integers(0, len(words), n // 3 + 8)])[:n].copy()
+    n = d.size
+    shape = it % 6
+    if it % 5 == 0 and n > 5000:
+        # an exotic but repetitive string: symbols that occur nowhere else (the code's sample gives their pairs the
+        # longest codewords: keys of one or two characters), in a run of thousands -- a hard group of little depth
+        rare = np.setdiff1d(np.arange(1, 256), alphabet)[:3].astype(np.uint8)
+        if rare.size == 3:
+            a = int(rng.integers(0, n - 4000))
+            d[a:a + 3000] = np.tile(rare, 1000)
+    if shape == 1:                                    # planted repeats of many lengths
+        for _ in range(int(rng.integers(1, 30))):
+            ln = int(min(n // 3, rng.integers(1, 1 + int(rng.choice([40, 2000, 100000])))))
+            a, b = int(rng.integers(0, n - ln)), int(rng.integers(0, n - ln))
+            d[b:b + ln] = d[a:a + ln].copy()
+    elif shape == 2:                                  # a periodic stretch: one group of thousands of members
+        p = d[:int(rng.integers(1, 30))].copy()
+        a = int(rng.integers(0, n // 2))
+        ln = int(rng.integers(2000, max(2001, n // 2)))
+        d[a:a + ln] = np.tile(p, ln // p.size + 1)[:min(ln, n - a)]
+    elif shape == 3:                                  # long runs of one symbol
+        for _ in range(int(rng.integers(1, 8))):
+            a = int(rng.integers(0, n - 1))
+            d[a:a + int(rng.integers(1, 6000))] = alphabet[0]
+    elif shape == 4:                                  # the block ends in its own beginning
+        ln = int(rng.integers(1, n // 2))
+        d[n - ln:] = d[:ln].copy()
+    return d, shape, sigma
+
+
+@pytest.mark.parametrize("extra", STRUCTURED_EXTRAS)
 def test_long_key_route_on_small_structured_blocks(oracle, monkeypatch, extra):
     """The long-key route (long keys, ranking at the long key's depth, finisher, text rounds, late rank completion)
     on blocks small enough for the oracle but of every shape: BWTC_HIP_GRAM_MIN_N lets blocks of a few thousand bytes
@@ -473,38 +518,8 @@ def test_long_key_route_on_small_structured_blocks(oracle, monkeypatch, extra):
     taken = 0
     with hip.Context(0, 1 << 20) as ctx:
         for it in range(120):
-            n = int(rng.integers(300, 400000))
-            # alphabets of a generated text (18-64 symbols) and of a real one (150-230: round 5's code keys exist for those)
-            sigma = int(rng.integers(18, 64)) if it % 4 else int(rng.integers(150, 231))
-            alphabet = rng.choice(np.arange(1 if it % 3 else 0, 256), sigma, replace=False).astype(np.uint8)
-            words = [alphabet[rng.integers(0, sigma, int(rng.integers(1, 9)))] for _ in range(int(rng.integers(5, 200)))]
-            d = np.concatenate([words[int(i)] for i in rng.integers(0, len(words), n // 3 + 8)])[:n].copy()
+            d, shape, sigma = _structured_block(rng, it)
             n = d.size
-            shape = it % 6
-            if it % 5 == 0 and n > 5000:
-                # an exotic but repetitive string: symbols that occur nowhere else (the code's sample gives their pairs the
-                # longest codewords: keys of one or two characters), in a run of thousands -- a hard group of little depth
-                rare = np.setdiff1d(np.arange(1, 256), alphabet)[:3].astype(np.uint8)
-                if rare.size == 3:
-                    a = int(rng.integers(0, n - 4000))
-                    d[a:a + 3000] = np.tile(rare, 1000)
-            if shape == 1:                                    # planted repeats of many lengths
-                for _ in range(int(rng.integers(1, 30))):
-                    ln = int(min(n // 3, rng.integers(1, 1 + int(rng.choice([40, 2000, 100000])))))
-                    a, b = int(rng.integers(0, n - ln)), int(rng.integers(0, n - ln))
-                    d[b:b + ln] = d[a:a + ln].copy()
-            elif shape == 2:                                  # a periodic stretch: one group of thousands of members
-                p = d[:int(rng.integers(1, 30))].copy()
-                a = int(rng.integers(0, n // 2))
-                ln = int(rng.integers(2000, max(2001, n // 2)))
-                d[a:a + ln] = np.tile(p, ln // p.size + 1)[:min(ln, n - a)]
-            elif shape == 3:                                  # long runs of one symbol
-                for _ in range(int(rng.integers(1, 8))):
-                    a = int(rng.integers(0, n - 1))
-                    d[a:a + int(rng.integers(1, 6000))] = alphabet[0]
-            elif shape == 4:                                  # the block ends in its own beginning
-                ln = int(rng.integers(1, n // 2))
-                d[n - ln:] = d[:ln].copy()
             sp = int(rng.choice([1, 2, 8, 256]))
             a = ctx.bwt_block(d, sp)
             taken += 1 if ctx.stats().route & 1 else 0
@@ -539,6 +554,22 @@ def test_long_keys_with_a_second_word_of_less_than_one_digit(oracle, monkeypatch
             assert (a[0] == b[0]).all() and (a[1] == b[1]).all() and (a[2] == b[2]).all(), (extra, it, n, sigma, sp)
 
 
+def _deep_repeat_block(size):
+    """The deep-repeat block in sixteenths of `size`: three of them twice more, 60 copies of a stretch (40 KB at 16 MiB)
+    and copies of a 300-byte stretch (2000 at 16 MiB), the stretches and their counts in proportion to the size."""
+    u, full = size >> 4, 16 << 20
+    d = synth.gen_text(size, 77)
+    d[5 * u:8 * u] = d[:3 * u]
+    d[11 * u:14 * u] = d[:3 * u]
+    ln, src = 40000 * size // full, 1234567 * size // full
+    for k in range(60):
+        d[9 * u + ln * k:9 * u + ln * (k + 1)] = d[src:src + ln]
+    src = 7654321 * size // full
+    for k in range(2000 * size // full):
+        d[15 * u + 300 * k:15 * u + 300 * (k + 1)] = d[src:src + 300]
+    return d
+
+
 def test_deep_repeats_take_the_local_rounds(oracle):
     """Copies of whole files: after the finisher's passes most of what is tied sits in small groups that share thousands
     of characters.  Those double group by group in LDS (k_finish<RANK>, route bit 64) beside the global list of the
@@ -547,13 +578,7 @@ def test_deep_repeats_take_the_local_rounds(oracle):
     global) -- against the reference's sorter."""
     from bwtc_amd import hip
     size = 16 << 20
-    d = synth.gen_text(size, 77)
-    d[5 << 20:8 << 20] = d[:3 << 20]
-    d[11 << 20:14 << 20] = d[:3 << 20]
-    for k in range(60):
-        d[(9 << 20) + 40000 * k:(9 << 20) + 40000 * (k + 1)] = d[1234567:1234567 + 40000]
-    for k in range(2000):
-        d[(15 << 20) + 300 * k:(15 << 20) + 300 * (k + 1)] = d[7654321:7654321 + 300]
+    d = _deep_repeat_block(size)
     want = oracle.ref_bwt_block(d, 8) if oracle.ref() is not None else oracle.oracle_bwt_block(d, 8)
     with hip.Context(0, size) as ctx:
         got = ctx.bwt_block(d, 8)
@@ -567,21 +592,25 @@ def test_deep_repeats_take_the_local_rounds(oracle):
 _TIED_INPUTS = []
 
 
+def _mostly_tied_blocks(size):
+    """Blocks whose finisher list is most of the block: (a) the lines of the real-text snapshot, each repeated
+    16 times, shuffled with a fixed seed; (b) a text of a quarter of the size copied four times."""
+    import lzma
+    with lzma.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "real_text.txt.xz")) as f:
+        lines = f.read().split(b"\n")
+    rng = np.random.default_rng(1616)
+    order = rng.permutation(np.repeat(np.arange(len(lines)), 16))
+    text = b"\n".join(lines[i] for i in order)
+    assert len(text) >= size
+    a = np.frombuffer(text[:size], np.uint8).copy()
+    b = np.tile(synth.gen_text(size // 4, 17), 4)
+    return ("repeated_lines", a), ("four_copies", b)
+
+
 def _mostly_tied_inputs(oracle, size):
-    """16 MiB blocks whose finisher list is most of the block: (a) the lines of the real-text snapshot,
-    each repeated 16 times, shuffled with a fixed seed; (b) a 4 MiB text copied four times.  With the
-    reference's sorter's answer where it was built, else the oracle's."""
+    """_mostly_tied_blocks at 16 MiB, with the reference's sorter's answer where it was built, else the oracle's."""
     if not _TIED_INPUTS:
-        import lzma
-        with lzma.open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "real_text.txt.xz")) as f:
-            lines = f.read().split(b"\n")
-        rng = np.random.default_rng(1616)
-        order = rng.permutation(np.repeat(np.arange(len(lines)), 16))
-        text = b"\n".join(lines[i] for i in order)
-        assert len(text) >= size
-        a = np.frombuffer(text[:size], np.uint8).copy()
-        b = np.tile(synth.gen_text(size // 4, 17), 4)
-        for name, d in (("repeated_lines", a), ("four_copies", b)):
+        for name, d in _mostly_tied_blocks(size):
             want = oracle.ref_bwt_block(d, 8) if oracle.ref() is not None else oracle.oracle_bwt_block(d, 8)
             _TIED_INPUTS.append((name, d, want))
     return _TIED_INPUTS
