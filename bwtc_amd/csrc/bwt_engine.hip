@@ -2088,9 +2088,9 @@ static ArenaPlan plan_arena(u64 cap) {
   a.off_table = take(radix_table_words(cap) * 4);
   a.off_partial = take(radix_partial_words(cap) * 4);
   const u64 rr_tiles = (cap + kRrTile - 1) / kRrTile + 1;
-  a.off_aggA = take(rr_tiles * 4);
-  a.off_aggB = take(rr_tiles * 4);
-  a.off_aggC = take(rr_tiles * 4);
+  a.off_aggA = take((rr_tiles + 64) * 4);   // (64 spare words each: the test hooks' canaries behind the last tile's entry)
+  a.off_aggB = take((rr_tiles + 64) * 4);
+  a.off_aggC = take((rr_tiles + 64) * 4);
   a.off_agg_part = take((rr_tiles / 4096 + 2) * 12);
   a.off_small = take(1024 * 4);
   a.off_ent = take(2u << 20);
@@ -2445,24 +2445,111 @@ void BwtEngine::sort_pairs(K* k0, K* k1, u32* v0, u32* v1, u64 n, int nbits, K**
   }
 }
 
+// The window kernels' and the rounds' key kernels' launches: rank_step's and scatter_rank_pairs', and the test hooks'
+// (BwtEngine::test_rank_scatter, test_round_keys).
+static u32 win_grid(u32 m) { return (ceil_div(m, kWinTile) + 7u) / 8u * 8u; }   // whole eighths: win_chunk deals the chunks to the XCDs
+static void launch_scatter_pairs(BwtEngine& e, const u32* where, const u32* what, u32 m, int bin_shift) {
+  hipLaunchKernelGGL(k_scatter_pairs, dim3(win_grid(m)), dim3(kWinTPB), 0, e.stream, e.d_rank, where, what, m, bin_shift);
+}
+static void launch_scatter_dense(BwtEngine& e, const u64* rec, u32 m, int bin_shift) {
+  hipLaunchKernelGGL(k_scatter_dense, dim3(win_grid(m)), dim3(kWinTPB), 0, e.stream, e.d_rank, rec, m, bin_shift);
+}
+static void launch_gather_dense(BwtEngine& e, u64* rec, u32* val, u32 m, u32 n, u32 h, int b2, int emit, int bin_shift, const RunKeys& rk) {
+  hipLaunchKernelGGL(k_gather_dense, dim3(win_grid(m)), dim3(kWinTPB), 0, e.stream, rec, val, (const u32*)e.d_rank, (const u8*)e.d_T, m, n, h,
+                     b2, emit, bin_shift, rk);
+}
+static void launch_gather_key2(BwtEngine& e, const u32* aidx, const u32* agrp, const u32* rank, const u8* achr, u64* key, u32 m, u32 n, u32 h,
+                               int b2, const RunKeys& rk) {
+  hipLaunchKernelGGL(k_gather_key2, dim3(ceil_div(m, 256 * kSimpleE)), dim3(256), 0, e.stream, aidx, agrp, rank, achr, key, m, n, h, b2, rk,
+                     (const u8*)e.d_T);
+}
+static void launch_gather_text(BwtEngine& e, const u32* aidx, const u32* agrp, const u8* achr, u64* key, u32 m, u32 n, u32 h, u32 c,
+                               const RunKeys& rk) {
+  hipLaunchKernelGGL(k_gather_text, dim3(ceil_div(m, 256)), dim3(256), 0, e.stream, aidx, agrp, (const u8*)e.d_T, achr, key, m, n, h, c, rk);
+}
+
 // rank[pairs_s[i]] = pairs_r[i] for i < m, made cache-friendly: the pairs (two arrays of
 // `cap` words inside one 8*cap-byte region) are first partitioned by the top 16 bits of the
 // destination with two stable radix passes (tmp = another 8*cap-byte region), after which
 // consecutive pairs write into the same 4096-word window of rank[].
-constexpr u32 kPairsMin = 1u << 21;
-
 void BwtEngine::scatter_rank_pairs(u32* pairs, u32* tmp, u32 m, u32 n) {
-  hipStream_t st = stream;
   const int bits = bit_width_u64(n ? n - 1 : 0);
   const int lo = bits > window_bits ? bits - window_bits : 0;
   u32 *ws = pairs, *wr = pairs + cap;
-  if (m >= kPairsMin && bits > 12) {
+  if (m >= pairs_min && bits > 12) {
     sort_pairs<u32>(pairs, tmp, pairs + cap, tmp + cap, m, bits, &ws, &wr, false, lo);
     stats.alg_bytes += sort_bytes(m, (bits - lo + kRadixBits - 1) / kRadixBits, 8, 4, digit_planes);
   }
   stats.alg_bytes += (u64)m * (8 + 4);                   // k_scatter_pairs
-  hipLaunchKernelGGL(k_scatter_pairs, dim3((ceil_div(m, kWinTile) + 7u) / 8u * 8u), dim3(kWinTPB), 0, st,
-                     d_rank, ws, wr, m, lo > 8 ? lo - 8 : 0);
+  launch_scatter_pairs(*this, ws, wr, m, lo > 8 ? lo - 8 : 0);
+}
+
+// The ranking kernels' one launch path: rank_step's, and the test hooks' (BwtEngine::test_rank_pass).  A form is what
+// rank_step decides per list: 16-bit suffix halves (split) and long items (lng) -- both only for the initial ranking of
+// 64-bit keys -- the MODE of k_rerank_apply and where a finished suffix's character comes from (RrEmit: 0 nothing is
+// emitted, 1 bits 56..63 of a round's key, 2 T[s-1], 3 the long key's code).  Long items emit with form 3 or not at all,
+// split ones with form 2 or not at all, an initial ranking never with form 1.
+// parts: kRrReduceScan -- the tile reduce and both scan phases, which leave the aggregates in d_aggA/B/C as apply reads
+// them and the two counts in d_small -- and kRrApply; rank_step reads the counts between the two to choose the MODE.
+struct RrForm { bool split, lng; int mode, emit; };
+struct RrOut { u32* rank; u32* SA; u32* aidx; u32* aglob; u32* agrp; u32* pair_s; u32* pair_r; };
+constexpr u32 kRrReduceScan = 1u, kRrApply = 2u;
+
+// both phases of the aggregates' scan over d_aggA/B/C, the parts in d_agg_part, the totals in d_small[kSmallCounts ..]
+static void launch_rerank_scan(BwtEngine& e, u32 tiles) {
+  u32* counts = e.d_small + kSmallCounts;
+  const u32 parts = ceil_div(tiles, kRrScanChunk);
+  hipLaunchKernelGGL(k_rerank_scan_tiles<0>, dim3(parts), dim3(1024), 0, e.stream, e.d_aggA, e.d_aggB, e.d_aggC, tiles, e.d_agg_part, counts);
+  hipLaunchKernelGGL(k_rerank_scan_tiles<1>, dim3(parts), dim3(1024), 0, e.stream, e.d_aggA, e.d_aggB, e.d_aggC, tiles, e.d_agg_part, counts);
+}
+template <typename K, bool INIT, bool SP, bool LG>
+static void launch_rerank_reduce(BwtEngine& e, u32 tiles, const K* ks, const u32* vs, u32 m, u32 n, u32 short_len, K kmask, const RrLong& lg) {
+  hipLaunchKernelGGL((k_rerank_reduce<K, INIT, SP, LG>), dim3(tiles), dim3(kRrTPB), 0, e.stream, ks, vs, m, n, short_len, kmask,
+                     e.d_aggA, e.d_aggB, e.d_aggC, lg);
+}
+template <typename K, bool INIT, int MODE, int EMIT, bool SP, bool LG>
+static void launch_rerank_apply(BwtEngine& e, u32 tiles, const K* ks, const u32* vs, const u32* aglob, u32 m, u32 n, u32 short_len, K kmask,
+                                const RrLong& lg, const RrOut& o, const RrEmit& re) {
+  hipLaunchKernelGGL((k_rerank_apply<K, INIT, MODE, EMIT, SP, LG>), dim3(tiles), dim3(kRrTPB), 0, e.stream, ks, vs, aglob, m, n, short_len,
+                     kmask, e.d_aggA, e.d_aggB, e.d_aggC, o.rank, o.SA, o.aidx, o.aglob, o.agrp, o.pair_s, o.pair_r, re, lg);
+}
+template <typename K, bool INIT, int MODE>
+static void launch_rerank_mode(BwtEngine& e, u32 tiles, const RrForm& f, const K* ks, const u32* vs, const u32* aglob, u32 m, u32 n,
+                               u32 short_len, K kmask, const RrLong& lg, const RrOut& o, const RrEmit& re) {
+  constexpr bool kCanSplit = INIT && sizeof(K) == 8;
+  if (f.lng && f.split) {
+    if (f.emit) launch_rerank_apply<K, INIT, MODE, 3, kCanSplit, kCanSplit>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+    else launch_rerank_apply<K, INIT, MODE, 0, kCanSplit, kCanSplit>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+  } else if (f.lng) {
+    if (f.emit) launch_rerank_apply<K, INIT, MODE, 3, false, kCanSplit>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+    else launch_rerank_apply<K, INIT, MODE, 0, false, kCanSplit>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+  } else if (f.split) {
+    if (f.emit) launch_rerank_apply<K, INIT, MODE, 2, kCanSplit, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+    else launch_rerank_apply<K, INIT, MODE, 0, kCanSplit, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+  } else if (!f.emit) launch_rerank_apply<K, INIT, MODE, 0, false, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+  else if (INIT || f.emit == 2) launch_rerank_apply<K, INIT, MODE, 2, false, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+  else launch_rerank_apply<K, INIT, MODE, 1, false, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+}
+template <typename K, bool INIT>
+static void launch_rerank(BwtEngine& e, u32 parts, const RrForm& f, const K* ks, const u32* vs, const u32* aglob, u32 m, u32 n, u32 short_len,
+                          K kmask, const RrLong& lg, const RrOut& o, const RrEmit& re) {
+  constexpr bool kCanSplit = INIT && sizeof(K) == 8;
+  const u32 tiles = ceil_div(m, kRrTile);
+  if (parts & kRrReduceScan) {
+    if (f.lng && f.split) launch_rerank_reduce<K, INIT, kCanSplit, kCanSplit>(e, tiles, ks, vs, m, n, short_len, kmask, lg);
+    else if (f.lng) launch_rerank_reduce<K, INIT, false, kCanSplit>(e, tiles, ks, vs, m, n, short_len, kmask, lg);
+    else if (f.split) launch_rerank_reduce<K, INIT, kCanSplit, false>(e, tiles, ks, vs, m, n, short_len, kmask, lg);
+    else launch_rerank_reduce<K, INIT, false, false>(e, tiles, ks, vs, m, n, short_len, kmask, lg);
+    launch_rerank_scan(e, tiles);
+  }
+  if (parts & kRrApply) {
+    switch (f.mode) {
+      case 0: launch_rerank_mode<K, INIT, 0>(e, tiles, f, ks, vs, aglob, m, n, short_len, kmask, lg, o, re); break;
+      case 1: launch_rerank_mode<K, INIT, 1>(e, tiles, f, ks, vs, aglob, m, n, short_len, kmask, lg, o, re); break;
+      case 2: launch_rerank_mode<K, INIT, 2>(e, tiles, f, ks, vs, aglob, m, n, short_len, kmask, lg, o, re); break;
+      default: launch_rerank_mode<K, INIT, 3>(e, tiles, f, ks, vs, aglob, m, n, short_len, kmask, lg, o, re); break;
+    }
+  }
 }
 
 // One ranking step over a sorted list (INIT: all suffixes by their initial key; rounds: the
@@ -2475,24 +2562,12 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
                          RankBuffers& rb, RrEmit re, bool emit, u64 h_next, RankResult* res, u32 split,
                          const RrLong* lg, bool text, bool carry_in, bool raw_out, int run_mode) {
   hipStream_t st = stream;
-  u32* counts = d_small + kSmallCounts;
-  const u32 tiles = ceil_div(m, kRrTile);
+  const u32* counts = d_small + kSmallCounts;
   constexpr bool kCanSplit = INIT && sizeof(K) == 8;
   const bool lng = kCanSplit && lg && lg->w;              // items of the long-key sort (split: 16-bit values + upper bits in the key)
   const RrLong lgv = lng ? *lg : RrLong();
-  if (lng && split) hipLaunchKernelGGL((k_rerank_reduce<K, INIT, kCanSplit, kCanSplit>), dim3(tiles), dim3(kRrTPB), 0, st, ks, vs, m, n,
-                              short_len, kmask, d_aggA, d_aggB, d_aggC, lgv);
-  else if (lng) hipLaunchKernelGGL((k_rerank_reduce<K, INIT, false, kCanSplit>), dim3(tiles), dim3(kRrTPB), 0, st, ks, vs, m, n,
-                              short_len, kmask, d_aggA, d_aggB, d_aggC, lgv);
-  else if (split) hipLaunchKernelGGL((k_rerank_reduce<K, INIT, kCanSplit>), dim3(tiles), dim3(kRrTPB), 0, st, ks, vs, m, n,
-                                short_len, kmask, d_aggA, d_aggB, d_aggC, lgv);
-  else hipLaunchKernelGGL((k_rerank_reduce<K, INIT, false>), dim3(tiles), dim3(kRrTPB), 0, st, ks, vs, m, n,
-                          short_len, kmask, d_aggA, d_aggB, d_aggC, lgv);
-  {
-    const u32 parts = ceil_div(tiles, kRrScanChunk);
-    hipLaunchKernelGGL(k_rerank_scan_tiles<0>, dim3(parts), dim3(1024), 0, st, d_aggA, d_aggB, d_aggC, tiles, d_agg_part, counts);
-    hipLaunchKernelGGL(k_rerank_scan_tiles<1>, dim3(parts), dim3(1024), 0, st, d_aggA, d_aggB, d_aggC, tiles, d_agg_part, counts);
-  }
+  const RrForm form{split != 0, lng, 0, 0};
+  launch_rerank<K, INIT>(*this, kRrReduceScan, form, ks, vs, (const u32*)nullptr, m, n, short_len, kmask, lgv, RrOut{}, re);
   // how much stays active decides the route, so the counts are read before the apply kernel
   BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallCounts, counts, 12, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(wait());
@@ -2520,7 +2595,7 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
   const RunKeys rkeys{d_runK, run_now ? 0u : blk.step.depth, run_now ? 1 : (run_mode == 2 ? 2 : 0), blk.step.p};
   const bool carry_next = emit && kbits <= 56;
   res->carry = carry_next;
-  const bool dense = !text && dense_route && m_next > 0 && (u64)m_next * 2 >= m && m >= kPairsMin && !use_sweep;
+  const bool dense = !text && dense_route && m_next > 0 && (u64)m_next * 2 >= m && m >= pairs_min && !use_sweep;
   u32* sa_out = (emit && !blk.fin_active) ? nullptr : d_SA;   // finisher route: the bridge will want the finished suffixes' slots
   u32* rank_arg = (text && !blk.ranks_live) ? nullptr : d_rank;   // text rounds before rank[] is completed: neither complete nor needed; after: kept exact
   // Long items of which at most half is still tied (a 256 MiB text block: 21 %, a 1 GiB one: 37 %): the finisher
@@ -2532,36 +2607,23 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
   if (res->finish) {
     sa_out = d_SA;
     blk.fin_active = true;
-    if constexpr (kCanSplit) {
-      if (split)
-        hipLaunchKernelGGL((k_rerank_apply<K, INIT, 3, 3, true, true>), dim3(tiles), dim3(kRrTPB), 0, st, ks, vs,
-                           (const u32*)rb.aglob, m, n, short_len, kmask, d_aggA, d_aggB, d_aggC, d_rank, sa_out,
-                           rb.v_free, rb.aglob_next, d_GRP, (u32*)nullptr, (u32*)nullptr, re, lgv);
-      else
-        hipLaunchKernelGGL((k_rerank_apply<K, INIT, 3, 3, false, true>), dim3(tiles), dim3(kRrTPB), 0, st, ks, vs,
-                           (const u32*)rb.aglob, m, n, short_len, kmask, d_aggA, d_aggB, d_aggC, d_rank, sa_out,
-                           rb.v_free, rb.aglob_next, d_GRP, (u32*)nullptr, (u32*)nullptr, re, lgv);
-    }
+    if constexpr (kCanSplit)
+      launch_rerank<K, INIT>(*this, kRrApply, RrForm{split != 0, true, 3, 3}, ks, vs, (const u32*)rb.aglob, m, n, short_len, kmask, lgv,
+                             RrOut{d_rank, sa_out, rb.v_free, rb.aglob_next, d_GRP, nullptr, nullptr}, re);
     res->carry = true;
     return 0;
   }
   u64* recA = static_cast<u64*>(rb.rec_free);
   u64* recB = static_cast<u64*>(rb.rec_keys);
 
-#define BWTC_APPLY_S(MODE, EMIT, SP, LG, PS, PR, AIDX)                                                      \
-  hipLaunchKernelGGL((k_rerank_apply<K, INIT, MODE, EMIT, SP, LG>), dim3(tiles), dim3(kRrTPB), 0, st, ks, vs, \
-                     (const u32*)rb.aglob, m, n, short_len, kmask, d_aggA, d_aggB, d_aggC, rank_arg, sa_out, \
-                     AIDX, rb.aglob_next, d_GRP, PS, PR, re, lgv)
   // Where a finished suffix's character comes from (see RrEmit): long items carry its code in the key (3); the
   // initial ranking of other items, and rounds whose keys had no room for it, read T[s-1] (2); rounds find it in
   // bits 56..63 of their key (1); 0: nothing is emitted.
-#define BWTC_APPLY(MODE, PS, PR, AIDX)                                                                    \
-  do { if (lng && split) { if (emit) BWTC_APPLY_S(MODE, 3, kCanSplit, kCanSplit, PS, PR, AIDX); else BWTC_APPLY_S(MODE, 0, kCanSplit, kCanSplit, PS, PR, AIDX); } \
-       else if (lng) { if (emit) BWTC_APPLY_S(MODE, 3, false, kCanSplit, PS, PR, AIDX); else BWTC_APPLY_S(MODE, 0, false, kCanSplit, PS, PR, AIDX); } \
-       else if (split) { if (emit) BWTC_APPLY_S(MODE, 2, kCanSplit, false, PS, PR, AIDX); else BWTC_APPLY_S(MODE, 0, kCanSplit, false, PS, PR, AIDX); } \
-       else if (!emit) BWTC_APPLY_S(MODE, 0, false, false, PS, PR, AIDX);                                 \
-       else if (INIT || !carry_in) BWTC_APPLY_S(MODE, 2, false, false, PS, PR, AIDX);                     \
-       else BWTC_APPLY_S(MODE, 1, false, false, PS, PR, AIDX); } while (0)
+  const int emit_form = !emit ? 0 : lng ? 3 : (split || INIT || !carry_in) ? 2 : 1;
+  auto apply = [&](int mode, u32* ps, u32* pr, u32* aidx) {
+    launch_rerank<K, INIT>(*this, kRrApply, RrForm{split != 0, lng, mode, emit_form}, ks, vs, (const u32*)rb.aglob, m, n, short_len, kmask, lgv,
+                           RrOut{rank_arg, sa_out, aidx, rb.aglob_next, d_GRP, ps, pr}, re);
+  };
   if (dense) {
     u32* tri_key = reinterpret_cast<u32*>(recA);
     // records partitioned by the top 16 bits of s (bits 32.. of the record), two stable passes
@@ -2569,17 +2631,14 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
     const int lo = bits > window_bits ? bits - window_bits : 0;
     re.rec_plane = digit_planes ? d_P0 : nullptr;
     re.rec_shift = lo;
-    BWTC_APPLY(2, tri_key, rb.v_free, (u32*)nullptr);
+    apply(2, tri_key, rb.v_free, nullptr);
     u64* ws = nullptr; u32* wv = nullptr;
     sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m, 32 + bits, &ws, &wv, false, 32 + lo, 0, true);
     u64* ws_other = ws == recA ? recB : recA;
     u32* wv_other = wv == rb.v_free ? rb.v_keys : rb.v_free;
-    const u32 grid = (ceil_div(m, kWinTile) + 7u) / 8u * 8u;
     const int bin_shift = lo > 8 ? lo - 8 : 0;           // the eight bits of s below the window bits
-    hipLaunchKernelGGL(k_scatter_dense, dim3(grid), dim3(kWinTPB), 0, st, d_rank, (const u64*)ws, m, bin_shift);
-    hipLaunchKernelGGL(k_gather_dense, dim3(grid), dim3(kWinTPB), 0, st, ws, wv, (const u32*)d_rank,
-                       (const u8*)d_T, m, n, (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k,
-                       carry_next ? 1 : 0, bin_shift, rkeys);
+    launch_scatter_dense(*this, (const u64*)ws, m, bin_shift);
+    launch_gather_dense(*this, ws, wv, m, n, (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k, carry_next ? 1 : 0, bin_shift, rkeys);
     const bool timed = n_sort_events + 2 <= kMaxSortEvents;
     if (timed) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
     sort_pairs<u64>(ws, ws_other, wv, wv_other, m_next, kbits, &res->ks, &res->vs, true, 0, (u64)(m - m_next));
@@ -2600,23 +2659,21 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
   u32* pairs = reinterpret_cast<u32*>(recA);
   if (raw_out) {
     // the list goes back to its owner as it is now grouped: suffix, slot, head slot (rb.v_free, rb.aglob_next, d_GRP)
-    BWTC_APPLY(3, (u32*)nullptr, (u32*)nullptr, rb.v_free);
+    apply(3, nullptr, nullptr, rb.v_free);
     res->carry = emit;
     return 0;
   }
   if (text) {
     // text round: rank[] is neither complete nor needed
     res->text_chars = (u32)std::min(6, (56 - b1 - 4) / 8);
-    BWTC_APPLY(0, (u32*)nullptr, (u32*)nullptr, rb.v_free);
+    apply(0, nullptr, nullptr, rb.v_free);
     res->carry = emit;
     if (m_next == 0) return 0;
     if (run_now) {
       // the run step before rank[] is complete: the members without a long run keep their groups (key 0)
       res->carry = carry_next;
-      hipLaunchKernelGGL(k_gather_key2, dim3(ceil_div(m_next, 256 * kSimpleE)), dim3(256), 0, st,
-                         (const u32*)rb.v_free, (const u32*)d_GRP, (const u32*)nullptr,
-                         carry_next ? (const u8*)re.achr_out : (const u8*)nullptr, recA, m_next, n,
-                         (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k, rkeys, (const u8*)d_T);
+      launch_gather_key2(*this, (const u32*)rb.v_free, (const u32*)d_GRP, (const u32*)nullptr, carry_next ? (const u8*)re.achr_out : (const u8*)nullptr,
+                         recA, m_next, n, (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k, rkeys);
       sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m_next, kbits, &res->ks, &res->vs, false);
       stats.sort_pass_items += (u64)m_next * (u64)((kbits + kRadixBits - 1) / kRadixBits);
       stats.alg_bytes += (u64)m_next * (4 + 4 + 4 + 1 + 1 + 8) + sort_bytes(m_next, (kbits + kRadixBits - 1) / kRadixBits, 12, 8, digit_planes);
@@ -2626,8 +2683,8 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
       return 0;
     }
     const int tbits = b1 + 8 * (int)res->text_chars + 4;
-    hipLaunchKernelGGL(k_gather_text, dim3(ceil_div(m_next, 256)), dim3(256), 0, st, (const u32*)rb.v_free, (const u32*)d_GRP,
-                       (const u8*)d_T, emit ? (const u8*)re.achr_out : (const u8*)nullptr, recA, m_next, n, (u32)h_next, res->text_chars, rkeys);
+    launch_gather_text(*this, (const u32*)rb.v_free, (const u32*)d_GRP, emit ? (const u8*)re.achr_out : (const u8*)nullptr, recA, m_next, n,
+                       (u32)h_next, res->text_chars, rkeys);
     sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m_next, tbits, &res->ks, &res->vs, false);
     stats.sort_pass_items += (u64)m_next * (u64)((tbits + kRadixBits - 1) / kRadixBits);
     stats.alg_bytes += (u64)m_next * (4 + 4 + 1 + 16 + 8 + (rkeys.mode ? 4 : 0)) + sort_bytes(m_next, (tbits + kRadixBits - 1) / kRadixBits, 12, 8, digit_planes);
@@ -2636,19 +2693,15 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
     res->v_other = res->vs == rb.v_free ? rb.v_keys : rb.v_free;
     return 0;
   }
-  if (m >= kPairsMin || INIT) {
-    BWTC_APPLY(1, pairs, pairs + cap, rb.v_free);
+  if (m >= pairs_min || INIT) {
+    apply(1, pairs, pairs + cap, rb.v_free);
     scatter_rank_pairs(pairs, reinterpret_cast<u32*>(recB), m, n);
   } else {
-    BWTC_APPLY(0, (u32*)nullptr, (u32*)nullptr, rb.v_free);
+    apply(0, nullptr, nullptr, rb.v_free);
   }
-#undef BWTC_APPLY
-#undef BWTC_APPLY_S
   if (m_next == 0) return 0;
-  hipLaunchKernelGGL(k_gather_key2, dim3(ceil_div(m_next, 256 * kSimpleE)), dim3(256), 0, st,
-                     (const u32*)rb.v_free, (const u32*)d_GRP, (const u32*)d_rank,
-                     carry_next ? (const u8*)re.achr_out : (const u8*)nullptr, recA, m_next, n,
-                     (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k, rkeys, (const u8*)d_T);
+  launch_gather_key2(*this, (const u32*)rb.v_free, (const u32*)d_GRP, (const u32*)d_rank, carry_next ? (const u8*)re.achr_out : (const u8*)nullptr,
+                     recA, m_next, n, (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k, rkeys);
   const bool timed = n_sort_events + 2 <= kMaxSortEvents;
   if (timed) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
   sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m_next, kbits, &res->ks, &res->vs, true);
@@ -3977,6 +4030,299 @@ int BwtEngine::transform(const u8* d_src, u8* d_dst, u32 size, bool raw, u32* lf
     stats.ms_sort += ms;
   }
   return 0;
+}
+
+// ---- test hooks: the ranking step and the rounds' kernels ("The ranking hooks") -----------------------
+// What the ranking kernels assume of their list, checked on the host.  Of these only m <= n, the suffixes and slots below n
+// and m == n with INIT keep the stores inside their arrays; the others (distinct suffixes, ascending slots, the forms
+// rank_step pairs, the long items' fields) are what an honest list satisfies and what the model is defined for.
+static bool rank_test_pass_ok(const bwtc_hip_rank_pass& t, u64 cap) {
+  const u32 m = t.m, n = t.n;
+  if (m < 1u || m > n || (u64)n + TestCanaries::kBytes > cap) return false;
+  if (!t.keys || !t.idx) return false;
+  if (t.key_bytes != 4 && t.key_bytes != 8) return false;
+  if (t.init ? m != n : t.key_bytes != 8) return false;
+  if ((t.split || t.lng) && !(t.init && t.key_bytes == 8)) return false;
+  if (t.mode < 0 || t.mode > 3 || t.emit < 0 || t.emit > 3) return false;
+  if (t.lng ? (t.emit != 0 && t.emit != 3) : t.split ? (t.emit != 0 && t.emit != 2) : t.init ? (t.emit != 0 && t.emit != 2) : t.emit == 3) return false;
+  if (t.split && n > (1u << 29)) return false;
+  if (t.lng) {
+    if (!t.w || t.wmask == 0u || t.hi_shift < 0 || t.chr_shift < 0 || t.chr_shift > 63 || t.chr_mask > 255u) return false;
+    if (t.hi_shift > (t.split ? 51 : 63) || t.lvl_shift < -1 || t.lvl_shift > 61 || t.depth >= (1u << 24)) return false;
+  }
+  if (t.emit == 3 && !t.inv_lut) return false;
+  if (t.out_n != n && t.out_n + 1u != n) return false;
+  if (t.lf_n > 256u || (t.lf_n > 1u && (t.lf_x != n / t.lf_n || t.lf_x < 1u))) return false;
+  if (t.rec_shift < 0 || t.rec_shift > 31) return false;
+  std::vector<u8> seen(n, 0);
+  for (u32 p = 0; p < m; ++p) {
+    u32 s;
+    if (t.split) {
+      const u64 k = static_cast<const u64*>(t.keys)[p];
+      const u32 hi = t.lng ? ((u32)(k >> t.hi_shift) & 0x1FFFu) : (u32)(k >> 48);
+      if (hi >= (1u << 13)) return false;
+      s = (hi << 16) | static_cast<const unsigned short*>(t.idx)[p];
+    } else s = static_cast<const u32*>(t.idx)[p];
+    if (s >= n || seen[s]) return false;
+    seen[s] = 1;
+  }
+  if (!t.init) {
+    if (!t.aglob) return false;
+    for (u32 p = 0; p < m; ++p) if (t.aglob[p] >= n || (p > 0 && t.aglob[p] <= t.aglob[p - 1])) return false;
+  }
+  return true;
+}
+
+int BwtEngine::test_rank_pass(bwtc_hip_rank_pass& t) {
+  if (!rank_test_pass_ok(t, cap)) return -1;
+  hipStream_t st = stream;
+  const u32 m = t.m, n = t.n, tiles = ceil_div(m, kRrTile);
+  const bool wide = t.key_bytes == 8, mode3 = t.mode == 3;
+  // the list where suffix_sort's stages leave it (keys in R1, values in V0, second words in W0, slots in G0); what apply
+  // writes where rank_step points it: the next list in V1 / G1 / GRP / C0, pairs or records in R2, the records' values in
+  // the free value array, their plane in P0
+  u32* pairs = static_cast<u32*>(d_R2);
+  u32* pair_s = t.mode == 1 || t.mode == 2 ? pairs : nullptr;
+  u32* pair_r = t.mode == 1 ? pairs + cap : t.mode == 2 ? d_V1 : nullptr;
+  const u64 idx_bytes = t.split ? ((u64)m * 2 + 3) / 4 * 4 : (u64)m * 4;
+  const u64 achr_bytes = mode3 ? (u64)m * 2 : (u64)m;
+  TestCanaries can;
+  BWTC_HIP_TRY(hipMemcpyAsync(d_R1, t.keys, (u64)m * (wide ? 8 : 4), hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemsetAsync(d_V0, 0, idx_bytes, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(d_V0, t.idx, (u64)m * (t.split ? 2 : 4), hipMemcpyHostToDevice, st));
+  if (t.lng) BWTC_HIP_TRY(hipMemcpyAsync(d_W0, t.w, (u64)m * 4, hipMemcpyHostToDevice, st));
+  if (!t.init) BWTC_HIP_TRY(hipMemcpyAsync(d_G0, t.aglob, (u64)m * 4, hipMemcpyHostToDevice, st));
+  if (t.emit == 3) BWTC_HIP_TRY(hipMemcpyAsync(d_small + kSmallInv, t.inv_lut, 256, hipMemcpyHostToDevice, st));
+  u32* const out4[] = {d_V1, d_G1, d_GRP};
+  for (u32* a : out4) { BWTC_HIP_TRY(hipMemsetAsync(a, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(a, (u64)m * 4, st)); }
+  BWTC_HIP_TRY(hipMemsetAsync(d_C0, 0xA5, (u64)m * 2, st)); BWTC_HIP_TRY(can.put(d_C0, achr_bytes, st));
+  BWTC_HIP_TRY(hipMemsetAsync(pairs, 0xA5, (u64)m * 8, st)); BWTC_HIP_TRY(can.put(pairs, (u64)m * (t.mode == 2 ? 8 : 4), st));
+  BWTC_HIP_TRY(hipMemsetAsync(pairs + cap, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(pairs + cap, (u64)m * 4, st));
+  BWTC_HIP_TRY(hipMemsetAsync(d_P0, 0xA5, m, st)); BWTC_HIP_TRY(can.put(d_P0, m, st));
+  BWTC_HIP_TRY(hipMemsetAsync(d_rank, 0xA5, (u64)n * 4, st)); BWTC_HIP_TRY(can.put(d_rank, (u64)n * 4, st));
+  u32* const agg[] = {d_aggA, d_aggB, d_aggC};
+  for (u32* a : agg) { BWTC_HIP_TRY(hipMemsetAsync(a, 0xA5, (u64)tiles * 4, st)); BWTC_HIP_TRY(can.put(a, (u64)tiles * 4, st)); }
+  BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallCounts, 0xA5, 8, st));
+  RrEmit re;
+  BWTC_HIP_TRY(fin_test_emit_begin(*this, n, t.out_n, t.lf_n, t.lf_x, &re));
+  BWTC_HIP_TRY(can.put(d_SA, (u64)n * 4, st)); BWTC_HIP_TRY(can.put(d_out, n, st));
+  re.achr_out = d_C0;
+  re.inv_lut = reinterpret_cast<const u8*>(d_small + kSmallInv);
+  re.rec_plane = t.mode == 2 && t.plane ? d_P0 : nullptr;
+  re.rec_shift = t.rec_shift;
+  const RrLong lg = t.lng ? RrLong{d_W0, t.wmask, t.hi_shift, t.chr_shift, t.chr_mask, t.lvl_shift, t.depth} : RrLong();
+  const RrForm form{t.split != 0, t.lng != 0, t.mode, t.emit};
+  const RrOut o{d_rank, d_SA, t.mode == 2 ? nullptr : d_V1, d_G1, d_GRP, pair_s, pair_r};
+  const u32* aglob = t.init ? nullptr : d_G0;
+  if (!wide) launch_rerank<u32, true>(*this, kRrReduceScan | kRrApply, form, static_cast<const u32*>(d_R1), d_V0, aglob, m, n, t.short_len, (u32)t.kmask, lg, o, re);
+  else if (t.init) launch_rerank<u64, true>(*this, kRrReduceScan | kRrApply, form, static_cast<const u64*>(d_R1), d_V0, aglob, m, n, t.short_len, (u64)t.kmask, lg, o, re);
+  else launch_rerank<u64, false>(*this, kRrReduceScan | kRrApply, form, static_cast<const u64*>(d_R1), d_V0, aglob, m, n, t.short_len, (u64)t.kmask, lg, o, re);
+  BWTC_HIP_TRY(hipMemcpyAsync(t.aggA, d_aggA, (u64)tiles * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.aggB, d_aggB, (u64)tiles * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.aggC, d_aggC, (u64)tiles * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.counts, d_small + kSmallCounts, 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.rank, d_rank, (u64)n * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.pair_s, pairs, (u64)m * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.pair_r, pairs + cap, (u64)m * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.rec, pairs, (u64)m * 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.val, d_V1, (u64)m * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.rplane, d_P0, m, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.aidx, d_V1, (u64)m * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.aglob_out, d_G1, (u64)m * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.agrp, d_GRP, (u64)m * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.achr, d_C0, (u64)m * 2, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(fin_test_emit_fetch(*this, n, t.SA, t.out, t.small, t.lf));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return can.verdict();
+}
+
+int BwtEngine::test_rank_scan(u32* a, u32* b, u32* c, u32 ntiles, u32* parts_out, u32 parts_cap, u32* counts_out) {
+  const u64 rr_tiles = (cap + kRrTile - 1) / kRrTile + 1;                 // what init reserved (plan_arena)
+  const u64 part_words = (rr_tiles / 4096 + 2) * 3;
+  if (ntiles < 1u || (u64)ntiles > rr_tiles || parts_cap > part_words) return -1;   // (the canaries lie in the arrays' 64 spare words)
+  if ((u64)ceil_div(ntiles, kRrScanChunk) * 3 > part_words) return -1;
+  hipStream_t st = stream;
+  TestCanaries can;
+  u32* const dev[] = {d_aggA, d_aggB, d_aggC};
+  u32* const host[] = {a, b, c};
+  for (int i = 0; i < 3; ++i) {
+    BWTC_HIP_TRY(hipMemcpyAsync(dev[i], host[i], (u64)ntiles * 4, hipMemcpyHostToDevice, st));
+    BWTC_HIP_TRY(can.put(dev[i], (u64)ntiles * 4, st));
+  }
+  BWTC_HIP_TRY(hipMemsetAsync(d_agg_part, 0xA5, part_words * 4, st));     // (d_small lies behind it: no room for a canary, the poison is returned)
+  BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallCounts, 0xA5, 8, st));
+  launch_rerank_scan(*this, ntiles);
+  for (int i = 0; i < 3; ++i) BWTC_HIP_TRY(hipMemcpyAsync(host[i], dev[i], (u64)ntiles * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(parts_out, d_agg_part, (u64)parts_cap * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(counts_out, d_small + kSmallCounts, 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return can.verdict();
+}
+
+int BwtEngine::test_rank_scatter(bool dense, const u32* where, const u32* what, const u64* rec, u32 m, u32 n, int bin_shift, u32* rank) {
+  if (m < 1u || m > n || (u64)n + TestCanaries::kBytes > cap || bin_shift < 0 || bin_shift > 24 || !rank) return -1;
+  if (dense ? !rec : (!where || !what)) return -1;
+  {
+    std::vector<u8> seen(n, 0);
+    for (u32 i = 0; i < m; ++i) {
+      const u32 s = dense ? (u32)(rec[i] >> 32) : where[i];
+      if (s >= n || seen[s]) return -1;
+      seen[s] = 1;
+    }
+  }
+  hipStream_t st = stream;
+  u32* pairs = static_cast<u32*>(d_R2);                  // where rank_step keeps its pairs and records
+  TestCanaries can;
+  if (dense) BWTC_HIP_TRY(hipMemcpyAsync(pairs, rec, (u64)m * 8, hipMemcpyHostToDevice, st));
+  else {
+    BWTC_HIP_TRY(hipMemcpyAsync(pairs, where, (u64)m * 4, hipMemcpyHostToDevice, st));
+    BWTC_HIP_TRY(hipMemcpyAsync(pairs + cap, what, (u64)m * 4, hipMemcpyHostToDevice, st));
+  }
+  BWTC_HIP_TRY(hipMemcpyAsync(d_rank, rank, (u64)n * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(can.put(d_rank, (u64)n * 4, st));
+  if (dense) launch_scatter_dense(*this, static_cast<const u64*>(d_R2), m, bin_shift);
+  else launch_scatter_pairs(*this, pairs, pairs + cap, m, bin_shift);
+  BWTC_HIP_TRY(hipMemcpyAsync(rank, d_rank, (u64)n * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return can.verdict();
+}
+
+int BwtEngine::test_round_keys(bwtc_hip_round_keys& t) {
+  const u32 m = t.m, n = t.n;
+  if (m < 1u || m > n || (u64)n + TestCanaries::kBytes > cap || t.kind < 0 || t.kind > 2 || !t.keys) return -1;
+  if (t.run_mode < 0 || t.run_mode > 2) return -1;
+  const bool dense = t.kind == 2, text = t.kind == 1;
+  if (dense ? (!t.rec || !t.val || !t.rank || t.bin_shift < 0 || t.bin_shift > 24) : (!t.aidx || !t.agrp)) return -1;
+  if (text && t.rank) return -1;
+  if (t.kind == 0 && !t.rank && t.run_mode != 1) return -1;             // (rank_step makes keys without rank[] in the run step alone)
+  const bool chr = dense ? t.emit != 0 : t.achr != nullptr;
+  const int room = chr ? 56 : 64;
+  int gshift;
+  if (text) {
+    if (t.bc < 1 || t.bc > 6 || t.run_mode == 1 || (t.run_mode == 2 && t.h_split > t.h)) return -1;
+    gshift = 8 * t.bc + 4;
+  } else {
+    if (t.bc < 1 || t.bc > 33 || ((u64)n >> (t.run_mode == 1 ? t.bc - 1 : t.bc)) != 0) return -1;
+    gshift = t.bc;
+  }
+  if (t.run_mode != 0) {
+    if (!t.k || t.p < 1u || (t.run_mode == 1 && t.p > t.h)) return -1;
+    for (u32 s = 0; s < n; ++s) if (t.k[s] > n - s) return -1;
+  }
+  if (t.rank) for (u32 s = 0; s < n; ++s) if (t.rank[s] >= n) return -1;
+  for (u32 i = 0; i < m; ++i) {
+    const u32 s = dense ? (u32)(t.rec[i] >> 32) : t.aidx[i];
+    const u32 g = dense ? t.val[i] : t.agrp[i];
+    if (s >= n) return -1;
+    if (dense && g == 0xFFFFFFFFu) continue;
+    if (gshift < 64 && ((u64)g >> (room - gshift)) != 0) return -1;
+  }
+  hipStream_t st = stream;
+  TestCanaries can;
+  u64* keys = static_cast<u64*>(d_R2);                   // rank_step's recA
+  const RunKeys rk{d_runK, t.h_split, t.run_mode, t.p};
+  if (t.run_mode) BWTC_HIP_TRY(hipMemcpyAsync(d_runK, t.k, (u64)n * 4, hipMemcpyHostToDevice, st));
+  if (t.rank) BWTC_HIP_TRY(hipMemcpyAsync(d_rank, t.rank, (u64)n * 4, hipMemcpyHostToDevice, st));
+  if (dense) {
+    BWTC_HIP_TRY(hipMemcpyAsync(keys, t.rec, (u64)m * 8, hipMemcpyHostToDevice, st));
+    BWTC_HIP_TRY(hipMemcpyAsync(d_V1, t.val, (u64)m * 4, hipMemcpyHostToDevice, st));
+    BWTC_HIP_TRY(can.put(keys, (u64)m * 8, st)); BWTC_HIP_TRY(can.put(d_V1, (u64)m * 4, st));
+    launch_gather_dense(*this, keys, d_V1, m, n, t.h, t.bc, t.emit ? 1 : 0, t.bin_shift, rk);
+    BWTC_HIP_TRY(hipMemcpyAsync(t.val, d_V1, (u64)m * 4, hipMemcpyDeviceToHost, st));
+  } else {
+    BWTC_HIP_TRY(hipMemcpyAsync(d_V1, t.aidx, (u64)m * 4, hipMemcpyHostToDevice, st));
+    BWTC_HIP_TRY(hipMemcpyAsync(d_GRP, t.agrp, (u64)m * 4, hipMemcpyHostToDevice, st));
+    if (t.achr) BWTC_HIP_TRY(hipMemcpyAsync(d_C0, t.achr, m, hipMemcpyHostToDevice, st));
+    BWTC_HIP_TRY(hipMemsetAsync(keys, 0xA5, (u64)m * 8, st));
+    BWTC_HIP_TRY(can.put(keys, (u64)m * 8, st));
+    if (text) launch_gather_text(*this, d_V1, d_GRP, t.achr ? d_C0 : nullptr, keys, m, n, t.h, (u32)t.bc, rk);
+    else launch_gather_key2(*this, d_V1, d_GRP, t.rank ? d_rank : nullptr, t.achr ? d_C0 : nullptr, keys, m, n, t.h, t.bc, rk);
+  }
+  BWTC_HIP_TRY(hipMemcpyAsync(t.keys, keys, (u64)m * 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return can.verdict();
+}
+
+// The driver: rank_step<u64, false> once.  pairs_min and window_bits are the call's and are put back; the block state is
+// a new one in the finisher route with rank[] live (finished suffixes also go to SA, text rounds keep rank[] exact).
+struct RoundKnobScope {
+  BwtEngine& e;
+  const u32 pairs_min; const int window_bits;
+  RoundKnobScope(BwtEngine& eng, u32 pm, int wb) : e(eng), pairs_min(eng.pairs_min), window_bits(eng.window_bits) { e.pairs_min = pm; e.window_bits = wb; }
+  ~RoundKnobScope() { e.pairs_min = pairs_min; e.window_bits = window_bits; }
+};
+
+int BwtEngine::test_round(bwtc_hip_round& t) {
+  const u32 m = t.m, n = t.n;
+  if (m < 1u || m > n || (u64)n + TestCanaries::kBytes > cap || !t.ks || !t.vs || !t.aglob || !t.rank) return -1;
+  if (t.h_next < 1u || t.pairs_min < 1u || t.window_bits < 1 || t.window_bits > 32 || (t.raw_out && !t.text)) return -1;
+  if (t.run_mode < 0 || t.run_mode > 2 || (t.text && t.h_next >= (1ull << 31))) return -1;
+  if (t.out_n != n && t.out_n + 1u != n) return -1;
+  if (t.lf_n > 256u || (t.lf_n > 1u && (t.lf_x != n / t.lf_n || t.lf_x < 1u))) return -1;
+  if (t.run_mode != 0) {
+    if (!t.k || t.step_p < 1u || (t.run_mode == 1 && (u64)t.step_p > t.h_next) || (t.run_mode == 2 && t.text && (u64)t.step_depth > t.h_next)) return -1;
+    for (u32 s = 0; s < n; ++s) if (t.k[s] > n - s) return -1;
+  }
+  {
+    std::vector<u8> seen(n, 0);
+    for (u32 p = 0; p < m; ++p) {
+      const u32 s = t.vs[p];
+      if (s >= n || seen[s] || t.aglob[p] >= n || (p > 0 && t.aglob[p] <= t.aglob[p - 1])) return -1;
+      seen[s] = 1;
+    }
+    for (u32 s = 0; s < n; ++s) if (t.rank[s] >= n) return -1;
+  }
+  hipStream_t st = stream;
+  RoundKnobScope knobs(*this, t.pairs_min, t.window_bits);
+  blk = BlockSort{};
+  blk.fin_active = true; blk.ranks_live = true;
+  blk.step.p = t.run_mode ? t.step_p : 0u;
+  blk.step.depth = t.run_mode == 2 ? t.step_depth : 0u;
+  n_sort_events = 0;
+  TestCanaries can;
+  BWTC_HIP_TRY(hipMemcpyAsync(d_R1, t.ks, (u64)m * 8, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(d_V0, t.vs, (u64)m * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(d_G0, t.aglob, (u64)m * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(d_rank, t.rank, (u64)n * 4, hipMemcpyHostToDevice, st));
+  if (t.run_mode) BWTC_HIP_TRY(hipMemcpyAsync(d_runK, t.k, (u64)n * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(can.put(d_rank, (u64)n * 4, st));
+  u32* const out4[] = {d_G1, d_GRP};
+  for (u32* a : out4) { BWTC_HIP_TRY(hipMemsetAsync(a, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(a, (u64)m * 4, st)); }
+  BWTC_HIP_TRY(hipMemsetAsync(d_C0, 0xA5, (u64)m * 2, st)); BWTC_HIP_TRY(can.put(d_C0, t.raw_out ? (u64)m * 2 : (u64)m, st));
+  BWTC_HIP_TRY(hipMemsetAsync(d_V1, 0xA5, (u64)m * 4, st));
+  RrEmit re;
+  BWTC_HIP_TRY(fin_test_emit_begin(*this, n, t.out_n, t.lf_n, t.lf_x, &re));
+  BWTC_HIP_TRY(can.put(d_SA, (u64)n * 4, st)); BWTC_HIP_TRY(can.put(d_out, n, st));
+  re.achr_out = d_C0;
+  RankBuffers rb{d_R1, d_R2, d_V0, d_V1, d_G0, d_G1};
+  RankResult res{};
+  const int rc = rank_step<u64, false>(static_cast<const u64*>(d_R1), d_V0, m, n, 0u, t.carry_in ? ((1ull << 56) - 1ull) : ~0ull, rb, re, t.emit != 0,
+                                       t.h_next, &res, 0u, nullptr, t.text != 0, t.carry_in != 0, t.raw_out != 0, t.run_mode);
+  if (rc) return rc;
+  t.result[0] = res.m; t.result[1] = res.groups; t.result[2] = res.carry ? 1u : 0u; t.result[3] = res.text_chars;
+  t.result[4] = res.ran_run ? 1u : 0u; t.result[5] = res.finish ? 1u : 0u;
+  if (t.raw_out) BWTC_HIP_TRY(hipMemcpyAsync(t.nvs, d_V1, (u64)m * 4, hipMemcpyDeviceToHost, st));
+  else if (res.m > 0) {
+    BWTC_HIP_TRY(hipMemcpyAsync(t.nks, res.ks, (u64)res.m * 8, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(hipMemcpyAsync(t.nvs, res.vs, (u64)res.m * 4, hipMemcpyDeviceToHost, st));
+  }
+  BWTC_HIP_TRY(hipMemcpyAsync(t.naglob, d_G1, (u64)m * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.ngrp, d_GRP, (u64)m * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.nchr, d_C0, (u64)m * 2, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(t.rank, d_rank, (u64)n * 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(fin_test_emit_fetch(*this, n, t.SA, t.out, t.small, t.lf));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return can.verdict();
 }
 
 }  // namespace bwtc_hip

@@ -464,6 +464,8 @@ struct BwtEngine {
                 int run_mode = 0);   // run_mode: RunKeys::mode of the next list's second keys
   bool dense_route = true;   // BWTC_HIP_DENSE=0: always the list-order route (random rank[s+h] gather)
   bool digit_planes = true;  // BWTC_HIP_PLANES=0: every histogram pass reads the keys
+  u32 pairs_min = 1u << 21;  // lists of at least this many entries take the window-ordered routes to rank[] (pairs partitioned before the
+                             // scatter, dense records); a field so that the round hook can lower it for one call (RoundKnobScope): no environment variable
   int window_bits = 16;      // BWTC_HIP_WINDOW_BITS: rank[] is updated / read in windows of n >> window_bits suffixes
   bool split_index = true;   // BWTC_HIP_SPLIT_INDEX=0: the initial sort always carries 32-bit suffix numbers
   bool gram_keys = true;     // BWTC_HIP_GRAMS=0: initial keys are always base-sigma numbers (no dense gram codes)
@@ -520,6 +522,14 @@ struct BwtEngine {
   // load_text left it.  -1: the list breaks a contract of k_finish (nothing is launched); -20 - i: a canary changed.
   int test_finish_pass(FinPassTest& t);
   int test_finisher(bwtc_hip_fin_run& t);   // the same for the driver, finisher_passes, over a one-region list
+  // Test hooks (bwtc_hip_test_rank_* / _round_keys): one ranking through launch_rerank, the aggregates' scan
+  // alone, a window scatter, a round's key kernel -- rank_step's launch code and shapes, on d_T as load_text left it.
+  // -1: a contract of the kernels fails (nothing is launched); -20 - i: a canary changed.
+  int test_rank_pass(bwtc_hip_rank_pass& t);
+  int test_rank_scan(u32* a, u32* b, u32* c, u32 ntiles, u32* parts_out, u32 parts_cap, u32* counts_out);
+  int test_rank_scatter(bool dense, const u32* where, const u32* what, const u64* rec, u32 m, u32 n, int bin_shift, u32* rank);
+  int test_round_keys(bwtc_hip_round_keys& t);
+  int test_round(bwtc_hip_round& t);        // the driver: rank_step<u64, false> once, pairs_min and window_bits set and restored
   // a raw list (suffix; head slot << 32 | slot) in (S, HP) -> a sorted list the rounds understand, in res / rb
   int dress_list(u32 n, u32 total, u32* S, u64* HP, RankBuffers& rb, RankResult* res, u32 holes = 0);
   // runs and periods (bwt_engine.hip, "Runs" / "Periods"): long runs of one byte (period 1) and stretches of a period p > 1

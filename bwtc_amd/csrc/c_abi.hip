@@ -1321,6 +1321,51 @@ int bwtc_hip_test_finisher(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_fin_run
   return e.test_finisher(*p);
 }
 
+// ---- test hooks of the ranking step and the rounds' kernels (bwtc_hip_test_rank_* / _round_keys; DESIGN.md, "The ranking hooks")
+// Through BwtEngine::test_rank_pass / _scan / _scatter / test_round_keys, which check the kernels' contracts on the host,
+// guard the arrays the kernels may write and share their launch code with rank_step (launch_rerank and its neighbours).
+static int test_load_text(BwtEngine& e, const uint8_t* T, u32 n) {
+  if (!T || n == 0 || (u64)n + kSortCanaryBytes > e.cap) return -1;
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_in, T, n, hipMemcpyHostToDevice, e.stream));
+  u32 hist[256];
+  return e.load_text(e.d_in, n, n, false, hist);
+}
+int bwtc_hip_test_rank_pass(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_rank_pass* p) {
+  if (!ctx || !T || !p) return -1;
+  if (!p->aggA || !p->aggB || !p->aggC || !p->counts || !p->rank || !p->pair_s || !p->pair_r || !p->rec || !p->val || !p->rplane || !p->aidx ||
+      !p->aglob_out || !p->agrp || !p->achr || !p->SA || !p->out || !p->small || !p->lf) return -1;
+  const int rc = test_load_text(ctx->eng, T, p->n);
+  if (rc) return rc;
+  return ctx->eng.test_rank_pass(*p);
+}
+int bwtc_hip_test_rank_scan(bwtc_hip_ctx* ctx, uint32_t* a, uint32_t* b, uint32_t* c, uint32_t ntiles, uint32_t* parts_out, uint32_t parts_cap,
+                            uint32_t* counts_out) {
+  if (!ctx || !a || !b || !c || !parts_out || !counts_out) return -1;
+  BWTC_HIP_TRY(hipSetDevice(ctx->eng.device));
+  return ctx->eng.test_rank_scan(a, b, c, ntiles, parts_out, parts_cap, counts_out);
+}
+int bwtc_hip_test_rank_scatter(bwtc_hip_ctx* ctx, int dense, const uint32_t* where, const uint32_t* what, const uint64_t* rec, uint32_t m,
+                               uint32_t n, int bin_shift, uint32_t* rank) {
+  if (!ctx) return -1;
+  BWTC_HIP_TRY(hipSetDevice(ctx->eng.device));
+  return ctx->eng.test_rank_scatter(dense != 0, where, what, rec, m, n, bin_shift, rank);
+}
+int bwtc_hip_test_round_keys(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_round_keys* rk) {
+  if (!ctx || !T || !rk) return -1;
+  const int rc = test_load_text(ctx->eng, T, rk->n);
+  if (rc) return rc;
+  return ctx->eng.test_round_keys(*rk);
+}
+
+int bwtc_hip_test_round(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_round* p) {
+  if (!ctx || !T || !p) return -1;
+  if (!p->result || !p->nks || !p->nvs || !p->naglob || !p->ngrp || !p->nchr || !p->SA || !p->out || !p->small || !p->lf) return -1;
+  const int rc = test_load_text(ctx->eng, T, p->n);
+  if (rc) return rc;
+  return ctx->eng.test_round(*p);
+}
+
 int bwtc_hip_test_radix_segmented(bwtc_hip_ctx* ctx, uint32_t* keys, uint64_t n, int bit_lo, const uint32_t* tile_first, uint32_t nseg) {
   if (!ctx || !keys || !tile_first) return -1;
   BwtEngine& e = ctx->eng;

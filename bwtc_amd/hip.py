@@ -206,6 +206,32 @@ class FinRun(ctypes.Structure):
                 ("lS", _vp), ("lP", _vp), ("lH", _vp), ("lC", _vp), ("SA", _vp), ("out", _vp), ("small", _vp), ("lf", _vp)]
 
 
+class RankPass(ctypes.Structure):
+    """bwtc_hip_rank_pass (include/bwtc_hip.h): one ranking through launch_rerank."""
+    _fields_ = [("m", _u32), ("n", _u32)] + [(f, ctypes.c_int) for f in ("key_bytes", "init", "split", "lng", "mode", "emit")] + \
+               [("keys", _vp), ("idx", _vp), ("w", _vp), ("aglob", _vp), ("short_len", _u32), ("kmask", _u64),
+                ("wmask", _u32), ("hi_shift", ctypes.c_int), ("chr_shift", ctypes.c_int), ("chr_mask", _u32), ("lvl_shift", ctypes.c_int),
+                ("depth", _u32), ("inv_lut", _vp), ("out_n", _u32), ("lf_n", _u32), ("lf_x", _u32), ("rec_shift", ctypes.c_int),
+                ("plane", ctypes.c_int)] + \
+               [(f, _vp) for f in ("aggA", "aggB", "aggC", "counts", "rank", "pair_s", "pair_r", "rec", "val", "rplane", "aidx", "aglob_out",
+                                   "agrp", "achr", "SA", "out", "small", "lf")]
+
+
+class RoundKeys(ctypes.Structure):
+    """bwtc_hip_round_keys (include/bwtc_hip.h): one launch of a round's key kernel."""
+    _fields_ = [("kind", ctypes.c_int), ("m", _u32), ("n", _u32), ("aidx", _vp), ("agrp", _vp), ("rec", _vp), ("val", _vp), ("rank", _vp),
+                ("achr", _vp), ("h", _u32), ("bc", ctypes.c_int), ("emit", ctypes.c_int), ("bin_shift", ctypes.c_int), ("run_mode", ctypes.c_int),
+                ("k", _vp), ("h_split", _u32), ("p", _u32), ("keys", _vp)]
+
+
+class Round(ctypes.Structure):
+    """bwtc_hip_round (include/bwtc_hip.h): rank_step<u64, false> once."""
+    _fields_ = [("m", _u32), ("n", _u32), ("ks", _vp), ("vs", _vp), ("aglob", _vp), ("rank", _vp), ("k", _vp), ("h_next", _u64)] + \
+               [(f, ctypes.c_int) for f in ("emit", "text", "carry_in", "raw_out", "run_mode")] + \
+               [("step_p", _u32), ("step_depth", _u32), ("pairs_min", _u32), ("window_bits", ctypes.c_int), ("out_n", _u32), ("lf_n", _u32),
+                ("lf_x", _u32)] + [(f, _vp) for f in ("result", "nks", "nvs", "naglob", "ngrp", "nchr", "SA", "out", "small", "lf")]
+
+
 class KernelTimers(ctypes.Structure):
     _fields_ = [("scatter_launches", _u64), ("scatter_bytes", _u64), ("scatter_ms", ctypes.c_double)]
 
@@ -232,6 +258,7 @@ EXPORTS = [
     "bwtc_hip_period_get", "bwtc_hip_test_period_lengths",
     "bwtc_hip_test_code_stage", "bwtc_hip_test_code_table", "bwtc_hip_test_code_keys",
     "bwtc_hip_test_finish_pass", "bwtc_hip_test_local_pass", "bwtc_hip_test_finisher",
+    "bwtc_hip_test_rank_pass", "bwtc_hip_test_rank_scan", "bwtc_hip_test_rank_scatter", "bwtc_hip_test_round_keys", "bwtc_hip_test_round",
     "bwtc_hip_wavelet_depth_needed", "bwtc_hip_grammar_create", "bwtc_hip_grammar_destroy", "bwtc_hip_grammar_rules", "bwtc_hip_grammar_special_symbols",
     "bwtc_hip_grammar_is_special", "bwtc_hip_grammar_write", "bwtc_hip_grammar_read", "bwtc_hip_pair_replace_device",
     "bwtc_hip_test_pair_stats", "bwtc_hip_precompress", "bwtc_hip_host_precompress", "bwtc_hip_postprocess",
@@ -397,6 +424,11 @@ def load():
     L.bwtc_hip_test_finish_pass.argtypes = [_vp, _vp, ctypes.POINTER(FinPass)]
     L.bwtc_hip_test_local_pass.argtypes = [_vp, _vp, ctypes.POINTER(FinPass)]
     L.bwtc_hip_test_finisher.argtypes = [_vp, _vp, ctypes.POINTER(FinRun)]
+    L.bwtc_hip_test_rank_pass.argtypes = [_vp, _vp, ctypes.POINTER(RankPass)]
+    L.bwtc_hip_test_rank_scan.argtypes = [_vp, _vp, _vp, _vp, _u32, _vp, _u32, _vp]
+    L.bwtc_hip_test_rank_scatter.argtypes = [_vp, ctypes.c_int, _vp, _vp, _vp, _u32, _u32, ctypes.c_int, _vp]
+    L.bwtc_hip_test_round_keys.argtypes = [_vp, _vp, ctypes.POINTER(RoundKeys)]
+    L.bwtc_hip_test_round.argtypes = [_vp, _vp, ctypes.POINTER(Round)]
     _lib = L
     return L
 
@@ -1195,6 +1227,159 @@ class Context:
                     shallow_depth=i[5], wait_depth=i[6], local_depth=i[7], park=(keep["pS"][:i[2]], keep["pHP"][:i[2]]),
                     shal=(keep["sS"][:i[4]], keep["sHP"][:i[4]]), local_list=(keep["lS"][:o[3]], keep["lP"][:o[3]], keep["lH"][:o[3]], keep["lC"][:o[3]]),
                     SA=keep["SA"][:n], out=keep["out"][:n], pidx=int(keep["small"][0]), last_char=int(keep["small"][1]), lf=keep["lf"])
+
+
+    # the suffix sorter's ranking step and round kernels (bwtc_hip_test_rank_* / _round_keys)
+    def test_rank_pass(self, T, keys, idx, m=None, init=True, split=False, mode=0, emit=0, w=None, aglob=None, short_len=0, kmask=None,
+                       long=None, inv_lut=None, out_n=None, lf_n=0, rec_shift=0, plane=True):
+        """One ranking (reduce, scan, apply) over the list (keys, idx[, w][, aglob]) of T as the sorter holds it.  keys: uint32
+        or uint64; idx: uint32 suffix numbers, or with split their uint16 lower halves; long: dict(wmask, hi_shift, chr_shift,
+        chr_mask, lvl_shift, depth) for long items (w given).  -> dict of every output array, cut to its size (aggA/B/C
+        per tile, counts[2], rank[n], pair_s / pair_r / rec / val / rplane [m], aidx / aglob / agrp [m], achr (uint8[m], in
+        mode 3 uint16[m]), SA, out, pidx, last_char, lf[256]); what the form does not write is still poison."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        n = T.size
+        keys = np.ascontiguousarray(keys)
+        assert keys.dtype in (np.uint32, np.uint64)
+        idx = np.ascontiguousarray(idx, dtype=np.uint16 if split else np.uint32)
+        m = keys.size if m is None else int(m)
+        assert idx.size == keys.size
+        p = RankPass()
+        p.m, p.n, p.key_bytes, p.init, p.split, p.lng, p.mode, p.emit = m, n, keys.dtype.itemsize, int(bool(init)), int(bool(split)), int(w is not None), int(mode), int(emit)
+        hold = [keys, idx]
+        p.keys, p.idx = _ptr(keys), _ptr(idx)
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.uint32)
+            assert w.size == keys.size
+            hold.append(w)
+            p.w = _ptr(w)
+            p.wmask, p.hi_shift, p.chr_shift, p.chr_mask = int(long["wmask"]), int(long["hi_shift"]), int(long["chr_shift"]), int(long["chr_mask"])
+            p.lvl_shift, p.depth = int(long["lvl_shift"]), int(long["depth"])
+        if aglob is not None:
+            aglob = np.ascontiguousarray(aglob, dtype=np.uint32)
+            assert aglob.size == keys.size
+            hold.append(aglob)
+            p.aglob = _ptr(aglob)
+        if inv_lut is not None:
+            inv_lut = np.ascontiguousarray(inv_lut, dtype=np.uint8)
+            assert inv_lut.size == 256
+            hold.append(inv_lut)
+            p.inv_lut = _ptr(inv_lut)
+        p.short_len = int(short_len)
+        p.kmask = int((1 << (8 * keys.dtype.itemsize)) - 1 if kmask is None else kmask)
+        p.out_n, p.lf_n = int(n if out_n is None else out_n), int(lf_n)
+        p.lf_x = n // lf_n if lf_n > 1 else 0
+        p.rec_shift, p.plane = int(rec_shift), int(bool(plane))
+        mm, tiles = max(m, 1), max(-(-m // 2048), 1)
+        keep = dict(aggA=np.zeros(tiles, np.uint32), aggB=np.zeros(tiles, np.uint32), aggC=np.zeros(tiles, np.uint32), counts=np.zeros(2, np.uint32),
+                    rank=np.zeros(n + 1, np.uint32), pair_s=np.zeros(mm, np.uint32), pair_r=np.zeros(mm, np.uint32), rec=np.zeros(mm, np.uint64),
+                    val=np.zeros(mm, np.uint32), rplane=np.zeros(mm, np.uint8), aidx=np.zeros(mm, np.uint32), aglob_out=np.zeros(mm, np.uint32),
+                    agrp=np.zeros(mm, np.uint32), achr=np.zeros(2 * mm, np.uint8), SA=np.zeros(n + 1, np.uint32), out=np.zeros(n + 1, np.uint8),
+                    small=np.zeros(2, np.uint32), lf=np.zeros(256, np.uint32))
+        for k, a in keep.items():
+            setattr(p, k, _ptr(a))
+        _check(self.lib.bwtc_hip_test_rank_pass(self.handle, _ptr(T) if n else None, ctypes.byref(p)), "bwtc_hip_test_rank_pass")
+        res = dict(keep)
+        res["rank"], res["SA"], res["out"] = keep["rank"][:n], keep["SA"][:n], keep["out"][:n]
+        res["aglob"] = res.pop("aglob_out")
+        res["achr"] = keep["achr"].view(np.uint16)[:mm] if mode == 3 else keep["achr"][:mm]
+        res["pidx"], res["last_char"] = int(keep["small"][0]), int(keep["small"][1])
+        return res
+
+    def test_rank_scan(self, a, b, c, parts_cap=None):
+        """k_rerank_scan_tiles<0> then <1> over three aggregate arrays -> (a, b, c scanned, the part array, counts[2])."""
+        a, b, c = (np.array(x, dtype=np.uint32) for x in (a, b, c))
+        nt = a.size
+        assert b.size == nt and c.size == nt
+        if parts_cap is None:
+            parts_cap = 3 * (-(-nt // 4096)) + 3
+        parts, counts = np.zeros(max(parts_cap, 1), np.uint32), np.zeros(2, np.uint32)
+        _check(self.lib.bwtc_hip_test_rank_scan(self.handle, _ptr(a), _ptr(b), _ptr(c), nt, _ptr(parts), int(parts_cap), _ptr(counts)),
+               "bwtc_hip_test_rank_scan")
+        return a, b, c, parts[:parts_cap], counts
+
+    def test_rank_scatter(self, rank, where=None, what=None, rec=None, bin_shift=0):
+        """k_scatter_pairs (where, what) or k_scatter_dense (rec = s << 32 | value) into a copy of rank[] -> rank[] afterwards."""
+        rank = np.array(rank, dtype=np.uint32)
+        dense = rec is not None
+        if dense:
+            rec = np.ascontiguousarray(rec, dtype=np.uint64)
+            m = rec.size
+            args = (None, None, _ptr(rec) if m else None)
+        else:
+            where, what = np.ascontiguousarray(where, dtype=np.uint32), np.ascontiguousarray(what, dtype=np.uint32)
+            m = where.size
+            assert what.size == m
+            args = (_ptr(where) if m else None, _ptr(what) if m else None, None)
+        _check(self.lib.bwtc_hip_test_rank_scatter(self.handle, int(dense), args[0], args[1], args[2], m, rank.size, int(bin_shift), _ptr(rank)),
+               "bwtc_hip_test_rank_scatter")
+        return rank
+
+    def test_round_keys(self, T, kind, h, bc, aidx=None, agrp=None, rec=None, val=None, rank=None, achr=None, emit=False, bin_shift=0,
+                        run_mode=0, k=None, h_split=0, p=1):
+        """One launch of k_gather_key2 (kind 0), k_gather_text (1) or k_gather_dense (2) -> keys, and for kind 2 (keys, vals)."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        q = RoundKeys()
+        q.kind, q.n, q.h, q.bc, q.emit, q.bin_shift, q.run_mode, q.h_split, q.p = int(kind), T.size, int(h), int(bc), int(bool(emit)), int(bin_shift), int(run_mode), int(h_split), int(p)
+        hold = []
+
+        def give(name, a, dt, copy=False):
+            if a is None:
+                return None
+            a = np.array(a, dtype=dt) if copy else np.ascontiguousarray(a, dtype=dt)
+            hold.append(a)
+            setattr(q, name, _ptr(a))
+            return a
+        if kind == 2:
+            rec, val = give("rec", rec, np.uint64, True), give("val", val, np.uint32, True)
+            m = rec.size
+        else:
+            aidx, agrp = give("aidx", aidx, np.uint32), give("agrp", agrp, np.uint32)
+            m = aidx.size
+            achr = give("achr", achr, np.uint8)
+        give("rank", rank, np.uint32)
+        give("k", k, np.uint32)
+        q.m = m
+        keys = np.zeros(max(m, 1), np.uint64)
+        q.keys = _ptr(keys)
+        _check(self.lib.bwtc_hip_test_round_keys(self.handle, _ptr(T) if T.size else None, ctypes.byref(q)), "bwtc_hip_test_round_keys")
+        return (keys[:m], val[:m]) if kind == 2 else keys[:m]
+
+
+    def test_round(self, T, ks, vs, aglob, rank, h_next, emit=False, text=False, carry_in=False, raw_out=False, run_mode=0, k=None, step_p=1,
+                   step_depth=0, pairs_min=1 << 21, window_bits=16, out_n=None, lf_n=0):
+        """rank_step<u64, false> once over the sorted list (ks, vs, aglob) -> dict: m, groups, carry, text_chars, ran_run,
+        the next list (ks, vs cut to m; raw_out: vs the raw list's suffixes), aglob, grp, chr (uint8, raw_out uint16), rank,
+        SA, out, pidx, last_char, lf."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        n = T.size
+        ks, vs, aglob = np.ascontiguousarray(ks, dtype=np.uint64), np.ascontiguousarray(vs, dtype=np.uint32), np.ascontiguousarray(aglob, dtype=np.uint32)
+        m = ks.size
+        assert vs.size == m and aglob.size == m
+        rank = np.array(rank, dtype=np.uint32)
+        assert rank.size == n
+        q = Round()
+        q.m, q.n, q.ks, q.vs, q.aglob, q.rank, q.h_next = m, n, _ptr(ks), _ptr(vs), _ptr(aglob), _ptr(rank), int(h_next)
+        q.emit, q.text, q.carry_in, q.raw_out, q.run_mode = int(bool(emit)), int(bool(text)), int(bool(carry_in)), int(bool(raw_out)), int(run_mode)
+        if k is not None:
+            k = np.ascontiguousarray(k, dtype=np.uint32)
+            q.k = _ptr(k)
+        q.step_p, q.step_depth, q.pairs_min, q.window_bits = int(step_p), int(step_depth), int(pairs_min), int(window_bits)
+        q.out_n, q.lf_n = int(n if out_n is None else out_n), int(lf_n)
+        q.lf_x = n // lf_n if lf_n > 1 else 0
+        mm = max(m, 1)
+        keep = dict(result=np.zeros(6, np.uint32), nks=np.zeros(mm, np.uint64), nvs=np.zeros(mm, np.uint32), naglob=np.zeros(mm, np.uint32),
+                    ngrp=np.zeros(mm, np.uint32), nchr=np.zeros(2 * mm, np.uint8), SA=np.zeros(n + 1, np.uint32), out=np.zeros(n + 1, np.uint8),
+                    small=np.zeros(2, np.uint32), lf=np.zeros(256, np.uint32))
+        for name, a in keep.items():
+            setattr(q, name, _ptr(a))
+        _check(self.lib.bwtc_hip_test_round(self.handle, _ptr(T) if n else None, ctypes.byref(q)), "bwtc_hip_test_round")
+        r = [int(v) for v in keep["result"]]
+        cut = m if raw_out else r[0]
+        return dict(m=r[0], groups=r[1], carry=bool(r[2]), text_chars=r[3], ran_run=bool(r[4]), finish=bool(r[5]), ks=keep["nks"][:r[0]],
+                    vs=keep["nvs"][:cut], aglob=keep["naglob"][:m], grp=keep["ngrp"][:m],
+                    chr=keep["nchr"].view(np.uint16)[:m] if raw_out else keep["nchr"][:m], rank=rank, SA=keep["SA"][:n], out=keep["out"][:n],
+                    pidx=int(keep["small"][0]), last_char=int(keep["small"][1]), lf=keep["lf"])
 
 
 def host_cpu_slice(numa_node, rank, ranks):

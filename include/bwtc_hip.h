@@ -543,6 +543,93 @@ typedef struct bwtc_hip_fin_run {
   uint32_t* SA; uint8_t* out; uint32_t* small; uint32_t* lf;
 } bwtc_hip_fin_run;
 int bwtc_hip_test_finisher(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_fin_run* run);
+/* Test hooks of the suffix sorter's ranking step and round kernels, over T[0..n) as the sorter
+ * holds it (loaded by load_text, zero padded), on the context's own buffers.  All pointers are the caller's arrays; every
+ * output is poisoned with 0xA5 bytes first and has 256 canary bytes behind the last item a kernel may write.  No
+ * environment variable takes part.  -1, before anything is launched, where a contract below fails; -20 - i when canary i
+ * changed.
+ *   _rank_pass: ONE ranking through launch_rerank (k_rerank_reduce, k_rerank_scan_tiles<0>, <1>, k_rerank_apply), the
+ *     launch code of rank_step, over a list of m items.
+ *     in:  keys (m words of key_bytes = 4 or 8), idx (m 32-bit suffix numbers; split: m 16-bit lower halves, the upper
+ *          bits in the key at bit 48, long items at hi_shift, 13 bits), w (long items' second words), aglob (rounds: the
+ *          items' slots); short_len, kmask; the RrLong fields wmask, hi_shift, chr_shift, chr_mask, lvl_shift (-1: every
+ *          item shares `depth`), depth; inv_lut[256] (emit 3); the form: init, split, lng, mode 0..3, emit 0..3; out_n,
+ *          lf_n, lf_x, rec_shift and plane (mode 2).
+ *     out: aggA/B/C (ceil(m / 2048) entries each) as apply read them, counts[2], rank[n] (mode 0), pair_s / pair_r (m
+ *          each, mode 1), rec / val / rplane (m each, mode 2), the next list aidx / aglob_out / agrp (m each) and achr (2 m
+ *          bytes: m characters, or in mode 3 m 16-bit entries), SA[n], out[n], small = {pidx, last_char}, lf[256].
+ *     contracts: 1 <= m <= n, n + 256 <= the context's capacity; init: m == n; 4-byte keys, split and lng only with init
+ *          (split, lng: 8-byte keys); every suffix number (the split undone) below n and distinct; rounds: aglob below n
+ *          and strictly ascending, emit 0, 1 or 2; init: emit 0 or 2, long items 0 or 3, split items 0 or 2; split: n <=
+ *          2^29; long: w given, wmask != 0, shifts below 64 (hi_shift + 13 <= 64 when split), chr_mask <= 255, lvl_shift
+ *          -1 or <= 61, depth < 2^24; emit 3: inv_lut given; out_n = n or n - 1; lf_n <= 256, lf_x = n / lf_n >= 1 where
+ *          lf_n > 1; rec_shift < 32.
+ *   _rank_scan: k_rerank_scan_tiles<0> then <1> over a, b, c (ntiles entries each, scanned in place) on the engine's
+ *     aggregate arrays; parts_out: the whole part array (3 words per 4096 entries, then poison; parts_cap words are
+ *     written back, at most what the context holds), counts_out[2].  1 <= ntiles <= what the context reserved
+ *     (block size / 2048 + 2).
+ *   _rank_scatter: k_scatter_pairs (dense == 0: where[m], what[m]) or k_scatter_dense (rec[m] = s << 32 | value) with the
+ *     engine's grid and bin_shift, into rank[n] as the caller preset it.  1 <= m <= n, n + 256 <= capacity, every
+ *     destination below n and distinct, 0 <= bin_shift <= 24.
+ *   _round_keys: kind 0 k_gather_key2, 1 k_gather_text, 2 k_gather_dense with the engine's launch shape.
+ *     in:  the list aidx / agrp (kinds 0, 1), or the records rec (s << 32 | any) and values val (group, or all ones:
+ *          finished) (kind 2, both rewritten in place); rank[n] or null (kind 0 only); achr[m] or null (kinds 0, 1); h; b2
+ *          (kinds 0, 2) or c (kind 1) in bc; emit and bin_shift (kind 2); RunKeys: run_mode 0, 1, 2 with k[n], h_split, p.
+ *     out: keys[m] (kind 2: rec), and for kind 2 val.
+ *     contracts: 1 <= m <= n, n + 256 <= capacity; every suffix below n; rank[] below n; kinds 0, 2: 1 <= b2 <= 33, n <
+ *          2^b2 (run_mode 1: n < 2^(b2 - 1)), every group << b2 below 2^56 (2^64 without achr / emit); kind 1: 1 <= c <= 6,
+ *          every group << (8 c + 4) below 2^56; kind 2: rank given, 0 <= bin_shift <= 24; run_mode != 0: k given, k[s] <=
+ *          n - s, 1 <= p; run_mode 1: p <= h (kind 1 has no run_mode 1); kind 1 with run_mode 2: h_split <= h. */
+typedef struct bwtc_hip_rank_pass {
+  uint32_t m, n;
+  int key_bytes, init, split, lng, mode, emit;
+  const void* keys; const void* idx; const uint32_t* w; const uint32_t* aglob;
+  uint32_t short_len; uint64_t kmask;
+  uint32_t wmask; int hi_shift, chr_shift; uint32_t chr_mask; int lvl_shift; uint32_t depth;
+  const uint8_t* inv_lut;
+  uint32_t out_n, lf_n, lf_x; int rec_shift, plane;
+  uint32_t *aggA, *aggB, *aggC, *counts;
+  uint32_t* rank; uint32_t *pair_s, *pair_r; uint64_t* rec; uint32_t* val; uint8_t* rplane;
+  uint32_t *aidx, *aglob_out, *agrp; uint8_t* achr;
+  uint32_t* SA; uint8_t* out; uint32_t* small; uint32_t* lf;
+} bwtc_hip_rank_pass;
+int bwtc_hip_test_rank_pass(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_rank_pass* pass);
+int bwtc_hip_test_rank_scan(bwtc_hip_ctx* ctx, uint32_t* a, uint32_t* b, uint32_t* c, uint32_t ntiles, uint32_t* parts_out, uint32_t parts_cap,
+                            uint32_t* counts_out);
+int bwtc_hip_test_rank_scatter(bwtc_hip_ctx* ctx, int dense, const uint32_t* where, const uint32_t* what, const uint64_t* rec, uint32_t m,
+                               uint32_t n, int bin_shift, uint32_t* rank);
+typedef struct bwtc_hip_round_keys {
+  int kind; uint32_t m, n;
+  const uint32_t *aidx, *agrp; uint64_t* rec; uint32_t* val;
+  const uint32_t* rank; const uint8_t* achr;
+  uint32_t h; int bc, emit, bin_shift;
+  int run_mode; const uint32_t* k; uint32_t h_split, p;
+  uint64_t* keys;
+} bwtc_hip_round_keys;
+int bwtc_hip_test_round_keys(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_round_keys* rk);
+/*   _round: the driver, rank_step<u64, false>, ONCE, from the state run_rounds gives it in the finisher route (finished
+ *     suffixes also go to SA; rank[] live), with pairs_min and window_bits set for this call and restored.
+ *     in:  a sorted list ks / vs / aglob (m each), rank[n] (in and out), h_next, the flags emit, text, carry_in, raw_out
+ *          (with text), run_mode 0, 1, 2 with k[n], step_p and step_depth (RunKeys::p and h_split), out_n, lf_n, lf_x.
+ *     out: result = {m_next, groups, carry, text_chars, ran_run, finish}; the next list as sorted (nks, nvs: m_next
+ *          entries) or, raw_out, the raw list's suffixes in nvs; naglob (slots), ngrp (the groups before the sort; raw_out:
+ *          head slots), nchr (2 m bytes: characters, raw_out: 16-bit entries), m entries each; rank[]; SA, out, small, lf.
+ *     contracts: the list's as for a round of _rank_pass; rank[] below n; 1 <= h_next; 1 <= pairs_min; 1 <= window_bits
+ *          <= 32; raw_out only with text; run_mode != 0: k given, k[s] <= n - s, 1 <= step_p; run_mode 1: step_p <=
+ *          h_next; text with run_mode 2: step_depth <= h_next; text: h_next < 2^31.  Canaries behind naglob, ngrp, nchr,
+ *          rank, SA, out (the keys and values ping-pong between the sort's own arrays). */
+typedef struct bwtc_hip_round {
+  uint32_t m, n;
+  const uint64_t* ks; const uint32_t* vs; const uint32_t* aglob;
+  uint32_t* rank; const uint32_t* k;
+  uint64_t h_next;
+  int emit, text, carry_in, raw_out, run_mode;
+  uint32_t step_p, step_depth, pairs_min; int window_bits;
+  uint32_t out_n, lf_n, lf_x;
+  uint32_t* result; uint64_t* nks; uint32_t* nvs; uint32_t* naglob; uint32_t* ngrp; uint8_t* nchr;
+  uint32_t* SA; uint8_t* out; uint32_t* small; uint32_t* lf;
+} bwtc_hip_round;
+int bwtc_hip_test_round(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_round* round);
 /* Test hook: k range-coder chains over w-elements (w = bit << 15 | probability of the coded bit), chain j = elements
  * [bounds[j], bounds[j+1]), on the GPU lane engine (mode 0; BitEncoder, BitCoders.cpp:59-113, one lane per chain) or by the
  * host's scalar loop (mode 1); bytes of chain j = out[offsets[j] .. offsets[j+1]). */
