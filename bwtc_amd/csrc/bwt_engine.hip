@@ -1726,6 +1726,47 @@ __device__ __forceinline__ u64 period_breaks(const u8* __restrict__ T, u32 at, u
   if (left < 64u) mask &= (1ull << left) - 1ull;
   return mask;
 }
+// The proper positions among the suffixes q = at + j - p that the 64 positions from `at` on stand for (k_stretch_lengths
+// stores k_p[x - p] at x): bit j set = q + 1 < n and T[q] != T[q + 1].  No position inside a run of one byte is proper,
+// and a unit that is not one byte over and over has a proper position among any p consecutive ones.  The bytes are the
+// second stream of period_breaks and one more: the same aligned loads (the caches hold them), shifted the same way.
+__device__ __forceinline__ u64 proper_starts(const u8* __restrict__ T, u32 at, u32 n, u32 p) {
+  if (at + 64u <= p || n < 2u) return 0ull;
+  u64 mask = 0;
+  if (at < p) {
+    for (u32 j = p - at; j < 64u && at + j - p + 1u < n; ++j)
+      if (T[at + j - p] != T[at + j - p + 1u]) mask |= 1ull << j;
+    return mask;
+  }
+  const u32 from = at - p;
+  if (from >= n - 1u) return 0ull;
+  const u32 a0 = from & ~15u, sh = from & 15u;
+  u32 w[20];
+#pragma unroll
+  for (int q = 0; q < 5; ++q) {                         // (T is padded: a 16-byte load that begins below n is the arena's)
+    const u32 x = a0 + 16u * q;
+    const uint4 v = x < n ? *reinterpret_cast<const uint4*>(T + x) : make_uint4(0u, 0u, 0u, 0u);
+    w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+  }
+  if (sh & 8u) {
+#pragma unroll
+    for (int i = 0; i < 18; ++i) w[i] = w[i + 2];
+  }
+  if (sh & 4u) {
+#pragma unroll
+    for (int i = 0; i < 17; ++i) w[i] = w[i + 1];
+  }
+  const u32 bs = sh & 3u;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {                        // (w[16] is the text's still: 3 words and 3 bytes of shift, 68 bytes wanted, 80 loaded)
+    const u64 two = ((u64)w[i + 1] << 32) | (u64)w[i];
+    const u32 b = (u32)(two >> (8u * bs)), c = (u32)(two >> (8u * bs + 8u));
+    mask |= (u64)differing_bytes(b ^ c) << (4 * i);
+  }
+  const u32 left = n - 1u - from;                       // suffixes from n - 1 on have no byte behind them
+  if (left < 64u) mask &= (1ull << left) - 1ull;
+  return mask;
+}
 // RUN: the pass of period 1, its mask from run_starts (p is 1 then); else period_breaks'
 template <bool RUN>
 __device__ __forceinline__ u64 stretch_breaks(const u8* __restrict__ T, u32 at, u32 n, u32 p) {
@@ -1767,8 +1808,10 @@ __global__ __launch_bounds__(1024) void k_run_carry(const u32* __restrict__ firs
     run = min(run, first[t - 1u]);
   }
 }
-// launch 3: k_p[x - p] for the positions x of the tile (coalesced 4-byte stores), and the block's longest k_p
-template <bool RUN>
+// launch 3: k_p[x - p] for the positions x of the tile (coalesced 4-byte stores), and the block's longest k_p.
+// PROPER (never with RUN): the longest k_p over the proper positions too (proper_starts), into longest[1] -- a second
+// mask per thread, a second maximum per wave; the instantiations without it are what they were
+template <bool RUN, bool PROPER = false>
 __global__ __launch_bounds__(kRunTPB) void k_stretch_lengths(const u8* __restrict__ T, u32 n, u32 p_any, const u32* __restrict__ behind,
                                                               u32* __restrict__ k, u32* __restrict__ longest) {
   __shared__ u64 s_mask[kRunTPB];
@@ -1779,6 +1822,8 @@ __global__ __launch_bounds__(kRunTPB) void k_stretch_lengths(const u8* __restric
   const u32 at = base + threadIdx.x * 64u;
   const u64 mask = stretch_breaks<RUN>(T, at, n, p);
   s_mask[threadIdx.x] = mask;
+  __shared__ u64 s_proper[PROPER ? kRunTPB : 1];
+  if constexpr (PROPER) s_proper[threadIdx.x] = proper_starts(T, at, n, p);
   // suffix minimum of the threads' first breaks: inside the wave by shuffles, across the four waves through LDS
   const u32 lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
   u32 incl = mask ? at + (u32)__builtin_ctzll(mask) : kRunNone;
@@ -1795,6 +1840,7 @@ __global__ __launch_bounds__(kRunTPB) void k_stretch_lengths(const u8* __restric
   s_next[threadIdx.x] = excl;
   __syncthreads();
   u32 best = 0;
+  [[maybe_unused]] u32 best_proper = 0;
   for (u32 j = 0; j < kRunTile / kRunTPB; ++j) {
     const u32 x = base + j * kRunTPB + threadIdx.x;     // chunk j * 4 + wave of the tile, bit `lane`
     const u32 c = j * (kRunTPB / 64u) + wave;
@@ -1816,9 +1862,14 @@ __global__ __launch_bounds__(kRunTPB) void k_stretch_lengths(const u8* __restric
     const u32 kk = min(nd, n) - q;
     if (k) k[q] = kk;                                   // (k == nullptr: a trial, for the longest stretch alone)
     best = max(best, kk);
+    if constexpr (PROPER) { if ((s_proper[c] >> lane) & 1ull) best_proper = max(best_proper, kk); }
   }
   for (int o = kWave / 2; o > 0; o >>= 1) best = max(best, (u32)__shfl_xor(best, o, kWave));
   if (lane == 0 && best) atomicMax(longest, best);
+  if constexpr (PROPER) {
+    for (int o = kWave / 2; o > 0; o >>= 1) best_proper = max(best_proper, (u32)__shfl_xor(best_proper, o, kWave));
+    if (lane == 0 && best_proper) atomicMax(longest + 1, best_proper);
+  }
 }
 
 // The period finder: one pass over a sorted list.  Neighbouring entries of one group (equal keys under kmask) that lie
@@ -1829,8 +1880,11 @@ constexpr u32 kVoteTPB = 256, kVoteTile = 16384, kVoteBins = kPeriodMax + 1;
 constexpr int kSmallPeriod = 802;      // d_small: the block's longest k_p; [803] the probe's flag; [804..805] the finder's winner and its votes
 constexpr u32 kPeriodMinVotes = 256;   // the winner's votes buy the period-length pass from max(this, n / 64) on (find_period)
 constexpr u64 kPeriodWorth = 8;        // a voted period's longest stretch must reach this many times max(the first round's depth, p)
+// RUNS_OUT (BWTC_HIP_MIXED, with k_1[] in k1): two members of one run of one byte do not vote -- a long run's group
+// comes in the order of the sort's windows, and its members would outvote the stretches with the windows' distance.
+template <bool RUNS_OUT>
 __global__ __launch_bounds__(kVoteTPB) void k_period_votes(const u64* __restrict__ ks, const u32* __restrict__ vs, u32 m, u64 kmask,
-                                                           u32* __restrict__ table) {
+                                                           u32* __restrict__ table, const u32* __restrict__ k1) {
   __shared__ u32 s_bin[kVoteBins];
   for (u32 b = threadIdx.x; b < kVoteBins; b += kVoteTPB) s_bin[b] = 0;
   __syncthreads();
@@ -1841,7 +1895,9 @@ __global__ __launch_bounds__(kVoteTPB) void k_period_votes(const u64* __restrict
     if (((ks[i] ^ ks[i + 1u]) & kmask) != 0ull) continue;
     const u32 a = vs[i], b = vs[i + 1u];
     const u32 d = a > b ? a - b : b - a;
-    if (d >= 2u && d <= kPeriodMax) atomicAdd(&s_bin[d], 1u);
+    if (d < 2u || d > kPeriodMax) continue;
+    if constexpr (RUNS_OUT) { if (k1[min(a, b)] > d) continue; }
+    atomicAdd(&s_bin[d], 1u);
   }
   __syncthreads();
   const u32 turn = (blockIdx.x * 67u) % kVoteBins;
@@ -2211,6 +2267,7 @@ int BwtEngine::init(int dev, u32 max_block_size) {
   env_int("BWTC_HIP_FIN_ROUNDS", &fin_rounds, 1, 4);
   run_ranks = !env_off("BWTC_HIP_RUNS"); period_ranks = !env_off("BWTC_HIP_PERIODS");
   if (env_int("BWTC_HIP_PERIOD", &v, 0, (int)kPeriodMax)) period_forced = (u32)v;
+  mixed_steps = env_is("BWTC_HIP_MIXED", "1");
   local_rounds = !env_off("BWTC_HIP_LOCAL_ROUNDS");
   if (env_int("BWTC_HIP_FIN_FLOOR", &v, 0)) fin_floor = (u32)v;
   text_rounds_fixed = env_int("BWTC_HIP_TEXT_ROUNDS", &text_rounds, 0);
@@ -3004,18 +3061,38 @@ int BwtEngine::initial_long(const InitialSort& in, const GramPlan& gp, int key_b
 
 // Is the block's step this round's?  The first round's (decide_step) is; the deferred period step waits for the round
 // whose depth h_round has reached p, as long as the stretches are longer than that.
-bool BwtEngine::step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool text_round) {
+// BWTC_HIP_MIXED: the period step behind a run step (blk.next) waits under the same conditions, gated by the longest
+// proper stretch; in its round the storing pass puts k_p[] where k_1[] was and the step becomes the block's.
+int BwtEngine::step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool text_round, bool* due) {
   StretchStep& step = blk.step;
-  if (step.when == StretchStep::kThisRound) { step.when = StretchStep::kNone; return m > 0; }
-  if (step.when != StretchStep::kWaiting || m == 0) return false;
+  *due = false;
+  if (step.when == StretchStep::kThisRound) { step.when = StretchStep::kNone; *due = m > 0; return 0; }
+  if (blk.next.when == StretchStep::kWaiting && m > 0) {
+    StretchStep& next = blk.next;
+    if ((u64)blk.proper_longest <= std::max<u64>(h_round, next.p)) {
+      next.when = StretchStep::kNone;
+      say_no_period_step(*this, h_first);
+    } else if (h_round >= (u64)next.p && L.ranks_complete && blk.local_m == 0 && !text_round) {
+      // a run's member with k_1 >= p has k_p = k_1, one with k_1 < p <= h_round would look up at h_round anyway: nothing
+      // is lost with k_1[]
+      next.when = StretchStep::kNone;
+      const int rc = stretch_lengths(L.n, next.p, true, &blk.period_longest, &blk.proper_longest);
+      if (rc) return rc;
+      blk.run_depth = step.depth;
+      step = StretchStep{next.p, StretchStep::kNone, 0};
+      *due = true;
+    }
+    return 0;
+  }
+  if (step.when != StretchStep::kWaiting || m == 0) return 0;
   if ((u64)blk.period_longest <= std::max<u64>(h_round, step.p)) {
     step.when = StretchStep::kNone;
     say_no_period_step(*this, h_first);
   } else if (h_round >= (u64)step.p && L.ranks_complete && blk.local_m == 0 && !text_round) {
     step.when = StretchStep::kNone;
-    return true;
+    *due = true;
   }
-  return false;
+  return 0;
 }
 
 // The rounds over the sorted list in L.res / L.rb, from depth h0 until nothing is tied.  text_rounds_now: rounds that compare
@@ -3044,7 +3121,9 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
     ++stats.rounds;
     stats.active_sum += m;
     const bool text_round = text_left > 0 && m > 0;
-    const bool run_req = step_due(L, m, keep_h ? h : h * 2, h_first, text_round);
+    bool run_req = false;
+    const int rcd = step_due(L, m, keep_h ? h : h * 2, h_first, text_round, &run_req);
+    if (rcd) return rcd;
     const bool period_req = run_req && step.p >= 2;
     const bool text = text_round || (run_req && !L.ranks_complete);   // the run step reads no rank[]: it does not need the completion either
     const bool raw = !text && !doubling;               // out of text rounds and not allowed to double: hand the list back
@@ -3082,6 +3161,7 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
       // the list is sorted to depth h still: a run's members by their closed-form keys, the others as they were (or by rank[s + h])
       step.depth = (u32)std::min<u64>(h, 0xFFFFFFFFull);
       stats.route |= period_req ? 256u : 32u;
+      if (period_req && blk.period_ranks_runs) { stats.route |= 32u; blk.run_depth = step.depth; }   // (BWTC_HIP_MIXED: one step over k_p[] ranked the runs too)
       keep_h = true;
       if (period_req && debug_on())
         std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: period step at depth %u\n",
@@ -3105,10 +3185,14 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
       if (text_left == 0 && m > 0 && (u64)m * 4096 < (u64)n && text_extra > 0) { text_left = 1; --text_extra; }
     }
   }
-  if (step.when == StretchStep::kWaiting) {              // (the rounds ended before their depth reached p)
-    step.when = StretchStep::kNone;
+  if (step.when == StretchStep::kWaiting || blk.next.when == StretchStep::kWaiting) {   // (the rounds ended before their depth reached p)
+    step.when = blk.next.when = StretchStep::kNone;
     say_no_period_step(*this, h_first);
   }
+  if (mixed_steps && doubling && debug_on())
+    std::fprintf(stderr, "steps: run step at depth %u, period step of period %u at depth %u, longest run %u, longest proper stretch %u\n",
+                 step.p == 1 ? step.depth : blk.run_depth, step.p >= 2 && step.depth ? step.p : 0u, step.p >= 2 ? step.depth : 0u,
+                 blk.run_longest, blk.proper_longest);
   if (left) { *left = 0; *h_left = h; }
   return 0;
 }
@@ -3264,27 +3348,31 @@ struct PassTimer {
 // The stretch-length pass (three launches behind whatever the stream holds, one host wait): k_p[] for every suffix of
 // the block into d_runK, unless this is a trial, and the block's longest stretch of period p.  p = 1 is the run-length
 // pass: the text read once per launch, and the block's longest run is known from then on.
-static constexpr int kSmallStretch = 800;   // d_small: the word a pass reads back
-int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest) {
+static constexpr int kSmallStretch = 800;   // d_small: the two words a pass reads back (the longest stretch; the longest proper one)
+int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* proper) {
+  if (proper) *proper = 0;
   // (the tiles reach n + p and their positions are 32-bit: a block within two tiles of 2^32 takes no step)
   if ((u64)n + p + 2ull * kRunTile > 0xFFFFFFFFull) { *longest = 0; return 0; }
   hipStream_t st = stream;
   const u32 tiles = (u32)(((u64)n + p + kRunTile - 1) / kRunTile);   // the tiles cover the positions x = s + p, s < n
   u32* k = store ? d_runK : nullptr;
   PassTimer timer(st);
-  BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallStretch, 0, 4, st));
+  BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallStretch, 0, proper ? 8 : 4, st));
   BWTC_HIP_TRY(timer.start());
-  if (p == 1) {
+  if (p == 1 && !proper) {
     hipLaunchKernelGGL(k_stretch_tiles<true>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, d_runF);
     hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(1024), 0, st, (const u32*)d_runF, tiles, n, d_runB);
     hipLaunchKernelGGL(k_stretch_lengths<true>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch);
   } else {
     hipLaunchKernelGGL(k_stretch_tiles<false>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, d_runF);
     hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(1024), 0, st, (const u32*)d_runF, tiles, n, d_runB);
-    hipLaunchKernelGGL(k_stretch_lengths<false>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch);
+    if (proper)   // (the second maximum: BWTC_HIP_MIXED and its test hook only; p = 1 takes the general form for it)
+      hipLaunchKernelGGL((k_stretch_lengths<false, true>), dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch);
+    else
+      hipLaunchKernelGGL(k_stretch_lengths<false>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch);
   }
   BWTC_HIP_TRY(timer.stop());
-  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallStretch, d_small + kSmallStretch, 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallStretch, d_small + kSmallStretch, proper ? 8 : 4, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(wait());
   if (timer.on) {
     float ms = 0.f;
@@ -3294,10 +3382,11 @@ int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest) {
                                     : "periods: a trial pass (no lengths stored) took %.4f ms for %u suffixes, period %u\n", ms, n, p);
   }
   *longest = h_small[kSmallStretch];
+  if (proper) *proper = h_small[kSmallStretch + 1];
   if (store) blk.lengths_period = p;
   if (p == 1) { blk.run_longest = *longest; blk.run_longest_known = true; }
   // T read twice (p > 1: both streams of it), the lengths written; the tiles' words written and read
-  stats.alg_bytes += (u64)n * ((p == 1 ? 1 + 1 : 2 + 2) + (store ? 4 : 0)) + (u64)tiles * 16;
+  stats.alg_bytes += (u64)n * ((p == 1 && !proper ? 1 + 1 : 2 + 2) + (store ? 4 : 0)) + (u64)tiles * 16;
   return 0;
 }
 
@@ -3325,7 +3414,10 @@ int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* 
   // BWTC_HIP_PERIOD names it); votes above the threshold buy the period-length pass, which puts k_p[] where k[] was.
   // p <= the first round's depth: that round is the period step, exactly as the run step.  A deeper p: the step waits
   // for the first doubling round whose depth reaches p (kWaiting), with rank[] complete and no local list beside it.
-  if (!period_ranks || period_forced == 1 || blk.step.when != StretchStep::kNone || blk.period_looked) return 0;
+  // BWTC_HIP_MIXED=1 (with the run ranking on): the block that takes the run step looks for a period too (decide_mixed).
+  const bool mixed = mixed_steps && run_ranks && period_forced != 1;
+  const bool run_due = blk.step.when != StretchStep::kNone;
+  if (!period_ranks || period_forced == 1 || (run_due && !mixed) || blk.period_looked) return 0;
   blk.period_looked = true;
   const int rcp = find_period(n, ks, vs, m, kmask);
   if (rcp) return rcp;
@@ -3350,6 +3442,11 @@ int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* 
       if (debug_on()) std::fprintf(stderr, "periods: no window of %u positions of period %u without a break: no period-length pass\n", span, blk.period_p);
       blk.period_p = 0;
     }
+  }
+  if (mixed) {
+    if (blk.period_p >= 2) { const int rcm = decide_mixed(n, h_first, run_due); if (rcm) return rcm; }
+    if (blk.step.p < 2 && blk.next.when == StretchStep::kNone) say_no_period_step(*this, h_first);
+    return 0;
   }
   if (blk.period_p >= 2) {
     // (a run of one byte is a stretch of every period, and the run step's business: the block's longest run first --
@@ -3394,6 +3491,50 @@ int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* 
   return 0;
 }
 
+// decide_step under BWTC_HIP_MIXED=1, for the candidate period_p >= 2: the gates are the longest PROPER stretch's -- the
+// largest k_p over the positions s with T[s] != T[s + 1], which no run of one byte holds and every p positions of a
+// stretch of another unit do -- so a run neither counts as a stretch nor keeps one from its step.  run_due: the run
+// step is the first round and d_runK holds k_1[] for it, so only trial passes run here.  p <= h_first: that round is
+// one period step over k_p[] instead, which ranks the runs too (k_p = k_1 for k_1 >= p): the storing pass overwrites
+// k_1[].  p > h_first: the period step waits in blk.next for the round whose depth reaches p (step_due).
+int BwtEngine::decide_mixed(u32 n, u64 h_first, bool run_due) {
+  const bool voted = period_forced == 0;
+  int rc = stretch_lengths(n, blk.period_p, !run_due, &blk.period_longest, &blk.proper_longest);
+  if (rc) return rc;
+  if (voted && (u64)blk.proper_longest < kPeriodWorth * std::max<u64>(h_first, blk.period_p)) { blk.period_p = 0; return 0; }
+  if (voted && (u64)blk.period_p > h_first && (u64)blk.proper_longest > blk.period_p) {
+    // (the winner may be a multiple of the stretches' period: decide_step's division, by the proper stretch)
+    const u32 winner = blk.period_p, longest_voted = blk.period_longest, proper_voted = blk.proper_longest;
+    u32 rest = winner;
+    for (u32 q = 2; q <= rest && blk.period_p / q >= 2; ) {
+      if (rest % q) { ++q; continue; }
+      rest /= q;
+      u32 longest = 0, proper = 0;
+      rc = stretch_lengths(n, blk.period_p / q, false, &longest, &proper);
+      if (rc) return rc;
+      if (proper >= proper_voted) blk.period_p /= q;
+      else while (rest % q == 0) rest /= q;
+    }
+    blk.period_longest = longest_voted; blk.proper_longest = proper_voted;
+    if (blk.period_p != winner) {
+      rc = stretch_lengths(n, blk.period_p, !run_due, &blk.period_longest, &blk.proper_longest);
+      if (rc) return rc;
+    }
+  }
+  if ((u64)blk.period_p <= h_first) {
+    if ((u64)blk.proper_longest <= h_first) return 0;
+    if (run_due) {
+      rc = stretch_lengths(n, blk.period_p, true, &blk.period_longest, &blk.proper_longest);
+      if (rc) return rc;
+      blk.period_ranks_runs = true;
+    }
+    blk.step = StretchStep{blk.period_p, StretchStep::kThisRound, 0};
+  } else if (blk.proper_longest > blk.period_p) {
+    (run_due ? blk.next : blk.step) = StretchStep{blk.period_p, StretchStep::kWaiting, 0};
+  }
+  return 0;
+}
+
 // The block's period, into period_p (0: none worth the pass) and period_votes: BWTC_HIP_PERIOD's, or the vote's winner
 // if its votes reach the threshold -- a 64th of the block, and kPeriodMinVotes at the least.
 int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask) {
@@ -3404,7 +3545,11 @@ int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask
   const bool timed = timer.on;
   BWTC_HIP_TRY(hipMemsetAsync(d_votes, 0, (size_t)kVoteBins * 4, st));
   BWTC_HIP_TRY(timer.start());
-  hipLaunchKernelGGL(k_period_votes, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes);
+  // (d_runK holds k_1[] where the run step is due: decide_step made it just now)
+  if (mixed_steps && blk.lengths_period == 1 && blk.step.p == 1)
+    hipLaunchKernelGGL(k_period_votes<true>, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, (const u32*)d_runK);
+  else
+    hipLaunchKernelGGL(k_period_votes<false>, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, (const u32*)nullptr);
   BWTC_HIP_TRY(timer.stop());
   hipLaunchKernelGGL(k_period_winner, dim3(1), dim3(1024), 0, st, (const u32*)d_votes, d_small + kSmallPeriod + 2);
   BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 2, d_small + kSmallPeriod + 2, 8, hipMemcpyDeviceToHost, st));

@@ -447,6 +447,11 @@ struct BwtEngine {
     u32 run_longest = 0; bool run_longest_known = false;   // the longest run, once a pass of period 1 has found it (made at most once per block)
     StretchStep step;          // its period (1: the run step), when it is due (kWaiting: the first doubling round whose depth reaches p), the depth it ran at (0: it has not)
     bool period_looked = false;   // a period has been looked for (once per block)
+    // BWTC_HIP_MIXED: the period step that follows the block's run step (kWaiting; it becomes `step` in the round it is
+    // due, step_due), the depth the run step ran at, and the longest proper stretch (0: no pass has made it)
+    StretchStep next;
+    u32 run_depth = 0, proper_longest = 0;
+    bool period_ranks_runs = false;   // the first round is one period step over k_p[] in place of the run step that was due
     // the candidate period, its longest stretch, its votes: with the step's depth, what bwtc_hip_period_get reports until the next block begins
     u32 period_p = 0, period_longest = 0, period_votes = 0;
   } blk;
@@ -478,7 +483,7 @@ struct BwtEngine {
   int initial_keys64(const InitialSort& in, const GramPlan& gp, int key_bits, u32 short_len, int split, SortList& L, u64 h);
   int initial_long(const InitialSort& in, const GramPlan& gp, int key_bits, int split, bool coded, SortList& L, u64* h, bool* ranked);
   int run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool keep_first, bool doubling, u32* left, u64* h_left);
-  bool step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool text_round);
+  int step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool text_round, bool* due);
   int finisher_route(SortList& L, u32 n_lf);
   hipError_t finisher_begin(u32* S, FinList* a, FinList* b);
   bool no_emit = false;      // BWTC_HIP_NO_EMIT: suffix array + gather even for blocks that could carry
@@ -533,16 +538,20 @@ struct BwtEngine {
   // a raw list (suffix; head slot << 32 | slot) in (S, HP) -> a sorted list the rounds understand, in res / rb
   int dress_list(u32 n, u32 total, u32* S, u64* HP, RankBuffers& rb, RankResult* res, u32 holes = 0);
   // runs and periods (bwt_engine.hip, "Runs" / "Periods"): long runs of one byte (period 1) and stretches of a period p > 1
-  // are ranked in closed form by one round, the step.  One step per block, over the one length array d_runK.
+  // are ranked in closed form by one round, the step.  One step per block, over the one length array d_runK -- or, with
+// BWTC_HIP_MIXED=1, the run step and then one period step, whose lengths replace the runs' in d_runK.
   bool run_ranks = true;     // BWTC_HIP_RUNS=0: no run step; the longest run is found only to tell a run from a voted period (decide_step)
   bool period_ranks = true;  // BWTC_HIP_PERIODS=0: no votes, no period-length pass, no period step
   u32 period_forced = 0;     // BWTC_HIP_PERIOD=p: that period, no votes (1: the run path)
+  bool mixed_steps = false;  // BWTC_HIP_MIXED=1: a block may take the run step and a period step (decide_step)
   u32* d_runK = nullptr;     // k_p[s]: the leading characters of suffix s that are p-periodic (p = 1: the positions from s on that hold T[s])
   u32* d_runF = nullptr; u32* d_runB = nullptr;   // the stretch-length pass's words per tile
   u32* d_votes = nullptr;    // the finder's table: votes per distance 0 ... kPeriodMax
-  int stretch_lengths(u32 n, u32 p, bool store, u32* longest);   // store == false: the longest stretch alone (a trial)
+  // store == false: the longest stretch alone (a trial); proper: the longest proper stretch too (the general form for p = 1)
+  int stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* proper = nullptr);
   int find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask);
   int decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask);   // -> step
+  int decide_mixed(u32 n, u64 h_first, bool run_due);                                    // -> step, next
   int long_grams_override = 0;   // BWTC_HIP_LONG_G2=N: N grams in the second key word
   void scatter_rank_pairs(u32* pairs, u32* tmp, u32 m, u32 n);
   int load_text(const u8* d_src, u32 ncopy, u32 n, bool reverse, u32* hist_T);

@@ -1128,9 +1128,35 @@ int bwtc_hip_period_get(bwtc_hip_ctx* ctx, uint32_t* p, uint32_t* longest, uint3
   return 0;
 }
 
+// The closed-form steps of the last block: the depths the run step and the period step ran at (0: it did not; one
+// period step that ranked the runs too reports its depth as both), the period step's period, the block's longest run
+// and its longest proper stretch (0 where no pass made it).
+int bwtc_hip_steps_get(bwtc_hip_ctx* ctx, uint32_t* run_depth, uint32_t* period_p, uint32_t* period_depth, uint32_t* longest_run,
+                       uint32_t* longest_proper) {
+  if (!ctx) return -1;
+  const BwtEngine::BlockSort& b = ctx->eng.blk;
+  const bool period_ran = b.step.p >= 2 && b.step.depth != 0;
+  if (run_depth) *run_depth = b.step.p == 1 ? b.step.depth : b.run_depth;
+  if (period_p) *period_p = period_ran ? b.step.p : 0;
+  if (period_depth) *period_depth = period_ran ? b.step.depth : 0;
+  if (longest_run) *longest_run = b.run_longest;
+  if (longest_proper) *longest_proper = b.proper_longest;
+  return 0;
+}
+
 // The sorter's own stretch-length pass (BwtEngine::stretch_lengths: three launches; p = 1: the run-length pass) over T as
-// the sorter holds it -- loaded by load_text, padded with zero bytes -- on the context's buffers.
+// the sorter holds it -- loaded by load_text, padded with zero bytes -- on the context's buffers.  proper_out: the pass
+// with the second maximum (bwtc_hip_test_period_proper).
+static int test_period_pass(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest_out, uint32_t* proper_out);
 int bwtc_hip_test_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest_out) {
+  return test_period_pass(ctx, T, n, p, k_out, longest_out, nullptr);
+}
+int bwtc_hip_test_period_proper(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest_out,
+                                uint32_t* proper_out) {
+  if (!proper_out) return -1;
+  return test_period_pass(ctx, T, n, p, k_out, longest_out, proper_out);
+}
+static int test_period_pass(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest_out, uint32_t* proper_out) {
   if (!ctx || !T || !k_out || !longest_out) return -1;
   BwtEngine& e = ctx->eng;
   if (p == 0 || p > kPeriodMax || n == 0 || (u64)n > e.cap) return -1;
@@ -1139,7 +1165,7 @@ int bwtc_hip_test_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n
   u32 hist[256];
   int rc = e.load_text(e.d_in, n, n, false, hist);
   if (rc) return rc;
-  rc = e.stretch_lengths(n, p, true, longest_out);
+  rc = e.stretch_lengths(n, p, true, longest_out, proper_out);
   if (rc) return rc;
   BWTC_HIP_TRY(hipMemcpyAsync(k_out, e.d_runK, (u64)n * 4, hipMemcpyDeviceToHost, e.stream));
   BWTC_HIP_TRY(e.wait());

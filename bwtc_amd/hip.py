@@ -255,7 +255,7 @@ EXPORTS = [
     "bwtc_hip_host_sections", "bwtc_hip_host_bwtblock_header", "bwtc_hip_synth", "bwtc_hip_suffix_array",
     "bwtc_hip_test_sort_u32", "bwtc_hip_test_sort_u64", "bwtc_hip_test_scan_u32",
     "bwtc_hip_test_radix_pairs", "bwtc_hip_test_radix_long", "bwtc_hip_test_radix_segmented",
-    "bwtc_hip_period_get", "bwtc_hip_test_period_lengths",
+    "bwtc_hip_period_get", "bwtc_hip_test_period_lengths", "bwtc_hip_steps_get", "bwtc_hip_test_period_proper",
     "bwtc_hip_test_code_stage", "bwtc_hip_test_code_table", "bwtc_hip_test_code_keys",
     "bwtc_hip_test_finish_pass", "bwtc_hip_test_local_pass", "bwtc_hip_test_finisher",
     "bwtc_hip_test_rank_pass", "bwtc_hip_test_rank_scan", "bwtc_hip_test_rank_scatter", "bwtc_hip_test_round_keys", "bwtc_hip_test_round",
@@ -417,6 +417,8 @@ def load():
     L.bwtc_hip_test_radix_segmented.argtypes = [_vp, _vp, _u64, ctypes.c_int, _vp, _u32]
     L.bwtc_hip_period_get.argtypes = [_vp] + [ctypes.POINTER(_u32)] * 4
     L.bwtc_hip_test_period_lengths.argtypes = [_vp, _vp, _u32, _u32, _vp, ctypes.POINTER(_u32)]
+    L.bwtc_hip_steps_get.argtypes = [_vp] + [ctypes.POINTER(_u32)] * 5
+    L.bwtc_hip_test_period_proper.argtypes = [_vp, _vp, _u32, _u32, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]
     L.bwtc_hip_test_code_stage.argtypes = [_vp, _vp, _u32, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_u32), _vp, _vp,
                                            ctypes.POINTER(_u32), _vp, _vp, _vp]
     L.bwtc_hip_test_code_table.argtypes = [_vp, _vp, _u32, _vp, ctypes.POINTER(_u32)]
@@ -1099,6 +1101,25 @@ class Context:
         v = [_u32(0) for _ in range(4)]
         _check(self.lib.bwtc_hip_period_get(self.handle, *[ctypes.byref(x) for x in v]), "bwtc_hip_period_get")
         return tuple(int(x.value) for x in v)
+
+    def steps(self):
+        """The last block's closed-form steps (bwtc_hip_steps_get): (depth of the run step, the period step's period, its
+        depth, the longest run, the longest proper stretch); depths 0 for a step that did not run."""
+        v = [_u32(0) for _ in range(5)]
+        _check(self.lib.bwtc_hip_steps_get(self.handle, *[ctypes.byref(x) for x in v]), "bwtc_hip_steps_get")
+        return tuple(int(x.value) for x in v)
+
+    def test_period_proper(self, T, p, k_out=None):
+        """test_period_lengths() by the pass with the second maximum (bwtc_hip_test_period_proper) -> (k_p[], the longest,
+        the longest proper stretch)."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        if k_out is None:
+            k_out = np.zeros(max(T.size, 1), np.uint32)
+        assert k_out.dtype == np.uint32 and k_out.size >= T.size
+        longest, proper = _u32(0), _u32(0)
+        _check(self.lib.bwtc_hip_test_period_proper(self.handle, _ptr(T) if T.size else None, T.size, int(p), _ptr(k_out),
+                                                    ctypes.byref(longest), ctypes.byref(proper)), "bwtc_hip_test_period_proper")
+        return k_out[:T.size], int(longest.value), int(proper.value)
 
     def test_period_lengths(self, T, p, k_out=None):
         """The sorter's own period-length pass over T (bwtc_hip_test_period_lengths) -> (k_p[], the longest).  k_out: the

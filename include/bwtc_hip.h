@@ -42,7 +42,8 @@ typedef struct bwtc_hip_stats {
                                  bit 6: the finisher's small groups doubled beside the rounds' list (local list);
                                  bit 7: a finisher list too long for its pass's shape went to the rounds;
                                  bit 8: a period step ran -- stretches of a period p > 1 were ranked in closed form
-                                        (BWTC_HIP_PERIODS=0: never; never together with bit 5) */
+                                        (BWTC_HIP_PERIODS=0: never; together with bit 5 only under BWTC_HIP_MIXED=1: the block
+                                        took the run step and a period step, or one period step that ranked its runs too) */
   uint32_t finisher_entries;  /* list entries over all finisher passes                      */
   uint64_t alg_bytes;         /* compulsory bytes of the transform's kernels: every array a kernel
                                  reads counted once, every array it writes counted once (SURVEY.md
@@ -462,10 +463,21 @@ int bwtc_hip_test_radix_segmented(bwtc_hip_ctx* ctx, uint32_t* keys, uint64_t n,
  * threshold, or BWTC_HIP_PERIOD's), *longest the block's longest p-periodic stretch, *votes the winner's votes,
  * *step_depth the depth of the period step that ran.  Zeros where nothing was looked for or found. */
 int bwtc_hip_period_get(bwtc_hip_ctx* ctx, uint32_t* p, uint32_t* longest, uint32_t* votes, uint32_t* step_depth);
+/* The closed-form steps of the context's last block (BWTC_HIP_MIXED=1 lets a block take the run step and a period step):
+ * *run_depth and *period_depth the depths at which the run step and the period step ran, 0 for a step that did not run (one
+ * period step over k_p[] that ranked the block's long runs too reports its depth as both); *period_p that step's period;
+ * *longest_run the block's longest run of one byte; *longest_proper its longest proper stretch -- the largest k_p[s] over
+ * the s with s + 1 < n and T[s] != T[s + 1] -- and 0 where no pass made it (only passes under the switch do). */
+int bwtc_hip_steps_get(bwtc_hip_ctx* ctx, uint32_t* run_depth, uint32_t* period_p, uint32_t* period_depth, uint32_t* longest_run,
+                       uint32_t* longest_proper);
 /* Test hook: the sorter's own period-length pass (three launches; p = 1: the run-length pass) over T[0..n), on the
  * context's buffers: k_out[s] = the number of leading characters of suffix s that are p-periodic, *longest_out their
  * maximum.  -1, before anything is launched, for p = 0, p > 4096, n = 0 or n above the context's block size. */
 int bwtc_hip_test_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest_out);
+/* Test hook: the same pass with its second maximum, as the sorter launches it under BWTC_HIP_MIXED=1 (p = 1 in the general
+ * form): *proper_out = the longest proper stretch, 0 where no s has T[s] != T[s + 1].  The same refusals. */
+int bwtc_hip_test_period_proper(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest_out,
+                                uint32_t* proper_out);
 /* Test hooks of the suffix sorter's code-key stage: k_pair_counts, k_code_build and
  * k_make_keys_code with suffix_sort's launch shapes and key layout (hi_shift = code_bits - 32, 13 upper bits of the suffix
  * number when split, then the predecessor's code, then the level), over T[0..n) as the sorter holds it (loaded by
