@@ -2649,7 +2649,8 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
   res->ran_run = run_now;
   const int b2k = run_now ? b2 + 1 : b2;
   const int kbits = run_now ? nbits + 1 : nbits;
-  const RunKeys rkeys{d_runK, run_now ? 0u : blk.step.depth, run_now ? 1 : (run_mode == 2 ? 2 : 0), blk.step.p};
+  const StretchStep& step = blk.current_step();
+  const RunKeys rkeys{d_runK, run_now ? 0u : step.depth, run_now ? 1 : (run_mode == 2 ? 2 : 0), step.p};
   const bool carry_next = emit && kbits <= 56;
   res->carry = carry_next;
   const bool dense = !text && dense_route && m_next > 0 && (u64)m_next * 2 >= m && m >= pairs_min && !use_sweep;
@@ -3059,37 +3060,31 @@ int BwtEngine::initial_long(const InitialSort& in, const GramPlan& gp, int key_b
   return 0;
 }
 
-// Is the block's step this round's?  The first round's (decide_step) is; the deferred period step waits for the round
-// whose depth h_round has reached p, as long as the stretches are longer than that.
-// BWTC_HIP_MIXED: the period step behind a run step (blk.next) waits under the same conditions, gated by the longest
-// proper stretch; in its round the storing pass puts k_p[] where k_1[] was and the step becomes the block's.
+// Is a step of the block's this round's?  The front of the schedule, where decide_step made it the first round's, is.
+// Behind it the first entry that waits is due in the round whose depth h_round has reached its p, with rank[] complete,
+// no live local list and no text round pending -- as long as the stretches are longer than that: the step's gate, by
+// the longest stretch, or, behind a run step (BWTC_HIP_MIXED), by the longest proper stretch.  There d_runK still holds
+// k_1[]: the storing pass puts k_p[] in its place first.  The entry that is due becomes the current one.
 int BwtEngine::step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool text_round, bool* due) {
-  StretchStep& step = blk.step;
   *due = false;
-  if (step.when == StretchStep::kThisRound) { step.when = StretchStep::kNone; *due = m > 0; return 0; }
-  if (blk.next.when == StretchStep::kWaiting && m > 0) {
-    StretchStep& next = blk.next;
-    if ((u64)blk.proper_longest <= std::max<u64>(h_round, next.p)) {
-      next.when = StretchStep::kNone;
-      say_no_period_step(*this, h_first);
-    } else if (h_round >= (u64)next.p && L.ranks_complete && blk.local_m == 0 && !text_round) {
-      // a run's member with k_1 >= p has k_p = k_1, one with k_1 < p <= h_round would look up at h_round anyway: nothing
-      // is lost with k_1[] (DESIGN.md section 3 item 8)
-      next.when = StretchStep::kNone;
-      const int rc = stretch_lengths(L.n, next.p, true, &blk.period_longest, &blk.proper_longest);
-      if (rc) return rc;
-      blk.run_depth = step.depth;
-      step = StretchStep{next.p, StretchStep::kNone, 0};
-      *due = true;
-    }
-    return 0;
-  }
-  if (step.when != StretchStep::kWaiting || m == 0) return 0;
-  if ((u64)blk.period_longest <= std::max<u64>(h_round, step.p)) {
+  if (blk.steps[0].when == StretchStep::kThisRound) { blk.steps[0].when = StretchStep::kNone; *due = m > 0; return 0; }
+  int i = 0;
+  while (i < blk.n_steps && blk.steps[i].when != StretchStep::kWaiting) ++i;
+  if (i == blk.n_steps || m == 0) return 0;
+  StretchStep& step = blk.steps[i];
+  const bool behind_run = i > 0;
+  if ((u64)(behind_run ? blk.proper_longest : blk.period_longest) <= std::max<u64>(h_round, step.p)) {
     step.when = StretchStep::kNone;
     say_no_period_step(*this, h_first);
   } else if (h_round >= (u64)step.p && L.ranks_complete && blk.local_m == 0 && !text_round) {
     step.when = StretchStep::kNone;
+    if (blk.lengths_period != step.p) {
+      // a run's member with k_1 >= p has k_p = k_1, one with k_1 < p <= h_round would look up at h_round anyway: nothing
+      // is lost with k_1[] (DESIGN.md section 3 item 8)
+      const int rc = stretch_lengths(L.n, step.p, true, &blk.period_longest, behind_run ? &blk.proper_longest : nullptr);
+      if (rc) return rc;
+    }
+    blk.current = i;
     *due = true;
   }
   return 0;
@@ -3104,12 +3099,11 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
   RankBuffers& rb = L.rb;
   RankResult& res = L.res;
   RrEmit& re = L.re;
-  StretchStep& step = blk.step;
   u64 h = h0;
   bool keep_h = keep_first;                // the list is sorted to depth h as it stands (no doubling before the next step)
   int text_left = text_rounds_now;
-  // the block's closed-form step (runs, periods), decided where a list is about to double: step.when says whether it is
-  // the first round's or waits for a deeper one
+  // the block's closed-form steps (runs, periods), decided where a list is about to double: an entry's `when` says whether
+  // it is the first round's or waits for a deeper one
   const u64 h_first = keep_first ? h0 : h0 * 2;
   if (doubling && m > 0) {
     const int rcs = decide_step(n, m, h_first, res.ks, res.vs, (L.emit && res.carry) ? ((1ull << 56) - 1ull) : ~0ull);
@@ -3124,6 +3118,7 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
     bool run_req = false;
     const int rcd = step_due(L, m, keep_h ? h : h * 2, h_first, text_round, &run_req);
     if (rcd) return rcd;
+    StretchStep& step = blk.current_step();
     const bool period_req = run_req && step.p >= 2;
     const bool text = text_round || (run_req && !L.ranks_complete);   // the run step reads no rank[]: it does not need the completion either
     const bool raw = !text && !doubling;               // out of text rounds and not allowed to double: hand the list back
@@ -3161,7 +3156,7 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
       // the list is sorted to depth h still: a run's members by their closed-form keys, the others as they were (or by rank[s + h])
       step.depth = (u32)std::min<u64>(h, 0xFFFFFFFFull);
       stats.route |= period_req ? 256u : 32u;
-      if (period_req && blk.period_ranks_runs) { stats.route |= 32u; blk.run_depth = step.depth; }   // (BWTC_HIP_MIXED: one step over k_p[] ranked the runs too)
+      if (step.ranks_runs) stats.route |= 32u;           // (BWTC_HIP_MIXED: one step over k_p[] ranked the runs too)
       keep_h = true;
       if (period_req && debug_on())
         std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: period step at depth %u\n",
@@ -3185,14 +3180,15 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
       if (text_left == 0 && m > 0 && (u64)m * 4096 < (u64)n && text_extra > 0) { text_left = 1; --text_extra; }
     }
   }
-  if (step.when == StretchStep::kWaiting || blk.next.when == StretchStep::kWaiting) {   // (the rounds ended before their depth reached p)
-    step.when = blk.next.when = StretchStep::kNone;
-    say_no_period_step(*this, h_first);
-  }
-  if (mixed_steps && doubling && debug_on())
+  bool waited = false;                                   // (the rounds ended before their depth reached p)
+  for (int i = 0; i < blk.n_steps; ++i)
+    if (blk.steps[i].when == StretchStep::kWaiting) { blk.steps[i].when = StretchStep::kNone; waited = true; }
+  if (waited) say_no_period_step(*this, h_first);
+  if (mixed_steps && doubling && debug_on()) {
+    const StretchStep period = blk.period_ran();
     std::fprintf(stderr, "steps: run step at depth %u, period step of period %u at depth %u, longest run %u, longest proper stretch %u\n",
-                 step.p == 1 ? step.depth : blk.run_depth, step.p >= 2 && step.depth ? step.p : 0u, step.p >= 2 ? step.depth : 0u,
-                 blk.run_longest, blk.proper_longest);
+                 blk.run_depth(), period.p, period.depth, blk.run_longest, blk.proper_longest);
+  }
   if (left) { *left = 0; *h_left = h; }
   return 0;
 }
@@ -3384,44 +3380,44 @@ int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* prop
   *longest = h_small[kSmallStretch];
   if (proper) *proper = h_small[kSmallStretch + 1];
   if (store) blk.lengths_period = p;
-  if (p == 1) { blk.run_longest = *longest; blk.run_longest_known = true; }
+  if (p == 1) blk.run_longest = *longest;
   // T read twice (p > 1: both streams of it), the lengths written; the tiles' words written and read
   stats.alg_bytes += (u64)n * ((p == 1 && !proper ? 1 + 1 : 2 + 2) + (store ? 4 : 0)) + (u64)tiles * 16;
   return 0;
 }
 
-// The block's closed-form step, into `step`, for a list of m > 0 entries that is about to double and whose first round
-// establishes depth h_first.  Nothing where a step has run already: one step per block.
+// The block's closed-form steps, into blk.steps, for a list of m > 0 entries that is about to double and whose first round
+// establishes depth h_first.  Once per block: run_rounds calls it before the one doubling list a block has.
 int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask) {
-  if (blk.step.depth != 0) return 0;
   hipStream_t st = stream;
   // Runs: the list may hold long runs of one byte, which doubling takes log2(length) rounds over.  k[] and the block's
-  // longest run are made here (once per block, one host wait); a run longer than the depth the first round establishes
-  // gets the run step as that round, before any text round and before rank[] is completed.
+  // longest run are made here (one host wait); a run longer than the depth the first round establishes gets the run
+  // step as that round, before any text round and before rank[] is completed.
   // (BWTC_HIP_PERIOD=1: the run step is the period step of period 1, whatever BWTC_HIP_RUNS says)
   if (run_ranks || period_forced == 1) {
-    if (blk.lengths_period != 1) {
-      const int rcr = stretch_lengths(n, 1, true, &blk.run_longest);
-      if (rcr) return rcr;
-    }
-    if ((u64)blk.run_longest > h_first) blk.step = StretchStep{1, StretchStep::kThisRound, 0};
+    const int rcr = stretch_lengths(n, 1, true, &blk.run_longest);
+    if (rcr) return rcr;
+    if ((u64)blk.run_longest > h_first) blk.schedule(1, StretchStep::kThisRound);
     if (debug_on())
       std::fprintf(stderr, "runs: longest run %u, the rounds begin at depth %llu: %s\n", blk.run_longest, (unsigned long long)h_first,
-                   blk.step.when == StretchStep::kThisRound ? "run step" : "no run step");
+                   blk.n_steps ? "run step" : "no run step");
   }
   // Periods: a list that takes doubling rounds and no run step may hold stretches of a period p > 1, which tie their
   // suffixes for the stretch's length just as a run does.  The finder votes for p over the list as it stands (or
   // BWTC_HIP_PERIOD names it); votes above the threshold buy the period-length pass, which puts k_p[] where k[] was.
   // p <= the first round's depth: that round is the period step, exactly as the run step.  A deeper p: the step waits
   // for the first doubling round whose depth reaches p (kWaiting), with rank[] complete and no local list beside it.
-  // BWTC_HIP_MIXED=1 (with the run ranking on): the block that takes the run step looks for a period too (decide_mixed).
+  // BWTC_HIP_MIXED=1 (with the run ranking on): the block that takes the run step looks for a period too, and the gates
+  // are the longest PROPER stretch's -- the largest k_p over the positions s with T[s] != T[s + 1], which no run of one
+  // byte holds and every p positions of a stretch of another unit do -- so a run neither counts as a stretch nor keeps
+  // one from its step.
   const bool mixed = mixed_steps && run_ranks && period_forced != 1;
-  const bool run_due = blk.step.when != StretchStep::kNone;
-  if (!period_ranks || period_forced == 1 || (run_due && !mixed) || blk.period_looked) return 0;
-  blk.period_looked = true;
+  const bool run_due = blk.n_steps != 0;
+  if (!period_ranks || period_forced == 1 || (run_due && !mixed)) return 0;
   const int rcp = find_period(n, ks, vs, m, kmask);
   if (rcp) return rcp;
-  if (blk.period_p >= 2 && !period_forced) {
+  const bool voted = period_forced == 0;                // (a forced period skips the probe, the worth tests and the division)
+  if (blk.period_p >= 2 && voted) {
     // votes say how many members lie p apart, not for how long they tie: fixed-width records with a few free bytes
     // each vote for their width and tie for less than two records.  Before the pass, a probe: is any aligned window
     // of (W - p) / 2 positions free of breaks, W = kPeriodWorth x max(the first round's depth, p) being the stretch
@@ -3443,95 +3439,64 @@ int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* 
       blk.period_p = 0;
     }
   }
-  if (mixed) {
-    if (blk.period_p >= 2) { const int rcm = decide_mixed(n, h_first, run_due); if (rcm) return rcm; }
-    if (blk.step.p < 2 && blk.next.when == StretchStep::kNone) say_no_period_step(*this, h_first);
-    return 0;
-  }
+  // The passes' second maximum and the gate length g it feeds exist under the switch only.  While a run step is due d_runK
+  // holds k_1[] for it, so the passes here are trials (store == false).
+  u32* const proper = mixed ? &blk.proper_longest : nullptr;
+  const u32& g = mixed ? blk.proper_longest : blk.period_longest;
+  const bool store = !run_due;
   if (blk.period_p >= 2) {
     // (a run of one byte is a stretch of every period, and the run step's business: the block's longest run first --
     // known already unless BWTC_HIP_RUNS=0, where a trial pass of period 1 finds it -- and no period step where the
-    // longest stretch is no longer than that)
-    int rcb = (period_forced || blk.run_longest_known) ? 0 : stretch_lengths(n, 1, false, &blk.run_longest);
+    // longest stretch is no longer than that.  Under the switch runs do not count in g, and the test goes.)
+    const bool runs_count = !mixed && voted;
+    int rcb = (runs_count && !run_ranks) ? stretch_lengths(n, 1, false, &blk.run_longest) : 0;
     if (rcb) return rcb;
-    rcb = stretch_lengths(n, blk.period_p, true, &blk.period_longest);
+    rcb = stretch_lengths(n, blk.period_p, store, &blk.period_longest, proper);
     if (rcb) return rcb;
-    if (!period_forced && blk.run_longest >= blk.period_longest) blk.period_p = 0;
-    // ... and none where the longest stretch is short of kPeriodWorth times the depth it has to pass: doubling gets
-    // through it in three rounds, and the step's own round and the passes cost as much (fixed-width records with
-    // a few free bytes per record vote for their width and tie for less than two records)
-    if (!period_forced && (u64)blk.period_longest < kPeriodWorth * std::max<u64>(h_first, blk.period_p)) blk.period_p = 0;
+    // ... and none where g is short of kPeriodWorth times the depth it has to pass: doubling gets through it in three
+    // rounds, and the step's own round and the passes cost as much (fixed-width records with a few free bytes per
+    // record vote for their width and tie for less than two records)
+    if ((runs_count && blk.run_longest >= blk.period_longest) || (voted && (u64)g < kPeriodWorth * std::max<u64>(h_first, blk.period_p)))
+      blk.period_p = 0;
   }
-  if (blk.period_p >= 2) {
-    if (!period_forced && (u64)blk.period_p > h_first && (u64)blk.period_longest > blk.period_p) {
-      // The winner may be a multiple of the stretches' period: a list that a sort by windows of the suffix number
-      // has been through holds a group's members in another order than by position.  A period above the first
-      // round's depth defers the step, so it is worth dividing: p / q for the winner's prime factors q, kept while
-      // the longest stretch stays as long (trial passes: the longest stretch alone, no lengths stored).
-      const u32 voted = blk.period_p, longest_voted = blk.period_longest;
-      u32 rest = voted;
-      for (u32 q = 2; q <= rest && blk.period_p / q >= 2; ) {
-        if (rest % q) { ++q; continue; }
-        rest /= q;
-        const int rcb = stretch_lengths(n, blk.period_p / q, false, &blk.period_longest);
-        if (rcb) return rcb;
-        if (blk.period_longest >= longest_voted) blk.period_p /= q;
-        else while (rest % q == 0) rest /= q;          // (the same candidate again)
-      }
-      blk.period_longest = longest_voted;
-      if (blk.period_p != voted) {
-        const int rcb = stretch_lengths(n, blk.period_p, true, &blk.period_longest);
-        if (rcb) return rcb;
-      }
-    }
-    if ((u64)blk.period_p <= h_first) { if ((u64)blk.period_longest > h_first) blk.step = StretchStep{blk.period_p, StretchStep::kThisRound, 0}; }
-    else if (blk.period_longest > blk.period_p) blk.step = StretchStep{blk.period_p, StretchStep::kWaiting, 0};
-  }
-  if (blk.step.when == StretchStep::kNone) say_no_period_step(*this, h_first);
-  return 0;
-}
-
-// decide_step under BWTC_HIP_MIXED=1, for the candidate period_p >= 2: the gates are the longest PROPER stretch's -- the
-// largest k_p over the positions s with T[s] != T[s + 1], which no run of one byte holds and every p positions of a
-// stretch of another unit do -- so a run neither counts as a stretch nor keeps one from its step.  run_due: the run
-// step is the first round and d_runK holds k_1[] for it, so only trial passes run here.  p <= h_first: that round is
-// one period step over k_p[] instead, which ranks the runs too (k_p = k_1 for k_1 >= p): the storing pass overwrites
-// k_1[].  p > h_first: the period step waits in blk.next for the round whose depth reaches p (step_due).
-int BwtEngine::decide_mixed(u32 n, u64 h_first, bool run_due) {
-  const bool voted = period_forced == 0;
-  int rc = stretch_lengths(n, blk.period_p, !run_due, &blk.period_longest, &blk.proper_longest);
-  if (rc) return rc;
-  if (voted && (u64)blk.proper_longest < kPeriodWorth * std::max<u64>(h_first, blk.period_p)) { blk.period_p = 0; return 0; }
-  if (voted && (u64)blk.period_p > h_first && (u64)blk.proper_longest > blk.period_p) {
-    // (the winner may be a multiple of the stretches' period: decide_step's division, by the proper stretch)
-    const u32 winner = blk.period_p, longest_voted = blk.period_longest, proper_voted = blk.proper_longest;
+  if (blk.period_p >= 2 && voted && (u64)blk.period_p > h_first && (u64)g > blk.period_p) {
+    // The winner may be a multiple of the stretches' period: a list that a sort by windows of the suffix number
+    // has been through holds a group's members in another order than by position.  A period above the first
+    // round's depth defers the step, so it is worth dividing: p / q for the winner's prime factors q, kept while
+    // g stays as long (trial passes: the longest stretches alone, no lengths stored).
+    const u32 winner = blk.period_p, longest_voted = blk.period_longest, proper_voted = blk.proper_longest, g_voted = g;
     u32 rest = winner;
     for (u32 q = 2; q <= rest && blk.period_p / q >= 2; ) {
       if (rest % q) { ++q; continue; }
       rest /= q;
-      u32 longest = 0, proper = 0;
-      rc = stretch_lengths(n, blk.period_p / q, false, &longest, &proper);
-      if (rc) return rc;
-      if (proper >= proper_voted) blk.period_p /= q;
-      else while (rest % q == 0) rest /= q;
+      const int rcb = stretch_lengths(n, blk.period_p / q, false, &blk.period_longest, proper);
+      if (rcb) return rcb;
+      if (g >= g_voted) blk.period_p /= q;
+      else while (rest % q == 0) rest /= q;            // (the same candidate again)
     }
     blk.period_longest = longest_voted; blk.proper_longest = proper_voted;
     if (blk.period_p != winner) {
-      rc = stretch_lengths(n, blk.period_p, !run_due, &blk.period_longest, &blk.proper_longest);
-      if (rc) return rc;
+      const int rcb = stretch_lengths(n, blk.period_p, store, &blk.period_longest, proper);
+      if (rcb) return rcb;
     }
   }
-  if ((u64)blk.period_p <= h_first) {
-    if ((u64)blk.proper_longest <= h_first) return 0;
-    if (run_due) {
-      rc = stretch_lengths(n, blk.period_p, true, &blk.period_longest, &blk.proper_longest);
-      if (rc) return rc;
-      blk.period_ranks_runs = true;
+  bool period_step = false;
+  if (blk.period_p >= 2 && (u64)blk.period_p <= h_first) {
+    if ((u64)g > h_first) {
+      // this round.  Where the run step was due, it is ONE period step over k_p[] instead, which ranks the runs too
+      // (k_p = k_1 for k_1 >= p): the storing pass overwrites k_1[]
+      if (run_due) {
+        const int rcb = stretch_lengths(n, blk.period_p, true, &blk.period_longest, proper);
+        if (rcb) return rcb;
+      }
+      blk.set_step(StretchStep{blk.period_p, StretchStep::kThisRound, 0, run_due});
+      period_step = true;
     }
-    blk.step = StretchStep{blk.period_p, StretchStep::kThisRound, 0};
-  } else if (blk.proper_longest > blk.period_p) {
-    (run_due ? blk.next : blk.step) = StretchStep{blk.period_p, StretchStep::kWaiting, 0};
+  } else if (blk.period_p >= 2 && g > blk.period_p) {
+    blk.schedule(blk.period_p, StretchStep::kWaiting);   // behind the run step, if one is due (step_due)
+    period_step = true;
   }
+  if (!period_step) say_no_period_step(*this, h_first);
   return 0;
 }
 
@@ -3546,7 +3511,7 @@ int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask
   BWTC_HIP_TRY(hipMemsetAsync(d_votes, 0, (size_t)kVoteBins * 4, st));
   BWTC_HIP_TRY(timer.start());
   // (d_runK holds k_1[] where the run step is due: decide_step made it just now)
-  if (mixed_steps && blk.lengths_period == 1 && blk.step.p == 1)
+  if (mixed_steps && blk.lengths_period == 1 && blk.steps[0].p == 1)
     hipLaunchKernelGGL(k_period_votes<true>, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, (const u32*)d_runK);
   else
     hipLaunchKernelGGL(k_period_votes<false>, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, (const u32*)nullptr);
@@ -4429,8 +4394,7 @@ int BwtEngine::test_round(bwtc_hip_round& t) {
   RoundKnobScope knobs(*this, t.pairs_min, t.window_bits);
   blk = BlockSort{};
   blk.fin_active = true; blk.ranks_live = true;
-  blk.step.p = t.run_mode ? t.step_p : 0u;
-  blk.step.depth = t.run_mode == 2 ? t.step_depth : 0u;
+  blk.set_step(StretchStep{t.run_mode ? t.step_p : 0u, StretchStep::kNone, t.run_mode == 2 ? t.step_depth : 0u});
   n_sort_events = 0;
   TestCanaries can;
   BWTC_HIP_TRY(hipMemcpyAsync(d_R1, t.ks, (u64)m * 8, hipMemcpyHostToDevice, st));

@@ -431,7 +431,10 @@ struct BwtEngine {
   struct EmitTarget { u8* out; u32 out_n; u32 n_lf; };
   int suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const EmitTarget* em = nullptr, bool allow_code_keys = true);
   // This block's state: suffix_sort begins a block by assigning BlockSort{} (so does test_finisher), and nothing else resets it.
-  struct StretchStep { u32 p = 0; enum When { kNone, kThisRound, kWaiting } when = kNone; u32 depth = 0; };
+  // A closed-form step (runs and periods, below): its period (1: the run step), when it is due (kWaiting: the first doubling
+  // round whose depth reaches p; kNone: not any more), the depth it ran at (0: it has not), and whether it ranked the runs
+  // too (BWTC_HIP_MIXED: the first round is one period step over k_p[] in place of the run step that was due).
+  struct StretchStep { u32 p = 0; enum When { kNone, kThisRound, kWaiting } when = kNone; u32 depth = 0; bool ranks_runs = false; };
   struct BlockSort {
     u32 parked = 0;            // entries waiting in d_parkS / d_parkHP
     u32 park_holes = 0;        //   of which empty (all ones: they sort to the list's end)
@@ -444,14 +447,20 @@ struct BwtEngine {
     u32 local_m = 0, local_depth = 0; int local_home = 0, passes_done = 0; bool local_pending = false;
     FinRegions local_rg = {}, local_upd = {};   // where the local list lives now; where the last pass's notes lie
     u32 lengths_period = 0;    // the period d_runK's lengths were made for (0: none yet)
-    u32 run_longest = 0; bool run_longest_known = false;   // the longest run, once a pass of period 1 has found it (made at most once per block)
-    StretchStep step;          // its period (1: the run step), when it is due (kWaiting: the first doubling round whose depth reaches p), the depth it ran at (0: it has not)
-    bool period_looked = false;   // a period has been looked for (once per block)
-    // BWTC_HIP_MIXED: the period step that follows the block's run step (kWaiting; it becomes `step` in the round it is
-    // due, step_due), the depth the run step ran at, and the longest proper stretch (0: no pass has made it)
-    StretchStep next;
-    u32 run_depth = 0, proper_longest = 0;
-    bool period_ranks_runs = false;   // the first round is one period step over k_p[] in place of the run step that was due
+    u32 run_longest = 0;       // the longest run, once a pass of period 1 has found it (made at most once per block)
+    u32 proper_longest = 0;    // BWTC_HIP_MIXED: the longest proper stretch (0: no pass has made it)
+    // The block's closed-form steps in the order it takes them (decide_step): today the run step, then one period step,
+    // or either alone.  `current` is the entry whose lengths are in d_runK and whose period and depth the second keys take
+    // (RunKeys): the front, until a step behind it comes due (step_due).
+    static constexpr int kMaxSteps = 2;
+    StretchStep steps[kMaxSteps]; int n_steps = 0, current = 0;
+    void schedule(u32 p, StretchStep::When when) { if (n_steps < kMaxSteps) steps[n_steps++] = StretchStep{p, when}; }
+    void set_step(const StretchStep& s) { steps[0] = s; n_steps = 1; current = 0; }   // the one step, in place of whatever was scheduled
+    StretchStep& current_step() { return steps[current]; }                           // (no step scheduled: one of period 0 and depth 0)
+    // what the block's steps did, for bwtc_hip_period_get, bwtc_hip_steps_get and the debug line: the depth the runs were
+    // ranked at (0: they were not), and the period step that ran (period and depth 0: none did)
+    u32 run_depth() const { for (int i = 0; i < n_steps; ++i) if (steps[i].p == 1 || steps[i].ranks_runs) return steps[i].depth; return 0; }
+    StretchStep period_ran() const { for (int i = 0; i < n_steps; ++i) if (steps[i].p >= 2 && steps[i].depth) return steps[i]; return StretchStep{}; }
     // the candidate period, its longest stretch, its votes: with the step's depth, what bwtc_hip_period_get reports until the next block begins
     u32 period_p = 0, period_longest = 0, period_votes = 0;
   } blk;
@@ -538,8 +547,9 @@ struct BwtEngine {
   // a raw list (suffix; head slot << 32 | slot) in (S, HP) -> a sorted list the rounds understand, in res / rb
   int dress_list(u32 n, u32 total, u32* S, u64* HP, RankBuffers& rb, RankResult* res, u32 holes = 0);
   // runs and periods (bwt_engine.hip, "Runs" / "Periods"): long runs of one byte (period 1) and stretches of a period p > 1
-  // are ranked in closed form by one round, the step.  One step per block, over the one length array d_runK -- or, with
-// BWTC_HIP_MIXED=1, the run step and then one period step, whose lengths replace the runs' in d_runK.
+  // are ranked in closed form by one round, the step.  A block's steps stand in BlockSort::steps in the order it takes them,
+  // over the one length array d_runK: one step per block -- or, with BWTC_HIP_MIXED=1, the run step and then one period
+  // step, whose lengths replace the runs' in d_runK.  decide_step fills the schedule, step_due says which entry is a round's.
   bool run_ranks = true;     // BWTC_HIP_RUNS=0: no run step; the longest run is found only to tell a run from a voted period (decide_step)
   bool period_ranks = true;  // BWTC_HIP_PERIODS=0: no votes, no period-length pass, no period step
   u32 period_forced = 0;     // BWTC_HIP_PERIOD=p: that period, no votes (1: the run path)
@@ -550,8 +560,7 @@ struct BwtEngine {
   // store == false: the longest stretch alone (a trial); proper: the longest proper stretch too (the general form for p = 1)
   int stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* proper = nullptr);
   int find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask);
-  int decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask);   // -> step
-  int decide_mixed(u32 n, u64 h_first, bool run_due);                                    // -> step, next
+  int decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask);   // -> blk.steps
   int long_grams_override = 0;   // BWTC_HIP_LONG_G2=N: N grams in the second key word
   void scatter_rank_pairs(u32* pairs, u32* tmp, u32 m, u32 n);
   int load_text(const u8* d_src, u32 ncopy, u32 n, bool reverse, u32* hist_T);

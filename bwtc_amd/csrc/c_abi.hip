@@ -1124,7 +1124,7 @@ int bwtc_hip_period_get(bwtc_hip_ctx* ctx, uint32_t* p, uint32_t* longest, uint3
   if (p) *p = e.blk.period_p;
   if (longest) *longest = e.blk.period_longest;
   if (votes) *votes = e.blk.period_votes;
-  if (step_depth) *step_depth = e.blk.step.p >= 2 ? e.blk.step.depth : 0;
+  if (step_depth) *step_depth = e.blk.period_ran().depth;
   return 0;
 }
 
@@ -1135,10 +1135,10 @@ int bwtc_hip_steps_get(bwtc_hip_ctx* ctx, uint32_t* run_depth, uint32_t* period_
                        uint32_t* longest_proper) {
   if (!ctx) return -1;
   const BwtEngine::BlockSort& b = ctx->eng.blk;
-  const bool period_ran = b.step.p >= 2 && b.step.depth != 0;
-  if (run_depth) *run_depth = b.step.p == 1 ? b.step.depth : b.run_depth;
-  if (period_p) *period_p = period_ran ? b.step.p : 0;
-  if (period_depth) *period_depth = period_ran ? b.step.depth : 0;
+  const BwtEngine::StretchStep period = b.period_ran();
+  if (run_depth) *run_depth = b.run_depth();
+  if (period_p) *period_p = period.p;
+  if (period_depth) *period_depth = period.depth;
   if (longest_run) *longest_run = b.run_longest;
   if (longest_proper) *longest_proper = b.proper_longest;
   return 0;
