@@ -2422,6 +2422,16 @@ static constexpr int kSmallFreqs = 0, kSmallLf = 256, kSmallPidx = 512, kSmallCo
 // changes speed, never the result.
 struct KeyPlan { int k, bits; u32 sigma; bool wide; u8 lut[256]; };
 
+static int radix_passes(int bits) { return (bits + kRadixBits - 1) / kRadixBits; }
+static u32 depth32(u64 h) { return (u32)std::min<u64>(h, 0xFFFFFFFFull); }   // a depth as the kernels take it
+// rank[] in windows: a block's suffix numbers have `bits` bits; those from `lo` up pick the window (window_bits of
+// them), the eight below them (from bin_shift) the bin inside it
+struct WindowShifts { int bits, lo, bin_shift; };
+static WindowShifts window_shifts(u32 n, int window_bits) {
+  const int bits = bit_width_u64(n ? n - 1 : 0), lo = bits > window_bits ? bits - window_bits : 0;
+  return WindowShifts{bits, lo, lo > 8 ? lo - 8 : 0};
+}
+
 // most characters per 8-bit radix pass for keys of at most `maxbits` bits; ties -> longer key
 static void best_packing(u32 sigma, int maxbits, int* k_out, int* bits_out) {
   double best = -1.0;
@@ -2433,7 +2443,7 @@ static void best_packing(u32 sigma, int maxbits, int* k_out, int* bits_out) {
     int bits = 0;
     for (unsigned __int128 v = pow - 1; v; v >>= 1) ++bits;
     if (bits == 0) bits = 1;
-    const int passes = (bits + kRadixBits - 1) / kRadixBits;
+    const int passes = radix_passes(bits);
     const double ratio = (double)k / passes;
     if (ratio >= best) { best = ratio; *k_out = k; *bits_out = bits; }
   }
@@ -2530,27 +2540,37 @@ static void launch_gather_text(BwtEngine& e, const u32* aidx, const u32* agrp, c
 // destination with two stable radix passes (tmp = another 8*cap-byte region), after which
 // consecutive pairs write into the same 4096-word window of rank[].
 void BwtEngine::scatter_rank_pairs(u32* pairs, u32* tmp, u32 m, u32 n) {
-  const int bits = bit_width_u64(n ? n - 1 : 0);
-  const int lo = bits > window_bits ? bits - window_bits : 0;
+  const WindowShifts w = window_shifts(n, window_bits);
   u32 *ws = pairs, *wr = pairs + cap;
-  if (m >= pairs_min && bits > 12) {
-    sort_pairs<u32>(pairs, tmp, pairs + cap, tmp + cap, m, bits, &ws, &wr, false, lo);
-    stats.alg_bytes += sort_bytes(m, (bits - lo + kRadixBits - 1) / kRadixBits, 8, 4, digit_planes);
+  if (m >= pairs_min && w.bits > 12) {
+    sort_pairs<u32>(pairs, tmp, pairs + cap, tmp + cap, m, w.bits, &ws, &wr, false, w.lo);
+    stats.alg_bytes += sort_bytes(m, radix_passes(w.bits - w.lo), 8, 4, digit_planes);
   }
   stats.alg_bytes += (u64)m * (8 + 4);                   // k_scatter_pairs
-  launch_scatter_pairs(*this, ws, wr, m, lo > 8 ? lo - 8 : 0);
+  launch_scatter_pairs(*this, ws, wr, m, w.bin_shift);
 }
 
 // The ranking kernels' one launch path: rank_step's, and the test hooks' (BwtEngine::test_rank_pass).  A form is what
 // rank_step decides per list: 16-bit suffix halves (split) and long items (lng) -- both only for the initial ranking of
 // 64-bit keys -- the MODE of k_rerank_apply and where a finished suffix's character comes from (RrEmit: 0 nothing is
 // emitted, 1 bits 56..63 of a round's key, 2 T[s-1], 3 the long key's code).  Long items emit with form 3 or not at all,
-// split ones with form 2 or not at all, an initial ranking never with form 1.
+// split ones with form 2 or not at all, an initial ranking never with form 1 (rr_emit_legal).  RrForm::emit is that
+// form, as rank_step (rr_emit_form) or the hook's caller decided it: the launch code takes it as it stands and picks the
+// instantiation by the items' shape and the form.  A form the shape does not have never gets there: rank_step makes none,
+// and the hook refuses it before anything is launched.
 // parts: kRrReduceScan -- the tile reduce and both scan phases, which leave the aggregates in d_aggA/B/C as apply reads
 // them and the two counts in d_small -- and kRrApply; rank_step reads the counts between the two to choose the MODE.
 struct RrForm { bool split, lng; int mode, emit; };
 struct RrOut { u32* rank; u32* SA; u32* aidx; u32* aglob; u32* agrp; u32* pair_s; u32* pair_r; };
 constexpr u32 kRrReduceScan = 1u, kRrApply = 2u;
+static bool rr_emit_legal(bool split, bool lng, bool init, int emit) {
+  return emit == 0 || emit == (lng ? 3 : 2) || (emit == 1 && !lng && !split && !init);
+}
+// long items carry the character's code in the key (3); the initial ranking of other items, and rounds whose keys had
+// no room for it, read T[s-1] (2); rounds find it in bits 56..63 of their key (1)
+static int rr_emit_form(bool emit, bool split, bool lng, bool init, bool carried) {
+  return !emit ? 0 : lng ? 3 : (split || init || !carried) ? 2 : 1;
+}
 
 // both phases of the aggregates' scan over d_aggA/B/C, the parts in d_agg_part, the totals in d_small[kSmallCounts ..]
 static void launch_rerank_scan(BwtEngine& e, u32 tiles) {
@@ -2574,7 +2594,7 @@ template <typename K, bool INIT, int MODE>
 static void launch_rerank_mode(BwtEngine& e, u32 tiles, const RrForm& f, const K* ks, const u32* vs, const u32* aglob, u32 m, u32 n,
                                u32 short_len, K kmask, const RrLong& lg, const RrOut& o, const RrEmit& re) {
   constexpr bool kCanSplit = INIT && sizeof(K) == 8;
-  if (f.lng && f.split) {
+  if (f.lng && f.split) {                               // (the form is legal, rr_emit_legal: long and split items have one that emits)
     if (f.emit) launch_rerank_apply<K, INIT, MODE, 3, kCanSplit, kCanSplit>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
     else launch_rerank_apply<K, INIT, MODE, 0, kCanSplit, kCanSplit>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
   } else if (f.lng) {
@@ -2583,9 +2603,9 @@ static void launch_rerank_mode(BwtEngine& e, u32 tiles, const RrForm& f, const K
   } else if (f.split) {
     if (f.emit) launch_rerank_apply<K, INIT, MODE, 2, kCanSplit, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
     else launch_rerank_apply<K, INIT, MODE, 0, kCanSplit, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
-  } else if (!f.emit) launch_rerank_apply<K, INIT, MODE, 0, false, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
-  else if (INIT || f.emit == 2) launch_rerank_apply<K, INIT, MODE, 2, false, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
-  else launch_rerank_apply<K, INIT, MODE, 1, false, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+  } else if (f.emit == 0) launch_rerank_apply<K, INIT, MODE, 0, false, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+  else if (f.emit == 1) launch_rerank_apply<K, INIT, MODE, 1, false, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
+  else launch_rerank_apply<K, INIT, MODE, 2, false, false>(e, tiles, ks, vs, aglob, m, n, short_len, kmask, lg, o, re);
 }
 template <typename K, bool INIT>
 static void launch_rerank(BwtEngine& e, u32 parts, const RrForm& f, const K* ks, const u32* vs, const u32* aglob, u32 m, u32 n, u32 short_len,
@@ -2609,24 +2629,76 @@ static void launch_rerank(BwtEngine& e, u32 parts, const RrForm& f, const K* ks,
   }
 }
 
-// One ranking step over a sorted list (INIT: all suffixes by their initial key; rounds: the
-// active list by (group, rank[s+h])): new ranks into rank[], finished suffixes out, and -- when
-// anything stays active -- the next round's list, sorted.  Buffers: `rec_free` / `v_free` are
-// an 8*cap-byte region and a 4*cap-byte array nobody uses; `rec_keys` / `v_keys` are the ones
-// that hold ks / vs (free once the apply kernel has run).
+// A block's list between suffix_sort's stages: where it lives (home), what the last ranking step reported (res), the
+// emitter with the spare plane of carried characters, and whether rank[] is complete.
+struct SortList { u32 n; bool emit; BwtEngine::ListHome home; RrEmit re; BwtEngine::RankResult res; u8* achr_other; bool ranks_complete; };
+
+// What differs between the calls of rank_step.  short_len, kmask, split and lg are an initial ranking's (a round's mask
+// follows from whether its keys carry the character: carried_mask); kind and run_mode are a round's.
+enum class RoundKind { kOrdinary, kText, kRaw };   // kText: rank[] is neither read nor (before it is complete) written; kRaw: the list goes back to its owner ungrouped
+struct RankRequest {
+  u32 m = 0;                     // entries of the list
+  u64 h_next = 0;                // the depth the next list's second keys look up at
+  u32 short_len = 0;             // suffixes of at most this length are finished by the initial ranking
+  u64 kmask = ~0ull;             // the key's own bits
+  u32 split = 0;                 // 16-bit suffix halves, the upper bits in the key
+  const RrLong* lg = nullptr;    // long items: the second key word and the fields of the first
+  RoundKind kind = RoundKind::kOrdinary;
+  int run_mode = 0;              // RunKeys::mode of the next list's second keys
+};
+static u64 carried_mask(bool carried) { return carried ? (1ull << 56) - 1ull : ~0ull; }   // a round's keys: the character rides in bits 56..63
+
+// The next list, shared by the routes that make one: the key kernel has left its keys in (ka, va) -- among them `holes`
+// finished entries where drop_holes says that the sort's first pass drops them -- and they are sorted between (ka, va) and
+// (kb, vb); the passes are counted, with key_bytes for what the route moved before the sort, and L.home moves to where
+// the sort ended.  timed: between two of the block's sort events (while there are any left), with the probe.
+int BwtEngine::next_list(SortList& L, u64* ka, u64* kb, u32* va, u32* vb, u32 m_next, int bits, u32 holes, bool drop_holes, u64 key_bytes, bool timed) {
+  const bool events = timed && n_sort_events + 2 <= kMaxSortEvents;
+  u64* ks = nullptr; u32* vs = nullptr;
+  if (events) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], stream));
+  sort_pairs<u64>(ka, kb, va, vb, m_next, bits, &ks, &vs, timed, 0, (u64)holes);
+  if (events) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], stream));
+  // the hole-dropping first pass reads every entry and writes the active ones; the others are plain passes
+  const int plain = drop_holes ? std::max(0, radix_passes(bits) - 1) : radix_passes(bits);
+  const u64 all = (u64)m_next + holes;
+  stats.sort_pass_items += (drop_holes ? all : 0) + (u64)m_next * (u64)plain;
+  stats.alg_bytes += key_bytes + (drop_holes ? all * (8 + 12) + (u64)m_next * 12 : 0) + sort_bytes(m_next, plain, 12, 8, digit_planes);
+  L.home.advance(ks, vs);
+  return 0;
+}
+
+// One ranking step over the sorted list in L.home (INIT: all suffixes by their initial key; rounds: the active list by
+// (group, rank[s+h])): new ranks into rank[], finished suffixes out, and -- when anything stays active -- the next
+// round's list, sorted, with L.home moved to it.  In three parts: decide (reduce and scan, the one read-back of the
+// counts, the bit widths and the route), apply (one launch_rerank, its MODE and outputs by the route), and the next list
+// (a key kernel by the route, then next_list).  L.res is what the step reports; L.home stays where it was when nothing
+// stays active and in the routes that hand the list on raw -- in (home.v_free, home.slots_next, d_GRP) --, kFinish and
+// kRaw.  L.re is copied: what the dense route sets in it is this call's.
+//   kFinish   long items with an emitter: the finisher takes what is tied, rank[] is not written (MODE 3)
+//   kDense    most of a long list stays active: window-ordered records (MODE 2)
+//   kRaw      a round that may neither read the text nor double: the list back to its owner (MODE 3)
+//   kTextRun  the run step before rank[] is complete: closed-form second keys, the others keep their groups (MODE 0)
+//   kText     the next list's keys are characters of the text (MODE 0)
+//   kPairs    list order, the new ranks as pairs through scatter_rank_pairs (MODE 1)
+//   kShort    list order, rank[] written by apply (MODE 0)
+enum class Route { kFinish, kDense, kRaw, kTextRun, kText, kPairs, kShort };
 template <typename K, bool INIT>
-int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len, K kmask,
-                         RankBuffers& rb, RrEmit re, bool emit, u64 h_next, RankResult* res, u32 split,
-                         const RrLong* lg, bool text, bool carry_in, bool raw_out, int run_mode) {
-  hipStream_t st = stream;
-  const u32* counts = d_small + kSmallCounts;
+int BwtEngine::rank_step(SortList& L, const RankRequest& rq) {
   constexpr bool kCanSplit = INIT && sizeof(K) == 8;
-  const bool lng = kCanSplit && lg && lg->w;              // items of the long-key sort (split: 16-bit values + upper bits in the key)
-  const RrLong lgv = lng ? *lg : RrLong();
-  const RrForm form{split != 0, lng, 0, 0};
-  launch_rerank<K, INIT>(*this, kRrReduceScan, form, ks, vs, (const u32*)nullptr, m, n, short_len, kmask, lgv, RrOut{}, re);
-  // how much stays active decides the route, so the counts are read before the apply kernel
-  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallCounts, counts, 12, hipMemcpyDeviceToHost, st));
+  ListHome& home = L.home;
+  RankResult& res = L.res;
+  RrEmit re = L.re;
+  const u32 m = rq.m, n = L.n;
+  const bool emit = L.emit, split = rq.split != 0;
+  const bool carried = !INIT && res.carry;                // this list's keys hold the characters in bits 56..63 (only an emitting list's do)
+  const K* ks = static_cast<const K*>(home.keys);
+  const K kmask = INIT ? (K)rq.kmask : (K)carried_mask(carried);
+  const bool lng = kCanSplit && rq.lg && rq.lg->w;        // items of the long-key sort (split: 16-bit values + upper bits in the key)
+  const RrLong lgv = lng ? *rq.lg : RrLong();
+
+  // ---- decide: how much stays active decides the route, so the counts are read before the apply kernel
+  launch_rerank<K, INIT>(*this, kRrReduceScan, RrForm{split, lng, 0, 0}, ks, home.vals, (const u32*)nullptr, m, n, rq.short_len, kmask, lgv, RrOut{}, re);
+  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallCounts, d_small + kSmallCounts, 12, hipMemcpyDeviceToHost, stream));
   BWTC_HIP_TRY(wait());
   if (h_small[kSmallError] & 1u) { std::fprintf(stderr, "bwtc_hip: chained radix sort timed out\n"); return -3; }
   if (h_small[kSmallError]) return -3;                  // (2: k_code_build -- suffix_sort retries the block with gram keys)
@@ -2637,138 +2709,81 @@ int BwtEngine::rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len
     const u64 in_bytes = sizeof(K) + (lng ? 2 + 4 : split ? 2 : 4) + (INIT ? 0 : 4);
     stats.alg_bytes += (u64)m * in_bytes * 2 + (u64)(m - m_next) * 5 + (u64)m_next * 13;
   }
-  res->m = m_next;
-  res->groups = groups;
-  const int b2 = rank_bits(n);
-  const int b1 = bit_width_u64(groups ? groups - 1 : 0);
-  const int nbits = b1 + b2;
+  const int b2 = rank_bits(n), b1 = bit_width_u64(groups ? groups - 1 : 0);
+  // the run step's second key takes one bit more than a rank (RunKeys); a key that would not fit 64 bits: an ordinary round
+  const bool run_now = !INIT && rq.run_mode == 1 && b1 + b2 + 1 <= 64;
+  const int b2k = run_now ? b2 + 1 : b2;
+  const int kbits = b1 + b2k;
+  const StretchStep& step = blk.current_step();
+  const RunKeys rkeys{d_runK, run_now ? 0u : step.depth, run_now ? 1 : (rq.run_mode == 2 ? 2 : 0), step.p};
   // a key of more than 56 bits has no room for the carried character (blocks above 256 MiB with many groups): the
   // next list then goes without, and its ranking reads T[s-1] for what it finishes
-  // the run step's second key takes one bit more than a rank (RunKeys); a key that would not fit 64 bits: an ordinary round
-  const bool run_now = !INIT && run_mode == 1 && nbits + 1 <= 64;
-  res->ran_run = run_now;
-  const int b2k = run_now ? b2 + 1 : b2;
-  const int kbits = run_now ? nbits + 1 : nbits;
-  const StretchStep& step = blk.current_step();
-  const RunKeys rkeys{d_runK, run_now ? 0u : step.depth, run_now ? 1 : (run_mode == 2 ? 2 : 0), step.p};
   const bool carry_next = emit && kbits <= 56;
-  res->carry = carry_next;
-  const bool dense = !text && dense_route && m_next > 0 && (u64)m_next * 2 >= m && m >= pairs_min && !use_sweep;
-  u32* sa_out = (emit && !blk.fin_active) ? nullptr : d_SA;   // finisher route: the bridge will want the finished suffixes' slots
-  u32* rank_arg = (text && !blk.ranks_live) ? nullptr : d_rank;   // text rounds before rank[] is completed: neither complete nor needed; after: kept exact
+  const bool text = rq.kind != RoundKind::kOrdinary;      // no look-ups in rank[]
   // Long items of which at most half is still tied (a 256 MiB text block: 21 %, a 1 GiB one: 37 %): the finisher
   // settles the rest by direct comparison (suffix_sort); rank[] is not written at all.  Above that the list is
   // dominated by long repeats and the doubling rounds are the better tool.
   // (with the last gram's low bits left out of the sort -- long_drop -- the list also holds what those bits would have
   // told apart: the bound is three fifths then)
-  res->finish = lng && emit && finisher;
-  if (res->finish) {
-    sa_out = d_SA;
-    blk.fin_active = true;
-    if constexpr (kCanSplit)
-      launch_rerank<K, INIT>(*this, kRrApply, RrForm{split != 0, true, 3, 3}, ks, vs, (const u32*)rb.aglob, m, n, short_len, kmask, lgv,
-                             RrOut{d_rank, sa_out, rb.v_free, rb.aglob_next, d_GRP, nullptr, nullptr}, re);
-    res->carry = true;
-    return 0;
-  }
-  u64* recA = static_cast<u64*>(rb.rec_free);
-  u64* recB = static_cast<u64*>(rb.rec_keys);
+  const Route route = lng && emit && finisher ? Route::kFinish
+                      : !text && dense_route && m_next > 0 && (u64)m_next * 2 >= m && m >= pairs_min && !use_sweep ? Route::kDense
+                      : rq.kind == RoundKind::kRaw ? Route::kRaw
+                      : text ? (run_now && m_next > 0 ? Route::kTextRun : Route::kText)
+                      : (m >= pairs_min || INIT) ? Route::kPairs : Route::kShort;
+  const bool raw_list = route == Route::kFinish || route == Route::kRaw;
+  res.m = m_next; res.groups = groups;
+  res.ran_run = run_now; res.finish = route == Route::kFinish;
+  // (the keys of the lists that the finisher's bridge and the text kernel make carry the character whenever there is an emitter)
+  res.carry = route == Route::kFinish ? true : (route == Route::kRaw || route == Route::kText) ? emit : carry_next;
+  if (route == Route::kText || route == Route::kTextRun) res.text_chars = route == Route::kText ? (u32)std::min(6, (56 - b1 - 4) / 8) : 0u;
 
-  // Where a finished suffix's character comes from (see RrEmit): long items carry its code in the key (3); the
-  // initial ranking of other items, and rounds whose keys had no room for it, read T[s-1] (2); rounds find it in
-  // bits 56..63 of their key (1); 0: nothing is emitted.
-  const int emit_form = !emit ? 0 : lng ? 3 : (split || INIT || !carry_in) ? 2 : 1;
-  auto apply = [&](int mode, u32* ps, u32* pr, u32* aidx) {
-    launch_rerank<K, INIT>(*this, kRrApply, RrForm{split != 0, lng, mode, emit_form}, ks, vs, (const u32*)rb.aglob, m, n, short_len, kmask, lgv,
-                           RrOut{rank_arg, sa_out, aidx, rb.aglob_next, d_GRP, ps, pr}, re);
-  };
-  if (dense) {
-    u32* tri_key = reinterpret_cast<u32*>(recA);
-    // records partitioned by the top 16 bits of s (bits 32.. of the record), two stable passes
-    const int bits = bit_width_u64(n ? n - 1 : 0);
-    const int lo = bits > window_bits ? bits - window_bits : 0;
-    re.rec_plane = digit_planes ? d_P0 : nullptr;
-    re.rec_shift = lo;
-    apply(2, tri_key, rb.v_free, nullptr);
-    u64* ws = nullptr; u32* wv = nullptr;
-    sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m, 32 + bits, &ws, &wv, false, 32 + lo, 0, true);
-    u64* ws_other = ws == recA ? recB : recA;
-    u32* wv_other = wv == rb.v_free ? rb.v_keys : rb.v_free;
-    const int bin_shift = lo > 8 ? lo - 8 : 0;           // the eight bits of s below the window bits
-    launch_scatter_dense(*this, (const u64*)ws, m, bin_shift);
-    launch_gather_dense(*this, ws, wv, m, n, (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k, carry_next ? 1 : 0, bin_shift, rkeys);
-    const bool timed = n_sort_events + 2 <= kMaxSortEvents;
-    if (timed) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-    sort_pairs<u64>(ws, ws_other, wv, wv_other, m_next, kbits, &res->ks, &res->vs, true, 0, (u64)(m - m_next));
-    if (timed) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-    stats.sort_pass_items += (u64)m + (u64)m_next * (u64)std::max(0, (kbits + kRadixBits - 1) / kRadixBits - 1);
-    {
-      const int P = (kbits + kRadixBits - 1) / kRadixBits;
-      stats.alg_bytes += sort_bytes(m, 2, 12, 8, digit_planes)                         // window partition of the records
-                         + (u64)m * (12 + 4) + (u64)m * (12 + 4 + 1 + 12)             // k_scatter_dense, k_gather_dense
-                         + (rkeys.mode ? (u64)m_next * (4 + (run_now ? 1 : 0)) : 0)    //   ... and k[], the byte behind the run
-                         + (u64)m * (8 + 12) + (u64)m_next * 12                        // hole-dropping first pass
-                         + sort_bytes(m_next, std::max(0, P - 1), 12, 8, digit_planes);
-    }
-    res->rec_other = res->ks == recA ? recB : recA;
-    res->v_other = res->vs == rb.v_free ? rb.v_keys : rb.v_free;
-    return 0;
-  }
+  // ---- apply: new ranks, finished suffixes out, what stays active raw into (v_free, slots_next, d_GRP)
+  u64* recA = static_cast<u64*>(home.rec_free);
+  u64* recB = static_cast<u64*>(home.rec_keys);
   u32* pairs = reinterpret_cast<u32*>(recA);
-  if (raw_out) {
-    // the list goes back to its owner as it is now grouped: suffix, slot, head slot (rb.v_free, rb.aglob_next, d_GRP)
-    apply(3, nullptr, nullptr, rb.v_free);
-    res->carry = emit;
-    return 0;
-  }
-  if (text) {
-    // text round: rank[] is neither complete nor needed
-    res->text_chars = (u32)std::min(6, (56 - b1 - 4) / 8);
-    apply(0, nullptr, nullptr, rb.v_free);
-    res->carry = emit;
-    if (m_next == 0) return 0;
-    if (run_now) {
-      // the run step before rank[] is complete: the members without a long run keep their groups (key 0)
-      res->carry = carry_next;
-      launch_gather_key2(*this, (const u32*)rb.v_free, (const u32*)d_GRP, (const u32*)nullptr, carry_next ? (const u8*)re.achr_out : (const u8*)nullptr,
-                         recA, m_next, n, (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k, rkeys);
-      sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m_next, kbits, &res->ks, &res->vs, false);
-      stats.sort_pass_items += (u64)m_next * (u64)((kbits + kRadixBits - 1) / kRadixBits);
-      stats.alg_bytes += (u64)m_next * (4 + 4 + 4 + 1 + 1 + 8) + sort_bytes(m_next, (kbits + kRadixBits - 1) / kRadixBits, 12, 8, digit_planes);
-      res->text_chars = 0;
-      res->rec_other = res->ks == recA ? recB : recA;
-      res->v_other = res->vs == rb.v_free ? rb.v_keys : rb.v_free;
-      return 0;
+  const WindowShifts w = window_shifts(n, window_bits);
+  const int mode = route == Route::kDense ? 2 : route == Route::kPairs ? 1 : raw_list ? 3 : 0;
+  if (route == Route::kFinish) blk.fin_active = true;
+  // dense: records partitioned by the top 16 bits of s (bits 32.. of the record), two stable passes: apply leaves the first one's digits
+  if (route == Route::kDense) { re.rec_plane = digit_planes ? d_P0 : nullptr; re.rec_shift = w.lo; }
+  u32* sa_out = (emit && !blk.fin_active) ? nullptr : d_SA;   // finisher route: the bridge will want the finished suffixes' slots
+  u32* rank_arg = (text && !blk.ranks_live) ? nullptr : d_rank;   // text rounds before rank[] is completed: neither complete nor needed; after: kept exact
+  launch_rerank<K, INIT>(*this, kRrApply, RrForm{split, lng, mode, rr_emit_form(emit, split, lng, INIT, carried)}, ks, home.vals, (const u32*)home.slots,
+                         m, n, rq.short_len, kmask, lgv,
+                         RrOut{rank_arg, sa_out, mode == 2 ? nullptr : home.v_free, home.slots_next, d_GRP, (mode == 1 || mode == 2) ? pairs : nullptr,
+                               mode == 1 ? pairs + cap : mode == 2 ? home.v_free : nullptr}, re);
+  if (route == Route::kPairs) scatter_rank_pairs(pairs, reinterpret_cast<u32*>(recB), m, n);
+  if (raw_list || m_next == 0) return 0;
+
+  // ---- the next list: its keys by the route, then the sort
+  const u8* achr = carry_next ? (const u8*)re.achr_out : (const u8*)nullptr;
+  const u32 run_bytes = rkeys.mode ? 4u + (run_now ? 1u : 0u) : 0u;      // k[], and the byte behind the run
+  switch (route) {
+    case Route::kDense: {
+      u64* ws = nullptr; u32* wv = nullptr;
+      sort_pairs<u64>(recA, recB, home.v_free, home.vals, m, 32 + w.bits, &ws, &wv, false, 32 + w.lo, 0, true);
+      home.sorted_into(ws, wv);                           // the records in window order: what is sorted next, their partners free
+      launch_scatter_dense(*this, (const u64*)ws, m, w.bin_shift);
+      launch_gather_dense(*this, ws, wv, m, n, depth32(rq.h_next), b2k, carry_next ? 1 : 0, w.bin_shift, rkeys);
+      const u64 bytes = sort_bytes(m, 2, 12, 8, digit_planes)                     // window partition of the records
+                        + (u64)m * (12 + 4) + (u64)m * (12 + 4 + 1 + 12)          // k_scatter_dense, k_gather_dense
+                        + (u64)m_next * run_bytes;
+      return next_list(L, ws, static_cast<u64*>(home.rec_free), wv, home.v_free, m_next, kbits, m - m_next, true, bytes, true);
     }
-    const int tbits = b1 + 8 * (int)res->text_chars + 4;
-    launch_gather_text(*this, (const u32*)rb.v_free, (const u32*)d_GRP, emit ? (const u8*)re.achr_out : (const u8*)nullptr, recA, m_next, n,
-                       (u32)h_next, res->text_chars, rkeys);
-    sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m_next, tbits, &res->ks, &res->vs, false);
-    stats.sort_pass_items += (u64)m_next * (u64)((tbits + kRadixBits - 1) / kRadixBits);
-    stats.alg_bytes += (u64)m_next * (4 + 4 + 1 + 16 + 8 + (rkeys.mode ? 4 : 0)) + sort_bytes(m_next, (tbits + kRadixBits - 1) / kRadixBits, 12, 8, digit_planes);
-    stats.route |= 4u;
-    res->rec_other = res->ks == recA ? recB : recA;
-    res->v_other = res->vs == rb.v_free ? rb.v_keys : rb.v_free;
-    return 0;
+    case Route::kTextRun:
+      // the members without a long run keep their groups (key 0)
+      launch_gather_key2(*this, (const u32*)home.v_free, (const u32*)d_GRP, (const u32*)nullptr, achr, recA, m_next, n, depth32(rq.h_next), b2k, rkeys);
+      return next_list(L, recA, recB, home.v_free, home.vals, m_next, kbits, 0u, false, (u64)m_next * (4 + 4 + 4 + 1 + 1 + 8), false);
+    case Route::kText:
+      launch_gather_text(*this, (const u32*)home.v_free, (const u32*)d_GRP, emit ? (const u8*)re.achr_out : (const u8*)nullptr, recA, m_next, n,
+                         (u32)rq.h_next, res.text_chars, rkeys);
+      stats.route |= 4u;
+      return next_list(L, recA, recB, home.v_free, home.vals, m_next, b1 + 8 * (int)res.text_chars + 4, 0u, false,
+                       (u64)m_next * (4 + 4 + 1 + 16 + 8 + (rkeys.mode ? 4 : 0)), false);
+    default:
+      launch_gather_key2(*this, (const u32*)home.v_free, (const u32*)d_GRP, (const u32*)d_rank, achr, recA, m_next, n, depth32(rq.h_next), b2k, rkeys);
+      return next_list(L, recA, recB, home.v_free, home.vals, m_next, kbits, 0u, false, (u64)m_next * (4 + 4 + 4 + 1 + 8 + run_bytes), true);
   }
-  if (m >= pairs_min || INIT) {
-    apply(1, pairs, pairs + cap, rb.v_free);
-    scatter_rank_pairs(pairs, reinterpret_cast<u32*>(recB), m, n);
-  } else {
-    apply(0, nullptr, nullptr, rb.v_free);
-  }
-  if (m_next == 0) return 0;
-  launch_gather_key2(*this, (const u32*)rb.v_free, (const u32*)d_GRP, (const u32*)d_rank, carry_next ? (const u8*)re.achr_out : (const u8*)nullptr,
-                     recA, m_next, n, (u32)(h_next > 0xFFFFFFFFull ? 0xFFFFFFFFu : h_next), b2k, rkeys);
-  const bool timed = n_sort_events + 2 <= kMaxSortEvents;
-  if (timed) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-  sort_pairs<u64>(recA, recB, rb.v_free, rb.v_keys, m_next, kbits, &res->ks, &res->vs, true);
-  if (timed) BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-  stats.sort_pass_items += (u64)m_next * (u64)((kbits + kRadixBits - 1) / kRadixBits);
-  stats.alg_bytes += (u64)m_next * (4 + 4 + 4 + 1 + 8 + (rkeys.mode ? 4 + (run_now ? 1 : 0) : 0)) + sort_bytes(m_next, (kbits + kRadixBits - 1) / kRadixBits, 12, 8, digit_planes);
-  res->rec_other = res->ks == recA ? recB : recA;
-  res->v_other = res->vs == rb.v_free ? rb.v_keys : rb.v_free;
-  return 0;
 }
 
 // Decides whether the initial key is made of dense gram codes (K2g) and, if so, leaves the code
@@ -2808,8 +2823,8 @@ int BwtEngine::plan_grams(const KeyPlan& plan, u32 n, const u8* d_lut, GramPlan*
   if (g_max < 1) return 0;
   int G = std::min(g_max, (plan.k + g - 1) / g);
   if (gram_count_override > 0) G = std::min(g_max, gram_count_override);
-  const int passes = (b * G + kRadixBits - 1) / kRadixBits;
-  const int base_passes = (plan.bits + kRadixBits - 1) / kRadixBits;
+  const int passes = radix_passes(b * G);
+  const int base_passes = radix_passes(plan.bits);
   // fewer passes for at least as many characters, or the same passes for more
   const bool better = (g * G >= plan.k && passes < base_passes) || (g * G > plan.k && passes <= base_passes);
   if (debug_on())
@@ -2866,9 +2881,6 @@ int BwtEngine::test_code_stage(u32 parts, u32 n, const u32* hist, bool lone_sent
                            split_now, ck);
 }
 
-// A block's list between suffix_sort's stages: what the last ranking step left (res), the arrays the next one takes (rb),
-// the emitter with the spare plane of carried characters, and whether rank[] is complete.
-struct SortList { u32 n; bool emit; BwtEngine::RankBuffers rb; RrEmit re; BwtEngine::RankResult res; u8* achr_other; bool ranks_complete; };
 // What the stages of the initial sort share: the block, its key plan and where the key makers write.
 struct InitialSort {
   u32 n; const u32* hist; bool lone_sentinel; const KeyPlan& plan; const u8* d_lut;
@@ -2879,15 +2891,15 @@ struct InitialSort {
 static const LongKey kNoLongKey{nullptr, 0, -1, 0, 48, 0, 0};   // one key word: no second one, the suffix number's upper bits from bit 48
 static constexpr int kCodeTableFull = -1000;   // initial_long -> suffix_sort, and no further: the block is sorted again, with gram keys
 
-// the sorted keys and values reach the ranking step: the arrays the sort ended in, and their partners as free space
-static void hand_over(const BwtEngine& e, BwtEngine::RankBuffers& rb, void* ks, void* ka, void* kb, u32* vs) {
-  rb.rec_keys = ks; rb.rec_free = ks == ka ? kb : ka;
-  rb.v_keys = vs; rb.v_free = vs == e.d_V0 ? e.d_V1 : e.d_V0;
+// the sorted keys and values reach the ranking step: the arrays the sort ended in (between the regions ka / kb and
+// d_V0 / d_V1), their partners as free space; the list has no slots of its own, the next one's go to d_G0
+static void hand_over(const BwtEngine& e, SortList& L, void* ka, void* kb, const void* ks, u32* vs) {
+  L.home = BwtEngine::ListHome::sorted(ka, kb, e.d_V0, e.d_V1, e.d_G1, e.d_G0, ks, vs);
 }
 
 // the passes of an initial sort over keys of key_bits bits, and what they and the key maker move
 static void count_initial_sort(BwtEngine& e, u32 n, int key_bits, bool wide) {
-  const int passes = (key_bits + kRadixBits - 1) / kRadixBits;
+  const int passes = radix_passes(key_bits);
   e.stats.sort_pass_items += (u64)n * (u64)passes;
   // items of (u64, u32 or u16 + upper bits in the key) / (u32, u32)
   if (key_bits) e.stats.alg_bytes += (u64)n * (1 + (u64)(wide ? 8 : 4) + 1) + sort_bytes(n, passes, wide ? 12 : 8, wide ? 8 : 4, e.digit_planes);
@@ -2933,8 +2945,10 @@ int BwtEngine::initial_keys32(const InitialSort& in, SortList& L, u64 h) {
   u32* ks = nullptr; u32* vs = nullptr;
   sort_pairs<u32>(ka, kb, d_V0, d_V1, in.n, in.plan.bits, &ks, &vs, true, 0, 0, in.key_plane != nullptr, in.implied_idx);
   BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], stream));
-  hand_over(*this, L.rb, d_R1, d_R1, d_R2, vs);         // both 32-bit key arrays live in R1
-  const int rc = rank_step<u32, true>(ks, vs, in.n, in.n, (u32)in.plan.k, ~0u, L.rb, L.re, L.emit, h, &L.res);
+  hand_over(*this, L, d_R1, d_R2, ks, vs);              // both 32-bit key arrays live in R1
+  RankRequest rq;
+  rq.m = in.n; rq.h_next = h; rq.short_len = (u32)in.plan.k;
+  const int rc = rank_step<u32, true>(L, rq);
   if (rc) return rc;
   count_initial_sort(*this, in.n, in.plan.bits, false);
   return 0;
@@ -2978,8 +2992,11 @@ int BwtEngine::initial_keys64(const InitialSort& in, const GramPlan& gp, int key
     sort_pairs<u64>(ka, kb, d_V0, d_V1, n, key_bits, &ks, &vs, true, 0, 0, in.key_plane != nullptr, in.implied_idx);
   }
   BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], stream));
-  hand_over(*this, L.rb, ks, ka, kb, vs);
-  const int rc = rank_step<u64, true>(ks, vs, n, n, short_len, split ? ((1ull << 48) - 1ull) : ~0ull, L.rb, L.re, L.emit, h, &L.res, (u32)split);
+  hand_over(*this, L, ka, kb, ks, vs);
+  RankRequest rq;
+  rq.m = n; rq.h_next = h; rq.short_len = short_len; rq.split = (u32)split;
+  rq.kmask = split ? (1ull << 48) - 1ull : ~0ull;       // (split: the suffix numbers' upper bits lie above)
+  const int rc = rank_step<u64, true>(L, rq);
   if (rc) return rc;
   count_initial_sort(*this, n, key_bits, true);
   return 0;
@@ -3040,9 +3057,11 @@ int BwtEngine::initial_long(const InitialSort& in, const GramPlan& gp, int key_b
             : long_items_per_thread == 6 ? sort_long_as<unsigned short, 6>(*this, ka, kb, n, key_bits, w_bits, &ks, &ws)
                                          : sort_long_as<unsigned short, 8>(*this, ka, kb, n, key_bits, w_bits, &ks, &ws);
   BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], st));
-  hand_over(*this, L.rb, ks, ka, kb, vs);
+  hand_over(*this, L, ka, kb, ks, vs);
   lg.w = ws; lg.wmask = w_bits >= 32 ? ~0u : (1u << w_bits) - 1u;
-  const int rc = rank_step<u64, true>(ks, vs, n, n, short_len, (1ull << key_bits) - 1ull, L.rb, L.re, L.emit, *h, &L.res, (u32)split_now, &lg);
+  RankRequest rq;
+  rq.m = n; rq.h_next = *h; rq.short_len = short_len; rq.kmask = (1ull << key_bits) - 1ull; rq.split = (u32)split_now; rq.lg = &lg;
+  const int rc = rank_step<u64, true>(L, rq);
   if (rc == -3 && coded && (h_small[kSmallError] & 2u)) {
     // a codeword came out longer than the table's fields hold (k_code_build): nothing has been emitted yet --
     // this block again, with gram keys (suffix_sort, allow_code_keys == false)
@@ -3051,7 +3070,7 @@ int BwtEngine::initial_long(const InitialSort& in, const GramPlan& gp, int key_b
     return kCodeTableFull;
   }
   if (rc) return rc;
-  const int long_passes = (key_bits + w_bits + kRadixBits - 1) / kRadixBits;
+  const int long_passes = radix_passes(key_bits + w_bits);
   stats.sort_pass_items += (u64)n * (u64)long_passes;
   stats.alg_bytes += (u64)n * (1 + 12 + 1)               // the key maker: T read, key + second word + first plane written (the values are made up by the first pass)
                      + sort_bytes(n, long_passes, split_now ? 14 : 16, 8, true);
@@ -3090,13 +3109,13 @@ int BwtEngine::step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool
   return 0;
 }
 
-// The rounds over the sorted list in L.res / L.rb, from depth h0 until nothing is tied.  text_rounds_now: rounds that compare
+// The rounds over the sorted list in L.home, from depth h0 until nothing is tied.  text_rounds_now: rounds that compare
 // the text itself first (finisher route: rank[] is not complete, and completing it costs an ISA scatter of the whole block).
-// doubling == false: text rounds only; what they leave tied comes back raw in (rb.v_free, rb.aglob_next, d_GRP) --
+// doubling == false: text rounds only; what they leave tied comes back raw in (home.v_free, home.slots_next, d_GRP) --
 // suffix, slot, head slot -- *left entries at depth *h_left.
 int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool keep_first, bool doubling, u32* left, u64* h_left) {
   const u32 n = L.n;
-  RankBuffers& rb = L.rb;
+  ListHome& home = L.home;
   RankResult& res = L.res;
   RrEmit& re = L.re;
   u64 h = h0;
@@ -3106,7 +3125,7 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
   // it is the first round's or waits for a deeper one
   const u64 h_first = keep_first ? h0 : h0 * 2;
   if (doubling && m > 0) {
-    const int rcs = decide_step(n, m, h_first, res.ks, res.vs, (L.emit && res.carry) ? ((1ull << 56) - 1ull) : ~0ull);
+    const int rcs = decide_step(n, m, h_first, static_cast<const u64*>(home.keys), home.vals, carried_mask(res.carry));
     if (rcs) return rcs;
   }
   int text_extra = text_rounds_fixed ? 0 : 12;        // further ones, one at a time, while the list is short (not when BWTC_HIP_TEXT_ROUNDS says how many)
@@ -3128,7 +3147,7 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
     if (!text && !raw && !L.ranks_complete) {
       // the doubling rounds start here: rank[] for everybody first (the finished from SA; the list's own
       // ranks come from the ranking step below, before anything reads them; a parked list's are its groups' heads)
-      complete_ranks(n, res.vs, rb.aglob_next, m, res.rec_other == d_R2 ? (res.ks == (u64*)d_R1 ? (void*)d_W0 : d_R1) : d_R2, res.rec_other);
+      complete_ranks(n, home.vals, home.slots, m, home.spare_region(d_R2, d_R1, d_W0), home.rec_free);
       L.ranks_complete = true;
       blk.ranks_live = true;
       stats.route |= 8u;
@@ -3137,24 +3156,20 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
     // what the local list's last pass noted reaches rank[] now: before this round's look-ups, after the last round's
     if (!text && !raw) { const int rcu = local_updates(); if (rcu) return rcu; }
     if (m == 0) { const int rcl = local_pass(n, 0, re); if (rcl) return rcl; continue; }   // only the local list is left
-    // the list just sorted: positions are the active list's, aglob gives their global slots
-    rb.aglob = rb.aglob_next;
-    rb.aglob_next = rb.aglob == d_G0 ? d_G1 : d_G0;
+    // the list just sorted lies in L.home (positions are the active list's, home.slots gives their global slots); the
+    // characters of what stays active go to the plane the list's own do not lie in
     std::swap(re.achr_out, L.achr_other);
-    rb.rec_keys = res.ks; rb.rec_free = res.rec_other;
-    rb.v_keys = res.vs; rb.v_free = res.v_other;
-    const u64* ks = res.ks; const u32* vs = res.vs;
-    const bool carried = L.emit && res.carry;           // this list's keys hold the characters in bits 56..63
-    // the second keys (RunKeys::mode): the run step, a round behind one, or no runs in play
-    const int rc2 = rank_step<u64, false>(ks, vs, m, n, 0u, carried ? ((1ull << 56) - 1ull) : ~0ull, rb, re, L.emit, h, &res, 0u, nullptr, text || raw, carried, raw,
-                                          run_req ? 1 : step.depth ? 2 : 0);
+    RankRequest rq;
+    rq.m = m; rq.h_next = h; rq.kind = raw ? RoundKind::kRaw : text ? RoundKind::kText : RoundKind::kOrdinary;
+    rq.run_mode = run_req ? 1 : step.depth ? 2 : 0;     // the second keys (RunKeys::mode): the run step, a round behind one, or no runs in play
+    const int rc2 = rank_step<u64, false>(L, rq);
     if (rc2) return rc2;
     m = res.m;
     const bool ran = run_req && res.ran_run;
     if (period_req && !ran) say_no_period_step(*this, h_first);   // (the key had no room for the step's bit: an ordinary round)
     if (ran) {
       // the list is sorted to depth h still: a run's members by their closed-form keys, the others as they were (or by rank[s + h])
-      step.depth = (u32)std::min<u64>(h, 0xFFFFFFFFull);
+      step.depth = depth32(h);
       stats.route |= period_req ? 256u : 32u;
       if (step.ranks_runs) stats.route |= 32u;           // (BWTC_HIP_MIXED: one step over k_p[] ranked the runs too)
       keep_h = true;
@@ -3208,15 +3223,15 @@ hipError_t BwtEngine::finisher_begin(u32* S, FinList* a, FinList* b) {
 int BwtEngine::finisher_route(SortList& L, u32 n_lf) {
   hipStream_t st = stream;
   const u32 n = L.n;
-  RankBuffers& rb = L.rb;
+  ListHome& home = L.home;
   RankResult& res = L.res;
   if (L.re.lf_n == 0 && n_lf > 1) return -3;
   blk.lf_noted = true;                     // every suffix that becomes final notes its LF power (lf_note), in every route
   L.ranks_complete = false;
   u32* cnt = d_small + kSmallFin;
   FinList la, lb;
-  BWTC_HIP_TRY(finisher_begin(rb.v_free, &la, &lb));
-  FinShallow shal{rb.v_keys, static_cast<u64*>(rb.rec_free), cnt + 4, fin_floor};
+  BWTC_HIP_TRY(finisher_begin(home.v_free, &la, &lb));
+  FinShallow shal{home.vals, static_cast<u64*>(home.rec_free), cnt + 4, fin_floor};
   FinOutcome fo;
   // Groups of hundreds of members on average (a period, one text many times over) are not the finisher's: its loop
   // costs a group's size per member.  The list then goes to the rounds as it is (shallow groups apart).
@@ -3245,17 +3260,17 @@ int BwtEngine::finisher_route(SortList& L, u32 n_lf) {
   if (shallow) {
     // The few hard groups of little depth first, on their own: text rounds only (rank[] must not go live while
     // finisher passes are still to come); what they leave tied joins the waiting list, at the depth they reached.
-    rc = dress_list(n, shallow, rb.v_keys, static_cast<u64*>(rb.rec_free), rb, &res);
+    rc = dress_list(L, shallow, home.vals, static_cast<u64*>(home.rec_free));
     if (rc) return rc;
     u32 left = 0; u64 h_left = 0;
     rc = run_rounds(L, shallow, std::max<u64>(1, h_sh), std::max(text_rounds, 3), true, false, &left, &h_left);
     if (rc) return rc;
     if (left) {
       if ((u64)blk.parked + left > cap) return -3;
-      hipLaunchKernelGGL(k_raw_to_park, dim3(ceil_div(left, 256)), dim3(256), 0, st, (const u32*)rb.v_free, (const u32*)rb.aglob_next,
+      hipLaunchKernelGGL(k_raw_to_park, dim3(ceil_div(left, 256)), dim3(256), 0, st, (const u32*)home.v_free, (const u32*)home.slots_next,
                          (const u32*)d_GRP, left, d_parkS, d_parkHP, blk.parked);
       blk.parked += left;
-      shallow_depth = (u32)std::min<u64>(h_left, 0xFFFFFFFFull);
+      shallow_depth = depth32(h_left);
       if (debug_on()) std::fprintf(stderr, "shallow groups: %u entries still tied at depth %llu join the waiting list\n", left, (unsigned long long)h_left);
     }
   }
@@ -3273,14 +3288,12 @@ int BwtEngine::finisher_route(SortList& L, u32 n_lf) {
     BWTC_HIP_TRY(hipMemcpyAsync(d_V0, d_parkS, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
     BWTC_HIP_TRY(hipMemcpyAsync(d_R1, d_parkHP, (size_t)total * 8, hipMemcpyDeviceToDevice, st));
     blk.parked = 0;                        // (the list is in the rounds' hands now: complete_ranks takes it from them)
-    rc = dress_list(n, total, d_V0, static_cast<u64*>(d_R1), rb, &res, blk.park_holes);
+    rc = dress_list(L, total, d_V0, static_cast<u64*>(d_R1), blk.park_holes);
     if (rc) return rc;
   } else {
     // no global list: the rounds still want free regions to complete rank[] in
     res.m = 0; res.groups = 0;
-    res.ks = reinterpret_cast<u64*>(d_W0); res.rec_other = d_R1;
-    res.vs = d_V0; res.v_other = d_V1;
-    rb.aglob_next = d_G0;
+    home = ListHome::at(d_W0, d_R1, d_V0, d_V1, d_G0, d_G1);
   }
   const u32 listed = total ? res.m : 0u;               // (the waiting list without its holes)
   // text rounds -- a global sort per six characters -- are for what is left of a text; a long list is deep repeats,
@@ -3307,7 +3320,7 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
   if (em && em->n_lf > 1 && n / em->n_lf >= 1) {
     re.lf_n = em->n_lf; re.lf_x = n / em->n_lf; re.lf_inv = re.lf_x > 1 ? (u32)((1ull << 32) / re.lf_x) : 0u;
   }
-  SortList L{n, em != nullptr, RankBuffers{nullptr, nullptr, nullptr, nullptr, nullptr, d_G0}, re, RankResult{}, d_C1, true};
+  SortList L{n, em != nullptr, ListHome{}, re, RankResult{}, d_C1, true};   // (hand_over gives the list its home)
   u64 h = (u64)plan.k;                     // the next round compares rank[s + h]
 
   BWTC_HIP_TRY(hipEventRecord(ev_sort[n_sort_events++], stream));
@@ -3428,7 +3441,7 @@ int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* 
     bool found = false;
     if (windows) {
       BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallPeriod + 1, 0, 4, st));
-      hipLaunchKernelGGL(k_period_probe, dim3((u32)((windows + 255) / 256)), dim3(256), 0, st, (const u8*)d_T, n, blk.period_p, span, (u32)std::min<u64>(windows, 0xFFFFFFFFull), d_small + kSmallPeriod + 1);
+      hipLaunchKernelGGL(k_period_probe, dim3((u32)((windows + 255) / 256)), dim3(256), 0, st, (const u8*)d_T, n, blk.period_p, span, depth32(windows), d_small + kSmallPeriod + 1);
       BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 1, d_small + kSmallPeriod + 1, 4, hipMemcpyDeviceToHost, st));
       BWTC_HIP_TRY(wait());
       found = h_small[kSmallPeriod + 1] != 0;
@@ -3538,7 +3551,7 @@ int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask
 // while the list shrinks: one that keeps more than three fifths of a list that is still longer than
 // n / 64 has met deep repeats (copies of whole files, not of lines), which only doubling gets through.
 // What is left for the rounds, as raw lists (suffix; head slot << 32 | slot), unsorted:
-//   *shallow entries in (rb.v_keys, rb.rec_free): groups too large for a window that share fewer than
+//   *shallow entries in (home.vals, home.rec_free): groups too large for a window that share fewer than
 //    fin_floor characters; they share at least *h_shallow
 //   `parked` entries in (d_parkS, d_parkHP): the other groups too large for a window, and what the last
 //    pass left tied; at least *h_parked characters
@@ -4032,9 +4045,12 @@ int BwtEngine::test_finisher(bwtc_hip_fin_run& t) {
 
 // A raw list becomes a list the rounds understand: sorted by slot (groups contiguous, a positional slot
 // array), key = head slot | character << 56, value = suffix.  S / HP must be one of (d_V0 | d_V1) and one
-// of (d_R1 | d_R2); d_W0 / d_W1 and d_G0 receive the list.
-int BwtEngine::dress_list(u32 n, u32 total, u32* S, u64* HP, RankBuffers& rb, RankResult* res, u32 holes) {
+// of (d_R1 | d_R2), between which the sort by slot runs; d_W0 / d_W1 and d_G0 receive the list, and L.home says so:
+// keys in W0 with R1 free, the values where the sort left them, slots in G0.  Of L.res only m and groups are the new
+// list's; carry stays (the keys made here hold the character, and so did the keys of every list the finisher route had).
+int BwtEngine::dress_list(SortList& L, u32 total, u32* S, u64* HP, u32 holes) {
   hipStream_t st = stream;
+  const u32 n = L.n;
   u64* hp_other = HP == static_cast<u64*>(d_R1) ? static_cast<u64*>(d_R2) : static_cast<u64*>(d_R1);
   u32* s_other = S == d_V0 ? d_V1 : d_V0;
   u64* hp_sorted = nullptr; u32* s_sorted = nullptr;
@@ -4043,10 +4059,8 @@ int BwtEngine::dress_list(u32 n, u32 total, u32* S, u64* HP, RankBuffers& rb, Ra
   total -= holes;                                        // (entries that left for the shallow list: all ones, sorted to the end)
   hipLaunchKernelGGL(k_bridge_dress, dim3(ceil_div(total, 256)), dim3(256), 0, st, (const u64*)hp_sorted, (const u32*)s_sorted,
                      total, (const u8*)d_T, fkey, d_G0);
-  res->m = total; res->groups = 0;
-  res->ks = fkey; res->rec_other = d_R1;
-  res->vs = s_sorted; res->v_other = s_sorted == d_V0 ? d_V1 : d_V0;
-  rb.aglob_next = d_G0;
+  L.res.m = total; L.res.groups = 0;
+  L.home = ListHome::sorted(fkey, d_R1, d_V0, d_V1, d_G0, d_G1, fkey, s_sorted);
   return 0;
 }
 
@@ -4154,7 +4168,7 @@ static bool rank_test_pass_ok(const bwtc_hip_rank_pass& t, u64 cap) {
   if (t.init ? m != n : t.key_bytes != 8) return false;
   if ((t.split || t.lng) && !(t.init && t.key_bytes == 8)) return false;
   if (t.mode < 0 || t.mode > 3 || t.emit < 0 || t.emit > 3) return false;
-  if (t.lng ? (t.emit != 0 && t.emit != 3) : t.split ? (t.emit != 0 && t.emit != 2) : t.init ? (t.emit != 0 && t.emit != 2) : t.emit == 3) return false;
+  if (!rr_emit_legal(t.split != 0, t.lng != 0, t.init != 0, t.emit)) return false;   // (t.emit is the form, as RrForm::emit takes it)
   if (t.split && n > (1u << 29)) return false;
   if (t.lng) {
     if (!t.w || t.wmask == 0u || t.hi_shift < 0 || t.chr_shift < 0 || t.chr_shift > 63 || t.chr_mask > 255u) return false;
@@ -4411,17 +4425,20 @@ int BwtEngine::test_round(bwtc_hip_round& t) {
   BWTC_HIP_TRY(fin_test_emit_begin(*this, n, t.out_n, t.lf_n, t.lf_x, &re));
   BWTC_HIP_TRY(can.put(d_SA, (u64)n * 4, st)); BWTC_HIP_TRY(can.put(d_out, n, st));
   re.achr_out = d_C0;
-  RankBuffers rb{d_R1, d_R2, d_V0, d_V1, d_G0, d_G1};
-  RankResult res{};
-  const int rc = rank_step<u64, false>(static_cast<const u64*>(d_R1), d_V0, m, n, 0u, t.carry_in ? ((1ull << 56) - 1ull) : ~0ull, rb, re, t.emit != 0,
-                                       t.h_next, &res, 0u, nullptr, t.text != 0, t.carry_in != 0, t.raw_out != 0, t.run_mode);
+  SortList L{n, t.emit != 0, ListHome::at(d_R1, d_R2, d_V0, d_V1, d_G0, d_G1), re, RankResult{}, d_C1, true};
+  L.res.carry = t.carry_in != 0;                         // what the step before reported of this list's keys
+  RankRequest rq;
+  rq.m = m; rq.h_next = t.h_next; rq.run_mode = t.run_mode;
+  rq.kind = t.raw_out ? RoundKind::kRaw : t.text ? RoundKind::kText : RoundKind::kOrdinary;
+  const int rc = rank_step<u64, false>(L, rq);
   if (rc) return rc;
+  const RankResult& res = L.res;
   t.result[0] = res.m; t.result[1] = res.groups; t.result[2] = res.carry ? 1u : 0u; t.result[3] = res.text_chars;
   t.result[4] = res.ran_run ? 1u : 0u; t.result[5] = res.finish ? 1u : 0u;
   if (t.raw_out) BWTC_HIP_TRY(hipMemcpyAsync(t.nvs, d_V1, (u64)m * 4, hipMemcpyDeviceToHost, st));
   else if (res.m > 0) {
-    BWTC_HIP_TRY(hipMemcpyAsync(t.nks, res.ks, (u64)res.m * 8, hipMemcpyDeviceToHost, st));
-    BWTC_HIP_TRY(hipMemcpyAsync(t.nvs, res.vs, (u64)res.m * 4, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(hipMemcpyAsync(t.nks, L.home.keys, (u64)res.m * 8, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(hipMemcpyAsync(t.nvs, L.home.vals, (u64)res.m * 4, hipMemcpyDeviceToHost, st));
   }
   BWTC_HIP_TRY(hipMemcpyAsync(t.naglob, d_G1, (u64)m * 4, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(hipMemcpyAsync(t.ngrp, d_GRP, (u64)m * 4, hipMemcpyDeviceToHost, st));

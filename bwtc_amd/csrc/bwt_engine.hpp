@@ -42,6 +42,7 @@ struct FinList;
 struct FinShallow;
 struct InitialSort;
 struct SortList;
+struct RankRequest;
 struct FinOutcome { u32 hard = 0, hard_depth = 0xFFFFFFFFu, left = 0, local = 0; };
 // A finisher list lives in up to kFinRegions regions of its arrays (bwt_engine.hip, k_finish)
 constexpr u32 kFinRegions = 16;
@@ -468,14 +469,35 @@ struct BwtEngine {
   template <typename K>
   void sort_pairs(K* k0, K* k1, u32* v0, u32* v1, u64 n, int nbits, K** ks, u32** vs, bool probe_it, int bit_lo = 0, u64 n_holes = 0, bool plane_ready = false, bool values_descend = false);
   // one ranking step of the suffix sorter (bwt_engine.hip)
-  struct RankBuffers { void* rec_keys; void* rec_free; u32* v_keys; u32* v_free; u32* aglob; u32* aglob_next; };
-  struct RankResult { u32 m, groups; u64* ks; u32* vs; void* rec_other; u32* v_other; bool finish; u32 text_chars; bool carry;
-                      bool ran_run; };   // ran_run: the step made the run step's keys (run_mode 1 and the key had room)
+  // Where a list lives between the steps: its sorted keys (u32 or u64, inside the 8 * cap-byte region rec_keys, which is
+  // free once a step's apply kernel has run) and values, the region and the value array nobody uses, the list's slots by
+  // position and the array the next list's slots go to.  A step writes what stays active raw into (v_free, slots_next,
+  // d_GRP) -- suffix, slot, head slot -- and sorts the next list between the two regions and the two value arrays.
+  struct ListHome {
+    const void* keys; void* rec_keys; void* rec_free; u32* vals; u32* v_free; u32* slots; u32* slots_next;
+    // a list that lies in the first of each pair
+    static ListHome at(void* rec, void* rec_free, u32* vals, u32* v_free, u32* slots, u32* slots_next) { return ListHome{rec, rec, rec_free, vals, v_free, slots, slots_next}; }
+    // a sort between the two regions and the two value arrays ended in (ks, vs): their partners are the free ones now
+    ListHome& sorted_into(const void* ks, u32* vs) {
+      if (ks == rec_free) std::swap(rec_keys, rec_free);
+      if (vs == v_free) std::swap(vals, v_free);
+      keys = ks;
+      return *this;
+    }
+    static ListHome sorted(void* rec_a, void* rec_b, u32* v_a, u32* v_b, u32* slots, u32* slots_next, const void* ks, u32* vs) {
+      return at(rec_a, rec_b, v_a, v_b, slots, slots_next).sorted_into(ks, vs);
+    }
+    // what a step left becomes what the next one reads: the list it sorted into (ks, vs), with the slots it wrote for it
+    void advance(const void* ks, u32* vs) { sorted_into(ks, vs); std::swap(slots, slots_next); }
+    // an 8 * cap-byte region of the three that is neither the keys' nor rec_free: with rec_free, two free ones
+    void* spare_region(void* a, void* b, void* c) const { return (a != rec_keys && a != rec_free) ? a : (b != rec_keys && b != rec_free) ? b : c; }
+  };
+  // what a step reports.  text_chars is rewritten by a text round alone; carry: the next list's keys hold the characters in
+  // bits 56..63; ran_run: the step made the run step's keys (run_mode 1 and the key had room)
+  struct RankResult { u32 m, groups; bool finish; u32 text_chars; bool carry; bool ran_run; };
   template <typename K, bool INIT>
-  int rank_step(const K* ks, const u32* vs, u32 m, u32 n, u32 short_len, K kmask, RankBuffers& rb,
-                struct RrEmit re, bool emit, u64 h_next, RankResult* res, u32 split = 0,
-                const struct RrLong* lg = nullptr, bool text = false, bool carry_in = true, bool raw_out = false,
-                int run_mode = 0);   // run_mode: RunKeys::mode of the next list's second keys
+  int rank_step(struct SortList& L, const struct RankRequest& rq);
+  int next_list(struct SortList& L, u64* ka, u64* kb, u32* va, u32* vb, u32 m_next, int bits, u32 holes, bool drop_holes, u64 key_bytes, bool timed);
   bool dense_route = true;   // BWTC_HIP_DENSE=0: always the list-order route (random rank[s+h] gather)
   bool digit_planes = true;  // BWTC_HIP_PLANES=0: every histogram pass reads the keys
   u32 pairs_min = 1u << 21;  // lists of at least this many entries take the window-ordered routes to rank[] (pairs partitioned before the
@@ -544,8 +566,8 @@ struct BwtEngine {
   int test_rank_scatter(bool dense, const u32* where, const u32* what, const u64* rec, u32 m, u32 n, int bin_shift, u32* rank);
   int test_round_keys(bwtc_hip_round_keys& t);
   int test_round(bwtc_hip_round& t);        // the driver: rank_step<u64, false> once, pairs_min and window_bits set and restored
-  // a raw list (suffix; head slot << 32 | slot) in (S, HP) -> a sorted list the rounds understand, in res / rb
-  int dress_list(u32 n, u32 total, u32* S, u64* HP, RankBuffers& rb, RankResult* res, u32 holes = 0);
+  // a raw list (suffix; head slot << 32 | slot) in (S, HP) -> a sorted list the rounds understand, in L.home / L.res
+  int dress_list(SortList& L, u32 total, u32* S, u64* HP, u32 holes = 0);
   // runs and periods (bwt_engine.hip, "Runs" / "Periods"): long runs of one byte (period 1) and stretches of a period p > 1
   // are ranked in closed form by one round, the step.  A block's steps stand in BlockSort::steps in the order it takes them,
   // over the one length array d_runK: one step per block -- or, with BWTC_HIP_MIXED=1, the run step and then one period
