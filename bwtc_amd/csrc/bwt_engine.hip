@@ -2117,6 +2117,10 @@ struct ArenaPlan {
       off_GRP, off_C0, off_C1, off_P0, off_P1, off_W0, off_W1, off_table, off_partial, off_aggA, off_aggB, off_aggC, off_agg_part, off_small, off_ent, off_comp, off_sweep, off_parkS, off_parkHP, off_hardS, off_hardHP, off_hardC, off_LP0, off_LH0, off_LH1, off_LC1, off_US, off_UR, off_pairs, off_codes, off_runK, off_runF, off_runB, off_votes, total;
 };
 
+// The entries an array of a finisher list holds (fin_room: what a pass needs of them), in a context of capacity cap.
+// (Whether that is room enough for the wide shape is ADVICE.md's item; the formula is as it was.)
+static constexpr u64 fin_list_cap(u64 cap) { return cap + cap / 128 + 65536; }
+
 static ArenaPlan plan_arena(u64 cap) {
   ArenaPlan a;
   u64 o = 0;
@@ -2129,7 +2133,7 @@ static ArenaPlan plan_arena(u64 cap) {
   a.off_R1 = take(cap * 8);
   a.off_R2 = take(cap * 8);
   // (the finisher's lists live in regions sized for the most their workgroups can leave: up to 17 strides beyond the entries)
-  const u64 lcap = cap + cap / 128 + 65536;
+  const u64 lcap = fin_list_cap(cap);
   a.off_V0 = take(lcap * 4);
   a.off_V1 = take(lcap * 4);
   a.off_G0 = take(lcap * 4);
@@ -2791,8 +2795,8 @@ int BwtEngine::rank_step(SortList& L, const RankRequest& rq) {
 // the base-sigma key.  The gram length is the longest whose universe fits kGramMaxU; the key takes
 // as few grams as cover the base-sigma key's characters, and is used when that saves a radix pass.
 static constexpr int kSmallGram = 526;
-static constexpr int kSmallFin = 528;     // finisher: counts and smallest depths of the hard and shallow lists (finish_list)
-static constexpr int kSmallFinNext = 540; // finisher: entries of the next list's kFinRegions regions
+static constexpr int kSmallFin = 528;     // finisher: counts and smallest depths of the hard and shallow lists (FinWord)
+static constexpr int kSmallFinNext = 540; // finisher: entries of the next list's kFinRegions regions, then the groups it holds
 int BwtEngine::plan_grams(const KeyPlan& plan, u32 n, const u8* d_lut, GramPlan* gp) {
   hipStream_t st = stream;
   gp->G = 0;
@@ -3095,7 +3099,7 @@ int BwtEngine::step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool
   if ((u64)(behind_run ? blk.proper_longest : blk.period_longest) <= std::max<u64>(h_round, step.p)) {
     step.when = StretchStep::kNone;
     say_no_period_step(*this, h_first);
-  } else if (h_round >= (u64)step.p && L.ranks_complete && blk.local_m == 0 && !text_round) {
+  } else if (h_round >= (u64)step.p && L.ranks_complete && blk.fin.local_m == 0 && !text_round) {
     step.when = StretchStep::kNone;
     if (blk.lengths_period != step.p) {
       // a run's member with k_1 >= p has k_p = k_1, one with k_1 < p <= h_round would look up at h_round anyway: nothing
@@ -3109,27 +3113,28 @@ int BwtEngine::step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool
   return 0;
 }
 
-// The rounds over the sorted list in L.home, from depth h0 until nothing is tied.  text_rounds_now: rounds that compare
+// The rounds over the sorted list in L.home, from depth ask.h0 until nothing is tied.  ask.text_rounds: rounds that compare
 // the text itself first (finisher route: rank[] is not complete, and completing it costs an ISA scatter of the whole block).
-// doubling == false: text rounds only; what they leave tied comes back raw in (home.v_free, home.slots_next, d_GRP) --
-// suffix, slot, head slot -- *left entries at depth *h_left.
-int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool keep_first, bool doubling, u32* left, u64* h_left) {
+// ask.doubling == false: text rounds only; what they leave tied comes back raw in (home.v_free, home.slots_next, d_GRP) --
+// suffix, slot, head slot -- out->left entries at depth out->h_left.
+int BwtEngine::run_rounds(SortList& L, const RoundsRequest& ask, RoundsLeft* out) {
   const u32 n = L.n;
   ListHome& home = L.home;
   RankResult& res = L.res;
   RrEmit& re = L.re;
-  u64 h = h0;
-  bool keep_h = keep_first;                // the list is sorted to depth h as it stands (no doubling before the next step)
-  int text_left = text_rounds_now;
+  u32 m = ask.m;
+  u64 h = ask.h0;
+  bool keep_h = ask.keep_first;             // the list is sorted to depth h as it stands (no doubling before the next step)
+  int text_left = ask.text_rounds;
   // the block's closed-form steps (runs, periods), decided where a list is about to double: an entry's `when` says whether
   // it is the first round's or waits for a deeper one
-  const u64 h_first = keep_first ? h0 : h0 * 2;
-  if (doubling && m > 0) {
+  const u64 h_first = ask.keep_first ? ask.h0 : ask.h0 * 2;
+  if (ask.doubling && m > 0) {
     const int rcs = decide_step(n, m, h_first, static_cast<const u64*>(home.keys), home.vals, carried_mask(res.carry));
     if (rcs) return rcs;
   }
   int text_extra = text_rounds_fixed ? 0 : 12;        // further ones, one at a time, while the list is short (not when BWTC_HIP_TEXT_ROUNDS says how many)
-  while (m > 0 || (doubling && blk.local_m > 0)) {
+  while (m > 0 || (ask.doubling && blk.fin.local_m > 0)) {
     if (h >= (u64)n * 2 + 64) return -3;   // cannot happen: every group splits by then
     ++stats.rounds;
     stats.active_sum += m;
@@ -3140,7 +3145,7 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
     StretchStep& step = blk.current_step();
     const bool period_req = run_req && step.p >= 2;
     const bool text = text_round || (run_req && !L.ranks_complete);   // the run step reads no rank[]: it does not need the completion either
-    const bool raw = !text && !doubling;               // out of text rounds and not allowed to double: hand the list back
+    const bool raw = !text && !ask.doubling;           // out of text rounds and not allowed to double: hand the list back
     if (debug_on()) std::fprintf(stderr, "round %u%s: h=%llu m=%u groups=%u\n", stats.rounds, text ? " (text)" : "", (unsigned long long)h, m, res.groups);
     if (!keep_h) h *= 2;
     keep_h = false;
@@ -3180,11 +3185,11 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
       // without the completion of rank[] that the first doubling round costs.  Not beside a live local list: its
       // members' ranks are local_depth deep, and the first doubling look-up must not lie deeper than that (text rounds
       // raise h; that is why a list with a local list beside it takes none)
-      if (!L.ranks_complete && text_left == 0 && !text_rounds_fixed && blk.local_m == 0) text_left = 1;
+      if (!L.ranks_complete && text_left == 0 && !text_rounds_fixed && blk.fin.local_m == 0) text_left = 1;
     }
-    if (raw) { *left = m; *h_left = h; return 0; }
+    if (raw) { if (out) *out = RoundsLeft{m, h}; return 0; }
     // the local list's doubling step beside the global list's (both read the rank[] this round's ranking step left)
-    if (!text && doubling && blk.local_m > 0) { const int rcl = local_pass(n, h, re); if (rcl) return rcl; }
+    if (!text && ask.doubling && blk.fin.local_m > 0) { const int rcl = local_pass(n, h, re); if (rcl) return rcl; }
     if (text && !ran) {
       h += res.text_chars; keep_h = true;
       if (text_round) --text_left;
@@ -3199,40 +3204,79 @@ int BwtEngine::run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool 
   for (int i = 0; i < blk.n_steps; ++i)
     if (blk.steps[i].when == StretchStep::kWaiting) { blk.steps[i].when = StretchStep::kNone; waited = true; }
   if (waited) say_no_period_step(*this, h_first);
-  if (mixed_steps && doubling && debug_on()) {
+  if (mixed_steps && ask.doubling && debug_on()) {
     const StretchStep period = blk.period_ran();
     std::fprintf(stderr, "steps: run step at depth %u, period step of period %u at depth %u, longest run %u, longest proper stretch %u\n",
                  blk.run_depth(), period.p, period.depth, blk.run_longest, blk.proper_longest);
   }
-  if (left) { *left = 0; *h_left = h; }
+  if (out) *out = RoundsLeft{0, h};
   return 0;
 }
+
+// The finisher's counter words in d_small, by their place from kSmallFin on.  The kernels take a pair of them, (entries,
+// smallest depth), and index [0] and [1] from there: the hard pair and the shallow pair.
+enum FinWord : int {
+  kFinSpare,                       // (reset and read back with the hard pair; nothing counts in it)
+  kFinHard, kFinHardDepth,         // the hard list (groups too large for a window): its entries, the smallest depth among them
+  kFinWaitDepth,                   // the smallest depth of what waits for the rounds (k_fin_to_hard)
+  kFinShallow, kFinShallowDepth,   // the shallow list (hard groups that share fewer than fin_floor characters): the same pair
+  kFinLocalDepth,                  // the smallest depth of the local list (k_list_copy)
+  kFinWords,
+  kFinNext = kSmallFinNext - kSmallFin,                       // the list a launch leaves: the entries of its kFinRegions regions,
+  kFinNextLast = kFinNext + kFinRegions - 1, kFinGroupsLeft   //   then the groups it holds
+};
+static_assert(kFinWords <= kFinNext, "the finisher's counter words end before the next list's");
+static_assert(kSmallFin + kFinGroupsLeft < kSmallLut, "the next list's words end before the next words of d_small in use");
+// The words on the device (word), their mirror in h_small ([]), and the transfers of words first .. last between the two
+// on the engine's stream (to: a test hook's array in place of the mirror).
+struct FinCounters {
+  u32* d; u32* h; hipStream_t st;
+  explicit FinCounters(const BwtEngine& e) : d(e.d_small + kSmallFin), h(e.h_small + kSmallFin), st(e.stream) {}
+  u32& operator[](int w) const { return h[w]; }
+  u32* word(int w) const { return d + w; }
+  FinShallow shallow_sink(u32* S, u64* HP, u32 floor) const { return FinShallow{S, HP, d + kFinShallow, floor}; }
+  hipError_t upload(int first, int last) const { return hipMemcpyAsync(d + first, h + first, (last - first + 1) * 4, hipMemcpyHostToDevice, st); }
+  hipError_t fetch(int first, int last, u32* to = nullptr) const { return hipMemcpyAsync(to ? to : h + first, d + first, (last - first + 1) * 4, hipMemcpyDeviceToHost, st); }
+  hipError_t clear(int first, int last) const { return hipMemsetAsync(d + first, 0, (last - first + 1) * 4, st); }
+};
+// The finisher's list between its passes: where it lies (a) and where a pass puts what it leaves (b), its entries and
+// regions (finisher_passes begins with the m entries as one region).  And what the passes are asked: the block's size and
+// emitter, the shallow sink, whether what they leave tied may become the local list, and how many they may be.
+struct FinWork { FinList a, b; u32 m; FinRegions rg; };
+struct FinRequest { u32 n; RrEmit& re; FinShallow shal; bool keep_local; int max_passes; };
 
 // The finisher's start: its counter words, and the two homes its lists alternate between.  The first list's suffixes lie
 // in S (the ranking's free value array; d_V0 in the test hooks), its slots in d_G0, its characters in d_C0, where the
 // initial ranking leaves them.
-hipError_t BwtEngine::finisher_begin(u32* S, FinList* a, FinList* b) {
-  *a = FinList{S, d_G0, d_GRP, reinterpret_cast<unsigned short*>(d_C0)};
-  *b = FinList{d_W0, d_W1, d_G1, reinterpret_cast<unsigned short*>(d_C1)};
-  h_small[kSmallFin + 3] = 0xFFFFFFFFu; h_small[kSmallFin + 4] = 0; h_small[kSmallFin + 5] = 0xFFFFFFFFu; h_small[kSmallFin + 6] = 0xFFFFFFFFu;
-  return hipMemcpyAsync(d_small + kSmallFin + 3, h_small + kSmallFin + 3, 16, hipMemcpyHostToDevice, stream);
+hipError_t BwtEngine::finisher_begin(u32* S, u32 m, FinWork* w) {
+  *w = FinWork{FinList{S, d_G0, d_GRP, reinterpret_cast<unsigned short*>(d_C0)}, FinList{d_W0, d_W1, d_G1, reinterpret_cast<unsigned short*>(d_C1)}, m, FinRegions{}};
+  const FinCounters fc(*this);
+  fc[kFinWaitDepth] = 0xFFFFFFFFu; fc[kFinShallow] = 0; fc[kFinShallowDepth] = 0xFFFFFFFFu; fc[kFinLocalDepth] = 0xFFFFFFFFu;
+  return fc.upload(kFinWaitDepth, kFinLocalDepth);
 }
 
 // The finisher route: the long-key ranking's list through the finisher's passes; the shallow list's rounds, what they
 // and the passes leave waiting (parked), the local list, and the rounds that end the block.
 int BwtEngine::finisher_route(SortList& L, u32 n_lf) {
-  hipStream_t st = stream;
-  const u32 n = L.n;
-  ListHome& home = L.home;
-  RankResult& res = L.res;
+  const ListHome& home = L.home;
   if (L.re.lf_n == 0 && n_lf > 1) return -3;
   blk.lf_noted = true;                     // every suffix that becomes final notes its LF power (lf_note), in every route
   L.ranks_complete = false;
-  u32* cnt = d_small + kSmallFin;
-  FinList la, lb;
-  BWTC_HIP_TRY(finisher_begin(home.v_free, &la, &lb));
-  FinShallow shal{home.vals, static_cast<u64*>(home.rec_free), cnt + 4, fin_floor};
+  FinWork w;
+  BWTC_HIP_TRY(finisher_begin(home.v_free, L.res.m, &w));
+  const FinRequest rq{L.n, L.re, FinCounters(*this).shallow_sink(home.vals, static_cast<u64*>(home.rec_free), fin_floor), local_rounds,
+                      finisher_shape(L.n, L.res)};
   FinOutcome fo;
+  int rc = finisher_passes(w, rq, &fo);
+  if (rc) return rc;
+  u32 shallow_depth = 0xFFFFFFFFu;
+  if (fo.shallow) { rc = shallow_rounds(L, fo, &shallow_depth); if (rc) return rc; }
+  if (!blk.fin.parked && !blk.fin.local_m) return 0;
+  return waiting_to_rounds(L, fo, shallow_depth);
+}
+
+// The passes' shape for the list the long-key ranking left (-> blk.fin.window / group), and the passes it may take.
+int BwtEngine::finisher_shape(u32 n, const RankResult& res) {
   // Groups of hundreds of members on average (a period, one text many times over) are not the finisher's: its loop
   // costs a group's size per member.  The list then goes to the rounds as it is (shallow groups apart).
   const bool giant = res.groups > 0 && (u64)res.m > (u64)res.groups * 64;
@@ -3245,61 +3289,62 @@ int BwtEngine::finisher_route(SortList& L, u32 n_lf) {
   // no hard list is left for the text rounds, whose five rounds of tiny launches cost more than the whole pass
   // (256 MiB: 21.9 -> 21.3 ms).  Bounded: the wide shape costs at most 0.45 ns per entry more (measured on a real
   // text, where every group is large), n / 24 entries at most.
-  blk.fin_window_blk = fin_window; blk.fin_group_blk = fin_max_group;
+  blk.fin.window = fin_window; blk.fin.group = fin_max_group;
   // One pass only in that shape: what three rounds of sixteen characters leave tied in a short list is deep repeats
   // (copies of a long piece), the rounds' business -- further passes over groups of hundreds of members cost their size
   // per member and settle nothing (300 copies of a 10 KB piece in the generator's text: 32.6 ms with three passes, 30.0
   // in the narrow shape, where such groups are hard at once).
-  bool wide = false;
-  if (!fin_shape_fixed && fin_wide_short && !giant && (u64)res.m * 24 <= (u64)n) { blk.fin_window_blk = 2048; blk.fin_group_blk = 1024; wide = true; }
-  int rc = finisher_passes(n, res.m, la, lb, L.re, shal, &fo, local_rounds, giant ? 0 : wide ? std::min(1, fin_max_passes) : fin_max_passes);
+  const bool wide = !fin_shape_fixed && fin_wide_short && !giant && (u64)res.m * 24 <= (u64)n;
+  if (wide) { blk.fin.window = 2048; blk.fin.group = 1024; }
+  return giant ? 0 : wide ? std::min(1, fin_max_passes) : fin_max_passes;
+}
+
+// The few hard groups of little depth first, on their own: text rounds only (rank[] must not go live while
+// finisher passes are still to come); what they leave tied joins the waiting list, at the depth they reached.
+int BwtEngine::shallow_rounds(SortList& L, const FinOutcome& fo, u32* shallow_depth) {
+  const ListHome& home = L.home;
+  int rc = dress_list(L, fo.shallow, home.vals, static_cast<u64*>(home.rec_free));
   if (rc) return rc;
-  const u32 shallow = h_small[kSmallFin + 4];
-  const u64 h_sh = h_small[kSmallFin + 5];
-  u32 shallow_depth = 0xFFFFFFFFu;
-  if (shallow) {
-    // The few hard groups of little depth first, on their own: text rounds only (rank[] must not go live while
-    // finisher passes are still to come); what they leave tied joins the waiting list, at the depth they reached.
-    rc = dress_list(L, shallow, home.vals, static_cast<u64*>(home.rec_free));
-    if (rc) return rc;
-    u32 left = 0; u64 h_left = 0;
-    rc = run_rounds(L, shallow, std::max<u64>(1, h_sh), std::max(text_rounds, 3), true, false, &left, &h_left);
-    if (rc) return rc;
-    if (left) {
-      if ((u64)blk.parked + left > cap) return -3;
-      hipLaunchKernelGGL(k_raw_to_park, dim3(ceil_div(left, 256)), dim3(256), 0, st, (const u32*)home.v_free, (const u32*)home.slots_next,
-                         (const u32*)d_GRP, left, d_parkS, d_parkHP, blk.parked);
-      blk.parked += left;
-      shallow_depth = depth32(h_left);
-      if (debug_on()) std::fprintf(stderr, "shallow groups: %u entries still tied at depth %llu join the waiting list\n", left, (unsigned long long)h_left);
-    }
-  }
-  if (!blk.parked && !blk.local_m) return 0;
-  const u32 hard = fo.hard, hard_depth = fo.hard_depth;
-  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 3, cnt + 3, 4, hipMemcpyDeviceToHost, st));
+  RoundsLeft tied;
+  rc = run_rounds(L, RoundsRequest{fo.shallow, std::max<u64>(1, fo.shallow_depth), std::max(text_rounds, 3), true, false}, &tied);
+  if (rc || !tied.left) return rc;
+  if ((u64)blk.fin.parked + tied.left > cap) return -3;
+  hipLaunchKernelGGL(k_raw_to_park, dim3(ceil_div(tied.left, 256)), dim3(256), 0, stream, (const u32*)home.v_free, (const u32*)home.slots_next,
+                     (const u32*)d_GRP, tied.left, d_parkS, d_parkHP, blk.fin.parked);
+  blk.fin.parked += tied.left;
+  *shallow_depth = depth32(tied.h_left);
+  if (debug_on()) std::fprintf(stderr, "shallow groups: %u entries still tied at depth %llu join the waiting list\n", tied.left, (unsigned long long)tied.h_left);
+  return 0;
+}
+
+// The waiting list (what the passes and the shallow groups' rounds parked) goes to the rounds that end the block, at the
+// smallest depth any of it has, with the local list beside it.
+int BwtEngine::waiting_to_rounds(SortList& L, const FinOutcome& fo, u32 shallow_depth) {
+  const FinCounters fc(*this);
+  BWTC_HIP_TRY(fc.fetch(kFinWaitDepth, kFinWaitDepth));
   BWTC_HIP_TRY(wait());
-  u64 h_pk = std::min<u64>(std::min<u64>(h_small[kSmallFin + 3], hard ? hard_depth : 0xFFFFFFFFu), shallow_depth);
-  if (blk.local_m) h_pk = std::min<u64>(h_pk, blk.local_depth);   // every rank is at least as deep as the rounds' first look-up
-  const u32 total = blk.parked;
+  u64 h_pk = std::min<u64>(std::min<u64>(fc[kFinWaitDepth], fo.hard ? fo.hard_depth : 0xFFFFFFFFu), shallow_depth);
+  if (blk.fin.local_m) h_pk = std::min<u64>(h_pk, blk.fin.local_depth);   // every rank is at least as deep as the rounds' first look-up
+  const u32 total = blk.fin.parked;
   if (debug_on())
     std::fprintf(stderr, "finisher: %u entries (%u of groups too large) go on to the rounds at depth %llu; %u entries of small groups double beside them from depth %u\n",
-                 total, hard, (unsigned long long)h_pk, blk.local_m, blk.local_m ? blk.local_depth : 0u);
+                 total, fo.hard, (unsigned long long)h_pk, blk.fin.local_m, blk.fin.local_m ? blk.fin.local_depth : 0u);
   if (total) {
-    BWTC_HIP_TRY(hipMemcpyAsync(d_V0, d_parkS, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
-    BWTC_HIP_TRY(hipMemcpyAsync(d_R1, d_parkHP, (size_t)total * 8, hipMemcpyDeviceToDevice, st));
-    blk.parked = 0;                        // (the list is in the rounds' hands now: complete_ranks takes it from them)
-    rc = dress_list(L, total, d_V0, static_cast<u64*>(d_R1), blk.park_holes);
+    BWTC_HIP_TRY(hipMemcpyAsync(d_V0, d_parkS, (size_t)total * 4, hipMemcpyDeviceToDevice, stream));
+    BWTC_HIP_TRY(hipMemcpyAsync(d_R1, d_parkHP, (size_t)total * 8, hipMemcpyDeviceToDevice, stream));
+    blk.fin.parked = 0;                    // (the list is in the rounds' hands now: complete_ranks takes it from them)
+    const int rc = dress_list(L, total, d_V0, static_cast<u64*>(d_R1), blk.fin.park_holes);
     if (rc) return rc;
   } else {
     // no global list: the rounds still want free regions to complete rank[] in
-    res.m = 0; res.groups = 0;
-    home = ListHome::at(d_W0, d_R1, d_V0, d_V1, d_G0, d_G1);
+    L.res.m = 0; L.res.groups = 0;
+    L.home = ListHome::at(d_W0, d_R1, d_V0, d_V1, d_G0, d_G1);
   }
-  const u32 listed = total ? res.m : 0u;               // (the waiting list without its holes)
+  const u32 listed = total ? L.res.m : 0u;               // (the waiting list without its holes)
   // text rounds -- a global sort per six characters -- are for what is left of a text; a long list is deep repeats,
   // which only doubling gets through
-  const int text_now = (!blk.local_m && ((u64)listed * 16 < (u64)n || text_rounds_fixed)) ? text_rounds : 0;
-  return run_rounds(L, listed, std::max<u64>(1, h_pk), text_now, true, true, nullptr, nullptr);
+  const int text_now = (!blk.fin.local_m && ((u64)listed * 16 < (u64)L.n || text_rounds_fixed)) ? text_rounds : 0;
+  return run_rounds(L, RoundsRequest{listed, std::max<u64>(1, h_pk), text_now, true, true});
 }
 
 // The driver: the block's state and key plan, the initial sort and ranking, then the finisher route or the rounds.
@@ -3327,7 +3372,7 @@ int BwtEngine::suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const Emi
   int rc = plan.wide ? initial_wide(in, allow_code_keys, L, &h) : initial_keys32(in, L, h);
   if (rc == kCodeTableFull) return suffix_sort(n, hist, lone_sentinel, em, false);
   if (rc) return rc;
-  rc = L.res.finish ? finisher_route(L, em->n_lf) : run_rounds(L, L.res.m, h, 0, false, true, nullptr, nullptr);
+  rc = L.res.finish ? finisher_route(L, em->n_lf) : run_rounds(L, RoundsRequest{L.res.m, h, 0, false, true});
   if (rc) return rc;
   BWTC_HIP_TRY(hipGetLastError());
   BWTC_HIP_TRY(take_sticky_error());
@@ -3556,7 +3601,7 @@ int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask
 //   `parked` entries in (d_parkS, d_parkHP): the other groups too large for a window, and what the last
 //    pass left tied; at least *h_parked characters
 //
-// The lists a pass writes hold cap + cap / 128 + 65536 entries, and a pass needs room for its regions' worst case:
+// The lists a pass writes hold fin_list_cap(cap) entries, and a pass needs room for its regions' worst case:
 // chunk c of 64 workgroups appends to region c mod 16 and leaves at most its workgroups' strides of entries and one
 // group more -- m + m / 64 in the wide shape (stride and group 1024).  A pass (or the local list's steps) whose room
 // would not fit is not made: the list goes to the global rounds as it stands (stats.route bit 7).
@@ -3572,14 +3617,54 @@ static bool fin_room(const FinRegions& rg, u32 stride, u32 group, u64 lcap, FinO
   for (u32 r = 0; r < kFinRegions; ++r) { ob->base[r] = (u32)std::min<u64>(at, 0xFFFFFFFFu); at += room[r]; }
   return at <= lcap;
 }
+// A list of m entries as one region, from entry 0.
+static FinRegions fin_one_region(u32 m, u32 stride) {
+  FinRegions rg{};
+  rg.nreg = 1; rg.wfirst[1] = ceil_div(m, stride); rg.ecount[0] = m;
+  return rg;
+}
+// The regions a pass left, from its region counts and its FinOut (the empty ones left out); *total: their entries.
+static FinRegions fin_regions_left(const u32* counts, const FinOut& ob, u32 stride, u32* total) {
+  FinRegions nx{};
+  *total = 0;
+  for (u32 r = 0; r < kFinRegions; ++r) {
+    const u32 c = counts[r];
+    if (!c) continue;
+    nx.ebase[nx.nreg] = ob.base[r]; nx.ecount[nx.nreg] = c;
+    nx.wfirst[nx.nreg + 1] = nx.wfirst[nx.nreg] + ceil_div(c, stride);
+    ++nx.nreg;
+    *total += c;
+  }
+  if (nx.nreg == 0) nx.nreg = 1;
+  return nx;
+}
 
-// One k_finish launch over list a's regions rg, in this block's shape (fin_window_blk / fin_group_blk): the passes'
-// (rk == nullptr: fin_words words of characters, or fin_rounds rounds of two), the local list's steps (rk: ranks), and,
-// launch by launch, the test hooks' (BwtEngine::test_finish_pass).
-static void launch_finish(BwtEngine& e, FinList a, const FinRegions& rg, u32 n, FinList b, const FinOut& ob, u32* ncnt, u32* hardS, u64* hardHP,
-                          unsigned short* hardC, u32* hard_count, FinShallow shal, const RrEmit& re, const FinRank* rk) {
+// One k_finish launch: the list it reads and its regions, the list it leaves and where each region of that starts (fin_room),
+// the hard sink, the shallow sink, and the ranks of a local step.
+struct FinLaunch {
+  u32 n; FinList in; FinRegions rg; FinList out; FinOut ob;
+  u32* hardS; u64* hardHP; unsigned short* hardC; FinShallow shal; bool ranks; FinRank rk;
+  // a pass of the finisher: hard groups go to (hardS, hardHP) with their characters in d_hardC, shallow ones to shal
+  static FinLaunch pass(const BwtEngine& e, u32 n, FinList in, const FinRegions& rg, FinList out, const FinOut& ob, u32* hardS, u64* hardHP, FinShallow shal) {
+    return FinLaunch{n, in, rg, out, ob, hardS, hardHP, e.d_hardC, shal, false, FinRank()};
+  }
+  // a step of the local list, from its home `home` to the other, by rank[s + at] and rank[s + at2]: no group is too large
+  // and none is shallow, so the hard characters' array is never written and the shallow sink is a dummy with floor 0
+  static FinLaunch local_step(const BwtEngine& e, u32 n, int home, const FinRegions& rg, const FinOut& ob, u32 at, u32 at2) {
+    return FinLaunch{n, e.local_list(home), rg, e.local_list(1 - home), ob, e.d_parkS, e.d_parkHP, e.d_LC1,
+                     FinCounters(e).shallow_sink(e.d_parkS, e.d_parkHP, 0u), true, FinRank{e.d_rank, at, at2, e.d_US, e.d_UR}};
+  }
+};
+
+// One k_finish launch in this block's shape (blk.fin.window / group): the passes' (fin_words words of characters, or
+// fin_rounds rounds of two), the local list's steps (q.ranks), and, launch by launch, the test hooks'
+// (BwtEngine::test_finish_pass).  The counters are the finisher's own (FinCounters).
+static void launch_finish(BwtEngine& e, const FinLaunch& q, const RrEmit& re) {
   hipStream_t st = e.stream;
-  const int window = e.blk.fin_window_blk, group = e.blk.fin_group_blk, fin_words = e.fin_words, fin_rounds = e.fin_rounds;
+  const int window = e.blk.fin.window, group = e.blk.fin.group, fin_words = e.fin_words, fin_rounds = e.fin_rounds;
+  const auto& [n, a, rg, b, ob, hardS, hardHP, hardC, shal, ranks, ranks_by] = q;   // (the names the launches below are written in)
+  u32 *ncnt = FinCounters(e).word(kFinNext), *hard_count = FinCounters(e).word(kFinHard);
+  const FinRank* rk = ranks ? &ranks_by : nullptr;
   const u32 grid = rg.wfirst[rg.nreg];
 #define BWTC_FINISH_W(G, E, NW) hipLaunchKernelGGL((k_finish<G, E, NW>), dim3(grid), dim3(kFinTPB), 0, st, a, rg, (const u8*)e.d_T, n, \
                                              b, ob, ncnt, hardS, hardHP, hardC, hard_count, shal, e.d_SA, re)
@@ -3601,31 +3686,24 @@ static void launch_finish(BwtEngine& e, FinList a, const FinRegions& rg, u32 n, 
 #undef BWTC_FINISH_R
 }
 
-int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, FinShallow shal, FinOutcome* fo, bool keep_local, int max_passes) {
-  hipStream_t st = stream;
-  u32* cnt = d_small + kSmallFin;      // [1] hard list, [2] its smallest depth; [3] smallest depth of what waits for the rounds; [4] shallow list, [5] its smallest depth
-  u32* ncnt = d_small + kSmallFinNext; // entries of the next list, region by region
-  h_small[kSmallFin] = 0; h_small[kSmallFin + 1] = 0; h_small[kSmallFin + 2] = 0xFFFFFFFFu;
-  BWTC_HIP_TRY(hipMemcpyAsync(cnt, h_small + kSmallFin, 12, hipMemcpyHostToDevice, st));
-  u32 hard = 0;
-  blk.passes_done = 0;
-  const u32 park0 = blk.parked;            // the groups too large for a window join the waiting list from here
-  const int window = blk.fin_window_blk, group = blk.fin_group_blk;
-  const u32 stride = (u32)(window - group);
-  FinRegions rg;
-  std::memset(&rg, 0, sizeof rg);
-  rg.nreg = 1; rg.wfirst[0] = 0; rg.wfirst[1] = ceil_div(m, stride); rg.ebase[0] = 0; rg.ecount[0] = m;   // the list as given is one region
-  u32 groups_left = 0;
+int BwtEngine::finisher_passes(FinWork& w, const FinRequest& rq, FinOutcome* fo) {
+  u32& m = w.m;
+  const FinCounters fc(*this);
+  fc[kFinSpare] = 0; fc[kFinHard] = 0; fc[kFinHardDepth] = 0xFFFFFFFFu;
+  BWTC_HIP_TRY(fc.upload(kFinSpare, kFinHardDepth));
+  blk.fin.passes_done = 0;
+  const u32 park0 = blk.fin.parked;        // the groups too large for a window join the waiting list from here
+  const u32 stride = blk.fin.stride();
+  w.rg = fin_one_region(m, stride);        // the list as given is one region
   const u32 pass_chars = 8u * (u32)fin_words * (fin_words == 2 ? (u32)fin_rounds : 1u);
   const int depth_passes = (int)((255u - 48u) / pass_chars);      // the depth byte holds 255 (a level's depth is 48 at most)
-  const u64 lcap = cap + cap / 128 + 65536;
-  for (int it = 0; it < std::min(std::min(fin_max_passes, std::max(1, depth_passes)), max_passes) && m > 0; ++it) {
+  for (int it = 0; it < std::min(std::min(fin_max_passes, std::max(1, depth_passes)), rq.max_passes) && m > 0; ++it) {
     // the regions of the list this pass leaves
     FinOut ob;
-    if (!fin_room(rg, stride, (u32)group, lcap, &ob)) {
+    if (!fin_room(w.rg, stride, (u32)blk.fin.group, fin_list_cap(cap), &ob)) {
       stats.route |= 128u;
       if (debug_on())
-        std::fprintf(stderr, "finisher pass %d: %u entries would not fit the lists in this shape (%d / %d); on to the rounds\n", it, m, window, group);
+        std::fprintf(stderr, "finisher pass %d: %u entries would not fit the lists in this shape (%d / %d); on to the rounds\n", it, m, blk.fin.window, blk.fin.group);
       break;
     }
     ++stats.rounds;
@@ -3635,97 +3713,79 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
     // a window of entries is read by the workgroups whose windows overlap there (4/3 on average), sixteen characters
     // (three aligned words) per owned entry, a byte and a suffix per finished one, an entry per member that stays
     stats.alg_bytes += (u64)m * (14 * 4 / 3 + (pass_chars + 8) + 5);
-    BWTC_HIP_TRY(hipMemsetAsync(ncnt, 0, (kFinRegions + 1) * 4, st));
-    launch_finish(*this, a, rg, n, b, ob, ncnt, d_parkS + park0, d_parkHP + park0, d_hardC, cnt + 1, shal, re, nullptr);
-    BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin, cnt, 24, hipMemcpyDeviceToHost, st));
-    BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFinNext, ncnt, (kFinRegions + 1) * 4, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(fc.clear(kFinNext, kFinGroupsLeft));
+    launch_finish(*this, FinLaunch::pass(*this, rq.n, w.a, w.rg, w.b, ob, d_parkS + park0, d_parkHP + park0, rq.shal), rq.re);
+    BWTC_HIP_TRY(fc.fetch(kFinSpare, kFinShallowDepth));
+    BWTC_HIP_TRY(fc.fetch(kFinNext, kFinGroupsLeft));
     BWTC_HIP_TRY(wait());
     const u32 m_was = m;
-    groups_left = h_small[kSmallFinNext + kFinRegions];
-    // what the pass left, region by region
-    {
-      FinRegions nx;
-      std::memset(&nx, 0, sizeof nx);
-      u32 total = 0;
-      for (u32 r = 0; r < kFinRegions; ++r) {
-        const u32 c = h_small[kSmallFinNext + r];
-        if (!c) continue;
-        nx.ebase[nx.nreg] = ob.base[r]; nx.ecount[nx.nreg] = c;
-        nx.wfirst[nx.nreg + 1] = nx.wfirst[nx.nreg] + ceil_div(c, stride);
-        ++nx.nreg;
-        total += c;
-      }
-      if (nx.nreg == 0) nx.nreg = 1;
-      rg = nx;
-      m = total;
-    }
+    w.rg = fin_regions_left(&fc[kFinNext], ob, stride, &m);   // what the pass left, region by region
     if (debug_on())
       std::fprintf(stderr, "finisher pass %d: %u entries -> %u still tied; %u hard (depth from %u), %u shallow (from %u)\n", it, m_was, m,
-                   h_small[kSmallFin + 1], h_small[kSmallFin + 2], h_small[kSmallFin + 4], h_small[kSmallFin + 5]);
-    hard = h_small[kSmallFin + 1];
-    std::swap(a, b);
-    blk.passes_done = it + 1;
+                   fc[kFinHard], fc[kFinHardDepth], fc[kFinShallow], fc[kFinShallowDepth]);
+    std::swap(w.a, w.b);
+    blk.fin.passes_done = it + 1;
     if (m < 4096u) break;                                                          // a handful: they join the waiting list (a pass of their own is a launch and a host wait for nothing)
-    if (it >= 1 && (u64)m * 5 > (u64)m_was * 3 && (u64)m * 64 > (u64)n) break;     // deep repeats: on to the rounds
+    if (it >= 1 && (u64)m * 5 > (u64)m_was * 3 && (u64)m * 64 > (u64)rq.n) break;     // deep repeats: on to the rounds
     if (it >= 2 && (u64)m * 4 > (u64)m_was * 3) break;                             // a list that hardly shrinks any more: the rounds double, this creeps
   }
-  blk.parked += hard;
-  if ((u64)blk.parked > cap) return -3;
+  // (the mirror holds what the last pass read back: the hard list's words, or their reset values where no pass ran)
+  blk.fin.parked += fc[kFinHard];
+  if ((u64)blk.fin.parked > cap) return -3;
+  fo->hard = fc[kFinHard]; fo->hard_depth = fc[kFinHardDepth];
   // (a pass has run: no group above the bound is left in the list; and its groups are small -- the comparison loop costs a
   // group's size per member: a block that is one text 256 times over has groups of 256 throughout and is the global rounds')
   // (the local list's steps leave up to kFinRegions regions of it: room for that many more windows)
-  FinRegions worst;
-  std::memset(&worst, 0, sizeof worst);
-  worst.nreg = 1; worst.wfirst[1] = ceil_div(m, stride) + kFinRegions;
   FinOut unused;
-  const bool local_fits = fin_room(worst, stride, (u32)group, lcap, &unused);
-  const bool want_local = m && keep_local && blk.passes_done >= 1 && (u64)m * 64 >= (u64)n && (u64)groups_left * 24 >= (u64)m;
+  const bool local_fits = fin_room(fin_one_region(m + kFinRegions * stride, stride), stride, (u32)blk.fin.group, fin_list_cap(cap), &unused);
+  const bool want_local = m && rq.keep_local && blk.fin.passes_done >= 1 && (u64)m * 64 >= (u64)rq.n && (u64)fc[kFinGroupsLeft] * 24 >= (u64)m;
   if (want_local && !local_fits) stats.route |= 128u;
-  if (want_local && local_fits) {
-    // deep repeats in small groups: the doubling rounds take them group by group (local_pass), not through the global sort
-    FinList home{d_hardS, d_LP0, d_LH0, d_hardC};
-    u32 at = 0;
-    for (u32 r = 0; r < rg.nreg; ++r) {
-      if (!rg.ecount[r]) continue;
-      FinList part{a.S + rg.ebase[r], a.P + rg.ebase[r], a.H + rg.ebase[r], a.C + rg.ebase[r]};
-      hipLaunchKernelGGL(k_list_copy, dim3(ceil_div(rg.ecount[r], 256)), dim3(256), 0, st, part, rg.ecount[r], home, at, cnt + 6);
-      at += rg.ecount[r];
-    }
-    BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 6, cnt + 6, 4, hipMemcpyDeviceToHost, st));
+  const int rc = (want_local && local_fits) ? local_handover(w, fo) : m ? park_rest(w, rq, fo) : 0;
+  fo->shallow = fc[kFinShallow]; fo->shallow_depth = fc[kFinShallowDepth];
+  return rc;
+}
+
+// One region of a list's arrays as a list of its own.
+static FinList fin_part(const FinList& a, u32 base) { return FinList{a.S + base, a.P + base, a.H + base, a.C + base}; }
+
+// Deep repeats in small groups: the doubling rounds take them group by group (local_pass), not through the global sort.
+// What the last pass left becomes the local list, one region in its home 0.
+int BwtEngine::local_handover(const FinWork& w, FinOutcome* fo) {
+  const FinCounters fc(*this);
+  u32 at = 0;
+  for (u32 r = 0; r < w.rg.nreg; ++r) {
+    if (!w.rg.ecount[r]) continue;
+    hipLaunchKernelGGL(k_list_copy, dim3(ceil_div(w.rg.ecount[r], 256)), dim3(256), 0, stream, fin_part(w.a, w.rg.ebase[r]), w.rg.ecount[r], local_list(0), at,
+                       fc.word(kFinLocalDepth));
+    at += w.rg.ecount[r];
+  }
+  BWTC_HIP_TRY(fc.fetch(kFinLocalDepth, kFinLocalDepth));
+  BWTC_HIP_TRY(wait());
+  blk.fin.local_depth = fc[kFinLocalDepth];
+  // its smallest depth: every member has taken the same passes, from a level's depth
+  blk.fin.local_m = fo->local = w.m;
+  blk.fin.local_rg = fin_one_region(w.m, blk.fin.stride()); blk.fin.local_home = 0;
+  return 0;
+}
+
+// What the last pass left tied waits for the rounds: appended to d_parkS / d_parkHP.
+int BwtEngine::park_rest(const FinWork& w, const FinRequest& rq, FinOutcome* fo) {
+  const FinCounters fc(*this);
+  if ((u64)blk.fin.parked + w.m > cap) return -3;
+  for (u32 r = 0; r < w.rg.nreg; ++r) {
+    if (!w.rg.ecount[r]) continue;
+    hipLaunchKernelGGL(k_fin_to_hard, dim3(ceil_div(w.rg.ecount[r], 256)), dim3(256), 0, stream, fin_part(w.a, w.rg.ebase[r]), w.rg.ecount[r], d_parkS, d_parkHP,
+                       blk.fin.parked, fc.word(kFinWaitDepth), blk.fin.passes_done ? FinShallow{rq.shal.S, rq.shal.HP, rq.shal.count, 0u} : rq.shal);
+    blk.fin.parked += w.rg.ecount[r];
+  }
+  if (!blk.fin.passes_done) {
+    // a list no pass has looked at: its shallow entries went to the shallow list and left holes behind
+    const u32 before = fc[kFinShallow];
+    BWTC_HIP_TRY(fc.fetch(kFinShallow, kFinShallowDepth));
     BWTC_HIP_TRY(wait());
-    blk.local_depth = h_small[kSmallFin + 6];
-    // its smallest depth: every member has taken the same passes, from a level's depth
-    blk.local_m = m;
-    std::memset(&blk.local_rg, 0, sizeof blk.local_rg);
-    blk.local_rg.nreg = 1; blk.local_rg.wfirst[1] = ceil_div(m, stride); blk.local_rg.ecount[0] = m;
-    blk.local_home = 0;
-    fo->left = 0;
-    fo->hard = hard;
-    fo->hard_depth = h_small[kSmallFin + 2];
-    fo->local = m;
-    return 0;
+    blk.fin.park_holes += fc[kFinShallow] - before;
   }
-  if (m) {
-    // what the last pass left tied waits for the rounds
-    if ((u64)blk.parked + m > cap) return -3;
-    for (u32 r = 0; r < rg.nreg; ++r) {
-      if (!rg.ecount[r]) continue;
-      FinList part{a.S + rg.ebase[r], a.P + rg.ebase[r], a.H + rg.ebase[r], a.C + rg.ebase[r]};
-      hipLaunchKernelGGL(k_fin_to_hard, dim3(ceil_div(rg.ecount[r], 256)), dim3(256), 0, st, part, rg.ecount[r], d_parkS, d_parkHP, blk.parked, cnt + 3,
-                         blk.passes_done ? FinShallow{shal.S, shal.HP, shal.count, 0u} : shal);
-      blk.parked += rg.ecount[r];
-    }
-    if (!blk.passes_done) {
-      // a list no pass has looked at: its shallow entries went to the shallow list and left holes behind
-      const u32 before = h_small[kSmallFin + 4];
-      BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 4, cnt + 4, 8, hipMemcpyDeviceToHost, st));
-      BWTC_HIP_TRY(wait());
-      blk.park_holes += h_small[kSmallFin + 4] - before;
-    }
-  }
-  fo->hard = hard;
-  fo->hard_depth = h_small[kSmallFin + 2];
-  fo->left = m;
+  fo->left = w.m;
   return 0;
 }
 
@@ -3733,18 +3793,17 @@ int BwtEngine::finisher_passes(u32 n, u32 m, FinList a, FinList b, RrEmit& re, F
 // finisher's bound), many of them.  In the doubling rounds it is refined group by group in LDS (k_finish<RANK>)
 // beside the global list, which keeps the groups too large for that.
 FinList BwtEngine::local_list(int home) const {
-  const u64 lcap = cap + cap / 128 + 65536;
   if (home == 0) return FinList{d_hardS, d_LP0, d_LH0, d_hardC};
-  return FinList{reinterpret_cast<u32*>(d_hardHP), reinterpret_cast<u32*>(d_hardHP) + lcap, d_LH1, d_LC1};
+  return FinList{reinterpret_cast<u32*>(d_hardHP), reinterpret_cast<u32*>(d_hardHP) + fin_list_cap(cap), d_LH1, d_LC1};
 }
 int BwtEngine::local_updates() {
-  if (!blk.local_pending) return 0;
+  if (!blk.fin.local_pending) return 0;
   hipStream_t st = stream;
-  for (u32 r = 0; r < blk.local_upd.nreg; ++r)
-    if (blk.local_upd.ecount[r])
-      hipLaunchKernelGGL(k_rank_updates, dim3(ceil_div(blk.local_upd.ecount[r], 1024)), dim3(256), 0, st, (const u32*)d_US, (const u32*)d_UR,
-                         blk.local_upd.ebase[r], blk.local_upd.ecount[r], d_rank);
-  blk.local_pending = false;
+  for (u32 r = 0; r < blk.fin.local_upd.nreg; ++r)
+    if (blk.fin.local_upd.ecount[r])
+      hipLaunchKernelGGL(k_rank_updates, dim3(ceil_div(blk.fin.local_upd.ecount[r], 1024)), dim3(256), 0, st, (const u32*)d_US, (const u32*)d_UR,
+                         blk.fin.local_upd.ebase[r], blk.fin.local_upd.ecount[r], d_rank);
+  blk.fin.local_pending = false;
   return 0;
 }
 // One doubling step of the local list.  h_global: the depth the global list's groups are sorted to (0: there is no
@@ -3752,59 +3811,42 @@ int BwtEngine::local_updates() {
 // and, that far behind it, a second rank: the step adds twice that depth.  A local list far ahead of the global one
 // (two of its steps and more) sits the round out.
 int BwtEngine::local_pass(u32 n, u64 h_global, RrEmit& re) {
-  hipStream_t st = stream;
-  if (blk.local_m == 0) return 0;
-  if (h_global && (u64)blk.local_depth >= 2 * h_global) return 0;
-  const u64 delta = h_global ? std::min<u64>(h_global, blk.local_depth) : blk.local_depth;
-  const u64 at = blk.local_depth, at2 = (u64)blk.local_depth + delta;
+  if (blk.fin.local_m == 0) return 0;
+  if (h_global && (u64)blk.fin.local_depth >= 2 * h_global) return 0;
+  const u64 delta = h_global ? std::min<u64>(h_global, blk.fin.local_depth) : blk.fin.local_depth;
+  const u64 at = blk.fin.local_depth, at2 = (u64)blk.fin.local_depth + delta;
   if (at2 + delta > 0xFFFFFFF0ull) return -3;
-  u32* cnt = d_small + kSmallFin;
-  u32* ncnt = d_small + kSmallFinNext;
-  const int window = blk.fin_window_blk, group = blk.fin_group_blk;   // the local list's groups are as large as the finisher's passes left them
-  const u32 stride = (u32)(window - group);
-  BWTC_HIP_TRY(hipMemsetAsync(ncnt, 0, kFinRegions * 4, st));
-  BWTC_HIP_TRY(hipMemsetAsync(cnt + 1, 0, 4, st));
+  const FinCounters fc(*this);
+  BWTC_HIP_TRY(fc.clear(kFinNext, kFinNextLast));
+  BWTC_HIP_TRY(fc.clear(kFinHard, kFinHard));
   FinOut ob;
-  if (!fin_room(blk.local_rg, stride, (u32)group, cap + cap / 128 + 65536, &ob)) return -3;   // (finisher_passes keeps such lists off this route)
-  FinShallow none{d_parkS, d_parkHP, cnt + 4, 0u};
-  FinRank rk{d_rank, (u32)at, (u32)at2, d_US, d_UR};
-  launch_finish(*this, local_list(blk.local_home), blk.local_rg, n, local_list(1 - blk.local_home), ob, ncnt, d_parkS, d_parkHP,
-                d_LC1 /* never written: no group is too large */, cnt + 1, none, re, &rk);
-  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 1, cnt + 1, 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFinNext, ncnt, kFinRegions * 4, hipMemcpyDeviceToHost, st));
+  // (the shape is the passes': the local list's groups are as large as they left them; finisher_passes keeps lists without room off this route)
+  if (!fin_room(blk.fin.local_rg, blk.fin.stride(), (u32)blk.fin.group, fin_list_cap(cap), &ob)) return -3;
+  launch_finish(*this, FinLaunch::local_step(*this, n, blk.fin.local_home, blk.fin.local_rg, ob, (u32)at, (u32)at2), re);
+  BWTC_HIP_TRY(fc.fetch(kFinHard, kFinHard));
+  BWTC_HIP_TRY(fc.fetch(kFinNext, kFinNextLast));
   BWTC_HIP_TRY(wait());
-  if (h_small[kSmallFin + 1]) return -3;                  // a group above the finisher's bound in a list that has none
-  stats.finisher_entries += blk.local_m;
-  stats.active_sum += blk.local_m;
+  if (fc[kFinHard]) return -3;                            // a group above the finisher's bound in a list that has none
+  stats.finisher_entries += blk.fin.local_m;
+  stats.active_sum += blk.fin.local_m;
   stats.route |= 64u;
-  stats.alg_bytes += (u64)blk.local_m * (14 * 4 / 3 + 8 + 8 + 5 + 8 + 4);
-  blk.local_upd = blk.local_rg;
-  blk.local_pending = true;
-  FinRegions nx;
-  std::memset(&nx, 0, sizeof nx);
-  u32 total = 0;
-  for (u32 r = 0; r < kFinRegions; ++r) {
-    const u32 c = h_small[kSmallFinNext + r];
-    if (!c) continue;
-    nx.ebase[nx.nreg] = ob.base[r]; nx.ecount[nx.nreg] = c;
-    nx.wfirst[nx.nreg + 1] = nx.wfirst[nx.nreg] + ceil_div(c, stride);
-    ++nx.nreg;
-    total += c;
-  }
-  if (nx.nreg == 0) nx.nreg = 1;
+  stats.alg_bytes += (u64)blk.fin.local_m * (14 * 4 / 3 + 8 + 8 + 5 + 8 + 4);
+  blk.fin.local_upd = blk.fin.local_rg;
+  blk.fin.local_pending = true;
+  const u32 m_was = blk.fin.local_m;
+  blk.fin.local_rg = fin_regions_left(&fc[kFinNext], ob, blk.fin.stride(), &blk.fin.local_m);
   if (debug_on())
-    std::fprintf(stderr, "local pass: %u entries at depth %u (+ 2 x %llu) -> %u still tied\n", blk.local_m, blk.local_depth, (unsigned long long)delta, total);
-  blk.local_rg = nx;
-  blk.local_m = total;
-  blk.local_home = 1 - blk.local_home;
-  blk.local_depth = (u32)std::min<u64>(at2 + delta, 0xFFFFFFF0ull);
+    std::fprintf(stderr, "local pass: %u entries at depth %u (+ 2 x %llu) -> %u still tied\n", m_was, blk.fin.local_depth, (unsigned long long)delta, blk.fin.local_m);
+  blk.fin.local_home = 1 - blk.fin.local_home;
+  blk.fin.local_depth = (u32)std::min<u64>(at2 + delta, 0xFFFFFFF0ull);
   return 0;
 }
 
 // ---- test hook: one k_finish launch ("The finisher hooks") -------------------------------------------
 // What k_finish assumes of its list, checked on the host: a list that breaks it makes the kernel store past its arrays.
-static bool fin_test_list_ok(const FinPassTest& t, u64 cap, u64 lcap, FinRegions* rg, FinOut* ob, u32* m_out, u32* span_out, u64* room_out) {
+static bool fin_test_list_ok(const FinPassTest& t, u64 cap, FinRegions* rg, FinOut* ob, u32* m_out, u32* span_out, u64* room_out) {
   const u32 n = t.n;
+  const u64 lcap = fin_list_cap(cap);
   if (n < 1u || (u64)n + TestCanaries::kBytes > cap) return false;
   if (!((t.window == 1024 && (t.group == 256 || t.group == 512)) || (t.window == 2048 && (t.group == 256 || t.group == 512 || t.group == 1024)))) return false;
   if (t.words < 2 || t.words > 4 || t.rounds < 1 || t.rounds > 4 || (t.words != 2 && t.rounds != 1)) return false;
@@ -3858,6 +3900,24 @@ static bool fin_test_list_ok(const FinPassTest& t, u64 cap, u64 lcap, FinRegions
   return true;
 }
 
+// A test hook's arrays, each with its bytes: poisoned (fill), then a canary behind each (can); copied, array by array.  A
+// list's four arrays over `entries` entries, and a raw list's two (suffix; head slot << 32 | slot).
+struct TestSpan { const void* p; u64 bytes; };
+static hipError_t fin_test_guard(const std::vector<TestSpan>& arrays, bool fill, TestCanaries* can, hipStream_t st) {
+  hipError_t rc = hipSuccess;
+  for (const TestSpan& a : arrays) if (fill && rc == hipSuccess) rc = hipMemsetAsync(const_cast<void*>(a.p), 0xA5, a.bytes, st);
+  for (const TestSpan& a : arrays) if (can && rc == hipSuccess) rc = can->put(const_cast<void*>(a.p), a.bytes, st);
+  return rc;
+}
+static hipError_t fin_test_copy(const std::vector<TestSpan>& to, const std::vector<TestSpan>& from, hipMemcpyKind kind, hipStream_t st) {
+  hipError_t rc = hipSuccess;
+  for (size_t i = 0; i < to.size(); ++i) if (rc == hipSuccess) rc = hipMemcpyAsync(const_cast<void*>(to[i].p), from[i].p, to[i].bytes, kind, st);
+  return rc;
+}
+static std::vector<TestSpan> fin_spans(const void* S, const void* P, const void* H, const void* C, u64 entries) { return {{S, entries * 4}, {P, entries * 4}, {H, entries * 4}, {C, entries * 2}}; }
+static std::vector<TestSpan> fin_spans(const FinList& x, u64 entries) { return fin_spans(x.S, x.P, x.H, x.C, entries); }
+static std::vector<TestSpan> fin_spans(const void* S, const void* HP, u64 entries) { return {{S, entries * 4}, {HP, entries * 8}}; }
+
 // the emissions of a hooked launch: SA, out, pidx, last_char and lf[] poisoned, and the RrEmit that points at them
 static hipError_t fin_test_emit_begin(BwtEngine& e, u32 n, u32 out_n, u32 lf_n, u32 lf_x, RrEmit* re) {
   hipStream_t st = e.stream;
@@ -3890,79 +3950,59 @@ struct FinKnobScope {
   const int words, rounds, max_passes; const u32 floor;
   FinKnobScope(BwtEngine& eng, int w, int g, int nw, int nr, u32 fl)
       : e(eng), words(eng.fin_words), rounds(eng.fin_rounds), max_passes(eng.fin_max_passes), floor(eng.fin_floor) {
-    e.blk.fin_window_blk = w; e.blk.fin_group_blk = g; e.fin_words = nw; e.fin_rounds = nr; e.fin_floor = fl; e.fin_max_passes = 8;
+    e.blk.fin.window = w; e.blk.fin.group = g; e.fin_words = nw; e.fin_rounds = nr; e.fin_floor = fl; e.fin_max_passes = 8;
   }
   ~FinKnobScope() { e.fin_words = words; e.fin_rounds = rounds; e.fin_floor = floor; e.fin_max_passes = max_passes; }
 };
 
 int BwtEngine::test_finish_pass(FinPassTest& t) {
-  const u64 lcap = cap + cap / 128 + 65536;
   FinRegions rg; FinOut ob;
   u32 m = 0, span = 0; u64 room = 0;
-  if (!fin_test_list_ok(t, cap, lcap, &rg, &ob, &m, &span, &room)) return -1;
+  if (!fin_test_list_ok(t, cap, &rg, &ob, &m, &span, &room)) return -1;
   hipStream_t st = stream;
   const u32 n = t.n;
   FinKnobScope knobs(*this, t.window, t.group, t.words, t.rounds, t.floor);
   // the lists' homes: the passes' own arrays, the local list's two homes in RANK mode
-  FinList a, b;
-  BWTC_HIP_TRY(finisher_begin(d_V0, &a, &b));           // (and the shallow list's counter words)
-  if (t.ranks) { a = local_list(0); b = local_list(1); }
-  unsigned short* hardC = t.ranks ? d_LC1 : d_hardC;
-  u32* cnt = d_small + kSmallFin;
-  u32* ncnt = d_small + kSmallFinNext;
-  const FinShallow shal = t.ranks ? FinShallow{d_parkS, d_parkHP, cnt + 4, 0u} : FinShallow{d_V1, static_cast<u64*>(d_R2), cnt + 4, fin_floor};
+  FinWork w;
+  BWTC_HIP_TRY(finisher_begin(d_V0, m, &w));            // (and the shallow list's counter words)
+  const FinCounters fc(*this);
+  const FinLaunch q = t.ranks ? FinLaunch::local_step(*this, n, 0, rg, ob, t.at, t.at2)
+                              : FinLaunch::pass(*this, n, w.a, rg, w.b, ob, d_parkS, d_parkHP, fc.shallow_sink(d_V1, static_cast<u64*>(d_R2), fin_floor));
   TestCanaries can;
-  BWTC_HIP_TRY(hipMemcpyAsync(a.S, t.S, (u64)span * 4, hipMemcpyHostToDevice, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(a.P, t.P, (u64)span * 4, hipMemcpyHostToDevice, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(a.H, t.H, (u64)span * 4, hipMemcpyHostToDevice, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(a.C, t.C, (u64)span * 2, hipMemcpyHostToDevice, st));
-  BWTC_HIP_TRY(can.put(a.S, (u64)span * 4, st)); BWTC_HIP_TRY(can.put(a.P, (u64)span * 4, st));
-  BWTC_HIP_TRY(can.put(a.H, (u64)span * 4, st)); BWTC_HIP_TRY(can.put(a.C, (u64)span * 2, st));
-  BWTC_HIP_TRY(hipMemsetAsync(b.S, 0xA5, room * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(b.P, 0xA5, room * 4, st));
-  BWTC_HIP_TRY(hipMemsetAsync(b.H, 0xA5, room * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(b.C, 0xA5, room * 2, st));
-  BWTC_HIP_TRY(can.put(b.S, room * 4, st)); BWTC_HIP_TRY(can.put(b.P, room * 4, st));
-  BWTC_HIP_TRY(can.put(b.H, room * 4, st)); BWTC_HIP_TRY(can.put(b.C, room * 2, st));
-  BWTC_HIP_TRY(hipMemsetAsync(d_parkS, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(d_parkHP, 0xA5, (u64)m * 8, st));
-  BWTC_HIP_TRY(can.put(d_parkS, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(d_parkHP, (u64)m * 8, st));
+  BWTC_HIP_TRY(fin_test_copy(fin_spans(q.in, span), fin_spans(t.S, t.P, t.H, t.C, span), hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(fin_test_guard(fin_spans(q.in, span), false, &can, st));
+  BWTC_HIP_TRY(fin_test_guard(fin_spans(q.out, room), true, &can, st));
+  BWTC_HIP_TRY(fin_test_guard(fin_spans(d_parkS, d_parkHP, m), true, &can, st));
   if (t.ranks) {
     BWTC_HIP_TRY(hipMemcpyAsync(d_rank, t.rank, (u64)n * 4, hipMemcpyHostToDevice, st));
     BWTC_HIP_TRY(hipMemsetAsync(d_US, 0xFF, (u64)span * 4, st));       // kFinNone: a place no member notes is no update
     BWTC_HIP_TRY(hipMemsetAsync(d_UR, 0xA5, (u64)span * 4, st));
-    BWTC_HIP_TRY(can.put(d_US, (u64)span * 4, st)); BWTC_HIP_TRY(can.put(d_UR, (u64)span * 4, st));
+    BWTC_HIP_TRY(fin_test_guard({{d_US, (u64)span * 4}, {d_UR, (u64)span * 4}}, false, &can, st));
   } else {
-    BWTC_HIP_TRY(hipMemsetAsync(d_hardC, 0xA5, (u64)m * 2, st));
-    BWTC_HIP_TRY(can.put(d_hardC, (u64)m * 2, st));
-    BWTC_HIP_TRY(hipMemsetAsync(shal.S, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(shal.HP, 0xA5, (u64)m * 8, st));
-    BWTC_HIP_TRY(can.put(shal.S, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(shal.HP, (u64)m * 8, st));
+    BWTC_HIP_TRY(fin_test_guard({{d_hardC, (u64)m * 2}}, true, &can, st));
+    BWTC_HIP_TRY(fin_test_guard(fin_spans(q.shal.S, q.shal.HP, m), true, &can, st));
   }
-  h_small[kSmallFin + 1] = 0; h_small[kSmallFin + 2] = 0xFFFFFFFFu;
-  BWTC_HIP_TRY(hipMemcpyAsync(cnt + 1, h_small + kSmallFin + 1, 8, hipMemcpyHostToDevice, st));
-  BWTC_HIP_TRY(hipMemsetAsync(ncnt, 0, (kFinRegions + 1) * 4, st));
+  fc[kFinHard] = 0; fc[kFinHardDepth] = 0xFFFFFFFFu;
+  BWTC_HIP_TRY(fc.upload(kFinHard, kFinHardDepth));
+  BWTC_HIP_TRY(fc.clear(kFinNext, kFinGroupsLeft));
   RrEmit re;
   BWTC_HIP_TRY(fin_test_emit_begin(*this, n, t.out_n, t.lf_n, t.lf_x, &re));
-  const FinRank rk{d_rank, t.at, t.at2, d_US, d_UR};
-  launch_finish(*this, a, rg, n, b, ob, ncnt, d_parkS, d_parkHP, hardC, cnt + 1, shal, re, t.ranks ? &rk : nullptr);
+  launch_finish(*this, q, re);
   if (t.ranks) {
-    blk.local_upd = rg; blk.local_pending = true;
+    blk.fin.local_upd = rg; blk.fin.local_pending = true;
     const int rcu = local_updates();
     if (rcu) return rcu;
-    BWTC_HIP_TRY(hipMemcpyAsync(t.rank, d_rank, (u64)n * 4, hipMemcpyDeviceToHost, st));
-    BWTC_HIP_TRY(hipMemcpyAsync(t.us, d_US, (u64)span * 4, hipMemcpyDeviceToHost, st));
-    BWTC_HIP_TRY(hipMemcpyAsync(t.ur, d_UR, (u64)span * 4, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(fin_test_copy({{t.rank, (u64)n * 4}, {t.us, (u64)span * 4}, {t.ur, (u64)span * 4}},
+                               {{d_rank, (u64)n * 4}, {d_US, (u64)span * 4}, {d_UR, (u64)span * 4}}, hipMemcpyDeviceToHost, st));
   } else {
     BWTC_HIP_TRY(hipMemcpyAsync(t.hC, d_hardC, (u64)m * 2, hipMemcpyDeviceToHost, st));
-    BWTC_HIP_TRY(hipMemcpyAsync(t.sS, shal.S, (u64)m * 4, hipMemcpyDeviceToHost, st));
-    BWTC_HIP_TRY(hipMemcpyAsync(t.sHP, shal.HP, (u64)m * 8, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(fin_test_copy(fin_spans(t.sS, t.sHP, m), fin_spans(q.shal.S, q.shal.HP, m), hipMemcpyDeviceToHost, st));
   }
-  BWTC_HIP_TRY(hipMemcpyAsync(t.hS, d_parkS, (u64)m * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.hHP, d_parkHP, (u64)m * 8, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.nS, b.S, room * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.nP, b.P, room * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.nH, b.H, room * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.nC, b.C, room * 2, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.next_count, ncnt, (kFinRegions + 1) * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.hard_count, cnt + 1, 8, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.shal_count, cnt + 4, 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(fin_test_copy(fin_spans(t.hS, t.hHP, m), fin_spans(d_parkS, d_parkHP, m), hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(fin_test_copy(fin_spans(t.nS, t.nP, t.nH, t.nC, room), fin_spans(q.out, room), hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(fc.fetch(kFinNext, kFinGroupsLeft, t.next_count));
+  BWTC_HIP_TRY(fc.fetch(kFinHard, kFinHardDepth, t.hard_count));
+  BWTC_HIP_TRY(fc.fetch(kFinShallow, kFinShallowDepth, t.shal_count));
   BWTC_HIP_TRY(fin_test_emit_fetch(*this, n, t.SA, t.out, t.small, t.lf));
   BWTC_HIP_TRY(can.fetch(st));
   BWTC_HIP_TRY(wait());
@@ -3972,7 +4012,6 @@ int BwtEngine::test_finish_pass(FinPassTest& t) {
 }
 
 int BwtEngine::test_finisher(bwtc_hip_fin_run& t) {
-  const u64 lcap = cap + cap / 128 + 65536;
   // the list's contracts are one pass's, over one region from entry 0
   const u32 ebase = 0, ecount = t.m;
   FinPassTest one;
@@ -3982,60 +4021,41 @@ int BwtEngine::test_finisher(bwtc_hip_fin_run& t) {
   one.floor = t.floor; one.out_n = t.out_n; one.lf_n = t.lf_n; one.lf_x = t.lf_x; one.next_cap = 0xFFFFFFFFu;
   FinRegions rg; FinOut ob;
   u32 m = 0, span = 0; u64 room = 0;
-  if (t.max_passes < 0 || !fin_test_list_ok(one, cap, lcap, &rg, &ob, &m, &span, &room)) return -1;
+  if (t.max_passes < 0 || !fin_test_list_ok(one, cap, &rg, &ob, &m, &span, &room)) return -1;
   // a later pass reads up to 16 regions, each with a last window that is not full: 16 strides (and a chunk's group) more
   room += 16ull * (u32)(t.window - t.group) + 2ull * (u32)t.group;
-  if (room + 128u > lcap) return -1;
+  if (room + 128u > fin_list_cap(cap)) return -1;
   hipStream_t st = stream;
   const u32 n = t.n;
   blk = BlockSort{};                               // a block of its own
   stats.route = 0;
   FinKnobScope knobs(*this, t.window, t.group, t.words, t.rounds, t.floor);
-  FinList a, b;
-  BWTC_HIP_TRY(finisher_begin(d_V0, &a, &b));
-  u32* cnt = d_small + kSmallFin;
-  const FinShallow shal{d_V1, static_cast<u64*>(d_R2), cnt + 4, fin_floor};
-  const FinList home = local_list(0);
+  FinWork w;
+  BWTC_HIP_TRY(finisher_begin(d_V0, m, &w));
+  const FinCounters fc(*this);
+  const FinShallow shal = fc.shallow_sink(d_V1, static_cast<u64*>(d_R2), fin_floor);
   TestCanaries can;
   // both lists take a pass's output in turn: never more than the first pass's room, the longest list's
-  const FinList ab[2] = {a, b};
-  for (int i = 0; i < 2; ++i) {
-    BWTC_HIP_TRY(hipMemsetAsync(ab[i].S, 0xA5, room * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(ab[i].P, 0xA5, room * 4, st));
-    BWTC_HIP_TRY(hipMemsetAsync(ab[i].H, 0xA5, room * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(ab[i].C, 0xA5, room * 2, st));
-    BWTC_HIP_TRY(can.put(ab[i].S, room * 4, st)); BWTC_HIP_TRY(can.put(ab[i].P, room * 4, st));
-    BWTC_HIP_TRY(can.put(ab[i].H, room * 4, st)); BWTC_HIP_TRY(can.put(ab[i].C, room * 2, st));
-  }
-  BWTC_HIP_TRY(hipMemcpyAsync(a.S, t.S, (u64)m * 4, hipMemcpyHostToDevice, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(a.P, t.P, (u64)m * 4, hipMemcpyHostToDevice, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(a.H, t.H, (u64)m * 4, hipMemcpyHostToDevice, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(a.C, t.C, (u64)m * 2, hipMemcpyHostToDevice, st));
-  BWTC_HIP_TRY(hipMemsetAsync(d_parkS, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(d_parkHP, 0xA5, (u64)m * 8, st));
-  BWTC_HIP_TRY(can.put(d_parkS, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(d_parkHP, (u64)m * 8, st));
-  BWTC_HIP_TRY(hipMemsetAsync(shal.S, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(shal.HP, 0xA5, (u64)m * 8, st));
-  BWTC_HIP_TRY(can.put(shal.S, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(shal.HP, (u64)m * 8, st));
-  BWTC_HIP_TRY(hipMemsetAsync(home.S, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(home.P, 0xA5, (u64)m * 4, st));
-  BWTC_HIP_TRY(hipMemsetAsync(home.H, 0xA5, (u64)m * 4, st)); BWTC_HIP_TRY(hipMemsetAsync(home.C, 0xA5, (u64)m * 2, st));   // (d_hardC: the passes' dead output, then the local list's characters)
-  BWTC_HIP_TRY(can.put(home.S, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(home.P, (u64)m * 4, st));
-  BWTC_HIP_TRY(can.put(home.H, (u64)m * 4, st)); BWTC_HIP_TRY(can.put(home.C, (u64)m * 2, st));
+  BWTC_HIP_TRY(fin_test_guard(fin_spans(w.a, room), true, &can, st));
+  BWTC_HIP_TRY(fin_test_guard(fin_spans(w.b, room), true, &can, st));
+  BWTC_HIP_TRY(fin_test_copy(fin_spans(w.a, m), fin_spans(t.S, t.P, t.H, t.C, m), hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(fin_test_guard(fin_spans(d_parkS, d_parkHP, m), true, &can, st));
+  BWTC_HIP_TRY(fin_test_guard(fin_spans(shal.S, shal.HP, m), true, &can, st));
+  BWTC_HIP_TRY(fin_test_guard(fin_spans(local_list(0), m), true, &can, st));   // (d_hardC: the passes' dead output, then the local list's characters)
   RrEmit re;
   BWTC_HIP_TRY(fin_test_emit_begin(*this, n, t.out_n, t.lf_n, t.lf_x, &re));
   FinOutcome fo;
-  const int rc = finisher_passes(n, m, a, b, re, shal, &fo, t.keep_local != 0, t.max_passes);
+  const int rc = finisher_passes(w, FinRequest{n, re, shal, t.keep_local != 0, t.max_passes}, &fo);
   if (rc) return rc;
-  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallFin + 3, cnt + 3, 12, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(fc.fetch(kFinWaitDepth, kFinShallowDepth));
   BWTC_HIP_TRY(wait());
-  if (blk.parked > m || h_small[kSmallFin + 4] > m || fo.local > m) return -3;
+  if (blk.fin.parked > m || fc[kFinShallow] > m || fo.local > m) return -3;
   t.outcome[0] = fo.hard; t.outcome[1] = fo.hard_depth; t.outcome[2] = fo.left; t.outcome[3] = fo.local;
-  t.info[0] = (u32)blk.passes_done; t.info[1] = stats.route; t.info[2] = blk.parked; t.info[3] = blk.park_holes;
-  t.info[4] = h_small[kSmallFin + 4]; t.info[5] = h_small[kSmallFin + 5]; t.info[6] = h_small[kSmallFin + 3]; t.info[7] = fo.local ? blk.local_depth : 0u;
-  BWTC_HIP_TRY(hipMemcpyAsync(t.pS, d_parkS, (u64)blk.parked * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.pHP, d_parkHP, (u64)blk.parked * 8, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.sS, shal.S, (u64)t.info[4] * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.sHP, shal.HP, (u64)t.info[4] * 8, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.lS, home.S, (u64)fo.local * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.lP, home.P, (u64)fo.local * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.lH, home.H, (u64)fo.local * 4, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(hipMemcpyAsync(t.lC, home.C, (u64)fo.local * 2, hipMemcpyDeviceToHost, st));
+  t.info[0] = (u32)blk.fin.passes_done; t.info[1] = stats.route; t.info[2] = blk.fin.parked; t.info[3] = blk.fin.park_holes;
+  t.info[4] = fc[kFinShallow]; t.info[5] = fc[kFinShallowDepth]; t.info[6] = fc[kFinWaitDepth]; t.info[7] = fo.local ? blk.fin.local_depth : 0u;
+  BWTC_HIP_TRY(fin_test_copy(fin_spans(t.pS, t.pHP, blk.fin.parked), fin_spans(d_parkS, d_parkHP, blk.fin.parked), hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(fin_test_copy(fin_spans(t.sS, t.sHP, t.info[4]), fin_spans(shal.S, shal.HP, t.info[4]), hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(fin_test_copy(fin_spans(t.lS, t.lP, t.lH, t.lC, fo.local), fin_spans(local_list(0), fo.local), hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(fin_test_emit_fetch(*this, n, t.SA, t.out, t.small, t.lf));
   BWTC_HIP_TRY(can.fetch(st));
   BWTC_HIP_TRY(wait());
@@ -4071,13 +4091,12 @@ void BwtEngine::complete_ranks(u32 n, const u32* list_sfx, const u32* list_slot,
   u32* pairs = static_cast<u32*>(pairs_region);
   hipLaunchKernelGGL(k_bridge_pairs_all, dim3(ceil_div(n, 1024)), dim3(256), 0, st, (const u32*)d_SA, n, pairs, pairs + cap);
   if (m) hipLaunchKernelGGL(k_bridge_pairs_fix, dim3(ceil_div(m, 256)), dim3(256), 0, st, list_sfx, list_slot, m, pairs, pairs + cap);
-  for (u32 r = 0; blk.local_m && r < blk.local_rg.nreg; ++r) {
-    if (!blk.local_rg.ecount[r]) continue;
-    const FinList h = local_list(blk.local_home);
-    FinList part{h.S + blk.local_rg.ebase[r], h.P + blk.local_rg.ebase[r], h.H + blk.local_rg.ebase[r], h.C + blk.local_rg.ebase[r]};
-    hipLaunchKernelGGL(k_bridge_pairs_fix_list, dim3(ceil_div(blk.local_rg.ecount[r], 256)), dim3(256), 0, st, part, blk.local_rg.ecount[r], pairs, pairs + cap);
+  for (u32 r = 0; blk.fin.local_m && r < blk.fin.local_rg.nreg; ++r) {
+    if (!blk.fin.local_rg.ecount[r]) continue;
+    hipLaunchKernelGGL(k_bridge_pairs_fix_list, dim3(ceil_div(blk.fin.local_rg.ecount[r], 256)), dim3(256), 0, st,
+                       fin_part(local_list(blk.fin.local_home), blk.fin.local_rg.ebase[r]), blk.fin.local_rg.ecount[r], pairs, pairs + cap);
   }
-  if (blk.parked) hipLaunchKernelGGL(k_bridge_pairs_fix_parked, dim3(ceil_div(blk.parked, 256)), dim3(256), 0, st, (const u32*)d_parkS, (const u64*)d_parkHP, blk.parked, pairs, pairs + cap);
+  if (blk.fin.parked) hipLaunchKernelGGL(k_bridge_pairs_fix_parked, dim3(ceil_div(blk.fin.parked, 256)), dim3(256), 0, st, (const u32*)d_parkS, (const u64*)d_parkHP, blk.fin.parked, pairs, pairs + cap);
   scatter_rank_pairs(pairs, static_cast<u32*>(tmp_region), n, n);
 }
 

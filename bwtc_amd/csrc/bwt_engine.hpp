@@ -43,11 +43,15 @@ struct FinShallow;
 struct InitialSort;
 struct SortList;
 struct RankRequest;
-struct FinOutcome { u32 hard = 0, hard_depth = 0xFFFFFFFFu, left = 0, local = 0; };
+struct FinWork;
+struct FinRequest;
+// what finisher_passes left: entries of groups too large for a window (and their smallest depth), entries its last pass left
+// tied and parked, entries handed to the local list, entries of the shallow list (and their smallest depth)
+struct FinOutcome { u32 hard = 0, hard_depth = 0xFFFFFFFFu, left = 0, local = 0, shallow = 0, shallow_depth = 0xFFFFFFFFu; };
 // A finisher list lives in up to kFinRegions regions of its arrays (bwt_engine.hip, k_finish)
 constexpr u32 kFinRegions = 16;
 constexpr u32 kPeriodMax = 4096;   // the longest period the period step looks for (bwt_engine.hip, "Periods")
-struct FinRegions { u32 nreg; u32 wfirst[kFinRegions + 1]; u32 ebase[kFinRegions]; u32 ecount[kFinRegions]; };   // a finisher run: entries of groups too large (and their smallest depth), entries its last pass left tied
+struct FinRegions { u32 nreg; u32 wfirst[kFinRegions + 1]; u32 ebase[kFinRegions]; u32 ecount[kFinRegions]; };
 
 // 256 bytes of canary behind the last item a test hook's kernels may write (c_abi.hip, BwtEngine::test_finish_pass): a
 // changed canary is kBase - (index in the order they were put).
@@ -437,16 +441,20 @@ struct BwtEngine {
   // too (BWTC_HIP_MIXED: the first round is one period step over k_p[] in place of the run step that was due).
   struct StretchStep { u32 p = 0; enum When { kNone, kThisRound, kWaiting } when = kNone; u32 depth = 0; bool ranks_runs = false; };
   struct BlockSort {
-    u32 parked = 0;            // entries waiting in d_parkS / d_parkHP
-    u32 park_holes = 0;        //   of which empty (all ones: they sort to the list's end)
     bool ranks_live = false;   // rank[] has been completed (every ranking step keeps it exact from then on)
     bool fin_active = false;   // the block takes the finisher route: finished suffixes also go to d_SA
     bool lf_noted = false;     // the LF powers were noted as suffixes became final (rank[] is not complete)
-    // the passes' shape (finisher_passes and local_pass must agree: the local list's groups are as large as the passes left them):
-    int fin_window_blk = 1024, fin_group_blk = 256;   // set by finisher_route before the passes, by FinKnobScope for a test hook
-    // the local list (deep repeats in small groups, doubled group by group beside the global list: bwt_engine.hip, local_pass)
-    u32 local_m = 0, local_depth = 0; int local_home = 0, passes_done = 0; bool local_pending = false;
-    FinRegions local_rg = {}, local_upd = {};   // where the local list lives now; where the last pass's notes lie
+    // the finisher's state (bwt_engine.hip, finisher_route): the waiting list, the passes' shape, the local list
+    struct Finisher {
+      u32 parked = 0;            // entries waiting in d_parkS / d_parkHP
+      u32 park_holes = 0;        //   of which empty (all ones: they sort to the list's end)
+      // the passes' shape (finisher_passes and local_pass must agree: the local list's groups are as large as the passes left them):
+      int window = 1024, group = 256;   // set by finisher_shape before the passes, by FinKnobScope for a test hook
+      u32 stride() const { return (u32)(window - group); }   // entries whose groups a workgroup owns
+      // the local list (deep repeats in small groups, doubled group by group beside the global list: bwt_engine.hip, local_pass)
+      u32 local_m = 0, local_depth = 0; int local_home = 0, passes_done = 0; bool local_pending = false;
+      FinRegions local_rg = {}, local_upd = {};   // where the local list lives now; where the last pass's notes lie
+    } fin;
     u32 lengths_period = 0;    // the period d_runK's lengths were made for (0: none yet)
     u32 run_longest = 0;       // the longest run, once a pass of period 1 has found it (made at most once per block)
     u32 proper_longest = 0;    // BWTC_HIP_MIXED: the longest proper stretch (0: no pass has made it)
@@ -513,10 +521,17 @@ struct BwtEngine {
   int initial_wide(const InitialSort& in, bool allow_code_keys, SortList& L, u64* h);
   int initial_keys64(const InitialSort& in, const GramPlan& gp, int key_bits, u32 short_len, int split, SortList& L, u64 h);
   int initial_long(const InitialSort& in, const GramPlan& gp, int key_bits, int split, bool coded, SortList& L, u64* h, bool* ranked);
-  int run_rounds(SortList& L, u32 m, u64 h0, int text_rounds_now, bool keep_first, bool doubling, u32* left, u64* h_left);
+  // the rounds over a sorted list of m entries from depth h0: text_rounds rounds that compare the text first; keep_first: the
+  // list is sorted to h0 as it stands; doubling == false: text rounds only, and what they leave tied comes back in RoundsLeft
+  struct RoundsRequest { u32 m; u64 h0; int text_rounds; bool keep_first, doubling; };
+  struct RoundsLeft { u32 left = 0; u64 h_left = 0; };
+  int run_rounds(SortList& L, const RoundsRequest& ask, RoundsLeft* out = nullptr);
   int step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool text_round, bool* due);
   int finisher_route(SortList& L, u32 n_lf);
-  hipError_t finisher_begin(u32* S, FinList* a, FinList* b);
+  int finisher_shape(u32 n, const RankResult& res);                                        // -> blk.fin.window / group; the passes at most
+  int shallow_rounds(SortList& L, const FinOutcome& fo, u32* shallow_depth);
+  int waiting_to_rounds(SortList& L, const FinOutcome& fo, u32 shallow_depth);
+  hipError_t finisher_begin(u32* S, u32 m, FinWork* w);
   bool no_emit = false;      // BWTC_HIP_NO_EMIT: suffix array + gather even for blocks that could carry
   bool long_keys = true;     // BWTC_HIP_LONG=0: never the long-key initial sort
   int long_items_per_thread = 8;   // BWTC_HIP_LONG_E=6: tiles of 3072 items (three workgroups per CU instead of two)
@@ -544,9 +559,12 @@ struct BwtEngine {
   int text_rounds = 6;       // BWTC_HIP_TEXT_ROUNDS: rounds that compare the text itself before rank[] is completed for doubling
   bool text_rounds_fixed = false;
   void complete_ranks(u32 n, const u32* list_sfx, const u32* list_slot, u32 m, void* pairs_region, void* tmp_region);
-  // finisher passes over list a (m entries, one region; b: spare list arrays): groups too large for a window go to
-  // d_hardS / d_hardHP / d_hardC, shallow ones to shal, what the last pass leaves tied is appended to d_parkS / d_parkHP (`parked`)
-  int finisher_passes(u32 n, u32 m, struct FinList a, struct FinList b, struct RrEmit& re, struct FinShallow shal, FinOutcome* fo, bool keep_local = false, int max_passes = 1 << 30);
+  // finisher passes over the list w (m entries, one region; b: spare list arrays): groups too large for a window go to
+  // d_parkS / d_parkHP / d_hardC, shallow ones to rq.shal; what the last pass leaves tied becomes the local list
+  // (local_handover) or is appended to d_parkS / d_parkHP (park_rest; `parked`)
+  int finisher_passes(FinWork& w, const FinRequest& rq, FinOutcome* fo);
+  int local_handover(const FinWork& w, FinOutcome* fo);
+  int park_rest(const FinWork& w, const FinRequest& rq, FinOutcome* fo);
   // the local list (deep repeats in small groups, doubled group by group beside the global list: bwt_engine.hip, local_pass)
   bool local_rounds = true;  // BWTC_HIP_LOCAL_ROUNDS=0: what the finisher's passes leave joins the waiting list, as in round 4
   u32* d_LP0 = nullptr; u32* d_LH0 = nullptr; u32* d_LH1 = nullptr; unsigned short* d_LC1 = nullptr;

@@ -3,9 +3,10 @@
 
 A line holds the case's name and switch set, the block's size and starting points, SHA-256 of the transformed bytes, the
 LF powers, pidx (LF[0]), stats.rounds / route / active_sum / sort_pass_items / finisher_entries / alg_bytes, what
-bwtc_hip_period_get and bwtc_hip_steps_get say, and the sorter's debug lines that begin with "runs:", "periods:" or
-"steps:", their measured times masked ("took * ms"): every stretch-length pass (storing or trial, with its period), the
-vote kernel and each decision.  Two builds of the library whose traces are equal line for line sorted these blocks by
+bwtc_hip_period_get and bwtc_hip_steps_get say, and the sorter's debug lines that begin with "runs:", "periods:",
+"steps:", "finisher:", "finisher pass", "local pass:" or "shallow groups:", their measured times masked ("took * ms"):
+every stretch-length pass (storing or trial, with its period), the vote kernel and each decision, and every finisher
+pass and local step with its counts and depths.  Two builds of the library whose traces are equal line for line sorted these blocks by
 the same routes, with the same passes in the same order and the same launch-independent counters, to the same bytes:
 the check of a change to the sorter's host code that is meant to change nothing.
 
@@ -51,7 +52,9 @@ MIXED = "BWTC_HIP_MIXED=1"
 # What the cases with the switch must show between them (main's closing assertion)
 STEP_SIGHTS = ("one period step that ranked the runs too", "a period step behind the run step", "no period step after a run step",
                "no period step under a forced period")
-SAID = ("runs:", "periods:", "steps:")
+# ... and the finisher's own lines: each pass's entries in and out with the hard and shallow counts and depths, what goes on
+# to the rounds, the shallow groups' leftovers and the local list's steps, in order
+SAID = ("runs:", "periods:", "steps:", "finisher:", "finisher pass", "local pass:", "shallow groups:")
 TOOK = re.compile(r"took [0-9.]+ ms")
 VOTES = re.compile(r"with [0-9]+ votes")
 
