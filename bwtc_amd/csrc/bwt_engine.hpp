@@ -34,6 +34,8 @@
 #include <functional>
 #include <vector>
 
+namespace bwtc { namespace wavelet { namespace gm { struct Task; struct Chunk; } } }   // wavelet_gpu_models.hpp
+
 namespace bwtc_hip {
 
 struct RrEmit;
@@ -650,6 +652,10 @@ int wavelet_models_device(BwtEngine& e, const u32* d_packed, u32 n_coded, const 
 // that table, else read back with a short wait)
 int wavelet_models_prepare(BwtEngine& e, const u32* d_packed, u32 n_coded, const bwtc::wavelet::StreamPlan& plan,
                            const std::vector<u32>& coded_pos, GmPass* g, bool read_ends = false, hipStream_t side = nullptr);
+// the same from "tasks and chunks are known" on (gm::buildTasks / gm::cutChunks, wavelet_gpu_models.hpp)
+int wavelet_models_prepare_tasks(BwtEngine& e, const u32* d_packed, u32 n_coded, const std::vector<bwtc::wavelet::gm::Task>& tasks,
+                                 const std::vector<bwtc::wavelet::gm::Chunk>& chunks, GmPass* g, bool read_ends = false,
+                                 hipStream_t side = nullptr);
 int wavelet_models_run(BwtEngine& e, const GmPass& g, u32 state_in, uint16_t* h_w, u32* h_tail, u32* early_state);
 
 // WaveletEncoder: writeBlockHeader + encodeData + finishBlock (WaveletCoders.cpp:173-219,

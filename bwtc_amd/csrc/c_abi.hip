@@ -1479,6 +1479,154 @@ int bwtc_hip_test_gpu_lanes(bwtc_hip_ctx* ctx, const uint16_t* w, uint64_t n, co
   offsets[k] = at;
   return 0;
 }
+// ---- test hooks of the model passes (wavelet_gpu_models.hip / .hpp) ------------------------
+namespace {
+// the hooks' contract for a task list: types 0..3, tasks non-empty and tiling [0, n_coded) in order
+bool model_tasks_from(const uint32_t* tasks, uint32_t nt, uint32_t n_coded, std::vector<bwtc::wavelet::gm::Task>* out) {
+  if (!tasks || nt == 0 || n_coded == 0 || n_coded > 0xFFFFF800u) return false;
+  uint32_t at = 0;
+  for (uint32_t t = 0; t < nt; ++t) {
+    const uint32_t b = tasks[3 * (size_t)t], e = tasks[3 * (size_t)t + 1], type = tasks[3 * (size_t)t + 2];
+    if (type > 3u || b != at || e <= b || e > n_coded) return false;
+    at = e;
+  }
+  if (at != n_coded) return false;
+  out->resize(nt);
+  for (uint32_t t = 0; t < nt; ++t) (*out)[t] = bwtc::wavelet::gm::Task{tasks[3 * (size_t)t], tasks[3 * (size_t)t + 1], tasks[3 * (size_t)t + 2], 0};
+  return true;
+}
+}  // namespace
+
+int bwtc_hip_test_models(bwtc_hip_ctx* ctx, const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks, uint32_t nt,
+                         uint32_t state_in, uint32_t flags, bwtc_hip_models_out* out) {
+  namespace gm = bwtc::wavelet::gm;
+  if (!ctx || !packed || !tasks || !out || !out->w || state_in > 7u || flags > 3u) return -1;
+  const bool lean = (flags & 2u) != 0;
+  if (!lean && (!out->chunks || !out->cmap || !out->cstate || !out->base || !out->sb || !out->sbits || !out->smap || !out->snaps ||
+                !out->sstart)) return -1;
+  BwtEngine& e = ctx->eng;
+  const u64 piece_bytes = ((u64)n_coded + 63) / 64 * 16;              // the packed streams go to R1 (8 * cap bytes)
+  if (piece_bytes > e.cap * 8) return -1;
+  std::vector<gm::Task> tk;
+  if (!model_tasks_from(tasks, nt, n_coded, &tk)) return -1;
+  std::vector<gm::Chunk> chunks;
+  gm::cutChunks(&tk, &chunks);
+  const u32 nc = (u32)chunks.size();
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  BWTC_HIP_TRY(e.codes_wait());
+  BWTC_HIP_TRY(e.wait());
+  u32* d_packed = static_cast<u32*>(e.d_R1);
+  BWTC_HIP_TRY(hipMemsetAsync(d_packed, 0, piece_bytes, e.stream));
+  BWTC_HIP_TRY(hipMemcpyAsync(d_packed, packed, ((u64)n_coded + 15) / 16 * 4, hipMemcpyHostToDevice, e.stream));
+  struct Lines {                                                      // the form of the partition pass, for this call only
+    BwtEngine& e; bool was;
+    Lines(BwtEngine& en, bool on) : e(en), was(en.gm_partition_lines) { e.gm_partition_lines = on; }
+    ~Lines() { e.gm_partition_lines = was; }
+  } lines(e, (flags & 1u) != 0);
+  GmPass g;
+  int rc = wavelet_models_prepare_tasks(e, d_packed, n_coded, tk, chunks, &g, true);
+  if (rc) return rc;
+  if (!g.ends_ready) return -3;
+  for (int i = 0; i < 8; ++i) out->ends[i] = g.ends[i];
+  out->tail[0] = out->tail[1] = out->tail[2] = out->tail[3] = 0xFFFFFFFFu;
+  u32 early = 0xFFFFFFFFu;
+  rc = wavelet_models_run(e, g, state_in, out->w, out->tail, &early);
+  const hipError_t hw = e.codes_wait();                               // (also after an error: whatever was queued is through)
+  const hipError_t hs = e.wait();
+  if (rc) return rc;
+  BWTC_HIP_TRY(hw);
+  BWTC_HIP_TRY(hs);
+  BWTC_HIP_TRY(hipGetLastError());
+  if (early != g.ends[state_in]) return -3;
+  out->nc = nc;
+  out->nsc = g.nsc;
+  if (lean) return 0;
+  // the chunk table as the device holds it
+  {
+    std::vector<gm::Chunk> back(nc);
+    BWTC_HIP_TRY(hipMemcpy(back.data(), g.d_chunks, (size_t)nc * sizeof(gm::Chunk), hipMemcpyDeviceToHost));
+    for (u32 c = 0; c < nc; ++c) {
+      out->chunks[3 * (size_t)c] = back[c].begin; out->chunks[3 * (size_t)c + 1] = back[c].end; out->chunks[3 * (size_t)c + 2] = back[c].task_first;
+    }
+  }
+  BWTC_HIP_TRY(hipMemcpy(out->cmap, g.d_cmap, (size_t)nc * 8, hipMemcpyDeviceToHost));
+  BWTC_HIP_TRY(hipMemcpy(out->cstate, g.d_cstate, (size_t)nc * 4, hipMemcpyDeviceToHost));
+  BWTC_HIP_TRY(hipMemcpy(out->base, g.d_base, (size_t)g.n_base * 4, hipMemcpyDeviceToHost));
+  BWTC_HIP_TRY(hipMemcpy(out->sb, g.d_sb, ((size_t)g.ns + 1) * 4, hipMemcpyDeviceToHost));
+  BWTC_HIP_TRY(hipMemcpy(out->sbits, g.d_sbits, ((size_t)n_coded / 32 + 16) * 4, hipMemcpyDeviceToHost));
+  BWTC_HIP_TRY(hipMemcpy(out->smap, g.d_smap, (size_t)g.nsc * sizeof(gm::SlotMap), hipMemcpyDeviceToHost));
+  BWTC_HIP_TRY(hipMemcpy(out->snaps, g.d_snaps, (((size_t)n_coded + gm::kSample - 1) / gm::kSample) * sizeof(gm::SlotMap), hipMemcpyDeviceToHost));
+  BWTC_HIP_TRY(hipMemcpy(out->sstart, g.d_sstart, (size_t)g.nsc * 2, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int bwtc_hip_host_test_models(const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks, uint32_t nt,
+                              uint32_t state_in, uint16_t* w_out, uint32_t* state_out) {
+  namespace gm = bwtc::wavelet::gm;
+  if (!packed || !tasks || !w_out || !state_out || state_in > 7u) return -1;
+  std::vector<gm::Task> tk;
+  if (!model_tasks_from(tasks, nt, n_coded, &tk)) return -1;
+  std::vector<gm::Chunk> chunks;
+  gm::cutChunks(&tk, &chunks);
+  // buffers of exactly the sizes wavelet_models_prepare and reserve_models allot: whole 16-byte pieces, n_coded + 8 elements
+  std::vector<uint32_t> pk(((size_t)n_coded + 63) / 64 * 4, 0);
+  std::memcpy(pk.data(), packed, ((size_t)n_coded + 15) / 16 * 4);
+  std::vector<uint16_t> w((size_t)n_coded + 8);
+  uint32_t st = state_in;
+  if (!gm::modelsOnHostLanes(pk.data(), n_coded, tk, chunks, &st, w.data())) return -7;
+  std::memcpy(w_out, w.data(), (size_t)n_coded * 2);
+  *state_out = st;
+  return 0;
+}
+
+int bwtc_hip_host_wavelet_elements(uint32_t n_sections, const uint32_t* first_run,
+                                   const uint8_t* run_sym, const uint32_t* run_start,
+                                   const uint32_t* run_freqs, const uint32_t* dist_offset,
+                                   const uint32_t* dist_len, const uint32_t* dist_cnt, uint32_t* state,
+                                   uint32_t* n_coded, uint32_t* nt, uint32_t* packed, uint64_t packed_words,
+                                   uint32_t* tasks, uint32_t tasks_cap, uint16_t* w, uint64_t w_cap) {
+  if (!first_run || !run_sym || !run_start || !run_freqs || !dist_offset || !dist_len || !dist_cnt ||
+      !state || !n_coded || !nt || n_sections > 256) return -1;
+  std::vector<std::vector<std::pair<uint32_t, uint32_t> > > dist(n_sections);
+  std::vector<bwtc::wavelet::SectionRuns> secs(n_sections);
+  for (uint32_t s = 0; s < n_sections; ++s) {
+    for (uint32_t i = dist_offset[s]; i < dist_offset[s + 1]; ++i) dist[s].push_back(std::make_pair(dist_len[i], dist_cnt[i]));
+    secs[s].symbols = run_sym + first_run[s];
+    secs[s].starts = run_start + first_run[s];
+    secs[s].n_runs = first_run[s + 1] - first_run[s];
+    secs[s].run_freqs = run_freqs + (size_t)s * 256;
+    secs[s].dist = dist[s].data();
+    secs[s].n_dist = dist[s].size();
+  }
+  bwtc::wavelet::StreamPlan plan;
+  if (!bwtc::wavelet::planStreams(secs, &plan)) return -5;
+  std::vector<uint32_t> coded_pos;
+  std::vector<uint8_t> codes;
+  if (!bwtc::wavelet::expandStreamsOnHost(plan, secs, &coded_pos, &codes)) return -3;
+  const uint32_t total = coded_pos.back();
+  std::vector<bwtc::wavelet::gm::Task> tk;
+  std::vector<bwtc::wavelet::gm::Chunk> chunks;
+  bwtc::wavelet::gm::buildTasks(plan, coded_pos.data(), &tk, &chunks);
+  *n_coded = total;
+  *nt = (uint32_t)tk.size();
+  if (!packed && !tasks && !w) return 0;                              // the sizes alone
+  if (!packed || !tasks || !w || packed_words < ((uint64_t)total + 15) / 16 || tasks_cap < tk.size() || w_cap < total) return -1;
+  for (uint64_t i = 0; i < ((uint64_t)total + 15) / 16; ++i) packed[i] = 0;
+  std::memcpy(packed, codes.data(), std::min<size_t>(codes.size(), ((size_t)total + 3) / 4));
+  for (size_t t = 0; t < tk.size(); ++t) { tasks[3 * t] = tk[t].begin; tasks[3 * t + 1] = tk[t].end; tasks[3 * t + 2] = tk[t].type; }
+  // the sequential coder's models: group by group, the probability of a ONE per element -> w form
+  codes.push_back(0);
+  bwtc::wavelet::StreamCoder sc(plan, coded_pos.data(), codes.data(), *state, 'B');
+  std::vector<uint16_t> prob((size_t)total + 8, 0);
+  for (size_t k = 0; k < sc.modelTasks(); ++k) sc.model(k, prob.data());
+  for (uint32_t i = 0; i < total; ++i) {
+    const uint32_t bit = (codes[i >> 2] >> ((i & 3u) * 2u)) & 1u;
+    w[i] = (uint16_t)((bit << 15) | (bit ? prob[i] : 4096u - prob[i]));
+  }
+  *state = sc.endState();
+  return 0;
+}
+
 int bwtc_hip_test_scan_u32(bwtc_hip_ctx* ctx, uint32_t* data, uint64_t n) {
   if (!ctx || !data) return -1;
   BwtEngine& e = ctx->eng;

@@ -292,12 +292,18 @@ int BwtEngine::reserve_models(u64 device_bytes, u64 host_bytes, u64 w_bytes) {
 // of some tens of microseconds) and returned, before the long passes are queued.
 int wavelet_models_prepare(BwtEngine& e, const u32* d_packed, u32 n_coded, const bwtc::wavelet::StreamPlan& plan,
                            const std::vector<u32>& coded_pos, GmPass* g, bool read_ends, hipStream_t side) {
-  BwtEngine::ScanScope scan_scope(e);
-  hipStream_t st = side ? side : e.stream;             // side: the passes run beside the next block's transform (wavelet_models_device)
-  g->side = side;
   std::vector<gm::Task> tasks;
   std::vector<gm::Chunk> chunks;
   gm::buildTasks(plan, coded_pos.data(), &tasks, &chunks);
+  return wavelet_models_prepare_tasks(e, d_packed, n_coded, tasks, chunks, g, read_ends, side);
+}
+
+// The same from "tasks and chunks are known" on (the test hook bwtc_hip_test_models enters here with a given task list).
+int wavelet_models_prepare_tasks(BwtEngine& e, const u32* d_packed, u32 n_coded, const std::vector<gm::Task>& tasks,
+                                 const std::vector<gm::Chunk>& chunks, GmPass* g, bool read_ends, hipStream_t side) {
+  BwtEngine::ScanScope scan_scope(e);
+  hipStream_t st = side ? side : e.stream;             // side: the passes run beside the next block's transform (wavelet_models_device)
+  g->side = side;
   const u32 nt = (u32)tasks.size(), nc = (u32)chunks.size();
   if (nt == 0 || nc == 0 || n_coded == 0) return -1;
   g->d_packed = d_packed; g->n_coded = n_coded; g->nt = nt; g->nc = nc;

@@ -591,6 +591,8 @@ BWTC_GM_HD void laneEmit(const u32* packed, u32 begin, u32 end, u32 type, u32 st
 // Tasks (in coding order) and chunks of a block from its plan and the groups' coded positions.
 void buildTasks(const ::bwtc::wavelet::StreamPlan& plan, const u32* coded_pos, std::vector<Task>* tasks,
                 std::vector<Chunk>* chunks);
+// The chunks of given tasks (begin, end, type): every task cut along the aligned grid of kChunk elements; sets first_chunk.
+void cutChunks(std::vector<Task>* tasks, std::vector<Chunk>* chunks);
 
 // The passes above run lane by lane on the host (tests; the product runs them on the GPU).
 // state: the main machine's carried state, updated.  false: an error flag was raised.

@@ -34,6 +34,11 @@ void buildTasks(const ::bwtc::wavelet::StreamPlan& plan, const u32* coded_pos, s
       if (e > b) tasks->push_back(Task{b, e, kTInts, 0});
     }
   }
+  cutChunks(tasks, chunks);
+}
+
+void cutChunks(std::vector<Task>* tasks, std::vector<Chunk>* chunks) {
+  chunks->clear();
   for (size_t t = 0; t < tasks->size(); ++t) {
     Task& task = (*tasks)[t];
     task.first_chunk = static_cast<u32>(chunks->size());

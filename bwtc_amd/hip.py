@@ -232,6 +232,12 @@ class Round(ctypes.Structure):
                 ("lf_x", _u32)] + [(f, _vp) for f in ("result", "nks", "nvs", "naglob", "ngrp", "nchr", "SA", "out", "small", "lf")]
 
 
+class ModelsOut(ctypes.Structure):
+    """bwtc_hip_models_out (include/bwtc_hip.h): what the model passes left, copied back by bwtc_hip_test_models."""
+    _fields_ = [("w", _vp), ("tail", _u32 * 4), ("ends", _u32 * 8), ("nc", _u32), ("nsc", _u32)] + \
+               [(f, _vp) for f in ("chunks", "cmap", "cstate", "base", "sb", "sbits", "smap", "snaps", "sstart")]
+
+
 class KernelTimers(ctypes.Structure):
     _fields_ = [("scatter_launches", _u64), ("scatter_bytes", _u64), ("scatter_ms", ctypes.c_double)]
 
@@ -258,6 +264,7 @@ EXPORTS = [
     "bwtc_hip_period_get", "bwtc_hip_test_period_lengths", "bwtc_hip_steps_get", "bwtc_hip_test_period_proper",
     "bwtc_hip_test_code_stage", "bwtc_hip_test_code_table", "bwtc_hip_test_code_keys",
     "bwtc_hip_test_finish_pass", "bwtc_hip_test_local_pass", "bwtc_hip_test_finisher",
+    "bwtc_hip_test_models", "bwtc_hip_host_test_models", "bwtc_hip_host_wavelet_elements",
     "bwtc_hip_test_rank_pass", "bwtc_hip_test_rank_scan", "bwtc_hip_test_rank_scatter", "bwtc_hip_test_round_keys", "bwtc_hip_test_round",
     "bwtc_hip_wavelet_depth_needed", "bwtc_hip_grammar_create", "bwtc_hip_grammar_destroy", "bwtc_hip_grammar_rules", "bwtc_hip_grammar_special_symbols",
     "bwtc_hip_grammar_is_special", "bwtc_hip_grammar_write", "bwtc_hip_grammar_read", "bwtc_hip_pair_replace_device",
@@ -356,6 +363,10 @@ def load():
     L.bwtc_hip_host_wavelet_sections.argtypes = [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, ctypes.c_char, _vp, _vp, _u64,
                                                  ctypes.POINTER(_u64)]
     L.bwtc_hip_host_wavelet_streams.argtypes = L.bwtc_hip_host_wavelet_sections.argtypes
+    L.bwtc_hip_test_models.argtypes = [_vp, _vp, _u32, _vp, _u32, _u32, _u32, ctypes.POINTER(ModelsOut)]
+    L.bwtc_hip_host_test_models.argtypes = [_vp, _u32, _vp, _u32, _u32, _vp, ctypes.POINTER(_u32)]
+    L.bwtc_hip_host_wavelet_elements.argtypes = [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
+                                                 ctypes.POINTER(_u32), _vp, _u64, _vp, _u32, _vp, _u64]
     L.bwtc_hip_host_wavelet_streams_lanes.argtypes = L.bwtc_hip_host_wavelet_sections.argtypes
     # pair-replacing pre-stage (`--prepr`)
     L.bwtc_hip_grammar_create.restype = _vp
@@ -608,6 +619,33 @@ class Context:
         _check(self.lib.bwtc_hip_test_gpu_lanes(self.handle, _ptr(w), w.size, _ptr(b), k, mode, _ptr(out), out.size, _ptr(off)),
                "bwtc_hip_test_gpu_lanes")
         return [out[int(off[j]):int(off[j + 1])].tobytes() for j in range(k)]
+
+    def test_models(self, packed, n_coded, tasks, state_in, flags=0):
+        """The model passes (wavelet_gpu_models.hip) over given packed streams and tasks [(begin, end, type)]: a dict of
+        w, tail, ends, nc, nsc and -- unless flags bit 1 -- chunks, cmap, cstate, base, sb, sbits, smap, snaps, sstart.
+        flags bit 0: the lines form of the partition pass (bwtc_hip_test_models)."""
+        packed, tasks = _models_args(packed, tasks)
+        nt, n = tasks.shape[0], int(n_coded)
+        nc_room, nsc = nt + n // 2048, (n + 2047) // 2048
+        r = {"w": np.zeros(n, np.uint16)}
+        if not flags & 2:
+            r.update(chunks=np.zeros((nc_room, 3), np.uint32), cmap=np.zeros(nc_room, np.uint64), cstate=np.zeros(nc_room, np.uint32),
+                     base=np.zeros(15 * nc_room + 1, np.uint32), sb=np.zeros(15 * nt + 1, np.uint32),
+                     sbits=np.zeros(n // 32 + 16, np.uint32), smap=np.zeros((nsc, 2), np.uint32),
+                     snaps=np.zeros(((n + 31) // 32, 2), np.uint32), sstart=np.zeros(nsc, np.uint16))
+        o = ModelsOut()
+        for k, a in r.items():
+            setattr(o, k, _ptr(a))
+        _check(self.lib.bwtc_hip_test_models(self.handle, _ptr(packed), n, _ptr(tasks), nt, state_in, flags, ctypes.byref(o)),
+               "bwtc_hip_test_models")
+        nc = int(o.nc)
+        for k in ("chunks", "cmap", "cstate"):
+            if k in r:
+                r[k] = r[k][:nc]
+        if "base" in r:
+            r["base"] = r["base"][:15 * nc + 1]
+        r.update(tail=np.array(list(o.tail), np.uint32), ends=np.array(list(o.ends), np.uint32), nc=nc, nsc=int(o.nsc))
+        return r
 
     def copy_probe(self, nbytes=1 << 30, reps=5):
         """GB/s (read + written) of the library's own 16-byte-per-lane copy kernel on this GPU (bwtc_hip_copy_probe)."""
@@ -1420,6 +1458,41 @@ def host_staging_bytes():
     a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
     L.bwtc_hip_host_staging_bytes(ctypes.byref(a), ctypes.byref(b))
     return a.value, b.value
+
+
+def _models_args(packed, tasks):
+    return np.ascontiguousarray(packed, np.uint32), np.ascontiguousarray(tasks, np.uint32).reshape(-1, 3)
+
+
+def host_test_models(packed, n_coded, tasks, state_in):
+    """The model passes lane by lane on the host over given packed streams and tasks (bwtc_hip_host_test_models;
+    no device): (w, state after the block)."""
+    packed, tasks = _models_args(packed, tasks)
+    w = np.zeros(int(n_coded), np.uint16)
+    st = _u32(0)
+    _check(load().bwtc_hip_host_test_models(_ptr(packed), int(n_coded), _ptr(tasks), tasks.shape[0], state_in, _ptr(w),
+                                            ctypes.byref(st)), "bwtc_hip_host_test_models")
+    return w, st.value
+
+
+def host_wavelet_elements(section_args, state):
+    """The coded elements of a real block, from the section-run arguments of bwtc_hip_host_wavelet_streams (a tuple of
+    n_sections and seven arrays): (packed codes, n_coded, tasks [(begin, end, type)], w of the sequential host coder,
+    state after the block) -- bwtc_hip_host_wavelet_elements."""
+    L = load()
+    nsec, arrays = section_args[0], [np.ascontiguousarray(a) for a in section_args[1:]]
+    ptrs = [_ptr(a) for a in arrays]
+    n, nt = _u32(0), _u32(0)
+    st = _u32(state)
+    _check(L.bwtc_hip_host_wavelet_elements(nsec, *ptrs, ctypes.byref(st), ctypes.byref(n), ctypes.byref(nt), None, 0, None, 0, None, 0),
+           "bwtc_hip_host_wavelet_elements")
+    packed = np.zeros((n.value + 15) // 16, np.uint32)
+    tasks = np.zeros((nt.value, 3), np.uint32)
+    w = np.zeros(n.value, np.uint16)
+    st = _u32(state)
+    _check(L.bwtc_hip_host_wavelet_elements(nsec, *ptrs, ctypes.byref(st), ctypes.byref(n), ctypes.byref(nt), _ptr(packed), packed.size,
+                                            _ptr(tasks), tasks.shape[0], _ptr(w), w.size), "bwtc_hip_host_wavelet_elements")
+    return packed, n.value, tasks, w, st.value
 
 
 def synth_into(kind, seed, out):

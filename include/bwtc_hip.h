@@ -648,6 +648,44 @@ int bwtc_hip_test_round(bwtc_hip_ctx* ctx, const uint8_t* T, bwtc_hip_round* rou
 int bwtc_hip_test_gpu_lanes(bwtc_hip_ctx* ctx, const uint16_t* w, uint64_t n, const uint64_t* bounds, uint32_t k, int mode,
                             uint8_t* out, uint64_t out_cap, uint64_t* offsets);
 
+/* Test hooks of the 'B' coder's model passes (wavelet_gpu_models.hip / .hpp).
+ * _test_models runs the product's wavelet_models_prepare (from "tasks and chunks are known" on, read_ends on) and
+ * wavelet_models_run over caller-given packed streams (16 elements per word: bit 0 the bit, bit 1 the gap flag;
+ * (n_coded + 15) / 16 words, padded on the device to whole 16-byte pieces by the hook) and tasks (three words each:
+ * begin, end, type 0 root | 1 gaps | 2 inner | 3 integers), and copies back w, the tail words and what every pass left.
+ * flags: bit 0 = the lines form of the partition pass for this call, bit 1 = no intermediate copies (only w, tail,
+ * ends, nc, nsc).  Checked before anything is launched, -1 otherwise: no null argument, n_coded > 0, nt > 0, every
+ * type <= 3, tasks non-empty and tiling [0, n_coded) in order, the packed streams within the context's workspace
+ * (n_coded <= 32 * (max_block + 1)).  Room the caller gives: chunks 3 words for each of nt + n_coded / 2048 chunks
+ * (begin, end, task | first chunk of its task << 31), cmap and cstate one per chunk, base 15 per chunk + 1,
+ * sb 15 nt + 1, sbits n_coded / 32 + 16, smap 2 words per slot-chunk of 2048 ({base L | end value << 16, mask}),
+ * snaps 2 words per 32 positions ({value of the lowest candidate, mask}), sstart one per slot-chunk. */
+typedef struct bwtc_hip_models_out {
+  uint16_t* w;                 /* n_coded */
+  uint32_t tail[4];            /* state after the block, error flags, elements counted, scan error */
+  uint32_t ends[8];            /* the state after the block by the state it starts in */
+  uint32_t nc, nsc;            /* chunks, slot-chunks */
+  uint32_t* chunks; uint64_t* cmap; uint32_t* cstate; uint32_t* base; uint32_t* sb; uint32_t* sbits;
+  uint32_t* smap; uint32_t* snaps; uint16_t* sstart;
+} bwtc_hip_models_out;
+int bwtc_hip_test_models(bwtc_hip_ctx* ctx, const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks, uint32_t nt,
+                         uint32_t state_in, uint32_t flags, bwtc_hip_models_out* out);
+/* The same input through the passes run lane by lane on the host (gm::modelsOnHostLanes; no context, no device), in
+ * buffers of exactly the sizes the device path allots: w_out[n_coded], *state_out the state after the block.
+ * -1 as above, -7: the passes raised their error flag. */
+int bwtc_hip_host_test_models(const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks, uint32_t nt,
+                              uint32_t state_in, uint16_t* w_out, uint32_t* state_out);
+/* The coded elements of a real block (arguments as bwtc_hip_host_wavelet_streams): *n_coded and *nt always; where
+ * packed, tasks and w are given (room: packed_words, tasks_cap tasks of three words, w_cap elements; -1 when too
+ * small) also the packed codes, the model tasks in coding order and the w of the SEQUENTIAL host coder
+ * (StreamCoder::model over planStreams / expandStreamsOnHost).  state: the carried state, updated.  -5 / -3 as there. */
+int bwtc_hip_host_wavelet_elements(uint32_t n_sections, const uint32_t* first_run,
+                                   const uint8_t* run_sym, const uint32_t* run_start,
+                                   const uint32_t* run_freqs, const uint32_t* dist_offset,
+                                   const uint32_t* dist_len, const uint32_t* dist_cnt, uint32_t* state,
+                                   uint32_t* n_coded, uint32_t* nt, uint32_t* packed, uint64_t packed_words,
+                                   uint32_t* tasks, uint32_t tasks_cap, uint16_t* w, uint64_t w_cap);
+
 /* ---- pair-replacing pre-stage, `--prepr p...` ------------------------------------------
  * Replaces preprocessors/PairReplacer.cpp (analyseData :53-63, decideReplacements :402-484,
  * writeReplacedVersion :330-400), Grammar.cpp (writeGrammar :309-320, readGrammar :198-307),
