@@ -1608,8 +1608,18 @@ __global__ __launch_bounds__(kWinTPB) void k_scatter_dense(u32* __restrict__ ran
 // round (mode 2) looks a member with k >= h_split up at rank[s + max(h, k)] instead of rank[s + h].  k[] is made by the
 // stretch-length pass below, as the lengths of period 1.
 // ---------------------------------------------------------------------------------------
-struct RunKeys { const u32* k; u32 h_split; int mode; u32 p; };   // mode 0: no runs in play (k is not read); 1: the run step; 2: a round after it; p: the period k[] was made for (1: runs)
+// merged (BWTC_HIP_MULTI, tests/multimodel.py): k[] holds the block's merged look-up words, which several steps have written
+// -- a length in bits 0 ... 30 (0: no step has taken s), and bit 31 = "member of the current step", which only that step's
+// own round (mode 1) reads.  The member takes the closed-form key; every other suffix with a length looks up at
+// max(h, length), in the step's own round too; h_split is not read.
+constexpr u32 kStepMember = 0x80000000u, kStepLength = 0x7FFFFFFFu;
+struct RunKeys { const u32* k; u32 h_split; int mode; u32 p; bool merged; };   // mode 0: no runs in play (k is not read); 1: the run step; 2: a round after it; p: the period k[] was made for (1: runs)
 __device__ __forceinline__ u32 run_offset(const RunKeys& rk, u32 s, u32 h) {
+  if (rk.merged) {
+    if (rk.mode == 0) return h;
+    const u32 kk = rk.k[s] & kStepLength;
+    return kk ? max(h, kk) : h;
+  }
   if (rk.mode != 2) return h;
   const u32 kk = rk.k[s];
   return kk >= rk.h_split ? max(h, kk) : h;
@@ -1619,8 +1629,9 @@ __device__ __forceinline__ u32 run_offset(const RunKeys& rk, u32 s, u32 h) {
 __device__ __forceinline__ u64 run_key2(const RunKeys& rk, const u32* __restrict__ rank, const u8* __restrict__ T,
                                         u32 s, u32 n, u32 h, int b2) {
   if (rk.mode == 1) {
-    const u32 kk = rk.k[s];
-    if (kk >= h) {
+    const u32 w = rk.k[s];
+    const u32 kk = rk.merged ? w & kStepLength : w;
+    if (rk.merged ? (w & kStepMember) != 0u : kk >= h) {
       const u64 e = (u64)s + kk;
       const bool falling = e >= (u64)n || T[e] < T[e - rk.p];   // (p = 1: T[e - 1] is the run's byte, T[s]; kk >= h >= p)
       return falling ? (u64)kk : (1ull << (b2 - 1)) | (u64)(n - kk);
@@ -1810,10 +1821,16 @@ __global__ __launch_bounds__(1024) void k_run_carry(const u32* __restrict__ firs
 }
 // launch 3: k_p[x - p] for the positions x of the tile (coalesced 4-byte stores), and the block's longest k_p.
 // PROPER (never with RUN): the longest k_p over the proper positions too (proper_starts), into longest[1] -- a second
-// mask per thread, a second maximum per wave; the instantiations without it are what they were
-template <bool RUN, bool PROPER = false>
+// mask per thread, a second maximum per wave; the instantiations without it are what they were.
+// MERGE (with PROPER, never with RUN; BWTC_HIP_MULTI): k[] holds the block's merged look-up words (tests/multimodel.py) --
+// a length in bits 0 ... 30, bit 31 = "member of the current step".  The step of period p at depth h takes s when
+// k_p[s] >= h and k_p[s] >= the old length (0 for everybody when fresh: the block's first step); it stores k_p | bit 31
+// there and the old length, its flag cleared, everywhere else.  One more coalesced 4-byte load per store; both maxima
+// are over k_p, not over the merged word.  h and fresh are read by this instantiation alone.
+template <bool RUN, bool PROPER = false, bool MERGE = false>
 __global__ __launch_bounds__(kRunTPB) void k_stretch_lengths(const u8* __restrict__ T, u32 n, u32 p_any, const u32* __restrict__ behind,
-                                                              u32* __restrict__ k, u32* __restrict__ longest) {
+                                                              u32* __restrict__ k, u32* __restrict__ longest, u32 h, u32 fresh) {
+  static_assert(!MERGE || (PROPER && !RUN), "the merging pass is the general form with both maxima");
   __shared__ u64 s_mask[kRunTPB];
   __shared__ u32 s_next[kRunTPB];                      // the first break behind the thread's 64 positions
   __shared__ u32 s_wave[kRunTPB / kWave];
@@ -1860,7 +1877,14 @@ __global__ __launch_bounds__(kRunTPB) void k_stretch_lengths(const u8* __restric
       nd = here ? x + (u32)__builtin_ctzll(here) : s_next[c];
     }
     const u32 kk = min(nd, n) - q;
-    if (k) k[q] = kk;                                   // (k == nullptr: a trial, for the longest stretch alone)
+    if constexpr (MERGE) {
+      if (k) {
+        const u32 was = fresh ? 0u : (k[q] & kStepLength);
+        k[q] = (kk >= h && kk >= was) ? (kk | kStepMember) : was;
+      }
+    } else {
+      if (k) k[q] = kk;                                 // (k == nullptr: a trial, for the longest stretch alone)
+    }
     best = max(best, kk);
     if constexpr (PROPER) { if ((s_proper[c] >> lane) & 1ull) best_proper = max(best_proper, kk); }
   }
@@ -1877,7 +1901,7 @@ __global__ __launch_bounds__(kRunTPB) void k_stretch_lengths(const u8* __restric
 // and are neighbours.  A histogram in LDS per workgroup, then one global add per non-empty bin, the workgroups
 // beginning at different bins.
 constexpr u32 kVoteTPB = 256, kVoteTile = 16384, kVoteBins = kPeriodMax + 1;
-constexpr int kSmallPeriod = 802;      // d_small: the block's longest k_p; [803] the probe's flag; [804..805] the finder's winner and its votes
+constexpr int kSmallPeriod = 802;      // d_small: the block's longest k_p; [803] the probe's flag; [804..805] the finder's winner and its votes (k_period_winners: [804..819], 8 such pairs)
 constexpr u32 kPeriodMinVotes = 256;   // the winner's votes buy the period-length pass from max(this, n / 64) on (find_period)
 constexpr u64 kPeriodWorth = 8;        // a voted period's longest stretch must reach this many times max(the first round's depth, p)
 // RUNS_OUT (BWTC_HIP_MIXED, with k_1[] in k1): two members of one run of one byte do not vote -- a long run's group
@@ -1940,6 +1964,41 @@ __global__ __launch_bounds__(1024) void k_period_winner(const u32* __restrict__ 
     const u64 v = s_best[0];
     out[0] = (v >> 32) ? kVoteBins - (u32)v : 0u;
     out[1] = (u32)(v >> 32);
+  }
+}
+
+// (one workgroup; BWTC_HIP_MULTI) The finder's candidates, tests/multimodel.py's candidates(): out[2 i], out[2 i + 1] = the
+// distance in 2 ... kPeriodMax with the i-th most votes among those with `need` votes or more (the smaller distance first
+// among equals) and its votes, i < kPeriodCandidates; zeros from where there are no more.  A bin's key is
+// votes << 32 | kVoteBins - distance, so no two are equal: selection i is the largest key below selection i - 1.
+__global__ __launch_bounds__(1024) void k_period_winners(const u32* __restrict__ table, u32 need, u32* __restrict__ out) {
+  __shared__ u64 s_best[1024];
+  u64 key[(kVoteBins + 1023u) / 1024u];
+#pragma unroll
+  for (u32 j = 0; j < (kVoteBins + 1023u) / 1024u; ++j) {
+    const u32 b = j * 1024u + threadIdx.x;
+    const u32 v = (b >= 2u && b < kVoteBins) ? table[b] : 0u;
+    key[j] = (v >= need && v) ? ((u64)v << 32) | (u64)(kVoteBins - b) : 0ull;
+  }
+  u64 below = ~0ull;
+  for (u32 i = 0; i < kPeriodCandidates; ++i) {
+    u64 best = 0;
+#pragma unroll
+    for (u32 j = 0; j < (kVoteBins + 1023u) / 1024u; ++j)
+      if (key[j] < below && key[j] > best) best = key[j];
+    s_best[threadIdx.x] = best;
+    __syncthreads();
+    for (u32 o = 512; o > 0; o >>= 1) {
+      if (threadIdx.x < o) { const u64 v = s_best[threadIdx.x + o]; if (v > s_best[threadIdx.x]) s_best[threadIdx.x] = v; }
+      __syncthreads();
+    }
+    below = s_best[0];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      out[2u * i] = below ? kVoteBins - (u32)below : 0u;
+      out[2u * i + 1u] = (u32)(below >> 32);
+    }
+    // (below == 0: nothing is left, and nothing is below 0 -- the entries from here on come out as zeros)
   }
 }
 
@@ -2042,8 +2101,9 @@ __global__ __launch_bounds__(256) void k_gather_text(const u32* __restrict__ aid
   // its sub-group shares its k characters and what the text rounds since the run step (at depth h_split) have compared
   u64 at = (u64)s + h;
   if (rk.mode == 2) {                                    // (rank[] is refined between rounds, the text is not: max(h, k) would read the same characters again)
-    const u32 kk = rk.k[s];
-    if (kk >= rk.h_split) at = (u64)s + kk + (h - rk.h_split);
+    const u32 kk = rk.merged ? rk.k[s] & kStepLength : rk.k[s];
+    // (merged: text rounds follow first-round steps only, which all ran at h_split, and a taken suffix has kk >= h_split)
+    if (rk.merged ? kk != 0u : kk >= rk.h_split) at = (u64)s + max((u64)h, (u64)kk + (h - rk.h_split));
   }
   fin_chars(T, (u32)min(at, (u64)n), n, &c0, &c1);
   const u64 chars = c0 >> (64u - 8u * c);
@@ -2271,7 +2331,8 @@ int BwtEngine::init(int dev, u32 max_block_size) {
   env_int("BWTC_HIP_FIN_ROUNDS", &fin_rounds, 1, 4);
   run_ranks = !env_off("BWTC_HIP_RUNS"); period_ranks = !env_off("BWTC_HIP_PERIODS");
   if (env_int("BWTC_HIP_PERIOD", &v, 0, (int)kPeriodMax)) period_forced = (u32)v;
-  mixed_steps = env_is("BWTC_HIP_MIXED", "1");
+  multi_steps = env_is("BWTC_HIP_MULTI", "1");
+  mixed_steps = env_is("BWTC_HIP_MIXED", "1") || multi_steps;   // (BWTC_HIP_MULTI switches MIXED's rules on)
   local_rounds = !env_off("BWTC_HIP_LOCAL_ROUNDS");
   if (env_int("BWTC_HIP_FIN_FLOOR", &v, 0)) fin_floor = (u32)v;
   text_rounds_fixed = env_int("BWTC_HIP_TEXT_ROUNDS", &text_rounds, 0);
@@ -2719,7 +2780,7 @@ int BwtEngine::rank_step(SortList& L, const RankRequest& rq) {
   const int b2k = run_now ? b2 + 1 : b2;
   const int kbits = b1 + b2k;
   const StretchStep& step = blk.current_step();
-  const RunKeys rkeys{d_runK, run_now ? 0u : step.depth, run_now ? 1 : (rq.run_mode == 2 ? 2 : 0), step.p};
+  const RunKeys rkeys{d_runK, run_now ? 0u : step.depth, run_now ? 1 : (rq.run_mode == 2 ? 2 : 0), step.p, blk.merged};
   // a key of more than 56 bits has no room for the carried character (blocks above 256 MiB with many groups): the
   // next list then goes without, and its ranking reads T[s-1] for what it finishes
   const bool carry_next = emit && kbits <= 56;
@@ -3083,34 +3144,66 @@ int BwtEngine::initial_long(const InitialSort& in, const GramPlan& gp, int key_b
   return 0;
 }
 
-// Is a step of the block's this round's?  The front of the schedule, where decide_step made it the first round's, is.
-// Behind it the first entry that waits is due in the round whose depth h_round has reached its p, with rank[] complete,
+// Is a step of the block's this round's?  The first entry still to come is, where decide_step made it the first round's
+// (BWTC_HIP_MULTI: several such entries take consecutive rounds at one depth, each storing its merged words when it is due).
+// Behind them the first entry that waits is due in the round whose depth h_round has reached its p, with rank[] complete,
 // no live local list and no text round pending -- as long as the stretches are longer than that: the step's gate, by
 // the longest stretch, or, behind a run step (BWTC_HIP_MIXED), by the longest proper stretch.  There d_runK still holds
-// k_1[]: the storing pass puts k_p[] in its place first.  The entry that is due becomes the current one.
+// k_1[]: the storing pass puts k_p[] in its place first (store_step).  An entry whose gate is shut is dropped and the
+// next one that waits is looked at.  The entry that is due becomes the current one.
 int BwtEngine::step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool text_round, bool* due) {
   *due = false;
-  if (blk.steps[0].when == StretchStep::kThisRound) { blk.steps[0].when = StretchStep::kNone; *due = m > 0; return 0; }
   int i = 0;
-  while (i < blk.n_steps && blk.steps[i].when != StretchStep::kWaiting) ++i;
-  if (i == blk.n_steps || m == 0) return 0;
-  StretchStep& step = blk.steps[i];
-  const bool behind_run = i > 0;
-  if ((u64)(behind_run ? blk.proper_longest : blk.period_longest) <= std::max<u64>(h_round, step.p)) {
-    step.when = StretchStep::kNone;
-    say_no_period_step(*this, h_first);
-  } else if (h_round >= (u64)step.p && L.ranks_complete && blk.fin.local_m == 0 && !text_round) {
-    step.when = StretchStep::kNone;
-    if (blk.lengths_period != step.p) {
-      // a run's member with k_1 >= p has k_p = k_1, one with k_1 < p <= h_round would look up at h_round anyway: nothing
-      // is lost with k_1[]
-      const int rc = stretch_lengths(L.n, step.p, true, &blk.period_longest, behind_run ? &blk.proper_longest : nullptr);
-      if (rc) return rc;
-    }
+  while (i < blk.n_steps && blk.steps[i].when == StretchStep::kNone) ++i;   // the first entry that is still to come
+  if (i == blk.n_steps) return 0;
+  if (blk.steps[i].when == StretchStep::kThisRound) {
+    // (BWTC_HIP_MULTI: several of the first round's take consecutive rounds at its depth; each stores when it is due)
+    blk.steps[i].when = StretchStep::kNone;
+    if (m == 0) return 0;
+    if (blk.merged) { const int rc = store_step(L.n, blk.steps[i], h_round, false); if (rc) return rc; }
     blk.current = i;
     *due = true;
+    return 0;
+  }
+  if (m == 0) return 0;
+  for (; i < blk.n_steps; ++i) {
+    StretchStep& step = blk.steps[i];
+    if (step.when != StretchStep::kWaiting) continue;
+    const bool behind_run = i > 0;
+    const u32 gate = blk.merged ? step.gate : behind_run ? blk.proper_longest : blk.period_longest;
+    if ((u64)gate <= std::max<u64>(h_round, step.p)) {
+      step.when = StretchStep::kNone;
+      step.dropped = true;
+      say_no_period_step(*this, h_first);
+      continue;                                          // (the next entry that waits may be this round's)
+    }
+    if (h_round >= (u64)step.p && L.ranks_complete && blk.fin.local_m == 0 && !text_round) {
+      step.when = StretchStep::kNone;
+      const int rc = store_step(L.n, step, h_round, behind_run);
+      if (rc) return rc;
+      blk.current = i;
+      *due = true;
+    }
+    return 0;
   }
   return 0;
+}
+
+// The storing pass of the step that is due at depth h_round.  One period's lengths: k_p[] over whatever d_runK held (a
+// run's member with k_1 >= p has k_p = k_1, one with k_1 < p <= h_round would look up at h_round anyway: nothing is lost
+// with k_1[]).  Merged words (BWTC_HIP_MULTI): the merging pass, which needs the step's depth
+// and the earlier steps' words -- the block's first one writes them fresh.
+int BwtEngine::store_step(u32 n, StretchStep& step, u64 h_round, bool behind_run) {
+  if (blk.merged) {
+    const StepMerge merge{depth32(h_round), !blk.merged_stored};
+    u32 longest = 0, proper = 0;
+    const int rc = stretch_lengths(n, step.p, true, &longest, &proper, &merge);
+    if (rc) return rc;
+    blk.merged_stored = true;
+    return 0;
+  }
+  if (blk.lengths_period == step.p) return 0;
+  return stretch_lengths(n, step.p, true, &blk.period_longest, behind_run ? &blk.proper_longest : nullptr);
 }
 
 // The rounds over the sorted list in L.home, from depth ask.h0 until nothing is tied.  ask.text_rounds: rounds that compare
@@ -3166,21 +3259,29 @@ int BwtEngine::run_rounds(SortList& L, const RoundsRequest& ask, RoundsLeft* out
     std::swap(re.achr_out, L.achr_other);
     RankRequest rq;
     rq.m = m; rq.h_next = h; rq.kind = raw ? RoundKind::kRaw : text ? RoundKind::kText : RoundKind::kOrdinary;
-    rq.run_mode = run_req ? 1 : step.depth ? 2 : 0;     // the second keys (RunKeys::mode): the run step, a round behind one, or no runs in play
+    rq.run_mode = run_req ? 1 : (blk.merged ? blk.merged_ran : step.depth != 0) ? 2 : 0;   // the second keys (RunKeys::mode): the run step, a round behind one, or no runs in play
     const int rc2 = rank_step<u64, false>(L, rq);
     if (rc2) return rc2;
     m = res.m;
     const bool ran = run_req && res.ran_run;
     if (period_req && !ran) say_no_period_step(*this, h_first);   // (the key had no room for the step's bit: an ordinary round)
+    if (run_req && !ran && blk.merged) {
+      // ... and the merged words name members that no closed-form key has ranked: nobody reads them again, no step follows
+      blk.merged_ran = false;
+      for (int i = 0; i < blk.n_steps; ++i)
+        if (blk.steps[i].when != StretchStep::kNone) { blk.steps[i].when = StretchStep::kNone; blk.steps[i].dropped = true; }
+    }
     if (ran) {
       // the list is sorted to depth h still: a run's members by their closed-form keys, the others as they were (or by rank[s + h])
       step.depth = depth32(h);
       stats.route |= period_req ? 256u : 32u;
       if (step.ranks_runs) stats.route |= 32u;           // (BWTC_HIP_MIXED: one step over k_p[] ranked the runs too)
+      if (blk.merged) blk.merged_ran = true;
+      if (blk.period_steps_ran() > 1) stats.route |= 512u;   // (BWTC_HIP_MULTI: more than one period step in the block)
       keep_h = true;
       if (period_req && debug_on())
         std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: period step at depth %u\n",
-                     blk.period_p, blk.period_votes, blk.period_longest, (unsigned long long)h_first, step.depth);
+                     step.p, blk.merged ? step.votes : blk.period_votes, blk.merged ? step.gate : blk.period_longest, (unsigned long long)h_first, step.depth);
       // rank[] still incomplete: one text round behind the runs first -- a block that is one giant run ends there,
       // without the completion of rank[] that the first doubling round costs.  Not beside a live local list: its
       // members' ranks are local_depth deep, and the first doubling look-up must not lie deeper than that (text rounds
@@ -3202,9 +3303,14 @@ int BwtEngine::run_rounds(SortList& L, const RoundsRequest& ask, RoundsLeft* out
   }
   bool waited = false;                                   // (the rounds ended before their depth reached p)
   for (int i = 0; i < blk.n_steps; ++i)
-    if (blk.steps[i].when == StretchStep::kWaiting) { blk.steps[i].when = StretchStep::kNone; waited = true; }
+    if (blk.steps[i].when == StretchStep::kWaiting) { blk.steps[i].when = StretchStep::kNone; blk.steps[i].dropped = true; waited = true; }
   if (waited) say_no_period_step(*this, h_first);
-  if (mixed_steps && ask.doubling && debug_on()) {
+  if (blk.merged && ask.doubling && debug_on()) {
+    std::fprintf(stderr, "steps: %d entries", blk.n_steps);
+    for (int i = 0; i < blk.n_steps; ++i)
+      std::fprintf(stderr, "%s (p %u, depth %u, gate %u, votes %u)", i ? "," : ":", blk.steps[i].p, blk.steps[i].depth, blk.steps[i].gate, blk.steps[i].votes);
+    std::fprintf(stderr, "\n");
+  } else if (mixed_steps && ask.doubling && debug_on()) {
     const StretchStep period = blk.period_ran();
     std::fprintf(stderr, "steps: run step at depth %u, period step of period %u at depth %u, longest run %u, longest proper stretch %u\n",
                  blk.run_depth(), period.p, period.depth, blk.run_longest, blk.proper_longest);
@@ -3403,7 +3509,10 @@ struct PassTimer {
 // the block into d_runK, unless this is a trial, and the block's longest stretch of period p.  p = 1 is the run-length
 // pass: the text read once per launch, and the block's longest run is known from then on.
 static constexpr int kSmallStretch = 800;   // d_small: the two words a pass reads back (the longest stretch; the longest proper one)
-int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* proper) {
+// merge (BWTC_HIP_MULTI and its test hook; with store and proper): d_runK holds the block's merged look-up words, and the
+// pass is the step's of depth merge->h -- the first of the block (fresh) or one behind others, whose words it reads.
+int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* proper, const StepMerge* merge) {
+  if (merge && (!store || !proper || n > kStepLength)) return -1;
   if (proper) *proper = 0;
   // (the tiles reach n + p and their positions are 32-bit: a block within two tiles of 2^32 takes no step)
   if ((u64)n + p + 2ull * kRunTile > 0xFFFFFFFFull) { *longest = 0; return 0; }
@@ -3416,14 +3525,17 @@ int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* prop
   if (p == 1 && !proper) {
     hipLaunchKernelGGL(k_stretch_tiles<true>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, d_runF);
     hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(1024), 0, st, (const u32*)d_runF, tiles, n, d_runB);
-    hipLaunchKernelGGL(k_stretch_lengths<true>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch);
+    hipLaunchKernelGGL(k_stretch_lengths<true>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch, 0u, 0u);
   } else {
     hipLaunchKernelGGL(k_stretch_tiles<false>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, d_runF);
     hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(1024), 0, st, (const u32*)d_runF, tiles, n, d_runB);
-    if (proper)   // (the second maximum: BWTC_HIP_MIXED and its test hook only; p = 1 takes the general form for it)
-      hipLaunchKernelGGL((k_stretch_lengths<false, true>), dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch);
+    if (merge)
+      hipLaunchKernelGGL((k_stretch_lengths<false, true, true>), dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch,
+                         merge->h, merge->fresh ? 1u : 0u);
+    else if (proper)   // (the second maximum: BWTC_HIP_MIXED and its test hook only; p = 1 takes the general form for it)
+      hipLaunchKernelGGL((k_stretch_lengths<false, true>), dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch, 0u, 0u);
     else
-      hipLaunchKernelGGL(k_stretch_lengths<false>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch);
+      hipLaunchKernelGGL(k_stretch_lengths<false>, dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)d_T, n, p, (const u32*)d_runB, k, d_small + kSmallStretch, 0u, 0u);
   }
   BWTC_HIP_TRY(timer.stop());
   BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallStretch, d_small + kSmallStretch, proper ? 8 : 4, hipMemcpyDeviceToHost, st));
@@ -3440,41 +3552,33 @@ int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* prop
   if (store) blk.lengths_period = p;
   if (p == 1) blk.run_longest = *longest;
   // T read twice (p > 1: both streams of it), the lengths written; the tiles' words written and read
-  stats.alg_bytes += (u64)n * ((p == 1 && !proper ? 1 + 1 : 2 + 2) + (store ? 4 : 0)) + (u64)tiles * 16;
+  stats.alg_bytes += (u64)n * ((p == 1 && !proper ? 1 + 1 : 2 + 2) + (store ? 4 : 0) + (merge && !merge->fresh ? 4 : 0)) + (u64)tiles * 16;
   return 0;
 }
 
-// The block's closed-form steps, into blk.steps, for a list of m > 0 entries that is about to double and whose first round
-// establishes depth h_first.  Once per block: run_rounds calls it before the one doubling list a block has.
-int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask) {
+// The finder's candidates over the vote table in d_votes (k_period_winners): up to kPeriodCandidates (distance, votes)
+// pairs with `need` votes or more into out[], most votes first -> their number (one host wait).
+int BwtEngine::period_winners(u32 need, u32* out, u32* n_out) {
   hipStream_t st = stream;
-  // Runs: the list may hold long runs of one byte, which doubling takes log2(length) rounds over.  k[] and the block's
-  // longest run are made here (one host wait); a run longer than the depth the first round establishes gets the run
-  // step as that round, before any text round and before rank[] is completed.
-  // (BWTC_HIP_PERIOD=1: the run step is the period step of period 1, whatever BWTC_HIP_RUNS says)
-  if (run_ranks || period_forced == 1) {
-    const int rcr = stretch_lengths(n, 1, true, &blk.run_longest);
-    if (rcr) return rcr;
-    if ((u64)blk.run_longest > h_first) blk.schedule(1, StretchStep::kThisRound);
-    if (debug_on())
-      std::fprintf(stderr, "runs: longest run %u, the rounds begin at depth %llu: %s\n", blk.run_longest, (unsigned long long)h_first,
-                   blk.n_steps ? "run step" : "no run step");
-  }
-  // Periods: a list that takes doubling rounds and no run step may hold stretches of a period p > 1, which tie their
-  // suffixes for the stretch's length just as a run does.  The finder votes for p over the list as it stands (or
-  // BWTC_HIP_PERIOD names it); votes above the threshold buy the period-length pass, which puts k_p[] where k[] was.
-  // p <= the first round's depth: that round is the period step, exactly as the run step.  A deeper p: the step waits
-  // for the first doubling round whose depth reaches p (kWaiting), with rank[] complete and no local list beside it.
-  // BWTC_HIP_MIXED=1 (with the run ranking on): the block that takes the run step looks for a period too, and the gates
-  // are the longest PROPER stretch's -- the largest k_p over the positions s with T[s] != T[s + 1], which no run of one
-  // byte holds and every p positions of a stretch of another unit do -- so a run neither counts as a stretch nor keeps
-  // one from its step.
-  const bool mixed = mixed_steps && run_ranks && period_forced != 1;
-  const bool run_due = blk.n_steps != 0;
-  if (!period_ranks || period_forced == 1 || (run_due && !mixed)) return 0;
-  const int rcp = find_period(n, ks, vs, m, kmask);
-  if (rcp) return rcp;
+  hipLaunchKernelGGL(k_period_winners, dim3(1), dim3(1024), 0, st, (const u32*)d_votes, need, d_small + kSmallPeriod + 2);
+  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 2, d_small + kSmallPeriod + 2, kPeriodCandidates * 8, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(wait());
+  u32 found = 0;
+  while (found < kPeriodCandidates && h_small[kSmallPeriod + 2 + 2 * found]) ++found;
+  std::memcpy(out, h_small + kSmallPeriod + 2, kPeriodCandidates * 8);
+  *n_out = found;
+  stats.alg_bytes += (u64)kVoteBins * 4;
+  return 0;
+}
+
+// blk.period_p, the finder's (or BWTC_HIP_PERIOD's), through what decides whether it is worth a step: the probe, the
+// period-length pass (a trial unless store), the worth test and the division of a period above the first round's depth.
+// Leaves blk.period_p (0: refused), blk.period_longest and, where mixed, blk.proper_longest.
+int BwtEngine::weigh_period(u32 n, u64 h_first, bool mixed, bool store) {
+  hipStream_t st = stream;
   const bool voted = period_forced == 0;                // (a forced period skips the probe, the worth tests and the division)
+  u32* const proper = mixed ? &blk.proper_longest : nullptr;
+  const u32& g = mixed ? blk.proper_longest : blk.period_longest;
   if (blk.period_p >= 2 && voted) {
     // votes say how many members lie p apart, not for how long they tie: fixed-width records with a few free bytes
     // each vote for their width and tie for less than two records.  Before the pass, a probe: is any aligned window
@@ -3497,11 +3601,6 @@ int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* 
       blk.period_p = 0;
     }
   }
-  // The passes' second maximum and the gate length g it feeds exist under the switch only.  While a run step is due d_runK
-  // holds k_1[] for it, so the passes here are trials (store == false).
-  u32* const proper = mixed ? &blk.proper_longest : nullptr;
-  const u32& g = mixed ? blk.proper_longest : blk.period_longest;
-  const bool store = !run_due;
   if (blk.period_p >= 2) {
     // (a run of one byte is a stretch of every period, and the run step's business: the block's longest run first --
     // known already unless BWTC_HIP_RUNS=0, where a trial pass of period 1 finds it -- and no period step where the
@@ -3538,6 +3637,91 @@ int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* 
       if (rcb) return rcb;
     }
   }
+  return 0;
+}
+
+// The block's closed-form steps, into blk.steps, for a list of m > 0 entries that is about to double and whose first round
+// establishes depth h_first.  Once per block: run_rounds calls it before the one doubling list a block has.
+int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask) {
+  // Runs: the list may hold long runs of one byte, which doubling takes log2(length) rounds over.  k[] and the block's
+  // longest run are made here (one host wait); a run longer than the depth the first round establishes gets the run
+  // step as that round, before any text round and before rank[] is completed.
+  // (BWTC_HIP_PERIOD=1: the run step is the period step of period 1, whatever BWTC_HIP_RUNS says)
+  if (run_ranks || period_forced == 1) {
+    const int rcr = stretch_lengths(n, 1, true, &blk.run_longest);
+    if (rcr) return rcr;
+    if ((u64)blk.run_longest > h_first) blk.schedule(1, StretchStep::kThisRound);
+    if (debug_on())
+      std::fprintf(stderr, "runs: longest run %u, the rounds begin at depth %llu: %s\n", blk.run_longest, (unsigned long long)h_first,
+                   blk.n_steps ? "run step" : "no run step");
+  }
+  // Periods: a list that takes doubling rounds and no run step may hold stretches of a period p > 1, which tie their
+  // suffixes for the stretch's length just as a run does.  The finder votes for p over the list as it stands (or
+  // BWTC_HIP_PERIOD names it); votes above the threshold buy the period-length pass, which puts k_p[] where k[] was.
+  // p <= the first round's depth: that round is the period step, exactly as the run step.  A deeper p: the step waits
+  // for the first doubling round whose depth reaches p (kWaiting), with rank[] complete and no local list beside it.
+  // BWTC_HIP_MIXED=1 (with the run ranking on): the block that takes the run step looks for a period too, and the gates
+  // are the longest PROPER stretch's -- the largest k_p over the positions s with T[s] != T[s + 1], which no run of one
+  // byte holds and every p positions of a stretch of another unit do -- so a run neither counts as a stretch nor keeps
+  // one from its step.
+  const bool mixed = mixed_steps && run_ranks && period_forced != 1;
+  const bool run_due = blk.n_steps != 0;
+  if (!period_ranks || period_forced == 1 || (run_due && !mixed)) return 0;
+  const int rcp = find_period(n, ks, vs, m, kmask);
+  if (rcp) return rcp;
+  const bool voted = period_forced == 0;                // (a forced period skips the probe, the worth tests and the division)
+  // The passes' second maximum and the gate length g it feeds exist under the switch only.  While a run step is due d_runK
+  // holds k_1[] for it, so the passes here are trials (store == false).
+  u32* const proper = mixed ? &blk.proper_longest : nullptr;
+  const u32& g = mixed ? blk.proper_longest : blk.period_longest;
+  const bool store = !run_due;
+  if (multi_steps && mixed && voted && (u64)n <= kStepLength) {
+    // BWTC_HIP_MULTI: every candidate of the finder's, most votes first, through the same probe, pass, worth test and
+    // division (tests/multimodel.py, accept()); a multiple or a divisor of an accepted period is skipped -- a p'-stretch
+    // longer than p is a p-stretch when p' divides p -- before its passes and again behind the division.  The passes are
+    // trials, but for the first one weighed where no run step is due: where one period is all there is, the block is
+    // MIXED's from here on, lengths stored.  (A block of 2^31 bytes or more has no bit for the merged words' flag.)
+    struct { u32 p, gate, votes, longest; } acc[BlockSort::kMaxPeriodSteps];
+    int na = 0;
+    const auto related = [&](u32 q) { for (int i = 0; i < na; ++i) if (q % acc[i].p == 0 || acc[i].p % q == 0) return true; return false; };
+    bool first = true;
+    for (u32 c = 0; c < blk.n_cands && na < BlockSort::kMaxPeriodSteps; ++c) {
+      if (related(blk.cand_p[c])) continue;
+      blk.period_p = blk.cand_p[c];
+      const int rcw = weigh_period(n, h_first, true, store && first);
+      if (rcw) return rcw;
+      first = false;
+      if (blk.period_p < 2 || related(blk.period_p)) continue;
+      acc[na].p = blk.period_p; acc[na].gate = blk.proper_longest; acc[na].votes = blk.cand_votes[c]; acc[na++].longest = blk.period_longest;
+    }
+    std::sort(acc, acc + na, [](const auto& a, const auto& b) { return a.p < b.p; });
+    blk.period_p = na ? acc[0].p : 0u;
+    if (na) { blk.period_votes = acc[0].votes; blk.period_longest = acc[0].longest; blk.proper_longest = acc[0].gate; }
+    if (na >= 2) {
+      // Several periods: the steps merge their look-up lengths in d_runK, each storing when it is due (step_due).  The
+      // first round's are those with p <= h_first, by ascending p; the first of them ranks the runs too, in place of the
+      // run step that was due.  The others wait, by ascending p.
+      blk.merged = true;
+      bool any_first = false;
+      for (int i = 0; i < na; ++i) any_first = any_first || ((u64)acc[i].p <= h_first && (u64)acc[i].gate > h_first);
+      if (run_due) { if (any_first) blk.n_steps = 0; else blk.steps[0].gate = blk.run_longest; }
+      for (int i = 0; i < na; ++i)
+        if ((u64)acc[i].p <= h_first && (u64)acc[i].gate > h_first) {
+          blk.schedule(acc[i].p, StretchStep::kThisRound, acc[i].gate, acc[i].votes);
+          if (run_due && blk.n_steps == 1) blk.steps[0].ranks_runs = true;
+        }
+      for (int i = 0; i < na; ++i)
+        if ((u64)acc[i].p > h_first && acc[i].gate > acc[i].p) blk.schedule(acc[i].p, StretchStep::kWaiting, acc[i].gate, acc[i].votes);
+      return 0;
+    }
+    if (na == 1 && store && blk.lengths_period != blk.period_p) {
+      const int rcb = stretch_lengths(n, blk.period_p, true, &blk.period_longest, proper);
+      if (rcb) return rcb;
+    }
+  } else {
+    const int rcw = weigh_period(n, h_first, mixed, store);
+    if (rcw) return rcw;
+  }
   bool period_step = false;
   if (blk.period_p >= 2 && (u64)blk.period_p <= h_first) {
     if ((u64)g > h_first) {
@@ -3555,6 +3739,11 @@ int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* 
     period_step = true;
   }
   if (!period_step) say_no_period_step(*this, h_first);
+  if (multi_steps)   // (one period or none: MIXED's schedule, with what the getter reports beside it)
+    for (int i = 0; i < blk.n_steps; ++i) {
+      blk.steps[i].gate = blk.steps[i].p == 1 ? blk.run_longest : g;
+      blk.steps[i].votes = blk.steps[i].p == 1 ? 0u : blk.period_votes;
+    }
   return 0;
 }
 
@@ -3574,9 +3763,18 @@ int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask
   else
     hipLaunchKernelGGL(k_period_votes<false>, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, (const u32*)nullptr);
   BWTC_HIP_TRY(timer.stop());
-  hipLaunchKernelGGL(k_period_winner, dim3(1), dim3(1024), 0, st, (const u32*)d_votes, d_small + kSmallPeriod + 2);
-  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 2, d_small + kSmallPeriod + 2, 8, hipMemcpyDeviceToHost, st));
-  BWTC_HIP_TRY(wait());
+  const u64 need = std::max<u64>(kPeriodMinVotes, (u64)n / 64);
+  if (multi_steps) {
+    // BWTC_HIP_MULTI: the up to kPeriodCandidates distances whose votes reach the threshold, not the winner alone
+    u32 found[2 * kPeriodCandidates];
+    const int rcw = period_winners((u32)need, found, &blk.n_cands);
+    if (rcw) return rcw;
+    for (u32 c = 0; c < blk.n_cands; ++c) { blk.cand_p[c] = found[2 * c]; blk.cand_votes[c] = found[2 * c + 1]; }
+  } else {
+    hipLaunchKernelGGL(k_period_winner, dim3(1), dim3(1024), 0, st, (const u32*)d_votes, d_small + kSmallPeriod + 2);
+    BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 2, d_small + kSmallPeriod + 2, 8, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(wait());
+  }
   if (timed) {
     float ms = 0.f;
     BWTC_HIP_TRY(timer.ms(&ms));
@@ -3584,7 +3782,6 @@ int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask
   }
   const u32 winner = h_small[kSmallPeriod + 2];
   blk.period_votes = h_small[kSmallPeriod + 3];
-  const u64 need = std::max<u64>(kPeriodMinVotes, (u64)n / 64);
   blk.period_p = (winner >= 2 && (u64)blk.period_votes >= need) ? winner : 0u;
   if (!blk.period_p && timed) std::fprintf(stderr, "periods: distance %u leads with %u votes of the %llu a pass takes\n", winner, blk.period_votes, (unsigned long long)need);
   stats.alg_bytes += (u64)m * (8 + 4) + (u64)kVoteBins * 8;   // the list's keys and suffixes read; the table zeroed and read

@@ -53,6 +53,7 @@ struct FinOutcome { u32 hard = 0, hard_depth = 0xFFFFFFFFu, left = 0, local = 0,
 // A finisher list lives in up to kFinRegions regions of its arrays (bwt_engine.hip, k_finish)
 constexpr u32 kFinRegions = 16;
 constexpr u32 kPeriodMax = 4096;   // the longest period the period step looks for (bwt_engine.hip, "Periods")
+constexpr u32 kPeriodCandidates = 8;   // the distances the finder returns under BWTC_HIP_MULTI (k_period_winners)
 struct FinRegions { u32 nreg; u32 wfirst[kFinRegions + 1]; u32 ebase[kFinRegions]; u32 ecount[kFinRegions]; };
 
 // 256 bytes of canary behind the last item a test hook's kernels may write (c_abi.hip, BwtEngine::test_finish_pass): a
@@ -441,7 +442,10 @@ struct BwtEngine {
   // A closed-form step (runs and periods, below): its period (1: the run step), when it is due (kWaiting: the first doubling
   // round whose depth reaches p; kNone: not any more), the depth it ran at (0: it has not), and whether it ranked the runs
   // too (BWTC_HIP_MIXED: the first round is one period step over k_p[] in place of the run step that was due).
-  struct StretchStep { u32 p = 0; enum When { kNone, kThisRound, kWaiting } when = kNone; u32 depth = 0; bool ranks_runs = false; };
+  // BWTC_HIP_MULTI: gate is the length the entry's gate goes by (the longest run; a period's longest proper stretch), votes
+  // the finder's for it -- they live here and nowhere else -- and dropped says that its gate was shut when its depth came.
+  struct StretchStep { u32 p = 0; enum When { kNone, kThisRound, kWaiting } when = kNone; u32 depth = 0; bool ranks_runs = false;
+                       u32 gate = 0, votes = 0; bool dropped = false; };
   struct BlockSort {
     bool ranks_live = false;   // rank[] has been completed (every ranking step keeps it exact from then on)
     bool fin_active = false;   // the block takes the finisher route: finished suffixes also go to d_SA
@@ -460,12 +464,22 @@ struct BwtEngine {
     u32 lengths_period = 0;    // the period d_runK's lengths were made for (0: none yet)
     u32 run_longest = 0;       // the longest run, once a pass of period 1 has found it (made at most once per block)
     u32 proper_longest = 0;    // BWTC_HIP_MIXED: the longest proper stretch (0: no pass has made it)
-    // The block's closed-form steps in the order it takes them (decide_step): today the run step, then one period step,
-    // or either alone.  `current` is the entry whose lengths are in d_runK and whose period and depth the second keys take
-    // (RunKeys): the front, until a step behind it comes due (step_due).
-    static constexpr int kMaxSteps = 2;
+    // The block's closed-form steps in the order it takes them (decide_step): the run step, then one period step, or
+    // either alone; with BWTC_HIP_MULTI the run step and up to three period steps, the first round's before those that
+    // wait, by ascending period.  `current` is the entry whose lengths went into d_runK last and whose period and depth the
+    // second keys take (RunKeys): the front, until a step behind it comes due (step_due).
+    static constexpr int kMaxSteps = 4, kMaxPeriodSteps = 3;
     StretchStep steps[kMaxSteps]; int n_steps = 0, current = 0;
-    void schedule(u32 p, StretchStep::When when) { if (n_steps < kMaxSteps) steps[n_steps++] = StretchStep{p, when}; }
+    void schedule(u32 p, StretchStep::When when, u32 gate = 0, u32 votes = 0) {
+      if (n_steps < kMaxSteps) { steps[n_steps] = StretchStep{p, when}; steps[n_steps].gate = gate; steps[n_steps++].votes = votes; }
+    }
+    // BWTC_HIP_MULTI: d_runK holds merged look-up words (tests/multimodel.py), not one period's lengths.  merged: this
+    // block's steps merge; merged_stored: a storing pass has written the words (the next one is not the first);
+    // merged_ran: a step has run over them, so every round's second keys read them.
+    bool merged = false, merged_stored = false, merged_ran = false;
+    int period_steps_ran() const { int c = 0; for (int i = 0; i < n_steps; ++i) c += steps[i].p >= 2 && steps[i].depth; return c; }
+    // the finder's candidates (BWTC_HIP_MULTI: find_period), most votes first
+    u32 n_cands = 0, cand_p[kPeriodCandidates] = {}, cand_votes[kPeriodCandidates] = {};
     void set_step(const StretchStep& s) { steps[0] = s; n_steps = 1; current = 0; }   // the one step, in place of whatever was scheduled
     StretchStep& current_step() { return steps[current]; }                           // (no step scheduled: one of period 0 and depth 0)
     // what the block's steps did, for bwtc_hip_period_get, bwtc_hip_steps_get and the debug line: the depth the runs were
@@ -591,18 +605,24 @@ struct BwtEngine {
   // runs and periods (bwt_engine.hip, "Runs" / "Periods"): long runs of one byte (period 1) and stretches of a period p > 1
   // are ranked in closed form by one round, the step.  A block's steps stand in BlockSort::steps in the order it takes them,
   // over the one length array d_runK: one step per block -- or, with BWTC_HIP_MIXED=1, the run step and then one period
-  // step, whose lengths replace the runs' in d_runK.  decide_step fills the schedule, step_due says which entry is a round's.
+  // step, whose lengths replace the runs' in d_runK; with BWTC_HIP_MULTI=1 up to three period steps, which merge their
+  // look-up lengths there (tests/multimodel.py).  decide_step fills the schedule, step_due says which entry is a round's.
   bool run_ranks = true;     // BWTC_HIP_RUNS=0: no run step; the longest run is found only to tell a run from a voted period (decide_step)
   bool period_ranks = true;  // BWTC_HIP_PERIODS=0: no votes, no period-length pass, no period step
   u32 period_forced = 0;     // BWTC_HIP_PERIOD=p: that period, no votes (1: the run path)
   bool mixed_steps = false;  // BWTC_HIP_MIXED=1: a block may take the run step and a period step (decide_step)
+  bool multi_steps = false;  // BWTC_HIP_MULTI=1: MIXED's rules, and up to three period steps per block over merged look-up words (decide_step)
   u32* d_runK = nullptr;     // k_p[s]: the leading characters of suffix s that are p-periodic (p = 1: the positions from s on that hold T[s])
   u32* d_runF = nullptr; u32* d_runB = nullptr;   // the stretch-length pass's words per tile
   u32* d_votes = nullptr;    // the finder's table: votes per distance 0 ... kPeriodMax
   // store == false: the longest stretch alone (a trial); proper: the longest proper stretch too (the general form for p = 1)
-  int stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* proper = nullptr);
+  struct StepMerge { u32 h; bool fresh; };   // a storing pass over the merged look-up words: the step's depth; the block's first step
+  int stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* proper = nullptr, const StepMerge* merge = nullptr);
+  int period_winners(u32 need, u32* out, u32* n_out);   // the finder's up to 8 candidates over d_votes (distance, votes)
   int find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask);
   int decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask);   // -> blk.steps
+  int weigh_period(u32 n, u64 h_first, bool mixed, bool store);   // blk.period_p through the probe, the pass, the worth test and the division
+  int store_step(u32 n, StretchStep& step, u64 h_round, bool behind_run);   // the storing pass of the step that is due
   int long_grams_override = 0;   // BWTC_HIP_LONG_G2=N: N grams in the second key word
   void scatter_rank_pairs(u32* pairs, u32* tmp, u32 m, u32 n);
   int load_text(const u8* d_src, u32 ncopy, u32 n, bool reverse, u32* hist_T);

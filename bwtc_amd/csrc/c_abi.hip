@@ -1144,6 +1144,21 @@ int bwtc_hip_steps_get(bwtc_hip_ctx* ctx, uint32_t* run_depth, uint32_t* period_
   return 0;
 }
 
+// The last block's schedule of closed-form steps, in the order it took them: 5 words per entry -- the period (1: the run
+// step), the depth it ran at or 0, its gate length, its votes, flags (1: it ranked the runs too; 2: it was dropped).
+// Gate lengths and votes are made under BWTC_HIP_MULTI only.  *n_out: the block's entries, of which min(cap, *n_out) are written.
+int bwtc_hip_schedule_get(bwtc_hip_ctx* ctx, uint32_t* entries, uint32_t cap, uint32_t* n_out) {
+  if (!ctx || !n_out || (cap && !entries)) return -1;
+  const BwtEngine::BlockSort& b = ctx->eng.blk;
+  *n_out = (uint32_t)b.n_steps;
+  for (u32 i = 0; i < cap && i < (u32)b.n_steps; ++i) {
+    const BwtEngine::StretchStep& s = b.steps[i];
+    uint32_t* w = entries + 5 * i;
+    w[0] = s.p; w[1] = s.depth; w[2] = s.gate; w[3] = s.votes; w[4] = (s.ranks_runs ? 1u : 0u) | (s.dropped ? 2u : 0u);
+  }
+  return 0;
+}
+
 // The sorter's own stretch-length pass (BwtEngine::stretch_lengths: three launches; p = 1: the run-length pass) over T as
 // the sorter holds it -- loaded by load_text, padded with zero bytes -- on the context's buffers.  proper_out: the pass
 // with the second maximum (bwtc_hip_test_period_proper).
@@ -1169,6 +1184,43 @@ static int test_period_pass(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uin
   if (rc) return rc;
   BWTC_HIP_TRY(hipMemcpyAsync(k_out, e.d_runK, (u64)n * 4, hipMemcpyDeviceToHost, e.stream));
   BWTC_HIP_TRY(e.wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The merging storing pass of BWTC_HIP_MULTI (stretch_lengths with a StepMerge: k_stretch_lengths<false, true, true>) over
+// T as the sorter holds it.  k_inout: the block's merged words before the step (not read when fresh) and after it; h: the
+// step's depth.  The refusals are bwtc_hip_test_period_lengths', and h == 0 or a word count above 2^31 - 1.
+int bwtc_hip_test_period_merge(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t h, int fresh, uint32_t* k_inout,
+                               uint32_t* longest_out, uint32_t* proper_out) {
+  if (!ctx || !T || !k_inout || !longest_out || !proper_out) return -1;
+  BwtEngine& e = ctx->eng;
+  if (p == 0 || p > kPeriodMax || n == 0 || (u64)n > e.cap || h == 0 || n > 0x7FFFFFFFu) return -1;
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_in, T, n, hipMemcpyHostToDevice, e.stream));
+  u32 hist[256];
+  int rc = e.load_text(e.d_in, n, n, false, hist);
+  if (rc) return rc;
+  if (!fresh) BWTC_HIP_TRY(hipMemcpyAsync(e.d_runK, k_inout, (u64)n * 4, hipMemcpyHostToDevice, e.stream));
+  else BWTC_HIP_TRY(hipMemsetAsync(e.d_runK, 0xA5, (u64)n * 4, e.stream));   // (a fresh pass must not read what lies there)
+  const BwtEngine::StepMerge merge{h, fresh != 0};
+  rc = e.stretch_lengths(n, p, true, longest_out, proper_out, &merge);
+  if (rc) return rc;
+  BWTC_HIP_TRY(hipMemcpyAsync(k_inout, e.d_runK, (u64)n * 4, hipMemcpyDeviceToHost, e.stream));
+  BWTC_HIP_TRY(e.wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The finder's candidates (BwtEngine::period_winners: k_period_winners, one workgroup) over a vote table of kPeriodMax + 1
+// words, copied into the context's own d_votes: up to 8 (distance, votes) pairs into out[16], their number into *n_out.
+int bwtc_hip_test_period_winners(bwtc_hip_ctx* ctx, const uint32_t* table, uint32_t need, uint32_t* out, uint32_t* n_out) {
+  if (!ctx || !table || !out || !n_out) return -1;
+  BwtEngine& e = ctx->eng;
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_votes, table, (size_t)(kPeriodMax + 1) * 4, hipMemcpyHostToDevice, e.stream));
+  const int rc = e.period_winners(need, out, n_out);
+  if (rc) return rc;
   BWTC_HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -262,6 +262,7 @@ EXPORTS = [
     "bwtc_hip_test_sort_u32", "bwtc_hip_test_sort_u64", "bwtc_hip_test_scan_u32",
     "bwtc_hip_test_radix_pairs", "bwtc_hip_test_radix_long", "bwtc_hip_test_radix_segmented",
     "bwtc_hip_period_get", "bwtc_hip_test_period_lengths", "bwtc_hip_steps_get", "bwtc_hip_test_period_proper",
+    "bwtc_hip_test_period_merge", "bwtc_hip_test_period_winners", "bwtc_hip_schedule_get",
     "bwtc_hip_test_code_stage", "bwtc_hip_test_code_table", "bwtc_hip_test_code_keys",
     "bwtc_hip_test_finish_pass", "bwtc_hip_test_local_pass", "bwtc_hip_test_finisher",
     "bwtc_hip_test_models", "bwtc_hip_host_test_models", "bwtc_hip_host_wavelet_elements",
@@ -430,6 +431,9 @@ def load():
     L.bwtc_hip_test_period_lengths.argtypes = [_vp, _vp, _u32, _u32, _vp, ctypes.POINTER(_u32)]
     L.bwtc_hip_steps_get.argtypes = [_vp] + [ctypes.POINTER(_u32)] * 5
     L.bwtc_hip_test_period_proper.argtypes = [_vp, _vp, _u32, _u32, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]
+    L.bwtc_hip_test_period_merge.argtypes = [_vp, _vp, _u32, _u32, _u32, ctypes.c_int, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]
+    L.bwtc_hip_schedule_get.argtypes = [_vp, _vp, _u32, ctypes.POINTER(_u32)]
+    L.bwtc_hip_test_period_winners.argtypes = [_vp, _vp, _u32, _vp, ctypes.POINTER(_u32)]
     L.bwtc_hip_test_code_stage.argtypes = [_vp, _vp, _u32, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_u32), _vp, _vp,
                                            ctypes.POINTER(_u32), _vp, _vp, _vp]
     L.bwtc_hip_test_code_table.argtypes = [_vp, _vp, _u32, _vp, ctypes.POINTER(_u32)]
@@ -1158,6 +1162,37 @@ class Context:
         _check(self.lib.bwtc_hip_test_period_proper(self.handle, _ptr(T) if T.size else None, T.size, int(p), _ptr(k_out),
                                                     ctypes.byref(longest), ctypes.byref(proper)), "bwtc_hip_test_period_proper")
         return k_out[:T.size], int(longest.value), int(proper.value)
+
+    def schedule(self):
+        """The last block's schedule of closed-form steps (bwtc_hip_schedule_get), in the order it took them:
+        [(period, depth it ran at or 0, gate length, votes, flags)], flags 1: ranked the runs too, 2: dropped."""
+        w, found = np.zeros(5 * 8, np.uint32), _u32(0)
+        _check(self.lib.bwtc_hip_schedule_get(self.handle, _ptr(w), 8, ctypes.byref(found)), "bwtc_hip_schedule_get")
+        return [tuple(int(x) for x in w[5 * i:5 * i + 5]) for i in range(min(int(found.value), 8))]
+
+    def test_period_merge(self, T, p, h, k=None):
+        """The merging storing pass of BWTC_HIP_MULTI (bwtc_hip_test_period_merge) for the step of period p at depth h.  k:
+        the uint32 array of the block's merged words, read and written in place; None: the block's first step (fresh).
+        -> (the words, the longest stretch, the longest proper stretch)."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        fresh = k is None
+        if fresh:
+            k = np.zeros(max(T.size, 1), np.uint32)
+        assert k.dtype == np.uint32 and k.size >= T.size and k.flags.c_contiguous
+        longest, proper = _u32(0), _u32(0)
+        _check(self.lib.bwtc_hip_test_period_merge(self.handle, _ptr(T) if T.size else None, T.size, int(p), int(h), 1 if fresh else 0, _ptr(k),
+                                                   ctypes.byref(longest), ctypes.byref(proper)), "bwtc_hip_test_period_merge")
+        return k[:T.size], int(longest.value), int(proper.value)
+
+    def test_period_winners(self, table, need):
+        """The finder's candidates over a vote table of 4097 words (bwtc_hip_test_period_winners) -> [(distance, votes)],
+        at most 8, and the 16 words as the kernel left them."""
+        table = np.ascontiguousarray(table, dtype=np.uint32)
+        assert table.size == 4097
+        out, found = np.full(16, 0xABCD1234, np.uint32), _u32(0)
+        _check(self.lib.bwtc_hip_test_period_winners(self.handle, _ptr(table), int(need), _ptr(out), ctypes.byref(found)),
+               "bwtc_hip_test_period_winners")
+        return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(int(found.value))], out
 
     def test_period_lengths(self, T, p, k_out=None):
         """The sorter's own period-length pass over T (bwtc_hip_test_period_lengths) -> (k_p[], the longest).  k_out: the

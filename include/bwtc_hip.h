@@ -470,6 +470,14 @@ int bwtc_hip_period_get(bwtc_hip_ctx* ctx, uint32_t* p, uint32_t* longest, uint3
  * the s with s + 1 < n and T[s] != T[s + 1] -- and 0 where no pass made it (only passes under the switch do). */
 int bwtc_hip_steps_get(bwtc_hip_ctx* ctx, uint32_t* run_depth, uint32_t* period_p, uint32_t* period_depth, uint32_t* longest_run,
                        uint32_t* longest_proper);
+/* The schedule of closed-form steps of the context's last block, in the order it took them (BWTC_HIP_MULTI=1 lets a
+ * block take the run step and up to three period steps): 5 words per entry -- the period (1: the run step), the depth
+ * the step ran at (0: it did not), its gate length (the longest run; a period's longest proper stretch), the finder's
+ * votes for it, flags (1: a period step that ranked the block's long runs too; 2: the entry was dropped, its gate shut
+ * when its depth came or the rounds over before).  Gate lengths and votes are 0 without the switch.  *n_out the entries
+ * the block has, of which the first min(cap, *n_out) are written.  bwtc_hip_period_get and bwtc_hip_steps_get report the
+ * first period step that ran. */
+int bwtc_hip_schedule_get(bwtc_hip_ctx* ctx, uint32_t* entries, uint32_t cap, uint32_t* n_out);
 /* Test hook: the sorter's own period-length pass (three launches; p = 1: the run-length pass) over T[0..n), on the
  * context's buffers: k_out[s] = the number of leading characters of suffix s that are p-periodic, *longest_out their
  * maximum.  -1, before anything is launched, for p = 0, p > 4096, n = 0 or n above the context's block size. */
@@ -478,6 +486,18 @@ int bwtc_hip_test_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n
  * form): *proper_out = the longest proper stretch, 0 where no s has T[s] != T[s + 1].  The same refusals. */
 int bwtc_hip_test_period_proper(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest_out,
                                 uint32_t* proper_out);
+/* Test hook: the merging storing pass that a block's second and later closed-form steps take under BWTC_HIP_MULTI, and,
+ * with fresh != 0, its first one (tests/multimodel.py, merge_words).  A word of k_inout[0..n) is a look-up length in bits
+ * 0 ... 30 (0: no step has taken the suffix) and, in bit 31, "member of the current step".  The step of period p at depth
+ * h takes suffix s when k_p[s] >= h and k_p[s] >= the old length (0 everywhere when fresh: k_inout is not read then); it
+ * stores k_p[s] | 1 << 31 there, and the old length with bit 31 clear elsewhere.  *longest_out and *proper_out are the
+ * two maxima over k_p[], as bwtc_hip_test_period_proper gives them.  The same refusals, and -1 for h = 0. */
+int bwtc_hip_test_period_merge(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t h, int fresh, uint32_t* k_inout,
+                               uint32_t* longest_out, uint32_t* proper_out);
+/* Test hook: the finder's candidates under BWTC_HIP_MULTI (k_period_winners, one workgroup) over table[0..4096], the
+ * votes per distance: out[2 i], out[2 i + 1] = the distance in 2 ... 4096 with the i-th most votes among those with `need`
+ * votes or more (and at least one), the smaller distance first among equals, and its votes; i < 8, zeros from *n_out on. */
+int bwtc_hip_test_period_winners(bwtc_hip_ctx* ctx, const uint32_t* table, uint32_t need, uint32_t* out, uint32_t* n_out);
 /* Test hooks of the suffix sorter's code-key stage: k_pair_counts, k_code_build and
  * k_make_keys_code with suffix_sort's launch shapes and key layout (hi_shift = code_bits - 32, 13 upper bits of the suffix
  * number when split, then the predecessor's code, then the level), over T[0..n) as the sorter holds it (loaded by
