@@ -1613,8 +1613,12 @@ __global__ __launch_bounds__(kWinTPB) void k_scatter_dense(u32* __restrict__ ran
 // own round (mode 1) reads.  The member takes the closed-form key; every other suffix with a length looks up at
 // max(h, length), in the step's own round too; h_split is not read.
 constexpr u32 kStepMember = 0x80000000u, kStepLength = 0x7FFFFFFFu;
-struct RunKeys { const u32* k; u32 h_split; int mode; u32 p; bool merged; };   // mode 0: no runs in play (k is not read); 1: the run step; 2: a round after it; p: the period k[] was made for (1: runs)
+struct RunKeys { const u32* k; u32 h_split; int mode; u32 p; bool merged; };   // mode 0: no runs in play (k is not read); 1: the run step; 2: a round after it; 3: a copy round (k[] is K[], "Copies" below); p: the period k[] was made for (1: runs)
 __device__ __forceinline__ u32 run_offset(const RunKeys& rk, u32 s, u32 h) {
+  if (rk.mode == 3) {                                   // K[s] + h; a sum past 32 bits lies past the end of every block
+    const u32 kk = rk.k[s];
+    return kk > ~h ? 0xFFFFFFFFu : kk + h;
+  }
   if (rk.merged) {
     if (rk.mode == 0) return h;
     const u32 kk = rk.k[s] & kStepLength;
@@ -1658,6 +1662,7 @@ __device__ __forceinline__ u64 run_key2(const RunKeys& rk, const u32* __restrict
 // registers and reads the text once; period_breaks (any p) compares with the text p bytes back, a second stream read
 // by aligned 16-byte loads and shifted into place.  The run instantiation also keeps its own store form, one
 // `if constexpr` in the store loop: the thread at q looks at the break bits behind q and stores k[q].
+// A third maker, flag_breaks, reads a flag byte per position in the text's place with p = 0 (copy rounds, "Copies" below).
 // ---------------------------------------------------------------------------------------
 constexpr u32 kRunTile = 16384, kRunTPB = 256, kRunNone = 0xFFFFFFFFu;
 // the 64 positions from `at` on (a multiple of 64): bit j set = position at + j starts a run
@@ -1778,18 +1783,37 @@ __device__ __forceinline__ u64 proper_starts(const u8* __restrict__ T, u32 at, u
   if (left < 64u) mask &= (1ull << left) - 1ull;
   return mask;
 }
-// RUN: the pass of period 1, its mask from run_starts (p is 1 then); else period_breaks'
-template <bool RUN>
+// The third maker (copy rounds, "Copies" below): T is not the text but one flag byte per position, P[]; bit j set =
+// P[at + j] is 0.  p is 0 then: the general store form stores K[q] = (the first break at or behind q) - q at q itself.
+__device__ __forceinline__ u64 flag_breaks(const u8* __restrict__ P, u32 at, u32 n) {
+  if (at >= n) return 0ull;
+  u64 mask = 0;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {                         // (P[] has the room of four bytes per position: the loads are its own)
+    const u32 a = at + 16u * q;
+    if (a >= n) break;
+    const uint4 v = *reinterpret_cast<const uint4*>(P + a);
+    const u64 set = (u64)differing_bytes(v.x) | ((u64)differing_bytes(v.y) << 4) | ((u64)differing_bytes(v.z) << 8) | ((u64)differing_bytes(v.w) << 12);
+    mask |= (~set & 0xFFFFull) << (16 * q);
+  }
+  const u32 left = n - at;                              // positions at or past n are not the block's
+  if (left < 64u) mask &= (1ull << left) - 1ull;
+  return mask;
+}
+// RUN: the pass of period 1, its mask from run_starts (p is 1 then); FLAGS: flag_breaks' (p is 0); else period_breaks'
+template <bool RUN, bool FLAGS = false>
 __device__ __forceinline__ u64 stretch_breaks(const u8* __restrict__ T, u32 at, u32 n, u32 p) {
+  static_assert(!(RUN && FLAGS), "one maker of the break mask");
   if constexpr (RUN) return run_starts(T, at, n);
+  else if constexpr (FLAGS) return flag_breaks(T, at, n);
   else return period_breaks(T, at, n, p);
 }
 // launch 1: first[t] = the first break in tile t, or none (tiles past n included: the lengths' tiles reach n + p)
-template <bool RUN>
+template <bool RUN, bool FLAGS = false>
 __global__ __launch_bounds__(kRunTPB) void k_stretch_tiles(const u8* __restrict__ T, u32 n, u32 p, u32* __restrict__ first) {
   __shared__ u32 s_min[kRunTPB / kWave];
   const u32 at = blockIdx.x * kRunTile + threadIdx.x * 64u;
-  const u64 mask = stretch_breaks<RUN>(T, at, n, p);
+  const u64 mask = stretch_breaks<RUN, FLAGS>(T, at, n, p);
   u32 f = mask ? at + (u32)__builtin_ctzll(mask) : kRunNone;
   for (int o = kWave / 2; o > 0; o >>= 1) f = min(f, (u32)__shfl_xor(f, o, kWave));
   if ((threadIdx.x & (kWave - 1)) == 0) s_min[threadIdx.x / kWave] = f;
@@ -1827,17 +1851,20 @@ __global__ __launch_bounds__(1024) void k_run_carry(const u32* __restrict__ firs
 // k_p[s] >= h and k_p[s] >= the old length (0 for everybody when fresh: the block's first step); it stores k_p | bit 31
 // there and the old length, its flag cleared, everywhere else.  One more coalesced 4-byte load per store; both maxima
 // are over k_p, not over the merged word.  h and fresh are read by this instantiation alone.
-template <bool RUN, bool PROPER = false, bool MERGE = false>
+// FLAGS (never with the others; copy rounds): the mask comes from flag_breaks over P[] in T's place, p_any is 0, and the
+// general store form writes K[q] at q itself -- the aligned stores the run instantiation keeps its own form for.
+template <bool RUN, bool PROPER = false, bool MERGE = false, bool FLAGS = false>
 __global__ __launch_bounds__(kRunTPB) void k_stretch_lengths(const u8* __restrict__ T, u32 n, u32 p_any, const u32* __restrict__ behind,
                                                               u32* __restrict__ k, u32* __restrict__ longest, u32 h, u32 fresh) {
   static_assert(!MERGE || (PROPER && !RUN), "the merging pass is the general form with both maxima");
+  static_assert(!FLAGS || (!RUN && !PROPER && !MERGE), "the flags' pass is the general form with p = 0");
   __shared__ u64 s_mask[kRunTPB];
   __shared__ u32 s_next[kRunTPB];                      // the first break behind the thread's 64 positions
   __shared__ u32 s_wave[kRunTPB / kWave];
   const u32 p = RUN ? 1u : p_any;
   const u32 base = blockIdx.x * kRunTile;
   const u32 at = base + threadIdx.x * 64u;
-  const u64 mask = stretch_breaks<RUN>(T, at, n, p);
+  const u64 mask = stretch_breaks<RUN, FLAGS>(T, at, n, p);
   s_mask[threadIdx.x] = mask;
   __shared__ u64 s_proper[PROPER ? kRunTPB : 1];
   if constexpr (PROPER) s_proper[threadIdx.x] = proper_starts(T, at, n, p);
@@ -1893,6 +1920,54 @@ __global__ __launch_bounds__(kRunTPB) void k_stretch_lengths(const u8* __restric
   if constexpr (PROPER) {
     for (int o = kWave / 2; o > 0; o >>= 1) best_proper = max(best_proper, (u32)__shfl_xor(best_proper, o, kWave));
     if (lane == 0 && best_proper) atomicMax(longest + 1, best_proper);
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// Copies (BWTC_HIP_COPIES, tests/copymodel.py).  Whole copies of a piece at places that are no period of the text between
+// them stay tied for the rest of the copy.  In a list at depth h with rank[] current:
+//   F(G)   every member s of the tied group G has s + 1 < n, and rank[s + 1] is one value for all of them
+//   P(s)   s is tied in this list and F holds for its group;  K(s) = the positions q = s, s + 1, ... with P(q)
+// All members of a group have one K and share K + h characters, so the round looks up rank[s + K(s) + h] (RunKeys mode 3)
+// and doubles its depth as ever.  K[] is made by three passes over the list the ranking's apply kernel has just left
+// (suffix and dense group number per entry, in list order), after rank[] is updated and before the key kernel:
+//   marks     bad[g] = 1 where two neighbours of group g differ in rank[s + 1] (none: all ones).  A lane takes its
+//             neighbour's value by a cross-lane move; lane 0 of a wave -- the wave and tile seams -- fetches it itself
+//   flags     P[s] = 1 for every entry whose group is not bad, over zeros
+//   lengths   the stretch-length pass with flag_breaks as the maker of the break mask, into d_runK
+// bad[] is cleared per pass (a byte per group); P[] is a byte per position: plain stores, no atomics.
+// ---------------------------------------------------------------------------------------
+constexpr u32 kCopyTPB = 256, kCopyE = 4, kCopyTile = kCopyTPB * kCopyE, kCopyNone = 0xFFFFFFFFu;
+__device__ __forceinline__ u32 copy_successor(const u32* __restrict__ rank, u32 s, u32 n) { return s + 1u < n ? rank[s + 1u] : kCopyNone; }
+__global__ __launch_bounds__(kCopyTPB) void k_copy_marks(const u32* __restrict__ aidx, const u32* __restrict__ agrp, u32 m,
+                                                         const u32* __restrict__ rank, u32 n, u8* __restrict__ bad) {
+  const u32 lane = threadIdx.x & (kWave - 1);
+  u32 g[kCopyE], v[kCopyE];
+#pragma unroll
+  for (u32 e = 0; e < kCopyE; ++e) {                    // (all of a wave's lanes make every cross-lane move: no early way out)
+    const u32 i = blockIdx.x * kCopyTile + e * kCopyTPB + threadIdx.x;
+    g[e] = i < m ? agrp[i] : kCopyNone;
+    v[e] = i < m ? copy_successor(rank, aidx[i], n) : kCopyNone;
+  }
+#pragma unroll
+  for (u32 e = 0; e < kCopyE; ++e) {
+    const u32 i = blockIdx.x * kCopyTile + e * kCopyTPB + threadIdx.x;
+    u32 pg = __shfl_up(g[e], 1, kWave), pv = __shfl_up(v[e], 1, kWave);
+    if (lane == 0) {
+      pg = kCopyNone;
+      if (i > 0 && i < m) { pg = agrp[i - 1u]; pv = copy_successor(rank, aidx[i - 1u], n); }
+    }
+    if (i < m && pg == g[e] && pv != v[e]) bad[g[e]] = 1;
+  }
+}
+__global__ __launch_bounds__(kCopyTPB) void k_copy_flags(const u32* __restrict__ aidx, const u32* __restrict__ agrp, u32 m,
+                                                         const u8* __restrict__ bad, u32 n, u8* __restrict__ P) {
+#pragma unroll
+  for (u32 e = 0; e < kCopyE; ++e) {
+    const u32 i = blockIdx.x * kCopyTile + e * kCopyTPB + threadIdx.x;
+    if (i >= m) continue;
+    const u32 s = aidx[i];
+    if (s + 1u < n && !bad[agrp[i]]) P[s] = 1;          // (a group of one whose member is n - 1 has no neighbour to differ from)
   }
 }
 
@@ -2331,6 +2406,7 @@ int BwtEngine::init(int dev, u32 max_block_size) {
   env_int("BWTC_HIP_FIN_ROUNDS", &fin_rounds, 1, 4);
   run_ranks = !env_off("BWTC_HIP_RUNS"); period_ranks = !env_off("BWTC_HIP_PERIODS");
   if (env_int("BWTC_HIP_PERIOD", &v, 0, (int)kPeriodMax)) period_forced = (u32)v;
+  copy_rounds = env_is("BWTC_HIP_COPIES", "1");
   multi_steps = env_is("BWTC_HIP_MULTI", "1");
   mixed_steps = env_is("BWTC_HIP_MIXED", "1") || multi_steps;   // (BWTC_HIP_MULTI switches MIXED's rules on)
   local_rounds = !env_off("BWTC_HIP_LOCAL_ROUNDS");
@@ -2710,6 +2786,7 @@ struct RankRequest {
   const RrLong* lg = nullptr;    // long items: the second key word and the fields of the first
   RoundKind kind = RoundKind::kOrdinary;
   int run_mode = 0;              // RunKeys::mode of the next list's second keys
+  bool copies = false;           // the round may be a copy round (run_rounds; run_mode is 0 then): the step decides by the next list's length
 };
 static u64 carried_mask(bool carried) { return carried ? (1ull << 56) - 1ull : ~0ull; }   // a round's keys: the character rides in bits 56..63
 
@@ -2780,7 +2857,11 @@ int BwtEngine::rank_step(SortList& L, const RankRequest& rq) {
   const int b2k = run_now ? b2 + 1 : b2;
   const int kbits = b1 + b2k;
   const StretchStep& step = blk.current_step();
-  const RunKeys rkeys{d_runK, run_now ? 0u : step.depth, run_now ? 1 : (rq.run_mode == 2 ? 2 : 0), step.p, blk.merged};
+  RunKeys rkeys{d_runK, run_now ? 0u : step.depth, run_now ? 1 : (rq.run_mode == 2 ? 2 : 0), step.p, blk.merged};
+  // a copy round ("Copies"): the list is worth a pass over the block from n / 32 entries on (3.4 ps per byte for a
+  // stretch pass against 116 ps per entry for a round); the marks want the list in list order, so not the dense route
+  const bool copy_now = !INIT && rq.copies && rq.run_mode == 0 && rq.kind == RoundKind::kOrdinary && m_next > 0 && (u64)m_next * 32 >= n &&
+                        (u64)n + 2ull * kRunTile <= 0xFFFFFFFFull;
   // a key of more than 56 bits has no room for the carried character (blocks above 256 MiB with many groups): the
   // next list then goes without, and its ranking reads T[s-1] for what it finishes
   const bool carry_next = emit && kbits <= 56;
@@ -2791,7 +2872,7 @@ int BwtEngine::rank_step(SortList& L, const RankRequest& rq) {
   // (with the last gram's low bits left out of the sort -- long_drop -- the list also holds what those bits would have
   // told apart: the bound is three fifths then)
   const Route route = lng && emit && finisher ? Route::kFinish
-                      : !text && dense_route && m_next > 0 && (u64)m_next * 2 >= m && m >= pairs_min && !use_sweep ? Route::kDense
+                      : !text && dense_route && m_next > 0 && (u64)m_next * 2 >= m && m >= pairs_min && !use_sweep && !copy_now ? Route::kDense
                       : rq.kind == RoundKind::kRaw ? Route::kRaw
                       : text ? (run_now && m_next > 0 ? Route::kTextRun : Route::kText)
                       : (m >= pairs_min || INIT) ? Route::kPairs : Route::kShort;
@@ -2822,6 +2903,21 @@ int BwtEngine::rank_step(SortList& L, const RankRequest& rq) {
 
   // ---- the next list: its keys by the route, then the sort
   const u8* achr = carry_next ? (const u8*)re.achr_out : (const u8*)nullptr;
+  if (copy_now) {
+    // rank[] is current and the list lies raw in (v_free, d_GRP): K[] for it, and the gate for the rounds to come
+    BlockSort::Copies& cp = blk.copies;
+    u32 longest = 0;
+    const int rcc = copy_lengths(home.v_free, d_GRP, m_next, groups, n, &longest);
+    if (rcc) return rcc;
+    ++cp.passes;
+    cp.longest = std::max(cp.longest, longest);
+    if ((u64)longest < rq.h_next) cp.open = false;
+    if (longest) {
+      rkeys = RunKeys{d_runK, 0u, 3, 0u, false};
+      if (!cp.rounds++) cp.first_depth = depth32(rq.h_next);
+      stats.route |= 1024u;
+    }
+  }
   const u32 run_bytes = rkeys.mode ? 4u + (run_now ? 1u : 0u) : 0u;      // k[], and the byte behind the run
   switch (route) {
     case Route::kDense: {
@@ -3260,6 +3356,10 @@ int BwtEngine::run_rounds(SortList& L, const RoundsRequest& ask, RoundsLeft* out
     RankRequest rq;
     rq.m = m; rq.h_next = h; rq.kind = raw ? RoundKind::kRaw : text ? RoundKind::kText : RoundKind::kOrdinary;
     rq.run_mode = run_req ? 1 : (blk.merged ? blk.merged_ran : step.depth != 0) ? 2 : 0;   // the second keys (RunKeys::mode): the run step, a round behind one, or no runs in play
+    // a copy round ("Copies"): an ordinary doubling round over a complete rank[], no local list beside it, nothing parked,
+    // no step that ran or waits (d_runK is nobody's), the gate open
+    rq.copies = copy_rounds && ask.doubling && !text && !raw && L.ranks_complete && blk.fin.local_m == 0 && blk.fin.parked == 0 &&
+                rq.run_mode == 0 && !blk.step_in_play() && blk.copies.open;
     const int rc2 = rank_step<u64, false>(L, rq);
     if (rc2) return rc2;
     m = res.m;
@@ -3315,6 +3415,9 @@ int BwtEngine::run_rounds(SortList& L, const RoundsRequest& ask, RoundsLeft* out
     std::fprintf(stderr, "steps: run step at depth %u, period step of period %u at depth %u, longest run %u, longest proper stretch %u\n",
                  blk.run_depth(), period.p, period.depth, blk.run_longest, blk.proper_longest);
   }
+  if (copy_rounds && ask.doubling && debug_on())
+    std::fprintf(stderr, "copies: %u passes, %u copy rounds, longest K %u, first depth %u, the rounds begin at depth %llu\n", blk.copies.passes,
+                 blk.copies.rounds, blk.copies.longest, blk.copies.first_depth, (unsigned long long)h_first);
   if (out) *out = RoundsLeft{0, h};
   return 0;
 }
@@ -3370,7 +3473,8 @@ int BwtEngine::finisher_route(SortList& L, u32 n_lf) {
   L.ranks_complete = false;
   FinWork w;
   BWTC_HIP_TRY(finisher_begin(home.v_free, L.res.m, &w));
-  const FinRequest rq{L.n, L.re, FinCounters(*this).shallow_sink(home.vals, static_cast<u64*>(home.rec_free), fin_floor), local_rounds,
+  const FinRequest rq{L.n, L.re, FinCounters(*this).shallow_sink(home.vals, static_cast<u64*>(home.rec_free), fin_floor),
+                      local_rounds && !copy_rounds,   // (copy rounds: no local list -- copies of up to 256 members would never meet the rule)
                       finisher_shape(L.n, L.res)};
   FinOutcome fo;
   int rc = finisher_passes(w, rq, &fo);
@@ -3553,6 +3657,48 @@ int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* prop
   if (p == 1) blk.run_longest = *longest;
   // T read twice (p > 1: both streams of it), the lengths written; the tiles' words written and read
   stats.alg_bytes += (u64)n * ((p == 1 && !proper ? 1 + 1 : 2 + 2) + (store ? 4 : 0) + (merge && !merge->fresh ? 4 : 0)) + (u64)tiles * 16;
+  return 0;
+}
+
+// The copy round's three passes ("Copies") behind whatever the stream holds, and one host wait for the one word a stretch
+// pass reads back: K[] for every position of the block into d_runK, and the longest K.  bad[] (a byte per group) lives in
+// d_LP0 and P[] (a byte per position, read by 16-byte loads that begin below n) in d_parkS: a local list's home and the
+// waiting list, both dead in a round with no local list live and nothing parked.  d_runK's lengths are no period's now.
+int BwtEngine::copy_lengths(const u32* aidx, const u32* agrp, u32 m, u32 groups, u32 n, u32* longest) {
+  *longest = 0;
+  if (m == 0 || groups == 0 || (u64)n + 2ull * kRunTile > 0xFFFFFFFFull) return -1;
+  hipStream_t st = stream;
+  u8* bad = reinterpret_cast<u8*>(d_LP0);
+  u8* P = reinterpret_cast<u8*>(d_parkS);
+  const u32 tiles = (u32)(((u64)n + kRunTile - 1) / kRunTile), grid = ceil_div(m, kCopyTile);
+  PassTimer t_marks(st), t_flags(st), t_lengths(st);
+  BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallStretch, 0, 4, st));
+  BWTC_HIP_TRY(t_marks.start());
+  BWTC_HIP_TRY(hipMemsetAsync(bad, 0, groups, st));
+  hipLaunchKernelGGL(k_copy_marks, dim3(grid), dim3(kCopyTPB), 0, st, aidx, agrp, m, (const u32*)d_rank, n, bad);
+  BWTC_HIP_TRY(t_marks.stop());
+  BWTC_HIP_TRY(t_flags.start());
+  BWTC_HIP_TRY(hipMemsetAsync(P, 0, n, st));
+  hipLaunchKernelGGL(k_copy_flags, dim3(grid), dim3(kCopyTPB), 0, st, aidx, agrp, m, (const u8*)bad, n, P);
+  BWTC_HIP_TRY(t_flags.stop());
+  BWTC_HIP_TRY(t_lengths.start());
+  hipLaunchKernelGGL((k_stretch_tiles<false, true>), dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)P, n, 0u, d_runF);
+  hipLaunchKernelGGL(k_run_carry, dim3(1), dim3(1024), 0, st, (const u32*)d_runF, tiles, n, d_runB);
+  hipLaunchKernelGGL((k_stretch_lengths<false, false, false, true>), dim3(tiles), dim3(kRunTPB), 0, st, (const u8*)P, n, 0u, (const u32*)d_runB, d_runK,
+                     d_small + kSmallStretch, 0u, 0u);
+  BWTC_HIP_TRY(t_lengths.stop());
+  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallStretch, d_small + kSmallStretch, 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(wait());
+  if (t_marks.on) {
+    float a = 0.f, b = 0.f, c = 0.f;
+    BWTC_HIP_TRY(t_marks.ms(&a)); BWTC_HIP_TRY(t_flags.ms(&b)); BWTC_HIP_TRY(t_lengths.ms(&c));
+    std::fprintf(stderr, "copies: marks %.4f ms, flags %.4f ms, lengths %.4f ms for %u entries in %u groups, %u suffixes: longest K %u\n", a, b, c, m, groups, n,
+                 h_small[kSmallStretch]);
+  }
+  *longest = h_small[kSmallStretch];
+  blk.lengths_period = 0;
+  // the marks read the list and gather a rank per entry; the flags read the list and store a byte; P[] cleared, read twice; K[] written
+  stats.alg_bytes += (u64)m * (8 + 4) + (u64)m * (8 + 1 + 1) + (u64)groups + (u64)n * (1 + 2 + 4) + (u64)tiles * 16;
   return 0;
 }
 
@@ -4661,6 +4807,36 @@ int BwtEngine::test_round(bwtc_hip_round& t) {
   BWTC_HIP_TRY(hipMemcpyAsync(t.nchr, d_C0, (u64)m * 2, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(hipMemcpyAsync(t.rank, d_rank, (u64)n * 4, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(fin_test_emit_fetch(*this, n, t.SA, t.out, t.small, t.lf));
+  BWTC_HIP_TRY(can.fetch(st));
+  BWTC_HIP_TRY(wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return can.verdict();
+}
+
+// Test hook (bwtc_hip_test_copy_lengths): copy_lengths over a given list and rank[]; no text is read.
+int BwtEngine::test_copy_lengths(const u32* suf, const u32* grp, u32 m, const u32* rank, u32 n, u32* k_out, u32* longest_out) {
+  if (m < 1u || n < 1u || m > n || n > max_block || (u64)n + TestCanaries::kBytes > cap || !suf || !grp || !rank || !k_out || !longest_out) return -1;
+  u32 groups = 0;
+  std::vector<u8> seen(n, 0);
+  for (u32 i = 0; i < m; ++i) {                          // dense group numbers in list order, as the ranking's apply kernel leaves them
+    if (suf[i] >= n || seen[suf[i]]) return -1;
+    seen[suf[i]] = 1;
+    if (i == 0 ? grp[i] != 0u : (grp[i] != grp[i - 1] && grp[i] != grp[i - 1] + 1u)) return -1;
+    groups = grp[i] + 1u;
+  }
+  hipStream_t st = stream;
+  blk = BlockSort{};
+  TestCanaries can;
+  BWTC_HIP_TRY(hipMemcpyAsync(d_V0, suf, (u64)m * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(d_GRP, grp, (u64)m * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(d_rank, rank, (u64)n * 4, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemsetAsync(d_runK, 0xA5, (u64)n * 4, st));
+  BWTC_HIP_TRY(can.put(d_runK, (u64)n * 4, st));
+  BWTC_HIP_TRY(can.put(d_parkS, n, st));
+  BWTC_HIP_TRY(can.put(d_LP0, groups, st));
+  const int rc = copy_lengths(d_V0, d_GRP, m, groups, n, longest_out);
+  if (rc) return rc;
+  BWTC_HIP_TRY(hipMemcpyAsync(k_out, d_runK, (u64)n * 4, hipMemcpyDeviceToHost, st));
   BWTC_HIP_TRY(can.fetch(st));
   BWTC_HIP_TRY(wait());
   BWTC_HIP_TRY(hipGetLastError());

@@ -488,6 +488,10 @@ struct BwtEngine {
     StretchStep period_ran() const { for (int i = 0; i < n_steps; ++i) if (steps[i].p >= 2 && steps[i].depth) return steps[i]; return StretchStep{}; }
     // the candidate period, its longest stretch, its votes: with the step's depth, what bwtc_hip_period_get reports until the next block begins
     u32 period_p = 0, period_longest = 0, period_votes = 0;
+    // BWTC_HIP_COPIES (bwt_engine.hip, "Copies"): a pass is taken every round that may until one finds a longest K below its
+    // round's depth (the gate shuts); rounds: those whose look-ups went by K[]; first_depth: the depth of the first of them
+    struct Copies { bool open = true; u32 passes = 0, rounds = 0, longest = 0, first_depth = 0; } copies;
+    bool step_in_play() const { for (int i = 0; i < n_steps; ++i) if (steps[i].depth || steps[i].when != StretchStep::kNone) return true; return false; }
   } blk;
   // radix sort front door: picks the chained single-read passes or the classic ones
   template <typename K>
@@ -615,6 +619,12 @@ struct BwtEngine {
   u32* d_runK = nullptr;     // k_p[s]: the leading characters of suffix s that are p-periodic (p = 1: the positions from s on that hold T[s])
   u32* d_runF = nullptr; u32* d_runB = nullptr;   // the stretch-length pass's words per tile
   u32* d_votes = nullptr;    // the finder's table: votes per distance 0 ... kPeriodMax
+  // copies (bwt_engine.hip, "Copies"): whole copies at places that are no period look up past the copy in a doubling round
+  bool copy_rounds = false;  // BWTC_HIP_COPIES=1
+  // K[] into d_runK for the list (aidx, agrp: suffix and dense group number, m entries in list order, `groups` groups) over
+  // the current rank[]: the marks, the flags, the lengths, one read-back -> the longest K.  bad[] lives in d_LP0, P[] in d_parkS
+  int copy_lengths(const u32* aidx, const u32* agrp, u32 m, u32 groups, u32 n, u32* longest);
+  int test_copy_lengths(const u32* suf, const u32* grp, u32 m, const u32* rank, u32 n, u32* k_out, u32* longest_out);
   // store == false: the longest stretch alone (a trial); proper: the longest proper stretch too (the general form for p = 1)
   struct StepMerge { u32 h; bool fresh; };   // a storing pass over the merged look-up words: the step's depth; the block's first step
   int stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* proper = nullptr, const StepMerge* merge = nullptr);

@@ -1144,6 +1144,26 @@ int bwtc_hip_steps_get(bwtc_hip_ctx* ctx, uint32_t* run_depth, uint32_t* period_
   return 0;
 }
 
+// The copy rounds of the last block (BWTC_HIP_COPIES=1): the rounds that looked up at K[s] + h, the passes that made K[],
+// the longest K any pass found, the depth of the first copy round (zeros without the switch or where no round took a pass).
+int bwtc_hip_copies_get(bwtc_hip_ctx* ctx, uint32_t* rounds, uint32_t* passes, uint32_t* longest, uint32_t* first_depth) {
+  if (!ctx) return -1;
+  const BwtEngine::BlockSort::Copies& c = ctx->eng.blk.copies;
+  if (rounds) *rounds = c.rounds;
+  if (passes) *passes = c.passes;
+  if (longest) *longest = c.longest;
+  if (first_depth) *first_depth = c.first_depth;
+  return 0;
+}
+
+// The copy round's three passes (BwtEngine::copy_lengths) over a given list and rank[]; no text is needed.
+int bwtc_hip_test_copy_lengths(bwtc_hip_ctx* ctx, const uint32_t* suf, const uint32_t* grp, uint32_t m, const uint32_t* rank, uint32_t n,
+                               uint32_t* k_out, uint32_t* longest_out) {
+  if (!ctx) return -1;
+  BWTC_HIP_TRY(hipSetDevice(ctx->eng.device));
+  return ctx->eng.test_copy_lengths(suf, grp, m, rank, n, k_out, longest_out);
+}
+
 // The last block's schedule of closed-form steps, in the order it took them: 5 words per entry -- the period (1: the run
 // step), the depth it ran at or 0, its gate length, its votes, flags (1: it ranked the runs too; 2: it was dropped).
 // Gate lengths and votes are made under BWTC_HIP_MULTI only.  *n_out: the block's entries, of which min(cap, *n_out) are written.

@@ -263,6 +263,7 @@ EXPORTS = [
     "bwtc_hip_test_radix_pairs", "bwtc_hip_test_radix_long", "bwtc_hip_test_radix_segmented",
     "bwtc_hip_period_get", "bwtc_hip_test_period_lengths", "bwtc_hip_steps_get", "bwtc_hip_test_period_proper",
     "bwtc_hip_test_period_merge", "bwtc_hip_test_period_winners", "bwtc_hip_schedule_get",
+    "bwtc_hip_copies_get", "bwtc_hip_test_copy_lengths",
     "bwtc_hip_test_code_stage", "bwtc_hip_test_code_table", "bwtc_hip_test_code_keys",
     "bwtc_hip_test_finish_pass", "bwtc_hip_test_local_pass", "bwtc_hip_test_finisher",
     "bwtc_hip_test_models", "bwtc_hip_host_test_models", "bwtc_hip_host_wavelet_elements",
@@ -433,6 +434,8 @@ def load():
     L.bwtc_hip_test_period_proper.argtypes = [_vp, _vp, _u32, _u32, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]
     L.bwtc_hip_test_period_merge.argtypes = [_vp, _vp, _u32, _u32, _u32, ctypes.c_int, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]
     L.bwtc_hip_schedule_get.argtypes = [_vp, _vp, _u32, ctypes.POINTER(_u32)]
+    L.bwtc_hip_copies_get.argtypes = [_vp] + [ctypes.POINTER(_u32)] * 4
+    L.bwtc_hip_test_copy_lengths.argtypes = [_vp, _vp, _vp, _u32, _vp, _u32, _vp, ctypes.POINTER(_u32)]
     L.bwtc_hip_test_period_winners.argtypes = [_vp, _vp, _u32, _vp, ctypes.POINTER(_u32)]
     L.bwtc_hip_test_code_stage.argtypes = [_vp, _vp, _u32, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_u32), _vp, _vp,
                                            ctypes.POINTER(_u32), _vp, _vp, _vp]
@@ -1169,6 +1172,31 @@ class Context:
         w, found = np.zeros(5 * 8, np.uint32), _u32(0)
         _check(self.lib.bwtc_hip_schedule_get(self.handle, _ptr(w), 8, ctypes.byref(found)), "bwtc_hip_schedule_get")
         return [tuple(int(x) for x in w[5 * i:5 * i + 5]) for i in range(min(int(found.value), 8))]
+
+    # the suffix sorter's copy rounds (BWTC_HIP_COPIES=1)
+    def copies(self):
+        """The last block's copy rounds (bwtc_hip_copies_get): (rounds that looked up at K[s] + h, passes that made K[], the
+        longest K, the depth of the first copy round); zeros without the switch or where no round took a pass."""
+        v = [_u32(0) for _ in range(4)]
+        _check(self.lib.bwtc_hip_copies_get(self.handle, *[ctypes.byref(x) for x in v]), "bwtc_hip_copies_get")
+        return tuple(int(x.value) for x in v)
+
+    def test_copy_lengths(self, suf, grp, rank, k_out=None):
+        """The copy round's three passes over a list (suffix and dense group number per entry, in list order) and rank[]
+        (bwtc_hip_test_copy_lengths) -> (K[], the longest).  A contract the hook refuses raises BwtcHipError with code -1
+        (k_out is left untouched), a changed canary with code -20 - its index."""
+        suf = np.ascontiguousarray(suf, dtype=np.uint32)
+        grp = np.ascontiguousarray(grp, dtype=np.uint32)
+        rank = np.ascontiguousarray(rank, dtype=np.uint32)
+        assert suf.size == grp.size
+        if k_out is None:
+            k_out = np.zeros(max(rank.size, 1), np.uint32)
+        assert k_out.dtype == np.uint32 and k_out.size >= rank.size
+        longest = _u32(0)
+        _check(self.lib.bwtc_hip_test_copy_lengths(self.handle, _ptr(suf) if suf.size else None, _ptr(grp) if grp.size else None, suf.size,
+                                                   _ptr(rank) if rank.size else None, rank.size, _ptr(k_out), ctypes.byref(longest)),
+               "bwtc_hip_test_copy_lengths")
+        return k_out[:rank.size], int(longest.value)
 
     def test_period_merge(self, T, p, h, k=None):
         """The merging storing pass of BWTC_HIP_MULTI (bwtc_hip_test_period_merge) for the step of period p at depth h.  k:

@@ -478,6 +478,21 @@ int bwtc_hip_steps_get(bwtc_hip_ctx* ctx, uint32_t* run_depth, uint32_t* period_
  * the block has, of which the first min(cap, *n_out) are written.  bwtc_hip_period_get and bwtc_hip_steps_get report the
  * first period step that ran. */
 int bwtc_hip_schedule_get(bwtc_hip_ctx* ctx, uint32_t* entries, uint32_t cap, uint32_t* n_out);
+/* The copy rounds of the context's last block.  With BWTC_HIP_COPIES=1 a doubling round over a
+ * list of at least n / 32 entries, in a block without a closed-form step, makes K[s] -- the positions from s on whose
+ * tied groups' successors all lie in one group -- and looks up rank[s + K[s] + h] in place of rank[s + h]: whole copies
+ * of a piece at places that are no period are passed in one round.  *rounds the rounds that looked up that way, *passes
+ * the passes that made K[] (one more: the pass whose longest K lay below its round's depth and shut the gate), *longest
+ * the longest K of any pass, *first_depth the depth h of the first copy round.  Zeros without the switch or where no
+ * round took a pass; route bit 10 (1024) of bwtc_hip_stats says that at least one copy round ran. */
+int bwtc_hip_copies_get(bwtc_hip_ctx* ctx, uint32_t* rounds, uint32_t* passes, uint32_t* longest, uint32_t* first_depth);
+/* Test hook: the copy round's three passes (marks, flags, lengths) with the sorter's launch code over a given list -- suf[i]
+ * the suffix and grp[i] the dense group number (0, then equal to or one above the entry before) of entry i < m, in list
+ * order -- and rank[0..n): k_out[s] = K[s] for every s < n, *longest_out their maximum.  No text is read.  -1, before
+ * anything is launched, for m = 0, n = 0, m > n, n above the context's block size, an entry at or above n or group
+ * numbers that are not dense; -20 - i: canary i behind an output changed. */
+int bwtc_hip_test_copy_lengths(bwtc_hip_ctx* ctx, const uint32_t* suf, const uint32_t* grp, uint32_t m, const uint32_t* rank, uint32_t n,
+                               uint32_t* k_out, uint32_t* longest_out);
 /* Test hook: the sorter's own period-length pass (three launches; p = 1: the run-length pass) over T[0..n), on the
  * context's buffers: k_out[s] = the number of leading characters of suffix s that are p-periodic, *longest_out their
  * maximum.  -1, before anything is launched, for p = 0, p > 4096, n = 0 or n above the context's block size. */
