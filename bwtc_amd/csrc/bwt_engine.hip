@@ -2077,6 +2077,165 @@ __global__ __launch_bounds__(1024) void k_period_winners(const u32* __restrict__
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// Long periods (BWTC_HIP_LONG_PERIODS, tests/longperiodmodel.py).  The rule, the stretch-length pass and the deferred step
+// know no limit on p; the finder above and its probe do.  Under the switch neighbours that lie kPeriodMax < d <= dmax apart
+// vote too, exactly, in two sweeps: sweep 1 is the vote kernel with a second LDS table of coarse bins d >> 12 beside the
+// short one (one pass over the list for both); a distance with `need` votes lies in a coarse bin with `need` votes, of
+// which a list holds at most kLongSel, so sweep 2 -- only behind such a bin -- makes the exact histograms of d & 4095 for
+// the bins k_long_coarse_pick selected, kFineGroup of them per workgroup.  k_long_period_winners merges them with the short
+// table by k_period_winners' order.  The long finder's words (d_lvotes): the coarse table, then the selected bins, then
+// kLongSel fine tables of kFineBins words.
+// ---------------------------------------------------------------------------------------
+constexpr u32 kCoarseShift = 12, kFineBins = 1u << kCoarseShift, kCoarseBins = (kLongPeriodMax >> kCoarseShift) + 1;
+constexpr u32 kLongSel = 64;           // (m - 1) / need: below 65 for need = max(256, n / 64) and m <= n
+constexpr u32 kLongSelAt = 4352, kLongFineAt = 8192;   // d_lvotes: the words of the selected bins, of the fine tables
+constexpr u32 kFineGroup = 3;          // fine tables per workgroup of sweep 2: 48 KiB of LDS
+constexpr u32 kLongVoteTile = kVoteTile;   // entries per workgroup of both sweeps (tiles of four times as many measured no faster on 268 M entries, 1.23 against 1.29 ms, and slower on shorter lists: DESIGN.md section 6)
+constexpr int kSmallLong = kSmallPeriod + 2 + 2 * (int)kPeriodCandidates;   // d_small: the coarse bins with `need` votes
+static_assert(kCoarseBins <= kLongSelAt && kLongSelAt + kLongSel <= kLongFineAt, "the long finder's words do not overlap");
+template <bool RUNS_OUT>
+__global__ __launch_bounds__(kVoteTPB) void k_period_votes_long(const u64* __restrict__ ks, const u32* __restrict__ vs, u32 m, u64 kmask,
+                                                                u32* __restrict__ table, const u32* __restrict__ k1,
+                                                                u32* __restrict__ coarse, u32 dmax) {
+  // one table for both: short bin b counts in the lower half of word b, coarse bin b in the upper half -- a tile's
+  // kLongVoteTile entries cannot carry out of 16 bits, and the kernel keeps k_period_votes' LDS and occupancy
+  __shared__ u32 s_bin[kVoteBins];
+  for (u32 b = threadIdx.x; b < kVoteBins; b += kVoteTPB) s_bin[b] = 0;
+  __syncthreads();
+  const u32 base = blockIdx.x * kLongVoteTile;
+  for (u32 j = 0; j < kLongVoteTile / kVoteTPB; ++j) {
+    const u32 i = base + j * kVoteTPB + threadIdx.x;
+    if (i + 1u >= m) break;
+    if (((ks[i] ^ ks[i + 1u]) & kmask) != 0ull) continue;
+    const u32 a = vs[i], b = vs[i + 1u];
+    const u32 d = a > b ? a - b : b - a;
+    if (d < 2u || (d > kPeriodMax && d > dmax)) continue;
+    if constexpr (RUNS_OUT) { if (k1[min(a, b)] > d) continue; }
+    if (d <= kPeriodMax) atomicAdd(&s_bin[d], 1u);
+    else atomicAdd(&s_bin[d >> kCoarseShift], 1u << 16);   // (dmax <= kLongPeriodMax: the bin is the table's)
+  }
+  __syncthreads();
+  const u32 turn = (blockIdx.x * 67u) % kVoteBins;
+  for (u32 b = threadIdx.x; b < kVoteBins; b += kVoteTPB) {
+    u32 bb = b + turn;
+    if (bb >= kVoteBins) bb -= kVoteBins;
+    const u32 c = s_bin[bb];
+    if (c & 0xFFFFu) atomicAdd(&table[bb], c & 0xFFFFu);
+    if (c >> 16) atomicAdd(&coarse[bb], c >> 16);
+  }
+}
+static_assert(kCoarseBins == kVoteBins && kLongVoteTile < (1u << 16), "k_period_votes_long: one LDS word per bin of both tables, 16 bits each");
+// (one workgroup) the coarse bins with `need` votes or more into sel[] (the first kLongSel of them), their number into *count
+__global__ __launch_bounds__(1024) void k_long_coarse_pick(const u32* __restrict__ coarse, u32 need, u32* __restrict__ sel, u32* __restrict__ count) {
+  __shared__ u32 s_count;
+  if (threadIdx.x == 0) s_count = 0;
+  __syncthreads();
+  for (u32 b = threadIdx.x; b < kCoarseBins; b += 1024u) {
+    const u32 v = coarse[b];
+    if (v && v >= need) {
+      const u32 at = atomicAdd(&s_count, 1u);
+      if (at < kLongSel) sel[at] = b;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) *count = s_count;
+}
+// Sweep 2: workgroup (x, y) votes over tile x of the list for the coarse bins sel[y * kFineGroup ...] alone, by d & 4095
+template <bool RUNS_OUT>
+__global__ __launch_bounds__(kVoteTPB) void k_period_votes_fine(const u64* __restrict__ ks, const u32* __restrict__ vs, u32 m, u64 kmask,
+                                                                const u32* __restrict__ k1, const u32* __restrict__ sel, u32 n_sel,
+                                                                u32* __restrict__ fine, u32 dmax) {
+  __shared__ u32 s_fine[kFineGroup * kFineBins];
+  const u32 g0 = blockIdx.y * kFineGroup;
+  if (g0 >= n_sel) return;
+  const u32 cnt = min(kFineGroup, n_sel - g0), bins = cnt * kFineBins;
+  u32 c[kFineGroup];
+#pragma unroll
+  for (u32 g = 0; g < kFineGroup; ++g) c[g] = g < cnt ? sel[g0 + g] : 0xFFFFFFFFu;
+  for (u32 b = threadIdx.x; b < bins; b += kVoteTPB) s_fine[b] = 0;
+  __syncthreads();
+  const u32 base = blockIdx.x * kLongVoteTile;
+  for (u32 j = 0; j < kLongVoteTile / kVoteTPB; ++j) {
+    const u32 i = base + j * kVoteTPB + threadIdx.x;
+    if (i + 1u >= m) break;
+    if (((ks[i] ^ ks[i + 1u]) & kmask) != 0ull) continue;
+    const u32 a = vs[i], b = vs[i + 1u];
+    const u32 d = a > b ? a - b : b - a;
+    if (d <= kPeriodMax || d > dmax) continue;
+    const u32 cb = d >> kCoarseShift;
+    u32 slot = kFineGroup;
+#pragma unroll
+    for (u32 g = 0; g < kFineGroup; ++g) if (cb == c[g]) slot = g;
+    if (slot == kFineGroup) continue;
+    if constexpr (RUNS_OUT) { if (k1[min(a, b)] > d) continue; }
+    atomicAdd(&s_fine[slot * kFineBins + (d & (kFineBins - 1u))], 1u);
+  }
+  __syncthreads();
+  const u32 turn = (blockIdx.x * 67u) % bins;
+  u32* const out = fine + (size_t)g0 * kFineBins;
+  for (u32 b = threadIdx.x; b < bins; b += kVoteTPB) {
+    u32 bb = b + turn;
+    if (bb >= bins) bb -= bins;
+    const u32 v = s_fine[bb];
+    if (v) atomicAdd(&out[bb], v);
+  }
+}
+// (one workgroup) k_period_winners over the short table and the n_sel fine tables together: the distance of word e of fine
+// table q is sel[q] << 12 | e.  A key is votes << 32 | kLongKeyBase - distance.
+constexpr u32 kLongKeyBase = 1u << 25;
+__global__ __launch_bounds__(1024) void k_long_period_winners(const u32* __restrict__ table, const u32* __restrict__ sel, u32 n_sel,
+                                                              const u32* __restrict__ fine, u32 need, u32* __restrict__ out) {
+  __shared__ u64 s_best[1024];
+  const u32 words = n_sel * kFineBins;
+  u64 below = ~0ull;
+  for (u32 i = 0; i < kPeriodCandidates; ++i) {
+    u64 best = 0;
+    for (u32 b = threadIdx.x; b < kVoteBins; b += 1024u) {
+      const u32 v = b >= 2u ? table[b] : 0u;
+      const u64 key = (v >= need && v) ? ((u64)v << 32) | (u64)(kLongKeyBase - b) : 0ull;
+      if (key < below && key > best) best = key;
+    }
+    for (u32 e = threadIdx.x; e < words; e += 1024u) {
+      const u32 v = fine[e], d = (sel[e >> kCoarseShift] << kCoarseShift) | (e & (kFineBins - 1u));
+      const u64 key = (v >= need && v && d > kPeriodMax) ? ((u64)v << 32) | (u64)(kLongKeyBase - d) : 0ull;
+      if (key < below && key > best) best = key;
+    }
+    s_best[threadIdx.x] = best;
+    __syncthreads();
+    for (u32 o = 512; o > 0; o >>= 1) {
+      if (threadIdx.x < o) { const u64 v = s_best[threadIdx.x + o]; if (v > s_best[threadIdx.x]) s_best[threadIdx.x] = v; }
+      __syncthreads();
+    }
+    below = s_best[0];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      out[2u * i] = below ? kLongKeyBase - (u32)below : 0u;
+      out[2u * i + 1u] = (u32)(below >> 32);
+    }
+  }
+}
+// The probe for p > kPeriodMax, k_period_probe's answer: one workgroup per window of `span` positions from p + i * span
+// on, 256 threads x 64 positions a turn by period_breaks' 16-byte loads of T beside T - p.  The workgroup leaves at the
+// first turn that holds a break; a window without one sets the flag, and workgroups that find it set do not begin.
+__global__ __launch_bounds__(256) void k_period_probe_wide(const u8* __restrict__ T, u32 n, u32 p, u32 span, u32* flag) {
+  __shared__ u32 s_set;
+  if (threadIdx.x == 0) s_set = *reinterpret_cast<volatile u32*>(flag);
+  __syncthreads();
+  if (s_set) return;
+  const u64 x0 = (u64)p + (u64)blockIdx.x * span;
+  if (x0 + span > (u64)n) return;
+  const u32 lo = (u32)x0, hi = lo + span;
+  for (u32 base = lo & ~63u; base < hi; base += 256u * 64u) {   // (the host keeps n two tiles below 2^32: no wrap)
+    const u32 at = base + threadIdx.x * 64u;
+    u64 mask = at < hi ? period_breaks(T, at, n, p) : 0ull;
+    if (at < lo) mask &= ~0ull << (lo - at);                    // (thread 0 of the first turn alone: lo - at < 64)
+    if (at < hi && hi - at < 64u) mask &= (1ull << (hi - at)) - 1ull;
+    if (__syncthreads_or(mask != 0ull)) return;
+  }
+  if (threadIdx.x == 0) atomicOr(flag, 1u);
+}
+
 // Dense route, step 3 (after ALL of rank[] is updated): the next round's sort input, written
 // over the records.  Record p of suffix s with dense group number grp (all ones: finished)
 // becomes key = grp << b2 | rank[s+h]+1 (0 when s+h is past the end; with runs in play run_key2: the run step's
@@ -2249,7 +2408,7 @@ static u64 align_up(u64 v, u64 a) { return (v + a - 1) / a * a; }
 
 struct ArenaPlan {
   u64 off_T, off_out, off_in, off_SA, off_rank, off_R1, off_R2, off_V0, off_V1, off_G0, off_G1,
-      off_GRP, off_C0, off_C1, off_P0, off_P1, off_W0, off_W1, off_table, off_partial, off_aggA, off_aggB, off_aggC, off_agg_part, off_small, off_ent, off_comp, off_sweep, off_parkS, off_parkHP, off_hardS, off_hardHP, off_hardC, off_LP0, off_LH0, off_LH1, off_LC1, off_US, off_UR, off_pairs, off_codes, off_runK, off_runF, off_runB, off_votes, total;
+      off_GRP, off_C0, off_C1, off_P0, off_P1, off_W0, off_W1, off_table, off_partial, off_aggA, off_aggB, off_aggC, off_agg_part, off_small, off_ent, off_comp, off_sweep, off_parkS, off_parkHP, off_hardS, off_hardHP, off_hardC, off_LP0, off_LH0, off_LH1, off_LC1, off_US, off_UR, off_pairs, off_codes, off_runK, off_runF, off_runB, off_votes, off_lvotes, total;
 };
 
 // The entries an array of a finisher list holds (fin_room: what a pass needs of them), in a context of capacity cap.
@@ -2305,10 +2464,11 @@ static ArenaPlan plan_arena(u64 cap) {
   a.off_pairs = take((u64)kPairReplicas * 65536 * 4);
   a.off_codes = take((u64)kCodeRows * 256 * 4);
   a.off_runK = take(cap * 4);            // runs: k[] of every suffix, and the run-length pass's two words per tile
-  const u64 run_tiles = (cap + kRunTile - 1) / kRunTile + 1;
+  const u64 run_tiles = 2 * ((cap + kRunTile - 1) / kRunTile) + 2;   // (the tiles reach n + p, and a long period is below n: stretch_lengths)
   a.off_runF = take(run_tiles * 4);
   a.off_runB = take(run_tiles * 4);
   a.off_votes = take((u64)kVoteBins * 4);   // periods: the finder's vote table
+  a.off_lvotes = take(((u64)kLongFineAt + (u64)kLongSel * kFineBins) * 4);   // long periods: the coarse table, the selected bins, the fine tables
   a.total = o;
   return a;
 }
@@ -2375,6 +2535,7 @@ int BwtEngine::init(int dev, u32 max_block_size) {
   d_runF = reinterpret_cast<u32*>(base + a.off_runF);
   d_runB = reinterpret_cast<u32*>(base + a.off_runB);
   d_votes = reinterpret_cast<u32*>(base + a.off_votes);
+  d_lvotes = reinterpret_cast<u32*>(base + a.off_lvotes);
   use_sweep = env_is("BWTC_HIP_SORT", "sweep");
   wavelet_on_host = env_is("BWTC_HIP_WAVELET", "host");
   device_models = !env_is("BWTC_HIP_MODELS", "host"); models_side_stream = !env_off("BWTC_HIP_MODELS_STREAM");
@@ -2407,6 +2568,9 @@ int BwtEngine::init(int dev, u32 max_block_size) {
   run_ranks = !env_off("BWTC_HIP_RUNS"); period_ranks = !env_off("BWTC_HIP_PERIODS");
   if (env_int("BWTC_HIP_PERIOD", &v, 0, (int)kPeriodMax)) period_forced = (u32)v;
   copy_rounds = env_is("BWTC_HIP_COPIES", "1");
+  long_periods = env_is("BWTC_HIP_LONG_PERIODS", "1");
+  // (BWTC_HIP_LONG_PERIOD=p, under the switch alone: what BWTC_HIP_PERIOD is below kPeriodMax, for tests)
+  if (long_periods && env_int("BWTC_HIP_LONG_PERIOD", &v, (int)kPeriodMax + 1, (int)kLongPeriodMax)) period_forced = (u32)v;
   multi_steps = env_is("BWTC_HIP_MULTI", "1");
   mixed_steps = env_is("BWTC_HIP_MIXED", "1") || multi_steps;   // (BWTC_HIP_MULTI switches MIXED's rules on)
   local_rounds = !env_off("BWTC_HIP_LOCAL_ROUNDS");
@@ -3378,6 +3542,7 @@ int BwtEngine::run_rounds(SortList& L, const RoundsRequest& ask, RoundsLeft* out
       if (step.ranks_runs) stats.route |= 32u;           // (BWTC_HIP_MIXED: one step over k_p[] ranked the runs too)
       if (blk.merged) blk.merged_ran = true;
       if (blk.period_steps_ran() > 1) stats.route |= 512u;   // (BWTC_HIP_MULTI: more than one period step in the block)
+      if (period_req && step.p > kPeriodMax) stats.route |= 2048u;   // (BWTC_HIP_LONG_PERIODS: a period step with p > kPeriodMax)
       keep_h = true;
       if (period_req && debug_on())
         std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: period step at depth %u\n",
@@ -3415,6 +3580,9 @@ int BwtEngine::run_rounds(SortList& L, const RoundsRequest& ask, RoundsLeft* out
     std::fprintf(stderr, "steps: run step at depth %u, period step of period %u at depth %u, longest run %u, longest proper stretch %u\n",
                  blk.run_depth(), period.p, period.depth, blk.run_longest, blk.proper_longest);
   }
+  if (long_periods && ask.doubling && debug_on())
+    std::fprintf(stderr, "steps: long periods on, route bit 11 %s (period step of period %u at depth %u)\n", (stats.route & 2048u) ? "set" : "clear",
+                 blk.period_ran().p, blk.period_ran().depth);
   if (copy_rounds && ask.doubling && debug_on())
     std::fprintf(stderr, "copies: %u passes, %u copy rounds, longest K %u, first depth %u, the rounds begin at depth %llu\n", blk.copies.passes,
                  blk.copies.rounds, blk.copies.longest, blk.copies.first_depth, (unsigned long long)h_first);
@@ -3620,6 +3788,8 @@ int BwtEngine::stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* prop
   if (proper) *proper = 0;
   // (the tiles reach n + p and their positions are 32-bit: a block within two tiles of 2^32 takes no step)
   if ((u64)n + p + 2ull * kRunTile > 0xFFFFFFFFull) { *longest = 0; return 0; }
+  // (... and the tiles' words have room for n + p <= 2 cap positions: a named long period at or above n is nobody's period)
+  if (p > kPeriodMax && p >= n) { *longest = 0; return 0; }
   hipStream_t st = stream;
   const u32 tiles = (u32)(((u64)n + p + kRunTile - 1) / kRunTile);   // the tiles cover the positions x = s + p, s < n
   u32* k = store ? d_runK : nullptr;
@@ -3717,6 +3887,90 @@ int BwtEngine::period_winners(u32 need, u32* out, u32* n_out) {
   return 0;
 }
 
+// The long finder ("Long periods") over the sorted list (ks, vs, m entries): sweep 1 with the short votes, the coarse bins
+// with `need` votes, and -- behind one -- sweep 2 and the merged candidates.  A list has fewer than m votes to give:
+// (m - 1) / need above kLongSel is refused before anything is launched (-1; the product's need never is).
+int BwtEngine::long_period_votes(const u64* ks, const u32* vs, u32 m, u64 kmask, const u32* k1, u32 need, u32 dmax, bool winner_only, u32* out,
+                                 u32* n_out, bool* swept) {
+  *n_out = 0; *swept = false;
+  std::memset(out, 0, kPeriodCandidates * 8);
+  if (need == 0 || m < 2 || (u64)(m - 1) / need > kLongSel || dmax > kLongPeriodMax) return -1;
+  hipStream_t st = stream;
+  u32* const coarse = d_lvotes;
+  u32* const sel = d_lvotes + kLongSelAt;
+  u32* const fine = d_lvotes + kLongFineAt;
+  u32* const d_cand = d_small + kSmallPeriod + 2;
+  u32* const h_cand = h_small + kSmallPeriod + 2;
+  const u32 tiles = ceil_div(m, kLongVoteTile);
+  PassTimer t_one(st), t_two(st);
+  BWTC_HIP_TRY(hipMemsetAsync(d_votes, 0, (size_t)kVoteBins * 4, st));
+  BWTC_HIP_TRY(hipMemsetAsync(coarse, 0, (size_t)kCoarseBins * 4, st));
+  BWTC_HIP_TRY(t_one.start());
+  if (k1) hipLaunchKernelGGL(k_period_votes_long<true>, dim3(tiles), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, k1, coarse, dmax);
+  else hipLaunchKernelGGL(k_period_votes_long<false>, dim3(tiles), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, (const u32*)nullptr, coarse, dmax);
+  BWTC_HIP_TRY(t_one.stop());
+  hipLaunchKernelGGL(k_long_coarse_pick, dim3(1), dim3(1024), 0, st, (const u32*)coarse, need, sel, d_small + kSmallLong);
+  if (winner_only) {
+    BWTC_HIP_TRY(hipMemsetAsync(d_cand + 2, 0, (kPeriodCandidates - 1) * 8, st));
+    hipLaunchKernelGGL(k_period_winner, dim3(1), dim3(1024), 0, st, (const u32*)d_votes, d_cand);
+  } else {
+    hipLaunchKernelGGL(k_period_winners, dim3(1), dim3(1024), 0, st, (const u32*)d_votes, need, d_cand);
+  }
+  BWTC_HIP_TRY(hipMemcpyAsync(h_cand, d_cand, (kPeriodCandidates * 2 + 1) * 4, hipMemcpyDeviceToHost, st));   // (the candidates and kSmallLong behind them)
+  BWTC_HIP_TRY(wait());
+  const u32 n_sel = h_small[kSmallLong];
+  if (t_one.on) {
+    float ms = 0.f;
+    BWTC_HIP_TRY(t_one.ms(&ms));
+    std::fprintf(stderr, "periods: the vote kernel took %.4f ms for %u entries\n", ms, m);
+    std::fprintf(stderr, "periods: sweep 1 of the long finder (the vote kernel with the coarse table) took %.4f ms, %u coarse bins with %u votes\n", ms, n_sel, need);
+  }
+  if (n_sel > kLongSel) return -1;                      // (cannot happen: the votes are fewer than m)
+  if (n_sel) {
+    const u32 groups = ceil_div(n_sel, kFineGroup);
+    BWTC_HIP_TRY(hipMemsetAsync(fine, 0, (size_t)n_sel * kFineBins * 4, st));
+    BWTC_HIP_TRY(t_two.start());
+    if (k1) hipLaunchKernelGGL(k_period_votes_fine<true>, dim3(tiles, groups), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, k1, (const u32*)sel, n_sel, fine, dmax);
+    else hipLaunchKernelGGL(k_period_votes_fine<false>, dim3(tiles, groups), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, (const u32*)nullptr, (const u32*)sel, n_sel, fine, dmax);
+    BWTC_HIP_TRY(t_two.stop());
+    // (winner_only: a short winner below `need` stays what it is where the merged candidates are none)
+    u32* const d_merged = winner_only ? d_lvotes + kLongSelAt + kLongSel : d_cand;
+    static_assert(kLongSelAt + kLongSel + 2 * kPeriodCandidates <= kLongFineAt, "the merged candidates' words");
+    hipLaunchKernelGGL(k_long_period_winners, dim3(1), dim3(1024), 0, st, (const u32*)d_votes, (const u32*)sel, n_sel, (const u32*)fine, need, d_merged);
+    u32* const merged = h_small + kSmallLong + 1;         // (2 * kPeriodCandidates spare words of the pinned mirror)
+    BWTC_HIP_TRY(hipMemcpyAsync(merged, d_merged, 2 * kPeriodCandidates * 4, hipMemcpyDeviceToHost, st));
+    BWTC_HIP_TRY(wait());
+    if (!winner_only || merged[0]) std::memcpy(h_cand, merged, 2 * kPeriodCandidates * 4);
+    if (t_two.on) {
+      float ms = 0.f;
+      BWTC_HIP_TRY(t_two.ms(&ms));
+      std::fprintf(stderr, "periods: sweep 2 of the long finder took %.4f ms for %u coarse bins\n", ms, n_sel);
+    }
+    *swept = true;
+  }
+  u32 found = 0;
+  while (found < kPeriodCandidates && h_cand[2 * found] && h_cand[2 * found + 1] >= need) ++found;
+  std::memcpy(out, h_cand, kPeriodCandidates * 8);
+  *n_out = found;
+  return 0;
+}
+
+// The wide probe ("Long periods") over d_T: is any aligned window of `span` positions from p on free of breaks of period p?
+int BwtEngine::long_period_probe(u32 n, u32 p, u32 span, bool* found) {
+  *found = false;
+  if (span == 0 || (u64)n + p + 2ull * kRunTile > 0xFFFFFFFFull) return 0;   // (the block that takes no step: stretch_lengths)
+  const u64 windows = (u64)n > (u64)p + span ? ((u64)n - p) / span : 0;
+  if (!windows) return 0;
+  hipStream_t st = stream;
+  BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallPeriod + 1, 0, 4, st));
+  hipLaunchKernelGGL(k_period_probe_wide, dim3(depth32(windows)), dim3(256), 0, st, (const u8*)d_T, n, p, span, d_small + kSmallPeriod + 1);
+  BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 1, d_small + kSmallPeriod + 1, 4, hipMemcpyDeviceToHost, st));
+  BWTC_HIP_TRY(wait());
+  *found = h_small[kSmallPeriod + 1] != 0;
+  stats.alg_bytes += windows * 2;                       // (at the least, as the short probe counts)
+  return 0;
+}
+
 // blk.period_p, the finder's (or BWTC_HIP_PERIOD's), through what decides whether it is worth a step: the probe, the
 // period-length pass (a trial unless store), the worth test and the division of a period above the first round's depth.
 // Leaves blk.period_p (0: refused), blk.period_longest and, where mixed, blk.proper_longest.
@@ -3734,7 +3988,11 @@ int BwtEngine::weigh_period(u32 n, u64 h_first, bool mixed, bool store) {
     const u32 span = (u32)std::min<u64>((worth - blk.period_p) / 2, 0x40000000ull);
     const u64 windows = (u64)n > blk.period_p + span ? ((u64)n - blk.period_p) / span : 0;
     bool found = false;
-    if (windows) {
+    if (blk.period_p > kPeriodMax) {
+      // (BWTC_HIP_LONG_PERIODS: a window of a long period is a workgroup's, not a thread's -- the wide probe)
+      const int rcl = long_period_probe(n, blk.period_p, span, &found);
+      if (rcl) return rcl;
+    } else if (windows) {
       BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallPeriod + 1, 0, 4, st));
       hipLaunchKernelGGL(k_period_probe, dim3((u32)((windows + 255) / 256)), dim3(256), 0, st, (const u8*)d_T, n, blk.period_p, span, depth32(windows), d_small + kSmallPeriod + 1);
       BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 1, d_small + kSmallPeriod + 1, 4, hipMemcpyDeviceToHost, st));
@@ -3770,7 +4028,7 @@ int BwtEngine::weigh_period(u32 n, u64 h_first, bool mixed, bool store) {
     const u32 winner = blk.period_p, longest_voted = blk.period_longest, proper_voted = blk.proper_longest, g_voted = g;
     u32 rest = winner;
     for (u32 q = 2; q <= rest && blk.period_p / q >= 2; ) {
-      if (rest % q) { ++q; continue; }
+      if (rest % q) { q = (u64)q * q > rest ? rest : q + 1; continue; }   // (no factor up to its root: what is left is prime)
       rest /= q;
       const int rcb = stretch_lengths(n, blk.period_p / q, false, &blk.period_longest, proper);
       if (rcb) return rcb;
@@ -3899,6 +4157,27 @@ int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask
   if (period_forced) { blk.period_p = period_forced; blk.period_votes = 0; return 0; }
   if (m < 2) return 0;
   hipStream_t st = stream;
+  const u64 need = std::max<u64>(kPeriodMinVotes, (u64)n / 64);
+  if (long_periods) {
+    // BWTC_HIP_LONG_PERIODS: the same pass over the list votes for the distances up to min(kLongPeriodMax, n / 8) too (a
+    // longer period's stretch of kPeriodWorth periods has no room in the block), and the candidates are the merged ones
+    const bool runs_out = mixed_steps && blk.lengths_period == 1 && blk.steps[0].p == 1;
+    const u32 dmax = (u32)std::min<u64>(kLongPeriodMax, (u64)n / kPeriodWorth);
+    u32 found[2 * kPeriodCandidates], n_found = 0;
+    bool swept = false;
+    const int rcl = long_period_votes(ks, vs, m, kmask, runs_out ? (const u32*)d_runK : nullptr, (u32)need, dmax, !multi_steps, found, &n_found, &swept);
+    if (rcl) return rcl;
+    if (multi_steps) {
+      blk.n_cands = n_found;
+      for (u32 c = 0; c < blk.n_cands; ++c) { blk.cand_p[c] = found[2 * c]; blk.cand_votes[c] = found[2 * c + 1]; }
+    }
+    const u32 winner = found[0];
+    blk.period_votes = found[1];
+    blk.period_p = (winner >= 2 && (u64)blk.period_votes >= need) ? winner : 0u;
+    // (what the short finder counts, so that a block without a long candidate counts what it did; sweep 2: the list again, its tables)
+    stats.alg_bytes += (u64)m * (8 + 4) + (u64)kVoteBins * 8 + (multi_steps ? (u64)kVoteBins * 4 : 0) + (swept ? (u64)m * (8 + 4) + (u64)kLongSel * kFineBins * 4 : 0);
+    return 0;
+  }
   PassTimer timer(st);
   const bool timed = timer.on;
   BWTC_HIP_TRY(hipMemsetAsync(d_votes, 0, (size_t)kVoteBins * 4, st));
@@ -3909,7 +4188,6 @@ int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask
   else
     hipLaunchKernelGGL(k_period_votes<false>, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, (const u32*)nullptr);
   BWTC_HIP_TRY(timer.stop());
-  const u64 need = std::max<u64>(kPeriodMinVotes, (u64)n / 64);
   if (multi_steps) {
     // BWTC_HIP_MULTI: the up to kPeriodCandidates distances whose votes reach the threshold, not the winner alone
     u32 found[2 * kPeriodCandidates];

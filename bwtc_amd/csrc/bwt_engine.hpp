@@ -53,7 +53,8 @@ struct FinOutcome { u32 hard = 0, hard_depth = 0xFFFFFFFFu, left = 0, local = 0,
 // A finisher list lives in up to kFinRegions regions of its arrays (bwt_engine.hip, k_finish)
 constexpr u32 kFinRegions = 16;
 constexpr u32 kPeriodMax = 4096;   // the longest period the period step looks for (bwt_engine.hip, "Periods")
-constexpr u32 kPeriodCandidates = 8;   // the distances the finder returns under BWTC_HIP_MULTI (k_period_winners)
+constexpr u32 kLongPeriodMax = 1u << 24;   // ... and the longest under BWTC_HIP_LONG_PERIODS (bwt_engine.hip, "Long periods")
+constexpr u32 kPeriodCandidates = 8;  // the distances the finder returns under BWTC_HIP_MULTI (k_period_winners)
 struct FinRegions { u32 nreg; u32 wfirst[kFinRegions + 1]; u32 ebase[kFinRegions]; u32 ecount[kFinRegions]; };
 
 // 256 bytes of canary behind the last item a test hook's kernels may write (c_abi.hip, BwtEngine::test_finish_pass): a
@@ -633,6 +634,18 @@ struct BwtEngine {
   int decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask);   // -> blk.steps
   int weigh_period(u32 n, u64 h_first, bool mixed, bool store);   // blk.period_p through the probe, the pass, the worth test and the division
   int store_step(u32 n, StretchStep& step, u64 h_round, bool behind_run);   // the storing pass of the step that is due
+  // long periods (bwt_engine.hip, "Long periods"): the finder votes for distances up to kLongPeriodMax too, and a period
+  // above kPeriodMax takes the wide probe; everything behind them is the code a short period goes through
+  bool long_periods = false;   // BWTC_HIP_LONG_PERIODS=1 (BWTC_HIP_LONG_PERIOD=p names a period above kPeriodMax, as BWTC_HIP_PERIOD does below)
+  u32* d_lvotes = nullptr;     // the long finder's words: the coarse table, the selected bins, the fine tables
+  // Both sweeps and the merged candidates over a sorted list: up to kPeriodCandidates (distance, votes) pairs with `need`
+  // votes or more, distances 2 ... kPeriodMax and kPeriodMax + 1 ... dmax, into out[16] and their number into *n_out
+  // (one host wait, a second one behind sweep 2).  k1: the RUNS_OUT rule.  winner_only (the product without
+  // BWTC_HIP_MULTI): the short table's winner whatever its votes, as k_period_winner leaves it, where no long distance
+  // has `need` votes.  *swept: sweep 2 ran.
+  int long_period_votes(const u64* ks, const u32* vs, u32 m, u64 kmask, const u32* k1, u32 need, u32 dmax, bool winner_only, u32* out,
+                        u32* n_out, bool* swept);
+  int long_period_probe(u32 n, u32 p, u32 span, bool* found);   // the wide probe over d_T (one host wait)
   int long_grams_override = 0;   // BWTC_HIP_LONG_G2=N: N grams in the second key word
   void scatter_rank_pairs(u32* pairs, u32* tmp, u32 m, u32 n);
   int load_text(const u8* d_src, u32 ncopy, u32 n, bool reverse, u32* hist_T);

@@ -1245,6 +1245,75 @@ int bwtc_hip_test_period_winners(bwtc_hip_ctx* ctx, const uint32_t* table, uint3
   return 0;
 }
 
+// ---- test hooks of the long periods (BWTC_HIP_LONG_PERIODS; they need no switch) -----------------------------------
+// The long finder (BwtEngine::long_period_votes: sweep 1, the coarse bins' pick, sweep 2, the merged candidates) over a
+// given sorted list of m entries: ks into d_R1, vs into d_V0, and -- the RUNS_OUT rule -- k1[0 ... max(vs)] into d_runK.
+// Up to 8 (distance, votes) pairs with `need` votes or more, distances 2 ... 2^24, into out16, zeros behind them; their
+// number into *found.  -1: m < 2, m or a suffix number above the context's block size, need == 0 or (m - 1) / need > 64.
+int bwtc_hip_test_long_period_votes(bwtc_hip_ctx* ctx, const uint64_t* ks, const uint32_t* vs, uint32_t m, uint64_t kmask, const uint32_t* k1,
+                                    uint32_t need, uint32_t* out16, uint32_t* found) {
+  if (!ctx || !ks || !vs || !out16 || !found) return -1;
+  BwtEngine& e = ctx->eng;
+  if (m < 2 || (u64)m > e.cap) return -1;
+  u32 top = 0;
+  for (u32 i = 0; i < m; ++i) top = std::max(top, vs[i]);
+  if ((u64)top >= e.cap) return -1;
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  hipStream_t st = e.stream;
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_R1, ks, (u64)m * 8, hipMemcpyHostToDevice, st));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_V0, vs, (u64)m * 4, hipMemcpyHostToDevice, st));
+  if (k1) BWTC_HIP_TRY(hipMemcpyAsync(e.d_runK, k1, ((u64)top + 1) * 4, hipMemcpyHostToDevice, st));
+  u32 cand[2 * kPeriodCandidates], n_found = 0;
+  bool swept = false;
+  const int rc = e.long_period_votes(reinterpret_cast<const u64*>(e.d_R1), e.d_V0, m, kmask, k1 ? (const u32*)e.d_runK : nullptr, need, kLongPeriodMax,
+                                     false, cand, &n_found, &swept);
+  if (rc) return rc;
+  BWTC_HIP_TRY(hipGetLastError());
+  std::memcpy(out16, cand, sizeof cand);
+  *found = n_found;
+  return 0;
+}
+
+// The wide probe (BwtEngine::long_period_probe: k_period_probe_wide) over T as the sorter holds it: *flag_out = 1 when an
+// aligned window of `span` positions from p on, p + i * span, holds no break of period p.  -1: p outside 4097 ... 2^24,
+// span == 0, n == 0 or above the context's block size.
+int bwtc_hip_test_long_period_probe(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t span, uint32_t* flag_out) {
+  if (!ctx || !T || !flag_out) return -1;
+  BwtEngine& e = ctx->eng;
+  if (p <= kPeriodMax || p > kLongPeriodMax || span == 0 || n == 0 || (u64)n > e.cap) return -1;
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_in, T, n, hipMemcpyHostToDevice, e.stream));
+  u32 hist[256];
+  int rc = e.load_text(e.d_in, n, n, false, hist);
+  if (rc) return rc;
+  bool found = false;
+  rc = e.long_period_probe(n, p, span, &found);
+  if (rc) return rc;
+  BWTC_HIP_TRY(hipGetLastError());
+  *flag_out = found ? 1u : 0u;
+  return 0;
+}
+
+// The sorter's own stretch-length pass with both maxima (bwtc_hip_test_period_proper's) for 4097 <= p <= 2^24 and p < n:
+// k_p[] into k_out, longest2[0] = the longest stretch, longest2[1] = the longest proper one.  -1 outside that range (and
+// for n above the context's block size); k_out is not written then.
+int bwtc_hip_test_long_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest2) {
+  if (!ctx || !T || !k_out || !longest2) return -1;
+  BwtEngine& e = ctx->eng;
+  if (p <= kPeriodMax || p > kLongPeriodMax || p >= n || (u64)n > e.cap) return -1;
+  BWTC_HIP_TRY(hipSetDevice(e.device));
+  BWTC_HIP_TRY(hipMemcpyAsync(e.d_in, T, n, hipMemcpyHostToDevice, e.stream));
+  u32 hist[256];
+  int rc = e.load_text(e.d_in, n, n, false, hist);
+  if (rc) return rc;
+  rc = e.stretch_lengths(n, p, true, longest2, longest2 + 1);
+  if (rc) return rc;
+  BWTC_HIP_TRY(hipMemcpyAsync(k_out, e.d_runK, (u64)n * 4, hipMemcpyDeviceToHost, e.stream));
+  BWTC_HIP_TRY(e.wait());
+  BWTC_HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // ---- test hooks of the code-key stage (bwtc_hip_test_code_*; DESIGN.md, "The code-key hooks") --------------------
 // k_pair_counts, k_code_build and k_make_keys_code through BwtEngine::test_code_stage: suffix_sort's launch shapes and
 // key layout, T loaded by load_text, the context's own d_pairs / d_codes / d_R1 / d_W0 / d_P0.  Contracts are checked on

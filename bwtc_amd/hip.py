@@ -264,6 +264,7 @@ EXPORTS = [
     "bwtc_hip_period_get", "bwtc_hip_test_period_lengths", "bwtc_hip_steps_get", "bwtc_hip_test_period_proper",
     "bwtc_hip_test_period_merge", "bwtc_hip_test_period_winners", "bwtc_hip_schedule_get",
     "bwtc_hip_copies_get", "bwtc_hip_test_copy_lengths",
+    "bwtc_hip_test_long_period_votes", "bwtc_hip_test_long_period_probe", "bwtc_hip_test_long_period_lengths",
     "bwtc_hip_test_code_stage", "bwtc_hip_test_code_table", "bwtc_hip_test_code_keys",
     "bwtc_hip_test_finish_pass", "bwtc_hip_test_local_pass", "bwtc_hip_test_finisher",
     "bwtc_hip_test_models", "bwtc_hip_host_test_models", "bwtc_hip_host_wavelet_elements",
@@ -437,6 +438,9 @@ def load():
     L.bwtc_hip_copies_get.argtypes = [_vp] + [ctypes.POINTER(_u32)] * 4
     L.bwtc_hip_test_copy_lengths.argtypes = [_vp, _vp, _vp, _u32, _vp, _u32, _vp, ctypes.POINTER(_u32)]
     L.bwtc_hip_test_period_winners.argtypes = [_vp, _vp, _u32, _vp, ctypes.POINTER(_u32)]
+    L.bwtc_hip_test_long_period_votes.argtypes = [_vp, _vp, _vp, _u32, _u64, _vp, _u32, _vp, ctypes.POINTER(_u32)]
+    L.bwtc_hip_test_long_period_probe.argtypes = [_vp, _vp, _u32, _u32, _u32, ctypes.POINTER(_u32)]
+    L.bwtc_hip_test_long_period_lengths.argtypes = [_vp, _vp, _u32, _u32, _vp, _vp]
     L.bwtc_hip_test_code_stage.argtypes = [_vp, _vp, _u32, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, ctypes.POINTER(_u32), _vp, _vp,
                                            ctypes.POINTER(_u32), _vp, _vp, _vp]
     L.bwtc_hip_test_code_table.argtypes = [_vp, _vp, _u32, _vp, ctypes.POINTER(_u32)]
@@ -1233,6 +1237,47 @@ class Context:
         _check(self.lib.bwtc_hip_test_period_lengths(self.handle, _ptr(T) if T.size else None, T.size, int(p), _ptr(k_out), ctypes.byref(longest)),
                "bwtc_hip_test_period_lengths")
         return k_out[:T.size], int(longest.value)
+
+    # the suffix sorter's long periods (BWTC_HIP_LONG_PERIODS=1: periods 4097 ... 2^24)
+    def test_long_period_votes(self, ks, vs, kmask, need, k1=None):
+        """The long finder's two sweeps and merged candidates over a sorted list (bwtc_hip_test_long_period_votes): ks the
+        uint64 keys, vs the uint32 suffixes, k1 the runs' lengths for the rule that two members of one run do not vote.
+        -> ([(distance, votes)], at most 8, and 24 words: the 16 the hook wrote and 8 guard words 0xABCD1234 behind them).
+        A contract the hook refuses raises BwtcHipError with code -1."""
+        ks = np.ascontiguousarray(ks, dtype=np.uint64)
+        vs = np.ascontiguousarray(vs, dtype=np.uint32)
+        assert ks.size == vs.size
+        if k1 is not None:
+            k1 = np.ascontiguousarray(k1, dtype=np.uint32)
+            assert vs.size == 0 or k1.size > int(vs.max())
+        out, found = np.full(24, 0xABCD1234, np.uint32), _u32(0)
+        _check(self.lib.bwtc_hip_test_long_period_votes(self.handle, _ptr(ks) if ks.size else None, _ptr(vs) if vs.size else None, ks.size,
+                                                        int(kmask), None if k1 is None else _ptr(k1), int(need), _ptr(out), ctypes.byref(found)),
+               "bwtc_hip_test_long_period_votes")
+        return [(int(out[2 * i]), int(out[2 * i + 1])) for i in range(int(found.value))], out
+
+    def test_long_period_probe(self, T, p, span):
+        """The wide probe over T (bwtc_hip_test_long_period_probe) -> True when an aligned window of `span` positions,
+        p + i * span on, holds no break of period p."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        flag = _u32(0xABCD1234)
+        _check(self.lib.bwtc_hip_test_long_period_probe(self.handle, _ptr(T) if T.size else None, T.size, int(p), int(span), ctypes.byref(flag)),
+               "bwtc_hip_test_long_period_probe")
+        assert flag.value in (0, 1), flag.value
+        return flag.value == 1
+
+    def test_long_period_lengths(self, T, p, k_out=None):
+        """The sorter's period-length pass with both maxima for 4097 <= p <= 2^24, p < len(T)
+        (bwtc_hip_test_long_period_lengths) -> (k_p[], the longest, the longest proper stretch).  k_out: the uint32 array to
+        fill (left untouched where the hook refuses: BwtcHipError, code -1)."""
+        T = np.ascontiguousarray(T, dtype=np.uint8)
+        if k_out is None:
+            k_out = np.zeros(max(T.size, 1), np.uint32)
+        assert k_out.dtype == np.uint32 and k_out.size >= T.size
+        two = np.zeros(2, np.uint32)
+        _check(self.lib.bwtc_hip_test_long_period_lengths(self.handle, _ptr(T) if T.size else None, T.size, int(p), _ptr(k_out), _ptr(two)),
+               "bwtc_hip_test_long_period_lengths")
+        return k_out[:T.size], int(two[0]), int(two[1])
 
     # the suffix sorter's code-key stage (DESIGN.md section 3 item 1), kernel by kernel (bwtc_hip_test_code_*): a
     # contract the hook refuses raises BwtcHipError with code -1, a changed canary with code -20 - its index

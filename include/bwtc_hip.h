@@ -513,6 +513,24 @@ int bwtc_hip_test_period_merge(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, 
  * votes per distance: out[2 i], out[2 i + 1] = the distance in 2 ... 4096 with the i-th most votes among those with `need`
  * votes or more (and at least one), the smaller distance first among equals, and its votes; i < 8, zeros from *n_out on. */
 int bwtc_hip_test_period_winners(bwtc_hip_ctx* ctx, const uint32_t* table, uint32_t need, uint32_t* out, uint32_t* n_out);
+/* Test hooks of the long periods (BWTC_HIP_LONG_PERIODS=1: periods 4097 ... 2^24; tests/longperiodmodel.py).  They run
+ * whatever the switch says; a period step with such a period sets route bit 11 (2048) of bwtc_hip_stats.
+ * _votes: the finder's two sweeps and its merged candidates over a given sorted list of m entries, ks[i] the key and vs[i]
+ *   the suffix of entry i.  Neighbours with (ks[i] ^ ks[i + 1]) & kmask == 0 that lie d apart, 2 <= d <= 2^24, vote for d;
+ *   with k1 != NULL (k1[0 ... max(vs)], the runs' lengths) a pair with k1[min(suffixes)] > d does not.  out16[2 i],
+ *   out16[2 i + 1] = the distance with the i-th most votes among those with `need` votes or more, the smaller distance
+ *   first among equals, and its votes, exactly; i < 8, zeros from *found on.  -1, before anything is launched, for m < 2,
+ *   m or a suffix above the context's block size, need = 0 or (m - 1) / need > 64.
+ * _probe: the probe of a period above 4096 over T[0..n): *flag_out = 1 when one of the windows of `span` positions that
+ *   begin at p + i * span and end at or below n holds no position q with T[q] != T[q - p], else 0.  -1 for p outside
+ *   4097 ... 2^24, span = 0, n = 0 or n above the context's block size.
+ * _lengths: the sorter's period-length pass with both maxima for 4097 <= p <= 2^24 and p < n: k_out[s] as
+ *   bwtc_hip_test_period_lengths gives it, longest2[0] their maximum, longest2[1] the longest proper stretch.  -1 outside
+ *   that range or for n above the context's block size; k_out is not written then. */
+int bwtc_hip_test_long_period_votes(bwtc_hip_ctx* ctx, const uint64_t* ks, const uint32_t* vs, uint32_t m, uint64_t kmask, const uint32_t* k1,
+                                    uint32_t need, uint32_t* out16, uint32_t* found);
+int bwtc_hip_test_long_period_probe(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t span, uint32_t* flag_out);
+int bwtc_hip_test_long_period_lengths(bwtc_hip_ctx* ctx, const uint8_t* T, uint32_t n, uint32_t p, uint32_t* k_out, uint32_t* longest2);
 /* Test hooks of the suffix sorter's code-key stage: k_pair_counts, k_code_build and
  * k_make_keys_code with suffix_sort's launch shapes and key layout (hi_shift = code_bits - 32, 13 upper bits of the suffix
  * number when split, then the predecessor's code, then the level), over T[0..n) as the sorter holds it (loaded by
