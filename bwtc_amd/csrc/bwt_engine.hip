@@ -2538,7 +2538,7 @@ int BwtEngine::init(int dev, u32 max_block_size) {
   d_lvotes = reinterpret_cast<u32*>(base + a.off_lvotes);
   use_sweep = env_is("BWTC_HIP_SORT", "sweep");
   wavelet_on_host = env_is("BWTC_HIP_WAVELET", "host");
-  device_models = !env_is("BWTC_HIP_MODELS", "host"); models_side_stream = !env_off("BWTC_HIP_MODELS_STREAM");
+  device_models = !env_is("BWTC_HIP_MODELS", "host"); letter_models = env_is("BWTC_HIP_LETTER_MODELS", "1"); models_side_stream = !env_off("BWTC_HIP_MODELS_STREAM");
   int v = 0;
   if (env_int("BWTC_HIP_WAVELET_DEPTH", &v) && v > 0) max_inflight = (unsigned)v;
   dense_route = !env_off("BWTC_HIP_DENSE");

@@ -272,6 +272,7 @@ struct GmPass {
   u32 ends[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // the carried state after the block, by the state it starts in
   bool ends_ready = false;
   void* side = nullptr;                        // the stream the passes run on when it is not the context's (wavelet_models_device)
+  u32 kind = 0;                                // the main model the passes were prepared for (gm::kKindB / kKindb / kKindu)
 };
 
 // A block of the pipeline whose streams came from this device: owns the page-locked bytes.
@@ -282,6 +283,7 @@ struct DeviceWaveletJob : WaveletJob {
   PinnedBytes w_owner;                 // device-modelled blocks: the w-elements (2 bytes per coded element)
   u32* h_tail = nullptr;               //   {state after the block, error flags, elements counted} (in w_owner, behind the elements)
   u32 gm_state_in = 0;                 //   the carried state the device passes were given
+  char gm_letter = 'B';                //   the main model the device passes were made for: the block's, whatever the context's becomes
   GmPass gm;                           // farmed streams: the passes' first part is done, the rest waits for the state (_queue)
   // between wavelet_encode_prepare and wavelet_encode_queue
   bool streams_ready = false;          // plan + coded_pos + codes are in place for HostPipeline::queue
@@ -377,6 +379,11 @@ struct BwtEngine {
     ~ScanScope() { current_scan_chain() = prev; }
   };
   bool device_models = true;           // BWTC_HIP_MODELS=host: the models stay on the worker threads (all routes of round 2)
+  bool letter_models = false;          // BWTC_HIP_LETTER_MODELS=1: the models of 'b' and 'u' blocks on the device too
+  // this letter's models run on the device
+  bool models_on_device(char letter) const {
+    return device_models && (letter == 'B' || (letter_models && (letter == 'b' || letter == 'u')));
+  }
   std::vector<u32> long_count;   // host scratch of the run statistics: counts of long run lengths, all zero between calls
   // blocks of the 'B' coder between _begin and _end (wavelet_pipeline.hpp)
   // run arrays of the 'B' coder's scanner, two buffers: block i is scanned while block i-1's runs still
@@ -688,17 +695,19 @@ int wavelet_streams_device(BwtEngine& e, const u32* d_run_start, const u8* d_run
 // The adaptive models of a block whose packed streams are in HBM (wavelet_gpu_models.hip): queues
 // the passes and the copy of the w-elements to h_w, of {state after, error flags, count} to h_tail.
 int wavelet_models_device(BwtEngine& e, const u32* d_packed, u32 n_coded, const bwtc::wavelet::StreamPlan& plan,
-                          const std::vector<u32>& coded_pos, u32 state_in, uint16_t* h_w, u32* h_tail);
+                          const std::vector<u32>& coded_pos, u32 state_in, uint16_t* h_w, u32* h_tail, u32 kind = 0);
 // the same in two parts: what does not depend on the carried state (read_ends: and, after a wait for the
 // device, the state after the block for each of the eight states it can start in), and the rest
 // (early_state != null: the state after the block is returned before the long passes are queued -- from
-// that table, else read back with a short wait)
+// that table, else read back with a short wait).  kind: the main model (gm::kKindB / kKindb / kKindu), kept in *g; a
+// letter's passes do not look at state_in, their table is ends[i] = i with or without read_ends, and nothing waits
 int wavelet_models_prepare(BwtEngine& e, const u32* d_packed, u32 n_coded, const bwtc::wavelet::StreamPlan& plan,
-                           const std::vector<u32>& coded_pos, GmPass* g, bool read_ends = false, hipStream_t side = nullptr);
+                           const std::vector<u32>& coded_pos, GmPass* g, bool read_ends = false, hipStream_t side = nullptr,
+                           u32 kind = 0);
 // the same from "tasks and chunks are known" on (gm::buildTasks / gm::cutChunks, wavelet_gpu_models.hpp)
 int wavelet_models_prepare_tasks(BwtEngine& e, const u32* d_packed, u32 n_coded, const std::vector<bwtc::wavelet::gm::Task>& tasks,
                                  const std::vector<bwtc::wavelet::gm::Chunk>& chunks, GmPass* g, bool read_ends = false,
-                                 hipStream_t side = nullptr);
+                                 hipStream_t side = nullptr, u32 kind = 0);
 int wavelet_models_run(BwtEngine& e, const GmPass& g, u32 state_in, uint16_t* h_w, u32* h_tail, u32* early_state);
 
 // WaveletEncoder: writeBlockHeader + encodeData + finishBlock (WaveletCoders.cpp:173-219,

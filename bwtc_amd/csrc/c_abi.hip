@@ -1640,8 +1640,14 @@ bool model_tasks_from(const uint32_t* tasks, uint32_t nt, uint32_t n_coded, std:
 
 int bwtc_hip_test_models(bwtc_hip_ctx* ctx, const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks, uint32_t nt,
                          uint32_t state_in, uint32_t flags, bwtc_hip_models_out* out) {
+  return bwtc_hip_test_models_letter(ctx, 'B', packed, n_coded, tasks, nt, state_in, flags, out);
+}
+
+int bwtc_hip_test_models_letter(bwtc_hip_ctx* ctx, char letter, const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks,
+                                uint32_t nt, uint32_t state_in, uint32_t flags, bwtc_hip_models_out* out) {
   namespace gm = bwtc::wavelet::gm;
-  if (!ctx || !packed || !tasks || !out || !out->w || state_in > 7u || flags > 3u) return -1;
+  if (!ctx || !packed || !tasks || !out || !out->w || state_in > 7u || flags > 3u || !bwtc::wavelet::isWaveletModel(letter)) return -1;
+  const u32 kind = gm::kindOfLetter(letter);
   const bool lean = (flags & 2u) != 0;
   if (!lean && (!out->chunks || !out->cmap || !out->cstate || !out->base || !out->sb || !out->sbits || !out->smap || !out->snaps ||
                 !out->sstart)) return -1;
@@ -1665,7 +1671,7 @@ int bwtc_hip_test_models(bwtc_hip_ctx* ctx, const uint32_t* packed, uint32_t n_c
     ~Lines() { e.gm_partition_lines = was; }
   } lines(e, (flags & 1u) != 0);
   GmPass g;
-  int rc = wavelet_models_prepare_tasks(e, d_packed, n_coded, tk, chunks, &g, true);
+  int rc = wavelet_models_prepare_tasks(e, d_packed, n_coded, tk, chunks, &g, true, nullptr, kind);
   if (rc) return rc;
   if (!g.ends_ready) return -3;
   for (int i = 0; i < 8; ++i) out->ends[i] = g.ends[i];
@@ -1678,7 +1684,7 @@ int bwtc_hip_test_models(bwtc_hip_ctx* ctx, const uint32_t* packed, uint32_t n_c
   BWTC_HIP_TRY(hw);
   BWTC_HIP_TRY(hs);
   BWTC_HIP_TRY(hipGetLastError());
-  if (early != g.ends[state_in]) return -3;
+  if (early != (kind == gm::kKindB ? g.ends[state_in] : gm::mainStart(kind))) return -3;
   out->nc = nc;
   out->nsc = g.nsc;
   if (lean) return 0;
@@ -1703,8 +1709,13 @@ int bwtc_hip_test_models(bwtc_hip_ctx* ctx, const uint32_t* packed, uint32_t n_c
 
 int bwtc_hip_host_test_models(const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks, uint32_t nt,
                               uint32_t state_in, uint16_t* w_out, uint32_t* state_out) {
+  return bwtc_hip_host_test_models_letter('B', packed, n_coded, tasks, nt, state_in, w_out, state_out);
+}
+
+int bwtc_hip_host_test_models_letter(char letter, const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks, uint32_t nt,
+                                     uint32_t state_in, uint16_t* w_out, uint32_t* state_out) {
   namespace gm = bwtc::wavelet::gm;
-  if (!packed || !tasks || !w_out || !state_out || state_in > 7u) return -1;
+  if (!packed || !tasks || !w_out || !state_out || state_in > 7u || !bwtc::wavelet::isWaveletModel(letter)) return -1;
   std::vector<gm::Task> tk;
   if (!model_tasks_from(tasks, nt, n_coded, &tk)) return -1;
   std::vector<gm::Chunk> chunks;
@@ -1714,7 +1725,7 @@ int bwtc_hip_host_test_models(const uint32_t* packed, uint32_t n_coded, const ui
   std::memcpy(pk.data(), packed, ((size_t)n_coded + 15) / 16 * 4);
   std::vector<uint16_t> w((size_t)n_coded + 8);
   uint32_t st = state_in;
-  if (!gm::modelsOnHostLanes(pk.data(), n_coded, tk, chunks, &st, w.data())) return -7;
+  if (!gm::modelsOnHostLanes(pk.data(), n_coded, tk, chunks, &st, w.data(), letter)) return -7;
   std::memcpy(w_out, w.data(), (size_t)n_coded * 2);
   *state_out = st;
   return 0;
@@ -1726,6 +1737,17 @@ int bwtc_hip_host_wavelet_elements(uint32_t n_sections, const uint32_t* first_ru
                                    const uint32_t* dist_len, const uint32_t* dist_cnt, uint32_t* state,
                                    uint32_t* n_coded, uint32_t* nt, uint32_t* packed, uint64_t packed_words,
                                    uint32_t* tasks, uint32_t tasks_cap, uint16_t* w, uint64_t w_cap) {
+  return bwtc_hip_host_wavelet_elements_letter('B', n_sections, first_run, run_sym, run_start, run_freqs, dist_offset, dist_len, dist_cnt,
+                                               state, n_coded, nt, packed, packed_words, tasks, tasks_cap, w, w_cap);
+}
+
+int bwtc_hip_host_wavelet_elements_letter(char letter, uint32_t n_sections, const uint32_t* first_run,
+                                          const uint8_t* run_sym, const uint32_t* run_start,
+                                          const uint32_t* run_freqs, const uint32_t* dist_offset,
+                                          const uint32_t* dist_len, const uint32_t* dist_cnt, uint32_t* state,
+                                          uint32_t* n_coded, uint32_t* nt, uint32_t* packed, uint64_t packed_words,
+                                          uint32_t* tasks, uint32_t tasks_cap, uint16_t* w, uint64_t w_cap) {
+  if (!bwtc::wavelet::isWaveletModel(letter)) return -1;
   if (!first_run || !run_sym || !run_start || !run_freqs || !dist_offset || !dist_len || !dist_cnt ||
       !state || !n_coded || !nt || n_sections > 256) return -1;
   std::vector<std::vector<std::pair<uint32_t, uint32_t> > > dist(n_sections);
@@ -1757,7 +1779,7 @@ int bwtc_hip_host_wavelet_elements(uint32_t n_sections, const uint32_t* first_ru
   for (size_t t = 0; t < tk.size(); ++t) { tasks[3 * t] = tk[t].begin; tasks[3 * t + 1] = tk[t].end; tasks[3 * t + 2] = tk[t].type; }
   // the sequential coder's models: group by group, the probability of a ONE per element -> w form
   codes.push_back(0);
-  bwtc::wavelet::StreamCoder sc(plan, coded_pos.data(), codes.data(), *state, 'B');
+  bwtc::wavelet::StreamCoder sc(plan, coded_pos.data(), codes.data(), *state, letter);
   std::vector<uint16_t> prob((size_t)total + 8, 0);
   for (size_t k = 0; k < sc.modelTasks(); ++k) sc.model(k, prob.data());
   for (uint32_t i = 0; i < total; ++i) {

@@ -8,6 +8,7 @@
 #include "bwt_engine.hpp"
 #include "entropy_host.hpp"
 #include "wavelet_host.hpp"
+#include "wavelet_gpu_models.hpp"
 #include "wavelet_pipeline.hpp"
 #include <algorithm>
 #include <chrono>
@@ -24,7 +25,8 @@ namespace bwtc_hip {
 
 // Why the device models of a block are not used (BWTC_HIP_REJECT_*, 0: used).  h_tail: [0] state after the
 // block, [1] the passes' error flags, [2] elements counted, [3] chained-scan error; state_ok: the block
-// starts and ends in the states its stream has there.
+// starts and ends in the states its stream has there, under the letter its passes were prepared for (a 'b' or
+// 'u' block carries nothing: only the letter can fail it).
 static u32 device_model_rejects(const u32* h_tail, u32 n_coded, bool state_ok) {
   u32 r = 0;
   if (h_tail[1]) r |= BWTC_HIP_REJECT_FLAGS;
@@ -78,10 +80,12 @@ static int wavelet_finish_device_half(BwtEngine& e, const std::shared_ptr<Device
     // block: known when every block begun before it has joined the stream -- the _begin flow, where
     // the block before the previous one joined while the scanner ran.  (_prepare / _queue callers
     // learn the state at _queue time: their models stay on the worker threads.)
-    const bool on_gpu = e.device_models && e.wavelet_model == 'B' && e.deferred_queue;
+    const bool on_gpu = e.models_on_device(e.wavelet_model) && e.deferred_queue;
     // A stream farmed over contexts (_prepare / _queue) learns the state at _queue time: the passes'
     // first part (tables, chunk maps, the tiles' state maps) is done now, the rest then.
-    const bool on_gpu_later = e.device_models && e.wavelet_model == 'B' && !e.deferred_queue && farm_prepare;
+    const bool on_gpu_later = e.models_on_device(e.wavelet_model) && !e.deferred_queue && farm_prepare;
+    const u32 kind = bwtc::wavelet::gm::kindOfLetter(e.wavelet_model);
+    job.gm_letter = e.wavelet_model;                  // the passes below are this letter's, whatever the context's is at _queue
     if (on_gpu)
       for (std::map<u64, std::shared_ptr<DeviceWaveletJob> >::iterator o = e.jobs.begin(); o != e.jobs.end() && o->first < job.rank; ++o)
         if (!o->second->queued) { const int rq = wavelet_encode_queue(e, o->first, e.wavelet_state, &e.wavelet_state); if (rq) return rq; }
@@ -113,7 +117,7 @@ static int wavelet_finish_device_half(BwtEngine& e, const std::shared_ptr<Device
       }
       job.h_tail = reinterpret_cast<u32*>(job.w_owner.data() + w_bytes);
       job.h_tail[0] = job.h_tail[1] = job.h_tail[2] = job.h_tail[3] = 0xFFFFFFFFu;
-      rc = wavelet_models_prepare(e, d_packed, (u32)e.wt_coded, job.plan, job.coded_pos, &job.gm, true);
+      rc = wavelet_models_prepare(e, d_packed, (u32)e.wt_coded, job.plan, job.coded_pos, &job.gm, true, nullptr, kind);
       if (rc) return rc;
       e.gm_pending = jobp;
     }
@@ -131,7 +135,7 @@ static int wavelet_finish_device_half(BwtEngine& e, const std::shared_ptr<Device
       job.h_tail[0] = job.h_tail[1] = job.h_tail[2] = job.h_tail[3] = 0xFFFFFFFFu;
       job.gm_state_in = e.wavelet_state;
       rc = wavelet_models_device(e, d_packed, (u32)e.wt_coded, job.plan, job.coded_pos, e.wavelet_state,
-                                 reinterpret_cast<uint16_t*>(job.w_owner.data()), job.h_tail);
+                                 reinterpret_cast<uint16_t*>(job.w_owner.data()), job.h_tail, kind);
       if (rc) return rc;
       job.w = reinterpret_cast<const uint16_t*>(job.w_owner.data());
       job.copying = true;                             // the w-elements are on their way (d2h stream) whatever async_copy says
@@ -261,7 +265,7 @@ static int wavelet_encode_queue_unguarded(BwtEngine& e, u64 ticket, u32 state_in
     if (e.codes_wait() != hipSuccess) return -3;
   }
   job.queued = true;
-  if (job.gm.ready && job.streams_ready && e.wavelet_model == 'B') {
+  if (job.gm.ready && job.streams_ready && e.wavelet_model == job.gm_letter) {
     // farmed stream, models on the device: the rest of the passes with the state that has just
     // arrived; the state after the block is looked up (_prepare left it for every state the block can
     // start in: nothing here waits for the device), the block joins the host pipeline from a host
@@ -274,8 +278,8 @@ static int wavelet_encode_queue_unguarded(BwtEngine& e, u64 ticket, u32 state_in
     job.gm_state_in = state_in;
     job.w_end_state = after;
     *state_out = after;
-    struct Join { std::shared_ptr<DeviceWaveletJob> job; HostPipeline* pipe; u32 state_in; WaveletRoutes* routes; };
-    Join* j = new Join{jobp, e.pipeline, state_in, &e.routes};
+    struct Join { std::shared_ptr<DeviceWaveletJob> job; HostPipeline* pipe; u32 state_in; WaveletRoutes* routes; char letter; };
+    Join* j = new Join{jobp, e.pipeline, state_in, &e.routes, job.gm_letter};
     const hipError_t hrc = hipLaunchHostFunc(e.d2h_stream, [](void* p) {
       std::unique_ptr<Join> j(static_cast<Join*>(p));
       DeviceWaveletJob& job = *j->job;
@@ -294,7 +298,7 @@ static int wavelet_encode_queue_unguarded(BwtEngine& e, u64 ticket, u32 state_in
       // (the state handed on came from the device's state maps: a host half that ends elsewhere means
       // the stream after this block is wrong -- reported at _end, never passed over)
       const u32 handed_on = job.w_end_state;
-      (void)j->pipe->queue(j->job, j->state_in, 'B', &handed_on);
+      (void)j->pipe->queue(j->job, j->state_in, j->letter, &handed_on);
     }, j);
     if (hrc != hipSuccess) {
       // the copies of the w-elements and of the tail words are queued: nothing may hand the block's buffers on
@@ -325,7 +329,8 @@ static int wavelet_encode_queue_unguarded(BwtEngine& e, u64 ticket, u32 state_in
   if (job.w) {
     // modelled on the device: the copy has landed (above); the passes report themselves
     const u32 n_coded = job.coded_pos.empty() ? 0u : job.coded_pos.back();
-    const u32 rejects = device_model_rejects(job.h_tail, n_coded, job.h_tail[0] < 8 && job.gm_state_in == state_in && e.wavelet_model == 'B');
+    const u32 rejects = device_model_rejects(job.h_tail, n_coded, job.h_tail[0] < 8 && e.wavelet_model == job.gm_letter &&
+                                                                      (job.gm_letter != 'B' || job.gm_state_in == state_in));
     if (!rejects) {
       job.w_end_state = job.h_tail[0];
       WaveletRoutes::bump(e.routes.models_device);
@@ -417,7 +422,7 @@ int wavelet_encode_prepare(BwtEngine& e, const u8* d_bwt, u32 size, const u32* l
   e.half_job = jobp;
   *ticket = e.next_ticket++;
   e.jobs[*ticket] = jobp;
-  if (!e.deferred_queue && e.device_models && e.wavelet_model == 'B' && !e.wavelet_on_host) {
+  if (!e.deferred_queue && e.models_on_device(e.wavelet_model) && !e.wavelet_on_host) {
     // _prepare / _queue flow with the models on the device: the streams of THIS block are made now
     // (its plan is waited for: a few milliseconds of GPU idle, once per block and context), so that
     // _queue -- which callers serialise over all contexts of a stream -- only has the state-dependent

@@ -1,4 +1,4 @@
-// The adaptive models of the 'B' coder on the GPU: the lane functions of wavelet_gpu_models.hpp as
+// The adaptive models of the 'B' coder (and, under BWTC_HIP_LETTER_MODELS, of 'b' and 'u') on the GPU: the lane functions of wavelet_gpu_models.hpp as
 // kernels, one lane per chunk (element passes) or per slot-chunk (slot-space passes).  Input: the
 // block's packed streams as wavelet_tree.hip left them in HBM; output: one 16-bit word per coded
 // element (bit, probability of the coded bit), copied to the host for the range coders.
@@ -143,12 +143,12 @@ __global__ __launch_bounds__(kGmTPB) void k_gm_partition(const u32* __restrict__
 constexpr int kGmPartTPB = 128;
 constexpr u32 kGmPartWords = kGmPartTPB * gm::kChunk / 32 + 32;     // every slot's stretch may start and end inside a word
 
-template <u32 TYPE>
+template <u32 TYPE, u32 KIND = gm::kKindB>
 __device__ __forceinline__ void gm_partition_walk(const u32* __restrict__ packed, u32 begin, u32 end, u32 state,
                                                   u32* pos, u32* region) {
   gm::Machines m = {state & 7u, (state >> 3) & 3u, (state >> 5) & 3u};
   gm::forElements(packed, begin, end, [&](u32, u32 v) {
-    const u32 slot = gm::stepMachinesT<TYPE>(v, m);
+    const u32 slot = gm::stepMachinesT<TYPE, KIND>(v, m);
     const u32 p = __hip_atomic_fetch_add(&pos[slot * kGmPartTPB], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (v & 1u) (void)__hip_atomic_fetch_or(&region[p >> 5], 1u << (p & 31u), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
   });
@@ -257,6 +257,186 @@ __global__ __launch_bounds__(kGmTPB) void k_gm_emit(const u32* __restrict__ pack
   if (e) atomicOr(err, e);
 }
 
+// ---- the letters 'b' and 'u' (BWTC_HIP_LETTER_MODELS) -------------------------------------------------------------
+// The passes that look at the main model, once more over its kind (gm::kKindb / kKindu): the text of the kernels above
+// with the lane functions' letter instantiations.  The 'B' kernels above are left as they were, name and code (one body
+// inlined into both families was tried: it changed the code of k_gm_state_tile, k_gm_partition_lines and k_gm_bracket);
+// the passes that do not look at the main model (k_gm_streams, the scan, k_gm_chain_*) serve every kind.
+template <u32 KIND>
+__global__ __launch_bounds__(kGmTPB) void k_gml_map(const u32* __restrict__ packed, const gm::Chunk* __restrict__ chunks,
+                                                    const gm::Task* __restrict__ tasks, const u32* __restrict__ order, u32 nc,
+                                                    u64* __restrict__ cmap) {
+  const u32 gid = blockIdx.x * kGmTPB + threadIdx.x;
+  if (gid >= nc) return;
+  const u32 c = order[gid];                          // lanes in type order: a wave walks one kind of loop
+  const gm::Chunk ch = chunks[c];
+  cmap[c] = gm::laneMapK<KIND>(packed, ch.begin, ch.end, tasks[ch.task_first & 0x7FFFFFFFu].type);
+}
+
+template <u32 KIND>
+__global__ __launch_bounds__(kGmStateTPB) void k_gml_state_tile(const gm::Chunk* __restrict__ chunks, const u64* __restrict__ cmap,
+                                                                u32 nc, u64* __restrict__ excl, u64* __restrict__ tagg) {
+  __shared__ u64 s_agg[kGmStateTPB];
+  const u32 tid = threadIdx.x;
+  const u32 c0 = blockIdx.x * (kGmStateTPB * kGmStateE) + tid * kGmStateE;
+  u64 agg = gm::kMapIdentity;
+#pragma unroll
+  for (int i = 0; i < kGmStateE; ++i) {
+    if (c0 + i < nc) {
+      if (chunks[c0 + i].task_first >> 31) agg = gm::mapTaskStart<KIND>(agg);
+      agg = gm::mapCompose(agg, cmap[c0 + i]);
+    }
+  }
+  s_agg[tid] = agg;
+  __syncthreads();
+  for (u32 off = 1; off < kGmStateTPB; off <<= 1) {
+    const u64 v = tid >= off ? gm::mapCompose(s_agg[tid - off], agg) : agg;
+    __syncthreads();
+    s_agg[tid] = agg = v;
+    __syncthreads();
+  }
+  excl[blockIdx.x * kGmStateTPB + tid] = tid ? s_agg[tid - 1] : gm::kMapIdentity;
+  if (tid == kGmStateTPB - 1) tagg[blockIdx.x] = agg;
+}
+
+template <u32 KIND>
+__global__ __launch_bounds__(kGmStateTPB) void k_gml_state_apply(const gm::Chunk* __restrict__ chunks, const u64* __restrict__ cmap,
+                                                                 u32 nc, const u64* __restrict__ excl, const u32* __restrict__ tstate,
+                                                                 u32* __restrict__ cstate) {
+  const u32 tid = threadIdx.x;
+  const u32 c0 = blockIdx.x * (kGmStateTPB * kGmStateE) + tid * kGmStateE;
+  if (c0 >= nc) return;
+  u32 st = gm::mapApply(excl[blockIdx.x * kGmStateTPB + tid], tstate[blockIdx.x]);
+#pragma unroll
+  for (int i = 0; i < kGmStateE; ++i) {
+    if (c0 + i < nc) {
+      if (chunks[c0 + i].task_first >> 31) st = gm::stateTaskStart<KIND>(st);
+      cstate[c0 + i] = st;
+      st = gm::mapApply(cmap[c0 + i], st);
+    }
+  }
+}
+
+template <u32 KIND>
+__global__ __launch_bounds__(kGmTPB) void k_gml_count(const u32* __restrict__ packed, const gm::Chunk* __restrict__ chunks,
+                                                      const gm::Task* __restrict__ tasks, const u32* __restrict__ cstate,
+                                                      const u32* __restrict__ order, u32 nc, u32* __restrict__ cnt) {
+  __shared__ u32 tab[gm::kSlotStride][kGmTPB];
+  const u32 gid = blockIdx.x * kGmTPB + threadIdx.x;
+  if (gid >= nc) return;
+  const u32 c = order[gid];
+  const gm::Chunk ch = chunks[c];
+  gm::laneCount<KIND>(packed, ch.begin, ch.end, tasks[ch.task_first & 0x7FFFFFFFu].type, cstate[c], &tab[0][threadIdx.x], kGmTPB);
+  for (u32 k = 0; k < gm::kSlots; ++k) cnt[(u64)k * nc + c] = tab[k][threadIdx.x];
+}
+
+template <u32 KIND>
+__global__ __launch_bounds__(kGmTPB) void k_gml_partition(const u32* __restrict__ packed, const gm::Chunk* __restrict__ chunks,
+                                                          const gm::Task* __restrict__ tasks, const u32* __restrict__ cstate,
+                                                          const u32* __restrict__ base, const u32* __restrict__ order, u32 nc,
+                                                          u32* __restrict__ sbits) {
+  __shared__ u32 pos[gm::kSlotStride][kGmTPB];
+  __shared__ u32 acc[gm::kSlotStride][kGmTPB];
+  const u32 gid = blockIdx.x * kGmTPB + threadIdx.x;
+  if (gid >= nc) return;
+  const u32 c = order[gid];
+  const gm::Chunk ch = chunks[c];
+  for (u32 k = 0; k < gm::kSlots; ++k) { pos[k][threadIdx.x] = base[(u64)k * nc + c]; acc[k][threadIdx.x] = 0; }
+  gm::lanePartition<KIND>(packed, ch.begin, ch.end, tasks[ch.task_first & 0x7FFFFFFFu].type, cstate[c], &pos[0][threadIdx.x],
+                        &acc[0][threadIdx.x], kGmTPB, sbits);
+}
+
+template <u32 KIND>
+__global__ __launch_bounds__(kGmPartTPB) void k_gml_partition_lines(const u32* __restrict__ packed, const gm::Chunk* __restrict__ chunks,
+                                                                    const gm::Task* __restrict__ tasks, const u32* __restrict__ cstate,
+                                                                    const u32* __restrict__ base, u32 nc, u32* __restrict__ sbits) {
+  __shared__ u32 region[kGmPartWords];
+  __shared__ u32 pos[gm::kSlots][kGmPartTPB];
+  __shared__ u32 s_g0[gm::kSlots], s_nw[gm::kSlots], s_off[gm::kSlots + 1];
+  const u32 tid = threadIdx.x;
+  const u32 c0 = blockIdx.x * kGmPartTPB, c1 = min(c0 + (u32)kGmPartTPB, nc);
+  const u32 c = c0 + tid;
+  for (u32 i = tid; i < kGmPartWords; i += kGmPartTPB) region[i] = 0;
+  if (tid < gm::kSlots) {
+    const u32 g0 = base[(u64)tid * nc + c0], g1 = base[(u64)tid * nc + c1];     // base[k nc + nc] = base[(k + 1) nc]: the array is one prefix
+    s_g0[tid] = g0 >> 5;
+    s_nw[tid] = g1 > g0 ? ((g1 - 1u) >> 5) - (g0 >> 5) + 1u : 0u;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    u32 at = 0;
+    for (u32 k = 0; k < gm::kSlots; ++k) { s_off[k] = at; at += s_nw[k]; }
+    s_off[gm::kSlots] = at;
+  }
+  __syncthreads();
+  if (s_off[gm::kSlots] > kGmPartWords) return;          // cannot happen (see kGmPartWords); the block then fails its element count
+  if (c < nc) {
+    const gm::Chunk ch = chunks[c];
+    for (u32 k = 0; k < gm::kSlots; ++k) pos[k][tid] = (s_off[k] << 5) + (base[(u64)k * nc + c] - (s_g0[k] << 5));
+    const u32 type = tasks[ch.task_first & 0x7FFFFFFFu].type;
+    const u32 st = cstate[c];
+    using namespace gm;
+    BWTC_GM_BY_TYPE(type, (gm_partition_walk<TYPE, KIND>(packed, ch.begin, ch.end, st, &pos[0][tid], region)));
+  }
+  __syncthreads();
+  for (u32 k = 0; k < gm::kSlots; ++k) {
+    const u32 nw = s_nw[k], off = s_off[k], g0 = s_g0[k];
+    for (u32 w = tid; w < nw; w += kGmPartTPB) {
+      const u32 v = region[off + w];
+      if (w == 0 || w + 1u == nw) { if (v) atomicOr(&sbits[g0 + w], v); }
+      else sbits[g0 + w] = v;
+    }
+  }
+}
+
+template <u32 KIND>
+__global__ __launch_bounds__(kGmTPB) void k_gml_emit(const u32* __restrict__ packed, const gm::Chunk* __restrict__ chunks,
+                                                     const gm::Task* __restrict__ tasks, const u32* __restrict__ cstate,
+                                                     const u32* __restrict__ base, const u32* __restrict__ sb,
+                                                     const u32* __restrict__ sbits, const gm::SlotMap* __restrict__ snaps,
+                                                     const gm::SlotMap* __restrict__ smap, const unsigned short* __restrict__ sstart,
+                                                     const u32* __restrict__ order, u32 nc, u32 nt, unsigned short* __restrict__ out,
+                                                     u32* __restrict__ err) {
+  __shared__ u32 q[gm::kSlotStride][kGmTPB];
+  __shared__ u32 stage[32][kGmTPB];                  // a lane's line of output (64 elements) on its way out
+  const u32 gid = blockIdx.x * kGmTPB + threadIdx.x;
+  if (gid >= nc) return;
+  const u32 c = order[gid];
+  const gm::Chunk ch = chunks[c];
+  const u32 t = ch.task_first & 0x7FFFFFFFu;
+  u32 e = 0;
+  gm::laneEmit<KIND>(packed, ch.begin, ch.end, tasks[t].type, cstate[c], t, c, nc, nt, base, sb, sbits, snaps, smap, sstart,
+               &q[0][threadIdx.x], kGmTPB, out, &e, &stage[0][threadIdx.x]);
+  if (e) atomicOr(err, e);
+}
+// The letters' walk over the tiles: every task starts all three machines afresh, so the block's first chunk starts a
+// task from `start` (gm::mainStart) whatever state the stream carries, and what is handed on is what StreamCoder hands
+// on after such a block: `start` again.
+__global__ void k_gml_state_top(const u64* __restrict__ tagg, u32 ntiles, u32 start, u32* __restrict__ tstate,
+                                u32* __restrict__ state_out) {
+  if (threadIdx.x || blockIdx.x) return;
+  u32 st = gm::packState(start, 2, 1);
+  for (u32 t = 0; t < ntiles; ++t) { tstate[t] = st; st = gm::mapApply(tagg[t], st); }
+  *state_out = start;
+}
+// (the two letters' main slots take the same form in slot space: one instantiation serves both)
+__global__ __launch_bounds__(kGmTPB) void k_gml_bracket(const u32* __restrict__ sbits, const u32* __restrict__ sb, u32 ns, u32 nt,
+                                                        u32 total, u32 nsc, gm::SlotMap* __restrict__ smap,
+                                                        gm::SlotMap* __restrict__ snaps, u32* __restrict__ err) {
+  const u32 j = blockIdx.x * kGmTPB + threadIdx.x;
+  if (j >= nsc) return;
+  u32 e = 0;
+  smap[j] = gm::laneBracket<gm::kKindb>(sbits, sb, ns, nt, total, j, snaps, &e);
+  if (e) atomicOr(err, e);
+}
+
+// a launch of a letter's instantiation: KIND is the constant inside CALL
+#define BWTC_GM_BY_LETTER(kind, CALL)                                     \
+  do {                                                                    \
+    if ((kind) == gm::kKindb) { constexpr u32 KIND = gm::kKindb; CALL; }  \
+    else { constexpr u32 KIND = gm::kKindu; CALL; }                       \
+  } while (0)
+
 static inline u64 gm_align(u64 v) { return (v + 255) / 256 * 256; }
 
 int BwtEngine::reserve_models(u64 device_bytes, u64 host_bytes, u64 w_bytes) {
@@ -291,19 +471,20 @@ int BwtEngine::reserve_models(u64 device_bytes, u64 host_bytes, u64 w_bytes) {
 // early_state != null -> the state after the block is read back right after the state scan (a wait
 // of some tens of microseconds) and returned, before the long passes are queued.
 int wavelet_models_prepare(BwtEngine& e, const u32* d_packed, u32 n_coded, const bwtc::wavelet::StreamPlan& plan,
-                           const std::vector<u32>& coded_pos, GmPass* g, bool read_ends, hipStream_t side) {
+                           const std::vector<u32>& coded_pos, GmPass* g, bool read_ends, hipStream_t side, u32 kind) {
   std::vector<gm::Task> tasks;
   std::vector<gm::Chunk> chunks;
   gm::buildTasks(plan, coded_pos.data(), &tasks, &chunks);
-  return wavelet_models_prepare_tasks(e, d_packed, n_coded, tasks, chunks, g, read_ends, side);
+  return wavelet_models_prepare_tasks(e, d_packed, n_coded, tasks, chunks, g, read_ends, side, kind);
 }
 
 // The same from "tasks and chunks are known" on (the test hook bwtc_hip_test_models enters here with a given task list).
 int wavelet_models_prepare_tasks(BwtEngine& e, const u32* d_packed, u32 n_coded, const std::vector<gm::Task>& tasks,
-                                 const std::vector<gm::Chunk>& chunks, GmPass* g, bool read_ends, hipStream_t side) {
+                                 const std::vector<gm::Chunk>& chunks, GmPass* g, bool read_ends, hipStream_t side, u32 kind) {
   BwtEngine::ScanScope scan_scope(e);
   hipStream_t st = side ? side : e.stream;             // side: the passes run beside the next block's transform (wavelet_models_device)
   g->side = side;
+  g->kind = kind;                                      // the block keeps it: the context's letter may change before _run
   const u32 nt = (u32)tasks.size(), nc = (u32)chunks.size();
   if (nt == 0 || nc == 0 || n_coded == 0) return -1;
   g->d_packed = d_packed; g->n_coded = n_coded; g->nt = nt; g->nc = nc;
@@ -364,6 +545,18 @@ int wavelet_models_prepare_tasks(BwtEngine& e, const u32* d_packed, u32 n_coded,
   BWTC_HIP_TRY(hipMemsetAsync(g->d_tail, 0, 16, st));
   BWTC_HIP_TRY(hipMemsetAsync(g->d_sbits, 0, ((u64)n_coded / 32 + 16) * 4, st));
   BWTC_HIP_TRY(hipMemsetAsync(static_cast<u32*>(g->d_base) + g->n_base - 1, 0, 4, st));
+  if (kind != gm::kKindB) {
+    BWTC_GM_BY_LETTER(kind, hipLaunchKernelGGL(k_gml_map<KIND>, dim3(ceil_div(nc, kGmTPB)), dim3(kGmTPB), 0, st, d_packed,
+                                               (const gm::Chunk*)g->d_chunks, (const gm::Task*)g->d_tasks, (const u32*)g->d_order, nc,
+                                               (u64*)g->d_cmap));
+    BWTC_GM_BY_LETTER(kind, hipLaunchKernelGGL(k_gml_state_tile<KIND>, dim3(g->ntiles), dim3(kGmStateTPB), 0, st,
+                                               (const gm::Chunk*)g->d_chunks, (const u64*)g->d_cmap, nc, (u64*)g->d_excl, (u64*)g->d_tagg));
+    // nothing is carried through a letter's block: the state after it by the state before it is known without the device
+    for (int i = 0; i < 8; ++i) g->ends[i] = (u32)i;
+    g->ends_ready = true;
+    g->ready = true;
+    return 0;
+  }
   hipLaunchKernelGGL(k_gm_map, dim3(ceil_div(nc, kGmTPB)), dim3(kGmTPB), 0, st, d_packed, (const gm::Chunk*)g->d_chunks,
                      (const gm::Task*)g->d_tasks, (const u32*)g->d_order, nc, (u64*)g->d_cmap);
   hipLaunchKernelGGL(k_gm_state_tile, dim3(g->ntiles), dim3(kGmStateTPB), 0, st, (const gm::Chunk*)g->d_chunks, (const u64*)g->d_cmap,
@@ -400,27 +593,51 @@ int wavelet_models_run(BwtEngine& e, const GmPass& g, u32 state_in, uint16_t* h_
   u32* d_tail = static_cast<u32*>(g.d_tail);                        // [0] state after the block, [1] error flags, [2] elements counted, [3] scan error
   unsigned short* d_w = static_cast<unsigned short*>(e.d_gm_w);
   const dim3 gc(ceil_div(nc, kGmTPB)), gs(ceil_div(nsc, kGmTPB)), tpb(kGmTPB);
-  hipLaunchKernelGGL(k_gm_state_top, dim3(1), dim3(64), 0, st, (const u64*)g.d_tagg, g.ntiles, state_in, (u32*)g.d_tstate, d_tail);
-  if (early_state) {
-    if (g.ends_ready) {
-      *early_state = g.ends[state_in & 7u];
-    } else {
-      BWTC_HIP_TRY(hipMemcpyAsync(e.h_small + kGmSmallEnds, d_tail, 4, hipMemcpyDeviceToHost, st));
-      BWTC_HIP_TRY(e.wait());
-      *early_state = e.h_small[kGmSmallEnds];
+  const u32 kind = g.kind;
+  const bool letter = kind != gm::kKindB;
+  if (letter) {
+    // (state_in is not looked at: every task of a letter's block starts its machines afresh)
+    hipLaunchKernelGGL(k_gml_state_top, dim3(1), dim3(64), 0, st, (const u64*)g.d_tagg, g.ntiles, gm::mainStart(kind), (u32*)g.d_tstate, d_tail);
+    if (early_state) *early_state = gm::mainStart(kind);
+  } else {
+    hipLaunchKernelGGL(k_gm_state_top, dim3(1), dim3(64), 0, st, (const u64*)g.d_tagg, g.ntiles, state_in, (u32*)g.d_tstate, d_tail);
+    if (early_state) {
+      if (g.ends_ready) {
+        *early_state = g.ends[state_in & 7u];
+      } else {
+        BWTC_HIP_TRY(hipMemcpyAsync(e.h_small + kGmSmallEnds, d_tail, 4, hipMemcpyDeviceToHost, st));
+        BWTC_HIP_TRY(e.wait());
+        *early_state = e.h_small[kGmSmallEnds];
+      }
     }
   }
-  hipLaunchKernelGGL(k_gm_state_apply, dim3(g.ntiles), dim3(kGmStateTPB), 0, st, d_chunks, (const u64*)g.d_cmap, nc, (const u64*)g.d_excl,
-                     (const u32*)g.d_tstate, d_cstate);
-  hipLaunchKernelGGL(k_gm_count, gc, tpb, 0, st, g.d_packed, d_chunks, d_tasks, d_cstate, d_order, nc, d_base);
+  if (letter) {
+    BWTC_GM_BY_LETTER(kind, hipLaunchKernelGGL(k_gml_state_apply<KIND>, dim3(g.ntiles), dim3(kGmStateTPB), 0, st, d_chunks, (const u64*)g.d_cmap,
+                                               nc, (const u64*)g.d_excl, (const u32*)g.d_tstate, d_cstate));
+    BWTC_GM_BY_LETTER(kind, hipLaunchKernelGGL(k_gml_count<KIND>, gc, tpb, 0, st, g.d_packed, d_chunks, d_tasks, d_cstate, d_order, nc, d_base));
+  } else {
+    hipLaunchKernelGGL(k_gm_state_apply, dim3(g.ntiles), dim3(kGmStateTPB), 0, st, d_chunks, (const u64*)g.d_cmap, nc, (const u64*)g.d_excl,
+                       (const u32*)g.d_tstate, d_cstate);
+    hipLaunchKernelGGL(k_gm_count, gc, tpb, 0, st, g.d_packed, d_chunks, d_tasks, d_cstate, d_order, nc, d_base);
+  }
   exclusive_scan_u32(d_base, g.n_base, static_cast<u32*>(g.d_partial), st);
   hipLaunchKernelGGL(k_gm_streams, dim3(ceil_div((u64)ns + 1, kGmTPB)), tpb, 0, st, d_base, d_tasks, nc, nt, d_sb);
-  if (e.gm_partition_lines)
-    hipLaunchKernelGGL(k_gm_partition_lines, dim3(ceil_div(nc, kGmPartTPB)), dim3(kGmPartTPB), 0, st, g.d_packed, d_chunks, d_tasks, d_cstate,
-                       d_base, nc, d_sbits);
-  else
-    hipLaunchKernelGGL(k_gm_partition, gc, tpb, 0, st, g.d_packed, d_chunks, d_tasks, d_cstate, d_base, d_order, nc, d_sbits);
-  hipLaunchKernelGGL(k_gm_bracket, gs, tpb, 0, st, d_sbits, d_sb, ns, nt, n_coded, nsc, d_smap, d_snaps, d_tail + 1);
+  if (letter) {
+    if (e.gm_partition_lines)
+      BWTC_GM_BY_LETTER(kind, hipLaunchKernelGGL(k_gml_partition_lines<KIND>, dim3(ceil_div(nc, kGmPartTPB)), dim3(kGmPartTPB), 0, st, g.d_packed,
+                                                 d_chunks, d_tasks, d_cstate, d_base, nc, d_sbits));
+    else
+      BWTC_GM_BY_LETTER(kind, hipLaunchKernelGGL(k_gml_partition<KIND>, gc, tpb, 0, st, g.d_packed, d_chunks, d_tasks, d_cstate, d_base, d_order,
+                                                 nc, d_sbits));
+    hipLaunchKernelGGL(k_gml_bracket, gs, tpb, 0, st, d_sbits, d_sb, ns, nt, n_coded, nsc, d_smap, d_snaps, d_tail + 1);
+  } else {
+    if (e.gm_partition_lines)
+      hipLaunchKernelGGL(k_gm_partition_lines, dim3(ceil_div(nc, kGmPartTPB)), dim3(kGmPartTPB), 0, st, g.d_packed, d_chunks, d_tasks, d_cstate,
+                         d_base, nc, d_sbits);
+    else
+      hipLaunchKernelGGL(k_gm_partition, gc, tpb, 0, st, g.d_packed, d_chunks, d_tasks, d_cstate, d_base, d_order, nc, d_sbits);
+    hipLaunchKernelGGL(k_gm_bracket, gs, tpb, 0, st, d_sbits, d_sb, ns, nt, n_coded, nsc, d_smap, d_snaps, d_tail + 1);
+  }
   hipLaunchKernelGGL(k_gm_chain_group, dim3(g.ng), dim3(64), 0, st, d_smap, nsc, g.gsize, (unsigned short*)g.d_gmap, (unsigned short*)g.d_gL);
   hipLaunchKernelGGL(k_gm_chain_top, dim3(1), dim3(1024), 0, st, (const unsigned short*)g.d_gmap, (const unsigned short*)g.d_gL, g.ng,
                      (unsigned short*)g.d_tg, d_tail + 1);
@@ -429,8 +646,12 @@ int wavelet_models_run(BwtEngine& e, const GmPass& g, u32 state_in, uint16_t* h_
   // d_gm_w is one buffer for every block: the copy of the previous block's w-elements (d2h stream, ev_codes) must have
   // read it before this block's emit pass writes it (so far the callers' codes_wait saw to that)
   if (e.codes_in_flight && e.ev_codes) BWTC_HIP_TRY(hipStreamWaitEvent(st, e.ev_codes, 0));
-  hipLaunchKernelGGL(k_gm_emit, gc, tpb, 0, st, g.d_packed, d_chunks, d_tasks, d_cstate, d_base, d_sb, d_sbits, d_snaps, d_smap,
-                     d_sstart, d_order, nc, nt, d_w, d_tail + 1);
+  if (letter)
+    BWTC_GM_BY_LETTER(kind, hipLaunchKernelGGL(k_gml_emit<KIND>, gc, tpb, 0, st, g.d_packed, d_chunks, d_tasks, d_cstate, d_base, d_sb, d_sbits,
+                                               d_snaps, d_smap, d_sstart, d_order, nc, nt, d_w, d_tail + 1));
+  else
+    hipLaunchKernelGGL(k_gm_emit, gc, tpb, 0, st, g.d_packed, d_chunks, d_tasks, d_cstate, d_base, d_sb, d_sbits, d_snaps, d_smap,
+                       d_sstart, d_order, nc, nt, d_w, d_tail + 1);
   // total of the scan = every element counted once (else the tables do not describe the streams)
   BWTC_HIP_TRY(hipMemcpyAsync(d_tail + 2, d_base + g.n_base - 1, 4, hipMemcpyDeviceToDevice, st));
   // a timed-out scan; the chain serves only the context's own stream (scan.hpp): the side stream's scans take the
@@ -444,13 +665,13 @@ int wavelet_models_run(BwtEngine& e, const GmPass& g, u32 state_in, uint16_t* h_
   BWTC_HIP_TRY(hipEventRecord(e.ev_codes, e.d2h_stream));
   e.codes_in_flight = true;
   if (std::getenv("BWTC_HIP_DEBUG"))
-    std::fprintf(stderr, "models on the device: %u coded elements, %u tasks, %u chunks, %u slot-chunks, state in %u\n",
-                 n_coded, nt, nc, nsc, state_in);
+    std::fprintf(stderr, "models on the device: %u coded elements, %u tasks, %u chunks, %u slot-chunks, state in %u, main model %c\n",
+                 n_coded, nt, nc, nsc, state_in, kind == gm::kKindb ? 'b' : kind == gm::kKindu ? 'u' : 'B');
   return 0;
 }
 
 int wavelet_models_device(BwtEngine& e, const u32* d_packed, u32 n_coded, const bwtc::wavelet::StreamPlan& plan,
-                          const std::vector<u32>& coded_pos, u32 state_in, uint16_t* h_w, u32* h_tail) {
+                          const std::vector<u32>& coded_pos, u32 state_in, uint16_t* h_w, u32* h_tail, u32 kind) {
   // One context's stream of blocks (the _begin flow): nothing here waits for the device, so the passes -- 2.9 ms of
   // kernels per 256 MiB text block that share nothing with the suffix sorter but HBM -- go to a stream of their own and
   // run beside the NEXT block's transform.  Ordered by events: they start when this block's packed streams are there
@@ -468,7 +689,7 @@ int wavelet_models_device(BwtEngine& e, const u32* d_packed, u32 n_coded, const 
     side = e.gm_stream;
   }
   GmPass g;
-  int rc = wavelet_models_prepare(e, d_packed, n_coded, plan, coded_pos, &g, false, side);
+  int rc = wavelet_models_prepare(e, d_packed, n_coded, plan, coded_pos, &g, false, side, kind);
   if (rc == 0) rc = wavelet_models_run(e, g, state_in, h_w, h_tail, nullptr);
   if (side) {
     // (also after an error: whatever was queued there must be through before the workspace changes hands)

@@ -30,6 +30,8 @@
 // which is all the range coder needs (wavelet_rc.hpp, runChainW).  Nothing is approximated: the
 // bytes are those of the sequential encoder, and an input the scheme cannot bracket raises an
 // error flag instead of a wrong byte.
+// The coders 'b' and 'u' differ in the main model alone; the lane functions take its kind as a template argument
+// ("the main-model kinds" below), 'B' being the default and the text above.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -78,6 +80,24 @@ BWTC_GM_HD u32 next8(u32 s, u32 bit) { return bit ? (s >= 4 ? (s < 7 ? s + 1 : 7
 BWTC_GM_HD u32 next4(u32 s, u32 bit) { return (bit << 1) | (s >> 1); }
 BWTC_GM_HD u32 next3(u32 s, u32 bit) { return bit ? (s < 2 ? s + 1 : 2u) : (s ? s - 1 : 0u); }
 
+// ---- the main-model kinds (the coder's letter) ------------------------------------------------------
+// 'B' is everything above.  'b' (FSM<6> of EvenIntervalPredictor<4>, FSM.hpp:41-52, BitPredictors.hpp:95-124) and 'u'
+// (one EvenIntervalPredictor<4>) differ in the main model alone: a machine of six states, or none (slot 0 always), that a
+// task start resets with the predictors (to 3, to 0), and predictors that are saturating counters over 1024, 2048, 3072
+// starting at 2048, the value itself the probability of a one.  Nothing is carried from task to task.
+// In slot space a main slot's value is the counter's INDEX 0, 1, 2 (value / 1024 - 1): the map "index at a slot-chunk's
+// start -> index at its end" is monotone with neighbouring images at most one apart, which is exactly what SlotMap
+// carries (base 0, image of candidate 0, two mask bits), and exactly: no warm-up, no width to check.  The chain walk
+// below serves both forms unchanged.  The 15-slot layout stays; slots 6, 7 ('b') and 1 ... 7 ('u') are empty streams.
+constexpr u32 kKindB = 0, kKindb = 1, kKindu = 2;
+BWTC_GM_HD u32 kindOfLetter(char letter) { return letter == 'b' ? kKindb : letter == 'u' ? kKindu : kKindB; }
+BWTC_GM_HD u32 mainStart(u32 kind) { return kind == kKindb ? 3u : 0u; }                 // the main machine after a task start
+BWTC_GM_HD u32 next6(u32 s, u32 bit) { return bit ? (s >= 3 ? (s < 5 ? s + 1 : 5u) : 3u) : (s < 3 ? (s ? s - 1 : 0u) : 2u); }
+template <u32 KIND>
+BWTC_GM_HD u32 nextMain(u32 s, u32 bit) { return KIND == kKindB ? next8(s, bit) : KIND == kKindb ? next6(s, bit) : 0u; }
+BWTC_GM_HD u32 counterMoved(u32 x, u32 bit) { return bit ? (x < 2u ? x + 1u : 2u) : (x ? x - 1u : 0u); }   // on the index
+BWTC_GM_HD u32 evenMoved(u32 p, u32 bit) { return bit ? (p < 3072u ? p + 1024u : p) : (p > 1024u ? p - 1024u : p); }
+
 // packed states of a chunk's start: mc | gc << 3 | ic << 5
 BWTC_GM_HD u32 packState(u32 mc, u32 gc, u32 ic) { return mc | (gc << 3) | (ic << 5); }
 
@@ -88,6 +108,14 @@ BWTC_GM_HD u64 mapConstGapsInts(u64 m, u32 gc, u32 ic) {           // the machin
   const u64 g = gc * 0x55u, i = ic * 0x15u;
   return (m & 0xFFFFFFull) | (g << 24) | (i << 32);
 }
+// what a task start does to a chunk's map and to the packed state: 'B' resets gaps and integers, the letters all three
+template <u32 KIND>
+BWTC_GM_HD u64 mapTaskStart(u64 m) {
+  if (KIND == kKindB) return mapConstGapsInts(m, 2, 1);
+  return (u64)(mainStart(KIND) * 0x249249u) | ((u64)(2u * 0x55u) << 24) | ((u64)(1u * 0x15u) << 32);
+}
+template <u32 KIND>
+BWTC_GM_HD u32 stateTaskStart(u32 st) { return ((KIND == kKindB ? st & 7u : mainStart(KIND))) | (2u << 3) | (1u << 5); }
 // g after f
 BWTC_GM_HD u64 mapCompose(u64 f, u64 g) {
   u64 h = 0;
@@ -187,8 +215,21 @@ BWTC_GM_HD u32 stepMachines(u32 type, u32 v, Machines& m) {
   return slot;
 }
 
-template <u32 TYPE>
-BWTC_GM_HD u32 stepMachinesT(u32 v, Machines& m) { return stepMachines(TYPE, v, m); }   // TYPE is a constant: one branch survives
+template <u32 TYPE, u32 KIND = kKindB>
+BWTC_GM_HD u32 stepMachinesT(u32 v, Machines& m) {
+  if (KIND == kKindB) return stepMachines(TYPE, v, m);                                  // TYPE is a constant: one branch survives
+  const u32 bit = v & 1u, flag = v >> 1;
+  u32 slot;
+  if (TYPE == kTRoot) { slot = m.mc; m.mc = nextMain<KIND>(m.mc, bit); }
+  else if (TYPE == kTGaps) { slot = 8u + m.gc; m.gc = next4(m.gc, bit); }
+  else if (TYPE == kTInts) { slot = 12u + m.ic; m.ic = next3(m.ic, bit); }
+  else {
+    slot = flag ? 8u + m.gc : m.mc;
+    m.mc = nextMain<KIND>(m.mc, bit);            // the 'b' machine too moves under a gap, its predictor is left alone
+    if (flag) m.gc = next4(m.gc, bit);
+  }
+  return slot;
+}
 
 // The walks are compiled once per task type (the inner loops then carry no type tests); a wave's
 // lanes nearly always share their type (a task's chunks are consecutive).
@@ -298,6 +339,33 @@ BWTC_GM_HD u64 laneMap(const u32* packed, u32 begin, u32 end, u32 type) {
   return m;
 }
 
+// The map of a letter's chunk: gaps and integers as above; the main field is the identity for 'u' and for 'b' six
+// images.  Three advancing elements fix the six-state machine whatever it was -- a change of bit value among them does
+// (to 3 or 2, then the run behind it), and so do three equal bits -- so the chunk's last three decide; below three
+// elements the six states are walked.
+template <u32 KIND>
+BWTC_GM_HD u64 laneMapK(const u32* packed, u32 begin, u32 end, u32 type) {
+  const u64 m = laneMap(packed, begin, end, type);
+  if (KIND == kKindB) return m;
+  u64 mainf = kMapIdentity & 0xFFFFFFull;
+  if (KIND == kKindb && (type == kTRoot || type == kTInner)) {
+    if (end - begin >= 3u) {
+      const u32 b1 = codeAt(packed, end - 1u) & 1u, b2 = codeAt(packed, end - 2u) & 1u, b3 = codeAt(packed, end - 3u) & 1u;
+      const u32 r = b2 != b1 ? 1u : b3 != b1 ? 2u : 3u;            // equal bits at the end, of the last three
+      const u32 st = r == 3u ? (b1 ? 5u : 0u) : (b1 ? 2u + r : 3u - r);
+      mainf = (u64)(st * 0x249249u);
+    } else {
+      mainf &= ~0x3FFFFull;
+      for (u32 s0 = 0; s0 < 6; ++s0) {
+        u32 x = s0;
+        for (u32 i = begin; i < end; ++i) x = next6(x, codeAt(packed, i) & 1u);
+        mainf |= (u64)x << (3 * s0);
+      }
+    }
+  }
+  return (m & ~0xFFFFFFull) | mainf;
+}
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #define BWTC_GM_LOCAL_ADD(ptr, val) __hip_atomic_fetch_add((ptr), (val), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)   /* ds_add_u32, no round trip */
 #else
@@ -305,17 +373,18 @@ BWTC_GM_HD u64 laneMap(const u32* packed, u32 begin, u32 end, u32 type) {
 #endif
 // ---- pass 2: updates per slot ------------------------------------------------------------------------
 // tab: kSlotStride rows, this lane's column (row k at tab[k * stride]); zeroed here
-template <u32 TYPE>
+template <u32 TYPE, u32 KIND = kKindB>
 BWTC_GM_HD void laneCountT(const u32* packed, u32 begin, u32 end, u32 state, u32* tab, u32 stride) {
   Machines m = {state & 7u, (state >> 3) & 3u, (state >> 5) & 3u};
   forElements(packed, begin, end, [&](u32, u32 v) {
-    const u32 slot = stepMachinesT<TYPE>(v, m);
+    const u32 slot = stepMachinesT<TYPE, KIND>(v, m);
     BWTC_GM_LOCAL_ADD(&tab[slot * stride], 1u);
   });
 }
+template <u32 KIND = kKindB>
 BWTC_GM_HD void laneCount(const u32* packed, u32 begin, u32 end, u32 type, u32 state, u32* tab, u32 stride) {
   for (u32 k = 0; k < kSlots; ++k) tab[k * stride] = 0;
-  BWTC_GM_BY_TYPE(type, laneCountT<TYPE>(packed, begin, end, state, tab, stride));
+  BWTC_GM_BY_TYPE(type, (laneCountT<TYPE, KIND>(packed, begin, end, state, tab, stride)));
 }
 
 // ---- pass 3: the bits, gathered by slot --------------------------------------------------------------
@@ -329,12 +398,12 @@ BWTC_GM_HD void laneCount(const u32* packed, u32 begin, u32 end, u32 type, u32 s
 // `shared`: bit k set = the word slot k is filling also holds bits of the chunk before (it did not
 // start on a word border): that one is OR-ed in; the words after it are this chunk's alone and are
 // stored (an atomic costs a 64-byte round trip to memory, and there would be one per 32 elements).
-template <u32 TYPE>
+template <u32 TYPE, u32 KIND = kKindB>
 BWTC_GM_HD void lanePartitionT(const u32* packed, u32 begin, u32 end, u32 state, u32* pos, u32* acc, u32 stride, u32* sbits,
                                u32& shared) {
   Machines m = {state & 7u, (state >> 3) & 3u, (state >> 5) & 3u};
   forElements(packed, begin, end, [&](u32, u32 v) {
-    const u32 slot = stepMachinesT<TYPE>(v, m);
+    const u32 slot = stepMachinesT<TYPE, KIND>(v, m);
     const u32 p = pos[slot * stride];
     u32 a = acc[slot * stride] | ((v & 1u) << (p & 31u));
     if ((p & 31u) == 31u) {
@@ -346,11 +415,12 @@ BWTC_GM_HD void lanePartitionT(const u32* packed, u32 begin, u32 end, u32 state,
     pos[slot * stride] = p + 1;
   });
 }
+template <u32 KIND = kKindB>
 BWTC_GM_HD void lanePartition(const u32* packed, u32 begin, u32 end, u32 type, u32 state, u32* pos, u32* acc,
                               u32 stride, u32* sbits) {
   u32 shared = 0;
   for (u32 k = 0; k < kSlots; ++k) shared |= ((pos[k * stride] & 31u) != 0u ? 1u : 0u) << k;
-  BWTC_GM_BY_TYPE(type, lanePartitionT<TYPE>(packed, begin, end, state, pos, acc, stride, sbits, shared));
+  BWTC_GM_BY_TYPE(type, (lanePartitionT<TYPE, KIND>(packed, begin, end, state, pos, acc, stride, sbits, shared)));
   for (u32 k = 0; k < kSlots; ++k) {
     const u32 a = acc[k * stride];
     if (a) BWTC_GM_OR(&sbits[(pos[k * stride] - 1u) >> 5], a);       // a != 0: at least one bit since the last flush
@@ -381,6 +451,14 @@ BWTC_GM_HD void bracketStep(u32& x0, u32& mask, u32 bit, u32 floor, u32 d) {
   x0 = moved(x0, bit, floor, d);
 }
 
+// The same step for a letter's main slot, on the counter's index: three candidates 0, 1, 2 at most, and the one pair a
+// step can merge is the top two under a one (the counter stands at 2) or the lowest two under a zero (at 0).
+BWTC_GM_HD void counterStep(u32& x0, u32& mask, u32 bit) {
+  if (bit) { if (x0 + popc(mask) == 2u) mask &= (mask >> 1) & 1u; }      // drops the highest set bit of the two
+  else if (x0 == 0u) mask &= mask - 1u;
+  x0 = counterMoved(x0, bit);
+}
+
 struct SlotMap { u32 lo_x0; u32 mask; };           // lo_x0 = bracket base L | x0 at the chunk's end << 16
 
 // pass 4: slot-chunk j = positions [j * kSlotChunk, ...): its map from start value to end value
@@ -388,16 +466,21 @@ struct SlotMap { u32 lo_x0; u32 mask; };           // lo_x0 = bracket base L | x
 // {image of the lowest candidate, mask}.  With the chunk's true start value t (pass 5) the true
 // value at that position is  x0 + popcount(mask & ((1 << (t - L)) - 1))  -- no second walk over slot
 // space is needed for the values the last pass starts from.
+// KIND: a letter's main slots (k < 8) take the counter form -- every candidate 0, 1, 2 from the chunk's start, no warm-up.
+template <u32 KIND = kKindB>
 BWTC_GM_HD SlotMap laneBracket(const u32* sbits, const u32* sb, u32 ns, u32 nt, u32 total, u32 j, SlotMap* snaps, u32* err) {
   const u32 p0 = j * kSlotChunk, p1 = p0 + kSlotChunk < total ? p0 + kSlotChunk : total;
   u32 sg = streamAt(sb, ns, p0);
   u32 k = sg / nt, floor = slotFloor(k), d = slotDelay(k);
   const u32 s0 = sb[sg];
+  bool ctr = KIND != kKindB && k < 8u;
   u32 x0, mask, L;
   if (p0 - s0 <= kWarm) {                          // the chain starts close by: exact
-    x0 = slotInit(k);
-    forBits(sbits, s0, p0, [&](u32, u32 b) { x0 = moved(x0, b, floor, d); });
+    x0 = ctr ? 1u : slotInit(k);
+    forBits(sbits, s0, p0, [&](u32, u32 b) { x0 = ctr ? counterMoved(x0, b) : moved(x0, b, floor, d); });
     L = x0; mask = 0;
+  } else if (ctr) {
+    L = 0; x0 = 0; mask = 3u;
   } else {
     u32 lo = floor, hi = 4096u - floor;
     forBits(sbits, p0 - kWarm, p0, [&](u32, u32 b) { lo = moved(lo, b, floor, d); hi = moved(hi, b, floor, d); });
@@ -421,6 +504,10 @@ BWTC_GM_HD SlotMap laneBracket(const u32* sbits, const u32* sb, u32 ns, u32 nt, 
       if (next >= hi || sg + 1u >= ns) {           // no chain starts inside this word
         sn[wk] = SlotMap{x0, mask};
         // equal bits that move no candidate any more: nothing to do for the whole word
+        if (ctr) {
+          if (!(hi - wp == 32u && ((word == 0u && x0 + popc(mask) == 0u) || (word == 0xFFFFFFFFu && x0 == 2u))))
+            for (u32 p = wp; p < hi; ++p, word >>= 1) counterStep(x0, mask, word & 1u);
+        } else
         if (!(hi - wp == 32u && ((word == 0u && ((x0 + popc(mask) - floor) >> d) == 0u) ||
                                  (word == 0xFFFFFFFFu && (((4096u - floor) - x0) >> d) == 0u))))
           for (u32 p = wp; p < hi; ++p, word >>= 1) bracketStep(x0, mask, word & 1u, floor, d);
@@ -429,10 +516,11 @@ BWTC_GM_HD SlotMap laneBracket(const u32* sbits, const u32* sb, u32 ns, u32 nt, 
           while (p >= next && sg + 1u < ns) {      // another chain starts here: fresh predictor, known exactly
             ++sg; next = sb[sg + 1];
             k = sg / nt; floor = slotFloor(k); d = slotDelay(k);
-            x0 = slotInit(k); mask = 0;
+            ctr = KIND != kKindB && k < 8u;
+            x0 = ctr ? 1u : slotInit(k); mask = 0;
           }
           if (p == wp) sn[wk] = SlotMap{x0, mask};
-          bracketStep(x0, mask, word & 1u, floor, d);
+          if (ctr) counterStep(x0, mask, word & 1u); else bracketStep(x0, mask, word & 1u, floor, d);
         }
       }
     }
@@ -490,12 +578,14 @@ BWTC_GM_HD void laneChainFill(const SlotMap* smap, u32 nsc, u32 gsize, u32 g, co
 
 // pass 7: the elements of a chunk in coding order with exact predictors.  q: table row k = slot k.
 // out[i] = bit << 15 | probability of the coded bit
-template <u32 TYPE>
+template <u32 TYPE, u32 KIND = kKindB>
 BWTC_GM_HD u32 emitStep(u32 v, Machines& m, u32* q, u32 stride) {
   const u32 bit = v & 1u;
-  const u32 slot = stepMachinesT<TYPE>(v, m);
+  const u32 slot = stepMachinesT<TYPE, KIND>(v, m);
   const u32 pr = q[slot * stride];
-  q[slot * stride] = moved(pr, bit, TYPE == kTInts ? 100u : 2u, (TYPE == kTGaps || TYPE == kTInts) ? 5u : slotDelay(slot));
+  const bool ctr = KIND != kKindB && (TYPE == kTRoot || (TYPE == kTInner && slot < 8u));   // a letter's main slot: the counter
+  q[slot * stride] = ctr ? evenMoved(pr, bit)
+                         : moved(pr, bit, TYPE == kTInts ? 100u : 2u, (TYPE == kTGaps || TYPE == kTInts) ? 5u : slotDelay(slot));
   return (bit << 15) | (bit ? pr : 4096u - pr);
 }
 // `stage` (stride `stride` between its 32 words): room for the 64 elements = 128 bytes = one line of
@@ -503,7 +593,7 @@ BWTC_GM_HD u32 emitStep(u32 v, Machines& m, u32* q, u32 stride) {
 // and leaves with eight 16-byte stores back to back: written 32 bytes at a time, sixteen elements' worth
 // of work apart, the lines of 130 000 lanes were open at once -- half of the L2 -- and part of them left
 // it half-written (1.6 x the bytes written, and fetched again to be completed).
-template <u32 TYPE>
+template <u32 TYPE, u32 KIND = kKindB>
 BWTC_GM_HD void laneEmitT(const u32* packed, u32 begin, u32 end, u32 state, u32* q, u32 stride, unsigned short* out, u32* stage) {
   Machines m = {state & 7u, (state >> 3) & 3u, (state >> 5) & 3u};
   if (begin >= end) return;
@@ -524,8 +614,8 @@ BWTC_GM_HD void laneEmitT(const u32* packed, u32 begin, u32 end, u32 state, u32*
 #pragma unroll
 #endif
         for (u32 e = 0; e < 8; ++e) {
-          const u32 a = emitStep<TYPE>(word & 3u, m, q, stride);
-          const u32 b = emitStep<TYPE>((word >> 2) & 3u, m, q, stride);
+          const u32 a = emitStep<TYPE, KIND>(word & 3u, m, q, stride);
+          const u32 b = emitStep<TYPE, KIND>((word >> 2) & 3u, m, q, stride);
           word >>= 4;
           o[e] = a | (b << 16);
         }
@@ -558,12 +648,13 @@ BWTC_GM_HD void laneEmitT(const u32* packed, u32 begin, u32 end, u32 state, u32*
         const u32 lo = wb > begin ? wb : begin, hi = wb + 16u < end ? wb + 16u : end;
         if (lo >= hi) continue;
         word >>= (lo & 15u) * 2u;
-        for (u32 i = lo; i < hi; ++i, word >>= 2) out[i] = (unsigned short)emitStep<TYPE>(word & 3u, m, q, stride);
+        for (u32 i = lo; i < hi; ++i, word >>= 2) out[i] = (unsigned short)emitStep<TYPE, KIND>(word & 3u, m, q, stride);
       }
     }
     cur = nxt;
   }
 }
+template <u32 KIND = kKindB>
 BWTC_GM_HD void laneEmit(const u32* packed, u32 begin, u32 end, u32 type, u32 state, u32 task, u32 chunk, u32 nc, u32 nt,
                          const u32* base, const u32* sb, const u32* sbits, const SlotMap* snaps, const SlotMap* smap,
                          const unsigned short* sstart, u32* q, u32 stride, unsigned short* out, u32* err, u32* stage) {
@@ -572,6 +663,7 @@ BWTC_GM_HD void laneEmit(const u32* packed, u32 begin, u32 end, u32 type, u32 st
   for (u32 k = k_lo; k < k_hi; ++k) {
     const u32 P = base[k * nc + chunk], s0 = sb[k * nt + task];
     const u32 floor = slotFloor(k), d = slotDelay(k);
+    const bool ctr = KIND != kKindB && k < 8u;      // a letter's main slot: its index in slot space, 1024 (index + 1) here
     const u32 a0 = P & ~(kSample - 1u);
     u32 a, x;
     if (a0 > s0) {                                 // the bracket as it stood at a0, resolved with its slot-chunk's true start value
@@ -580,11 +672,11 @@ BWTC_GM_HD void laneEmit(const u32* packed, u32 begin, u32 end, u32 type, u32 st
       const u32 off = (u32)sstart[jc] - (smap[jc].lo_x0 & 0xFFFFu);
       if (off > 31u && sn.mask) *err |= kErrChain;
       a = a0; x = sn.lo_x0 + popc(sn.mask & ((1u << (off > 31u ? 31u : off)) - 1u));
-    } else { a = s0; x = slotInit(k); }
-    forBits(sbits, a, P, [&](u32, u32 b) { x = moved(x, b, floor, d); });
-    q[k * stride] = x;
+    } else { a = s0; x = ctr ? 1u : slotInit(k); }
+    forBits(sbits, a, P, [&](u32, u32 b) { x = ctr ? counterMoved(x, b) : moved(x, b, floor, d); });
+    q[k * stride] = ctr ? (x + 1u) << 10 : x;
   }
-  BWTC_GM_BY_TYPE(type, laneEmitT<TYPE>(packed, begin, end, state, q, stride, out, stage));
+  BWTC_GM_BY_TYPE(type, (laneEmitT<TYPE, KIND>(packed, begin, end, state, q, stride, out, stage)));
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------
@@ -598,6 +690,9 @@ void cutChunks(std::vector<Task>* tasks, std::vector<Chunk>* chunks);
 // state: the main machine's carried state, updated.  false: an error flag was raised.
 bool modelsOnHostLanes(const u32* packed, u32 total, const std::vector<Task>& tasks, const std::vector<Chunk>& chunks,
                        u32* state, unsigned short* out);
+// letter: the main model ('B': the above); 'b' and 'u' carry nothing, *state then becomes what their tasks start from.
+bool modelsOnHostLanes(const u32* packed, u32 total, const std::vector<Task>& tasks, const std::vector<Chunk>& chunks,
+                       u32* state, unsigned short* out, char letter);
 
 }  // namespace gm
 }  // namespace wavelet

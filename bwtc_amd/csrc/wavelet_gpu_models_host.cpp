@@ -51,22 +51,24 @@ void cutChunks(std::vector<Task>* tasks, std::vector<Chunk>* chunks) {
   }
 }
 
-bool modelsOnHostLanes(const u32* packed, u32 total, const std::vector<Task>& tasks, const std::vector<Chunk>& chunks,
-                       u32* state, unsigned short* out) {
+namespace {
+template <u32 KIND>
+bool modelsOnHostLanesOf(const u32* packed, u32 total, const std::vector<Task>& tasks, const std::vector<Chunk>& chunks,
+                         u32* state, unsigned short* out) {
   const u32 nc = static_cast<u32>(chunks.size()), nt = static_cast<u32>(tasks.size());
   if (nc == 0 || nt == 0) return true;
   u32 err = 0;
   // pass 1 + the composition scan (the kernel composes per thread, scans the aggregates and
   // applies; here: aggregates of eight chunks, checked against the plain walk)
   std::vector<u64> cmap(nc);
-  for (u32 c = 0; c < nc; ++c) cmap[c] = laneMap(packed, chunks[c].begin, chunks[c].end, tasks[chunks[c].task_first & 0x7FFFFFFFu].type);
+  for (u32 c = 0; c < nc; ++c) cmap[c] = laneMapK<KIND>(packed, chunks[c].begin, chunks[c].end, tasks[chunks[c].task_first & 0x7FFFFFFFu].type);
   std::vector<u32> cstate(nc);
-  u32 st = packState(*state & 7u, 2, 1);
+  u32 st = packState(KIND == kKindB ? *state & 7u : mainStart(KIND), 2, 1);   // (a letter's block does not look at the carried state)
   for (u32 c0 = 0; c0 < nc; c0 += 8) {
     u64 agg = kMapIdentity;
     u32 walk = st;
     for (u32 c = c0; c < std::min(nc, c0 + 8); ++c) {
-      if (chunks[c].task_first >> 31) { agg = mapConstGapsInts(agg, 2, 1); walk = packState(walk & 7u, 2, 1); }
+      if (chunks[c].task_first >> 31) { agg = mapTaskStart<KIND>(agg); walk = stateTaskStart<KIND>(walk); }
       cstate[c] = walk;
       agg = mapCompose(agg, cmap[c]);
       walk = mapApply(cmap[c], walk);
@@ -74,13 +76,13 @@ bool modelsOnHostLanes(const u32* packed, u32 total, const std::vector<Task>& ta
     if (mapApply(agg, st) != walk) return false;
     st = walk;
   }
-  *state = st & 7u;
+  *state = KIND == kKindB ? st & 7u : mainStart(KIND);     // the letters: as StreamCoder::stateBefore hands it on
   // pass 2 + exclusive scan: slot space is slot-major, then chunk
   std::vector<u32> base(static_cast<size_t>(kSlots) * nc + 1, 0);
   {
     u32 tab[kSlotStride];
     for (u32 c = 0; c < nc; ++c) {
-      laneCount(packed, chunks[c].begin, chunks[c].end, tasks[chunks[c].task_first & 0x7FFFFFFFu].type, cstate[c], tab, 1);
+      laneCount<KIND>(packed, chunks[c].begin, chunks[c].end, tasks[chunks[c].task_first & 0x7FFFFFFFu].type, cstate[c], tab, 1);
       for (u32 k = 0; k < kSlots; ++k) base[static_cast<size_t>(k) * nc + c] = tab[k];
     }
     u32 run = 0;
@@ -99,13 +101,13 @@ bool modelsOnHostLanes(const u32* packed, u32 total, const std::vector<Task>& ta
     u32 pos[kSlotStride], acc[kSlotStride];
     for (u32 c = 0; c < nc; ++c) {
       for (u32 k = 0; k < kSlots; ++k) { pos[k] = base[static_cast<size_t>(k) * nc + c]; acc[k] = 0; }
-      lanePartition(packed, chunks[c].begin, chunks[c].end, tasks[chunks[c].task_first & 0x7FFFFFFFu].type, cstate[c], pos, acc, 1, sbits.data());
+      lanePartition<KIND>(packed, chunks[c].begin, chunks[c].end, tasks[chunks[c].task_first & 0x7FFFFFFFu].type, cstate[c], pos, acc, 1, sbits.data());
     }
   }
   // passes 4-6
   const u32 nsc = (total + kSlotChunk - 1) / kSlotChunk;
   std::vector<SlotMap> smap(nsc), snaps(total / kSample + 4);
-  for (u32 j = 0; j < nsc; ++j) smap[j] = laneBracket(sbits.data(), sb.data(), ns, nt, total, j, snaps.data(), &err);
+  for (u32 j = 0; j < nsc; ++j) smap[j] = laneBracket<KIND>(sbits.data(), sb.data(), ns, nt, total, j, snaps.data(), &err);
   if (err) return false;
   if (std::getenv("BWTC_HIP_DEBUG")) {
     u32 open_end = 0, far = 0;
@@ -129,10 +131,23 @@ bool modelsOnHostLanes(const u32* packed, u32 total, const std::vector<Task>& ta
   u32 q[kSlotStride], stage[32];
   for (u32 c = 0; c < nc; ++c) {
     const u32 t = chunks[c].task_first & 0x7FFFFFFFu;
-    laneEmit(packed, chunks[c].begin, chunks[c].end, tasks[t].type, cstate[c], t, c, nc, nt, base.data(), sb.data(), sbits.data(),
+    laneEmit<KIND>(packed, chunks[c].begin, chunks[c].end, tasks[t].type, cstate[c], t, c, nc, nt, base.data(), sb.data(), sbits.data(),
              snaps.data(), smap.data(), sstart.data(), q, 1, out, &err, stage);
   }
   return err == 0;
+}
+}  // namespace
+
+bool modelsOnHostLanes(const u32* packed, u32 total, const std::vector<Task>& tasks, const std::vector<Chunk>& chunks,
+                       u32* state, unsigned short* out) {
+  return modelsOnHostLanesOf<kKindB>(packed, total, tasks, chunks, state, out);
+}
+
+bool modelsOnHostLanes(const u32* packed, u32 total, const std::vector<Task>& tasks, const std::vector<Chunk>& chunks,
+                       u32* state, unsigned short* out, char letter) {
+  if (letter == 'b') return modelsOnHostLanesOf<kKindb>(packed, total, tasks, chunks, state, out);
+  if (letter == 'u') return modelsOnHostLanesOf<kKindu>(packed, total, tasks, chunks, state, out);
+  return modelsOnHostLanesOf<kKindB>(packed, total, tasks, chunks, state, out);
 }
 
 }  // namespace gm

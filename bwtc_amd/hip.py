@@ -268,6 +268,7 @@ EXPORTS = [
     "bwtc_hip_test_code_stage", "bwtc_hip_test_code_table", "bwtc_hip_test_code_keys",
     "bwtc_hip_test_finish_pass", "bwtc_hip_test_local_pass", "bwtc_hip_test_finisher",
     "bwtc_hip_test_models", "bwtc_hip_host_test_models", "bwtc_hip_host_wavelet_elements",
+    "bwtc_hip_test_models_letter", "bwtc_hip_host_test_models_letter", "bwtc_hip_host_wavelet_elements_letter",
     "bwtc_hip_test_rank_pass", "bwtc_hip_test_rank_scan", "bwtc_hip_test_rank_scatter", "bwtc_hip_test_round_keys", "bwtc_hip_test_round",
     "bwtc_hip_wavelet_depth_needed", "bwtc_hip_grammar_create", "bwtc_hip_grammar_destroy", "bwtc_hip_grammar_rules", "bwtc_hip_grammar_special_symbols",
     "bwtc_hip_grammar_is_special", "bwtc_hip_grammar_write", "bwtc_hip_grammar_read", "bwtc_hip_pair_replace_device",
@@ -368,8 +369,11 @@ def load():
     L.bwtc_hip_host_wavelet_streams.argtypes = L.bwtc_hip_host_wavelet_sections.argtypes
     L.bwtc_hip_test_models.argtypes = [_vp, _vp, _u32, _vp, _u32, _u32, _u32, ctypes.POINTER(ModelsOut)]
     L.bwtc_hip_host_test_models.argtypes = [_vp, _u32, _vp, _u32, _u32, _vp, ctypes.POINTER(_u32)]
+    L.bwtc_hip_test_models_letter.argtypes = [_vp, ctypes.c_char, _vp, _u32, _vp, _u32, _u32, _u32, ctypes.POINTER(ModelsOut)]
+    L.bwtc_hip_host_test_models_letter.argtypes = [ctypes.c_char, _vp, _u32, _vp, _u32, _u32, _vp, ctypes.POINTER(_u32)]
     L.bwtc_hip_host_wavelet_elements.argtypes = [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(_u32), ctypes.POINTER(_u32),
                                                  ctypes.POINTER(_u32), _vp, _u64, _vp, _u32, _vp, _u64]
+    L.bwtc_hip_host_wavelet_elements_letter.argtypes = [ctypes.c_char] + L.bwtc_hip_host_wavelet_elements.argtypes
     L.bwtc_hip_host_wavelet_streams_lanes.argtypes = L.bwtc_hip_host_wavelet_sections.argtypes
     # pair-replacing pre-stage (`--prepr`)
     L.bwtc_hip_grammar_create.restype = _vp
@@ -631,10 +635,11 @@ class Context:
                "bwtc_hip_test_gpu_lanes")
         return [out[int(off[j]):int(off[j + 1])].tobytes() for j in range(k)]
 
-    def test_models(self, packed, n_coded, tasks, state_in, flags=0):
+    def test_models(self, packed, n_coded, tasks, state_in, flags=0, letter="B"):
         """The model passes (wavelet_gpu_models.hip) over given packed streams and tasks [(begin, end, type)]: a dict of
         w, tail, ends, nc, nsc and -- unless flags bit 1 -- chunks, cmap, cstate, base, sb, sbits, smap, snaps, sstart.
-        flags bit 0: the lines form of the partition pass (bwtc_hip_test_models)."""
+        flags bit 0: the lines form of the partition pass (bwtc_hip_test_models); letter: the main model
+        (bwtc_hip_test_models_letter for 'b' and 'u')."""
         packed, tasks = _models_args(packed, tasks)
         nt, n = tasks.shape[0], int(n_coded)
         nc_room, nsc = nt + n // 2048, (n + 2047) // 2048
@@ -647,8 +652,12 @@ class Context:
         o = ModelsOut()
         for k, a in r.items():
             setattr(o, k, _ptr(a))
-        _check(self.lib.bwtc_hip_test_models(self.handle, _ptr(packed), n, _ptr(tasks), nt, state_in, flags, ctypes.byref(o)),
-               "bwtc_hip_test_models")
+        if letter == "B":
+            _check(self.lib.bwtc_hip_test_models(self.handle, _ptr(packed), n, _ptr(tasks), nt, state_in, flags, ctypes.byref(o)),
+                   "bwtc_hip_test_models")
+        else:
+            _check(self.lib.bwtc_hip_test_models_letter(self.handle, letter.encode(), _ptr(packed), n, _ptr(tasks), nt, state_in, flags,
+                                                        ctypes.byref(o)), "bwtc_hip_test_models_letter")
         nc = int(o.nc)
         for k in ("chunks", "cmap", "cstate"):
             if k in r:
@@ -1572,34 +1581,43 @@ def _models_args(packed, tasks):
     return np.ascontiguousarray(packed, np.uint32), np.ascontiguousarray(tasks, np.uint32).reshape(-1, 3)
 
 
-def host_test_models(packed, n_coded, tasks, state_in):
-    """The model passes lane by lane on the host over given packed streams and tasks (bwtc_hip_host_test_models;
-    no device): (w, state after the block)."""
+def host_test_models(packed, n_coded, tasks, state_in, letter="B"):
+    """The model passes lane by lane on the host over given packed streams and tasks (bwtc_hip_host_test_models, for
+    another main model than 'B' bwtc_hip_host_test_models_letter; no device): (w, state after the block)."""
     packed, tasks = _models_args(packed, tasks)
     w = np.zeros(int(n_coded), np.uint16)
     st = _u32(0)
-    _check(load().bwtc_hip_host_test_models(_ptr(packed), int(n_coded), _ptr(tasks), tasks.shape[0], state_in, _ptr(w),
-                                            ctypes.byref(st)), "bwtc_hip_host_test_models")
+    if letter == "B":
+        _check(load().bwtc_hip_host_test_models(_ptr(packed), int(n_coded), _ptr(tasks), tasks.shape[0], state_in, _ptr(w),
+                                                ctypes.byref(st)), "bwtc_hip_host_test_models")
+    else:
+        _check(load().bwtc_hip_host_test_models_letter(letter.encode(), _ptr(packed), int(n_coded), _ptr(tasks), tasks.shape[0], state_in,
+                                                       _ptr(w), ctypes.byref(st)), "bwtc_hip_host_test_models_letter")
     return w, st.value
 
 
-def host_wavelet_elements(section_args, state):
+def host_wavelet_elements(section_args, state, letter="B"):
     """The coded elements of a real block, from the section-run arguments of bwtc_hip_host_wavelet_streams (a tuple of
     n_sections and seven arrays): (packed codes, n_coded, tasks [(begin, end, type)], w of the sequential host coder,
-    state after the block) -- bwtc_hip_host_wavelet_elements."""
+    state after the block) -- bwtc_hip_host_wavelet_elements, for another main model than 'B' ..._elements_letter."""
     L = load()
+    if letter == "B":
+        elements = L.bwtc_hip_host_wavelet_elements
+    else:
+        def elements(*a):
+            return L.bwtc_hip_host_wavelet_elements_letter(letter.encode(), *a)
     nsec, arrays = section_args[0], [np.ascontiguousarray(a) for a in section_args[1:]]
     ptrs = [_ptr(a) for a in arrays]
     n, nt = _u32(0), _u32(0)
     st = _u32(state)
-    _check(L.bwtc_hip_host_wavelet_elements(nsec, *ptrs, ctypes.byref(st), ctypes.byref(n), ctypes.byref(nt), None, 0, None, 0, None, 0),
+    _check(elements(nsec, *ptrs, ctypes.byref(st), ctypes.byref(n), ctypes.byref(nt), None, 0, None, 0, None, 0),
            "bwtc_hip_host_wavelet_elements")
     packed = np.zeros((n.value + 15) // 16, np.uint32)
     tasks = np.zeros((nt.value, 3), np.uint32)
     w = np.zeros(n.value, np.uint16)
     st = _u32(state)
-    _check(L.bwtc_hip_host_wavelet_elements(nsec, *ptrs, ctypes.byref(st), ctypes.byref(n), ctypes.byref(nt), _ptr(packed), packed.size,
-                                            _ptr(tasks), tasks.shape[0], _ptr(w), w.size), "bwtc_hip_host_wavelet_elements")
+    _check(elements(nsec, *ptrs, ctypes.byref(st), ctypes.byref(n), ctypes.byref(nt), _ptr(packed), packed.size,
+                    _ptr(tasks), tasks.shape[0], _ptr(w), w.size), "bwtc_hip_host_wavelet_elements")
     return packed, n.value, tasks, w, st.value
 
 

@@ -131,8 +131,11 @@ int main(int argc, char** argv) {
       // the models on the GPU -- the default, also for a stream farmed over several contexts -- a block
       // is under way for 0.7 s and holds 1.3 GB of page-locked memory; 13-14 blocks are what the rate
       // takes, 20 leave room for the spread of the host half (16: an occasional 2-3 ms wait per block).
+      // ('b' and 'u': on the GPU under BWTC_HIP_LETTER_MODELS=1)
       const char* mv = std::getenv("BWTC_HIP_MODELS");
-      const bool host_models = (mv && std::strcmp(mv, "host") == 0) || enc != 'B';
+      const char* lv = std::getenv("BWTC_HIP_LETTER_MODELS");
+      const bool letters_on_device = lv && std::strcmp(lv, "1") == 0;
+      const bool host_models = (mv && std::strcmp(mv, "host") == 0) || (enc != 'B' && !letters_on_device);
       const bool deep = host_models && block_bytes >= 64e6 && stream_bytes / block_bytes >= 256.0 * n_ctx;
       pipeline = deep && gb >= 40.0 ? 128 : deep && gb >= 24.0 ? 96 : gb >= 48.0 ? 24 : gb >= 40.0 ? 20 : 16;   // an upper bound: the Compressor keeps what the stream shows to need (bwtc_hip_wavelet_depth_needed)
     }

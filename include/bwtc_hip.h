@@ -723,11 +723,18 @@ typedef struct bwtc_hip_models_out {
 } bwtc_hip_models_out;
 int bwtc_hip_test_models(bwtc_hip_ctx* ctx, const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks, uint32_t nt,
                          uint32_t state_in, uint32_t flags, bwtc_hip_models_out* out);
+/* The same passes for a main model given by its letter ('B' as above, 'b', 'u'; -1 for any other).  For 'b' and 'u'
+ * nothing is carried: state_in changes nothing, tail[0] is what every task starts from (3, 0), ends[i] = i, and in
+ * slot space (smap, snaps, sstart) a main slot's value is its counter's index 0, 1, 2. */
+int bwtc_hip_test_models_letter(bwtc_hip_ctx* ctx, char letter, const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks,
+                                uint32_t nt, uint32_t state_in, uint32_t flags, bwtc_hip_models_out* out);
 /* The same input through the passes run lane by lane on the host (gm::modelsOnHostLanes; no context, no device), in
  * buffers of exactly the sizes the device path allots: w_out[n_coded], *state_out the state after the block.
  * -1 as above, -7: the passes raised their error flag. */
 int bwtc_hip_host_test_models(const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks, uint32_t nt,
                               uint32_t state_in, uint16_t* w_out, uint32_t* state_out);
+int bwtc_hip_host_test_models_letter(char letter, const uint32_t* packed, uint32_t n_coded, const uint32_t* tasks, uint32_t nt,
+                                     uint32_t state_in, uint16_t* w_out, uint32_t* state_out);
 /* The coded elements of a real block (arguments as bwtc_hip_host_wavelet_streams): *n_coded and *nt always; where
  * packed, tasks and w are given (room: packed_words, tasks_cap tasks of three words, w_cap elements; -1 when too
  * small) also the packed codes, the model tasks in coding order and the w of the SEQUENTIAL host coder
@@ -738,6 +745,13 @@ int bwtc_hip_host_wavelet_elements(uint32_t n_sections, const uint32_t* first_ru
                                    const uint32_t* dist_len, const uint32_t* dist_cnt, uint32_t* state,
                                    uint32_t* n_coded, uint32_t* nt, uint32_t* packed, uint64_t packed_words,
                                    uint32_t* tasks, uint32_t tasks_cap, uint16_t* w, uint64_t w_cap);
+/* ... and of the sequential host coder under another main model ('B', 'b', 'u'; -1 for any other letter) */
+int bwtc_hip_host_wavelet_elements_letter(char letter, uint32_t n_sections, const uint32_t* first_run,
+                                          const uint8_t* run_sym, const uint32_t* run_start,
+                                          const uint32_t* run_freqs, const uint32_t* dist_offset,
+                                          const uint32_t* dist_len, const uint32_t* dist_cnt, uint32_t* state,
+                                          uint32_t* n_coded, uint32_t* nt, uint32_t* packed, uint64_t packed_words,
+                                          uint32_t* tasks, uint32_t tasks_cap, uint16_t* w, uint64_t w_cap);
 
 /* ---- pair-replacing pre-stage, `--prepr p...` ------------------------------------------
  * Replaces preprocessors/PairReplacer.cpp (analyseData :53-63, decideReplacements :402-484,
