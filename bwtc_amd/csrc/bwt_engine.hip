@@ -3165,7 +3165,7 @@ int BwtEngine::plan_grams(const KeyPlan& plan, u32 n, const u8* d_lut, GramPlan*
 static void say_no_period_step(const BwtEngine& e, u64 h_first) {
   if (debug_on())
     std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: no period step\n",
-                 e.blk.period_p, e.blk.period_votes, e.blk.period_longest, (unsigned long long)h_first);
+                 e.blk.weighed.p, e.blk.weighed.votes, e.blk.weighed.longest, (unsigned long long)h_first);
 }
 
 // The code-key stage as suffix_sort launches it (and, kernel by kernel, BwtEngine::test_code_stage).  The key word's
@@ -3430,8 +3430,7 @@ int BwtEngine::step_due(const SortList& L, u32 m, u64 h_round, u64 h_first, bool
     StretchStep& step = blk.steps[i];
     if (step.when != StretchStep::kWaiting) continue;
     const bool behind_run = i > 0;
-    const u32 gate = blk.merged ? step.gate : behind_run ? blk.proper_longest : blk.period_longest;
-    if ((u64)gate <= std::max<u64>(h_round, step.p)) {
+    if ((u64)blk.due_gate(i) <= std::max<u64>(h_round, step.p)) {
       step.when = StretchStep::kNone;
       step.dropped = true;
       say_no_period_step(*this, h_first);
@@ -3462,8 +3461,8 @@ int BwtEngine::store_step(u32 n, StretchStep& step, u64 h_round, bool behind_run
     blk.merged_stored = true;
     return 0;
   }
-  if (blk.lengths_period == step.p) return 0;
-  return stretch_lengths(n, step.p, true, &blk.period_longest, behind_run ? &blk.proper_longest : nullptr);
+  if (blk.lengths_period == step.p) return 0;            // (a waiting step at the front: its lengths were stored when it was decided)
+  return stretch_lengths(n, step.p, true, &step.longest, behind_run ? &step.proper : nullptr);
 }
 
 // The rounds over the sorted list in L.home, from depth ask.h0 until nothing is tied.  ask.text_rounds: rounds that compare
@@ -3546,7 +3545,7 @@ int BwtEngine::run_rounds(SortList& L, const RoundsRequest& ask, RoundsLeft* out
       keep_h = true;
       if (period_req && debug_on())
         std::fprintf(stderr, "periods: period %u with %u votes, longest stretch %u, the rounds begin at depth %llu: period step at depth %u\n",
-                     step.p, blk.merged ? step.votes : blk.period_votes, blk.merged ? step.gate : blk.period_longest, (unsigned long long)h_first, step.depth);
+                     step.p, step.votes, blk.said_longest(step), (unsigned long long)h_first, step.depth);
       // rank[] still incomplete: one text round behind the runs first -- a block that is one giant run ends there,
       // without the completion of rank[] that the first doubling round costs.  Not beside a live local list: its
       // members' ranks are local_depth deep, and the first doubling look-up must not lie deeper than that (text rounds
@@ -3573,12 +3572,12 @@ int BwtEngine::run_rounds(SortList& L, const RoundsRequest& ask, RoundsLeft* out
   if (blk.merged && ask.doubling && debug_on()) {
     std::fprintf(stderr, "steps: %d entries", blk.n_steps);
     for (int i = 0; i < blk.n_steps; ++i)
-      std::fprintf(stderr, "%s (p %u, depth %u, gate %u, votes %u)", i ? "," : ":", blk.steps[i].p, blk.steps[i].depth, blk.steps[i].gate, blk.steps[i].votes);
+      std::fprintf(stderr, "%s (p %u, depth %u, gate %u, votes %u)", i ? "," : ":", blk.steps[i].p, blk.steps[i].depth, blk.steps[i].shown_gate(true), blk.steps[i].votes);
     std::fprintf(stderr, "\n");
   } else if (mixed_steps && ask.doubling && debug_on()) {
     const StretchStep period = blk.period_ran();
     std::fprintf(stderr, "steps: run step at depth %u, period step of period %u at depth %u, longest run %u, longest proper stretch %u\n",
-                 blk.run_depth(), period.p, period.depth, blk.run_longest, blk.proper_longest);
+                 blk.run_depth(), period.p, period.depth, blk.run_longest, blk.weighed.proper);
   }
   if (long_periods && ask.doubling && debug_on())
     std::fprintf(stderr, "steps: long periods on, route bit 11 %s (period step of period %u at depth %u)\n", (stats.route & 2048u) ? "set" : "clear",
@@ -3971,76 +3970,82 @@ int BwtEngine::long_period_probe(u32 n, u32 p, u32 span, bool* found) {
   return 0;
 }
 
-// blk.period_p, the finder's (or BWTC_HIP_PERIOD's), through what decides whether it is worth a step: the probe, the
-// period-length pass (a trial unless store), the worth test and the division of a period above the first round's depth.
-// Leaves blk.period_p (0: refused), blk.period_longest and, where mixed, blk.proper_longest.
-int BwtEngine::weigh_period(u32 n, u64 h_first, bool mixed, bool store) {
+// Candidate p, the finder's with its votes (or BWTC_HIP_PERIOD's), through what decides whether it is worth a step: the
+// probe, the period-length pass (a trial unless store), the worth test and the division of a period above the first
+// round's depth.  -> *out: the period that is left (0: refused) with the lengths of the last pass over it; a candidate
+// that no pass was made for leaves lengths of 0.
+int BwtEngine::weigh_period(u32 n, u64 h_first, bool mixed, bool store, u32 p, u32 votes, WeighedPeriod* out) {
   hipStream_t st = stream;
   const bool voted = period_forced == 0;                // (a forced period skips the probe, the worth tests and the division)
-  u32* const proper = mixed ? &blk.proper_longest : nullptr;
-  const u32& g = mixed ? blk.proper_longest : blk.period_longest;
-  if (blk.period_p >= 2 && voted) {
+  WeighedPeriod w;
+  w.p = p >= 2 ? p : 0u; w.votes = votes;
+  u32* const proper = mixed ? &w.proper : nullptr;      // (the passes' second maximum exists under the rule only)
+  if (w.p && voted) {
     // votes say how many members lie p apart, not for how long they tie: fixed-width records with a few free bytes
     // each vote for their width and tie for less than two records.  Before the pass, a probe: is any aligned window
     // of (W - p) / 2 positions free of breaks, W = kPeriodWorth x max(the first round's depth, p) being the stretch
     // the step is worth?  A stretch of W characters holds such a window; the probe's threads stop at their first break.
-    const u64 worth = kPeriodWorth * std::max<u64>(h_first, blk.period_p);
-    const u32 span = (u32)std::min<u64>((worth - blk.period_p) / 2, 0x40000000ull);
-    const u64 windows = (u64)n > blk.period_p + span ? ((u64)n - blk.period_p) / span : 0;
+    const u64 worth = kPeriodWorth * std::max<u64>(h_first, w.p);
+    const u32 span = (u32)std::min<u64>((worth - w.p) / 2, 0x40000000ull);
+    const u64 windows = (u64)n > w.p + span ? ((u64)n - w.p) / span : 0;
     bool found = false;
-    if (blk.period_p > kPeriodMax) {
+    if (w.p > kPeriodMax) {
       // (BWTC_HIP_LONG_PERIODS: a window of a long period is a workgroup's, not a thread's -- the wide probe)
-      const int rcl = long_period_probe(n, blk.period_p, span, &found);
+      const int rcl = long_period_probe(n, w.p, span, &found);
       if (rcl) return rcl;
     } else if (windows) {
       BWTC_HIP_TRY(hipMemsetAsync(d_small + kSmallPeriod + 1, 0, 4, st));
-      hipLaunchKernelGGL(k_period_probe, dim3((u32)((windows + 255) / 256)), dim3(256), 0, st, (const u8*)d_T, n, blk.period_p, span, depth32(windows), d_small + kSmallPeriod + 1);
+      hipLaunchKernelGGL(k_period_probe, dim3((u32)((windows + 255) / 256)), dim3(256), 0, st, (const u8*)d_T, n, w.p, span, depth32(windows), d_small + kSmallPeriod + 1);
       BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 1, d_small + kSmallPeriod + 1, 4, hipMemcpyDeviceToHost, st));
       BWTC_HIP_TRY(wait());
       found = h_small[kSmallPeriod + 1] != 0;
       stats.alg_bytes += windows * 2;                   // (at the least: a byte of each stream per window)
     }
     if (!found) {
-      if (debug_on()) std::fprintf(stderr, "periods: no window of %u positions of period %u without a break: no period-length pass\n", span, blk.period_p);
-      blk.period_p = 0;
+      if (debug_on()) std::fprintf(stderr, "periods: no window of %u positions of period %u without a break: no period-length pass\n", span, w.p);
+      w.p = 0;
     }
   }
-  if (blk.period_p >= 2) {
+  if (w.p) {
     // (a run of one byte is a stretch of every period, and the run step's business: the block's longest run first --
     // known already unless BWTC_HIP_RUNS=0, where a trial pass of period 1 finds it -- and no period step where the
-    // longest stretch is no longer than that.  Under the switch runs do not count in g, and the test goes.)
+    // longest stretch is no longer than that.  Under the rule runs do not count in the gate length, and the test goes.)
     const bool runs_count = !mixed && voted;
     int rcb = (runs_count && !run_ranks) ? stretch_lengths(n, 1, false, &blk.run_longest) : 0;
     if (rcb) return rcb;
-    rcb = stretch_lengths(n, blk.period_p, store, &blk.period_longest, proper);
+    rcb = stretch_lengths(n, w.p, store, &w.longest, proper);
     if (rcb) return rcb;
-    // ... and none where g is short of kPeriodWorth times the depth it has to pass: doubling gets through it in three
-    // rounds, and the step's own round and the passes cost as much (fixed-width records with a few free bytes per
-    // record vote for their width and tie for less than two records)
-    if ((runs_count && blk.run_longest >= blk.period_longest) || (voted && (u64)g < kPeriodWorth * std::max<u64>(h_first, blk.period_p)))
-      blk.period_p = 0;
+    // ... and none where the gate length is short of kPeriodWorth times the depth it has to pass: doubling gets through
+    // it in three rounds, and the step's own round and the passes cost as much
+    if ((runs_count && blk.run_longest >= w.longest) || (voted && (u64)w.gate(mixed) < kPeriodWorth * std::max<u64>(h_first, w.p)))
+      w.p = 0;
   }
-  if (blk.period_p >= 2 && voted && (u64)blk.period_p > h_first && (u64)g > blk.period_p) {
+  if (w.p && voted && (u64)w.p > h_first && (u64)w.gate(mixed) > w.p) {
     // The winner may be a multiple of the stretches' period: a list that a sort by windows of the suffix number
     // has been through holds a group's members in another order than by position.  A period above the first
     // round's depth defers the step, so it is worth dividing: p / q for the winner's prime factors q, kept while
-    // g stays as long (trial passes: the longest stretches alone, no lengths stored).
-    const u32 winner = blk.period_p, longest_voted = blk.period_longest, proper_voted = blk.proper_longest, g_voted = g;
+    // the gate length stays as long (trial passes: the longest stretches alone, no lengths stored).
+    // (No block of the tests or of scripts/sorter_trace.py has a winner that this loop reduces, so its handling of the
+    // lengths is the one it always had, over the record instead of the block's words: the trial passes write into the
+    // record, g reads whichever length the gate goes by, and the voted lengths are put back behind the loop.)
+    const u32& g = mixed ? w.proper : w.longest;
+    const u32 winner = w.p, longest_voted = w.longest, proper_voted = w.proper, g_voted = g;
     u32 rest = winner;
-    for (u32 q = 2; q <= rest && blk.period_p / q >= 2; ) {
+    for (u32 q = 2; q <= rest && w.p / q >= 2; ) {
       if (rest % q) { q = (u64)q * q > rest ? rest : q + 1; continue; }   // (no factor up to its root: what is left is prime)
       rest /= q;
-      const int rcb = stretch_lengths(n, blk.period_p / q, false, &blk.period_longest, proper);
+      const int rcb = stretch_lengths(n, w.p / q, false, &w.longest, proper);
       if (rcb) return rcb;
-      if (g >= g_voted) blk.period_p /= q;
+      if (g >= g_voted) w.p /= q;
       else while (rest % q == 0) rest /= q;            // (the same candidate again)
     }
-    blk.period_longest = longest_voted; blk.proper_longest = proper_voted;
-    if (blk.period_p != winner) {
-      const int rcb = stretch_lengths(n, blk.period_p, store, &blk.period_longest, proper);
+    w.longest = longest_voted; w.proper = proper_voted;
+    if (w.p != winner) {
+      const int rcb = stretch_lengths(n, w.p, store, &w.longest, proper);
       if (rcb) return rcb;
     }
   }
+  *out = w;
   return 0;
 }
 
@@ -4054,7 +4059,7 @@ int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* 
   if (run_ranks || period_forced == 1) {
     const int rcr = stretch_lengths(n, 1, true, &blk.run_longest);
     if (rcr) return rcr;
-    if ((u64)blk.run_longest > h_first) blk.schedule(1, StretchStep::kThisRound);
+    if ((u64)blk.run_longest > h_first) blk.schedule(WeighedPeriod{1, blk.run_longest}, StretchStep::kThisRound);
     if (debug_on())
       std::fprintf(stderr, "runs: longest run %u, the rounds begin at depth %llu: %s\n", blk.run_longest, (unsigned long long)h_first,
                    blk.n_steps ? "run step" : "no run step");
@@ -4068,147 +4073,120 @@ int BwtEngine::decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* 
   // are the longest PROPER stretch's -- the largest k_p over the positions s with T[s] != T[s + 1], which no run of one
   // byte holds and every p positions of a stretch of another unit do -- so a run neither counts as a stretch nor keeps
   // one from its step.
-  const bool mixed = mixed_steps && run_ranks && period_forced != 1;
+  const bool mixed = mixed_rule();
   const bool run_due = blk.n_steps != 0;
-  if (!period_ranks || period_forced == 1 || (run_due && !mixed)) return 0;
-  const int rcp = find_period(n, ks, vs, m, kmask);
+  if (!looks_for_period(run_due)) return 0;
+  PeriodCandidates cands;
+  const int rcp = find_period(n, ks, vs, m, kmask, &cands);
   if (rcp) return rcp;
-  const bool voted = period_forced == 0;                // (a forced period skips the probe, the worth tests and the division)
-  // The passes' second maximum and the gate length g it feeds exist under the switch only.  While a run step is due d_runK
-  // holds k_1[] for it, so the passes here are trials (store == false).
-  u32* const proper = mixed ? &blk.proper_longest : nullptr;
-  const u32& g = mixed ? blk.proper_longest : blk.period_longest;
+  // BWTC_HIP_MULTI: every candidate of the finder's, most votes first, through the same probe, pass, worth test and
+  // division (tests/multimodel.py, accept()), up to kMaxPeriodSteps accepted; a multiple or a divisor of an accepted
+  // period is skipped -- a p'-stretch longer than p is a p-stretch when p' divides p -- before its passes and again
+  // behind the division.  (A forced period is one candidate; a block of 2^31 bytes or more has no bit for the merged
+  // words' flag.)  Else the leader alone.
+  const bool several = multi_steps && mixed && period_forced == 0 && (u64)n <= kStepLength;
+  const u32 n_cands = several ? cands.n : std::min(cands.n, 1u);
+  // While a run step is due d_runK holds k_1[] for it, so the passes are trials.  Else the first candidate weighed stores
+  // its lengths: where one period is all there is, the block is MIXED's from here on.
   const bool store = !run_due;
-  if (multi_steps && mixed && voted && (u64)n <= kStepLength) {
-    // BWTC_HIP_MULTI: every candidate of the finder's, most votes first, through the same probe, pass, worth test and
-    // division (tests/multimodel.py, accept()); a multiple or a divisor of an accepted period is skipped -- a p'-stretch
-    // longer than p is a p-stretch when p' divides p -- before its passes and again behind the division.  The passes are
-    // trials, but for the first one weighed where no run step is due: where one period is all there is, the block is
-    // MIXED's from here on, lengths stored.  (A block of 2^31 bytes or more has no bit for the merged words' flag.)
-    struct { u32 p, gate, votes, longest; } acc[BlockSort::kMaxPeriodSteps];
-    int na = 0;
-    const auto related = [&](u32 q) { for (int i = 0; i < na; ++i) if (q % acc[i].p == 0 || acc[i].p % q == 0) return true; return false; };
-    bool first = true;
-    for (u32 c = 0; c < blk.n_cands && na < BlockSort::kMaxPeriodSteps; ++c) {
-      if (related(blk.cand_p[c])) continue;
-      blk.period_p = blk.cand_p[c];
-      const int rcw = weigh_period(n, h_first, true, store && first);
-      if (rcw) return rcw;
-      first = false;
-      if (blk.period_p < 2 || related(blk.period_p)) continue;
-      acc[na].p = blk.period_p; acc[na].gate = blk.proper_longest; acc[na].votes = blk.cand_votes[c]; acc[na++].longest = blk.period_longest;
-    }
-    std::sort(acc, acc + na, [](const auto& a, const auto& b) { return a.p < b.p; });
-    blk.period_p = na ? acc[0].p : 0u;
-    if (na) { blk.period_votes = acc[0].votes; blk.period_longest = acc[0].longest; blk.proper_longest = acc[0].gate; }
-    if (na >= 2) {
-      // Several periods: the steps merge their look-up lengths in d_runK, each storing when it is due (step_due).  The
-      // first round's are those with p <= h_first, by ascending p; the first of them ranks the runs too, in place of the
-      // run step that was due.  The others wait, by ascending p.
-      blk.merged = true;
-      bool any_first = false;
-      for (int i = 0; i < na; ++i) any_first = any_first || ((u64)acc[i].p <= h_first && (u64)acc[i].gate > h_first);
-      if (run_due) { if (any_first) blk.n_steps = 0; else blk.steps[0].gate = blk.run_longest; }
-      for (int i = 0; i < na; ++i)
-        if ((u64)acc[i].p <= h_first && (u64)acc[i].gate > h_first) {
-          blk.schedule(acc[i].p, StretchStep::kThisRound, acc[i].gate, acc[i].votes);
-          if (run_due && blk.n_steps == 1) blk.steps[0].ranks_runs = true;
-        }
-      for (int i = 0; i < na; ++i)
-        if ((u64)acc[i].p > h_first && acc[i].gate > acc[i].p) blk.schedule(acc[i].p, StretchStep::kWaiting, acc[i].gate, acc[i].votes);
-      return 0;
-    }
-    if (na == 1 && store && blk.lengths_period != blk.period_p) {
-      const int rcb = stretch_lengths(n, blk.period_p, true, &blk.period_longest, proper);
-      if (rcb) return rcb;
-    }
-  } else {
-    const int rcw = weigh_period(n, h_first, mixed, store);
+  WeighedPeriod acc[BlockSort::kMaxPeriodSteps];
+  int na = 0;
+  const auto related = [&](u32 q) { for (int i = 0; i < na; ++i) if (q % acc[i].p == 0 || acc[i].p % q == 0) return true; return false; };
+  blk.weighed.votes = cands.at[0].votes;
+  for (u32 c = 0; c < n_cands && na < BlockSort::kMaxPeriodSteps; ++c) {
+    if (related(cands.at[c].p)) continue;
+    WeighedPeriod w;
+    const int rcw = weigh_period(n, h_first, mixed, store && c == 0, cands.at[c].p, cands.at[c].votes, &w);
     if (rcw) return rcw;
+    if (w.longest) { blk.weighed.longest = w.longest; blk.weighed.proper = w.proper; }   // (a refused candidate's too: the last pass made)
+    if (w.p && !related(w.p)) acc[na++] = w;
   }
-  bool period_step = false;
-  if (blk.period_p >= 2 && (u64)blk.period_p <= h_first) {
-    if ((u64)g > h_first) {
-      // this round.  Where the run step was due, it is ONE period step over k_p[] instead, which ranks the runs too
-      // (k_p = k_1 for k_1 >= p): the storing pass overwrites k_1[]
-      if (run_due) {
-        const int rcb = stretch_lengths(n, blk.period_p, true, &blk.period_longest, proper);
-        if (rcb) return rcb;
-      }
-      blk.set_step(StretchStep{blk.period_p, StretchStep::kThisRound, 0, run_due});
-      period_step = true;
-    }
-  } else if (blk.period_p >= 2 && g > blk.period_p) {
-    blk.schedule(blk.period_p, StretchStep::kWaiting);   // behind the run step, if one is due (step_due)
-    period_step = true;
+  std::sort(acc, acc + na, [](const WeighedPeriod& a, const WeighedPeriod& b) { return a.p < b.p; });
+  // The first round's steps are those with p <= h_first whose stretches are longer than that, by ascending p; the others
+  // wait, by ascending p, as long as their stretches are longer than p.
+  const auto first_round = [&](const WeighedPeriod& w) { return (u64)w.p <= h_first && (u64)w.gate(mixed) > h_first; };
+  const auto waits = [&](const WeighedPeriod& w) { return (u64)w.p > h_first && w.gate(mixed) > w.p; };
+  // Several periods: the steps merge their look-up lengths in d_runK, each storing when it is due (step_due, store_step).
+  // One period: d_runK holds its k_p[] alone, stored here -- by the first candidate's pass above, or now where another
+  // candidate stored or where the step is the first round's over a run step that was due: ONE period step over k_p[]
+  // instead, which ranks the runs too (k_p = k_1 for k_1 >= p), so the storing pass overwrites k_1[].  (A step that
+  // waits behind the run step stores when it is due.)
+  blk.merged = na >= 2;
+  if (na == 1 && (store ? blk.lengths_period != acc[0].p : first_round(acc[0]))) {
+    const int rcb = stretch_lengths(n, acc[0].p, true, &acc[0].longest, mixed ? &acc[0].proper : nullptr);
+    if (rcb) return rcb;
   }
-  if (!period_step) say_no_period_step(*this, h_first);
-  if (multi_steps)   // (one period or none: MIXED's schedule, with what the getter reports beside it)
-    for (int i = 0; i < blk.n_steps; ++i) {
-      blk.steps[i].gate = blk.steps[i].p == 1 ? blk.run_longest : g;
-      blk.steps[i].votes = blk.steps[i].p == 1 ? 0u : blk.period_votes;
+  if (na) blk.weighed = acc[0];
+  bool any_first = false;
+  for (int i = 0; i < na; ++i) any_first = any_first || first_round(acc[i]);
+  if (any_first) blk.n_steps = 0;                        // (the first of them ranks the runs too, in place of the run step that was due)
+  int period_steps = 0;
+  for (int i = 0; i < na; ++i)
+    if (first_round(acc[i])) {
+      blk.schedule(acc[i], StretchStep::kThisRound);
+      if (run_due && blk.n_steps == 1) blk.steps[0].ranks_runs = true;
+      ++period_steps;
     }
+  for (int i = 0; i < na; ++i)
+    if (waits(acc[i])) { blk.schedule(acc[i], StretchStep::kWaiting); ++period_steps; }   // behind the run step, if one is due (step_due)
+  // (a voted period that was accepted is the first round's or waits, by the worth test; a forced one may be neither)
+  if (!period_steps) say_no_period_step(*this, h_first);
   return 0;
 }
 
-// The block's period, into period_p (0: none worth the pass) and period_votes: BWTC_HIP_PERIOD's, or the vote's winner
-// if its votes reach the threshold -- a 64th of the block, and kPeriodMinVotes at the least.
-int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask) {
-  if (period_forced) { blk.period_p = period_forced; blk.period_votes = 0; return 0; }
+// The block's candidate periods, most votes first: BWTC_HIP_PERIOD's, or those of the vote over the list whose votes reach
+// the threshold -- a 64th of the block, and kPeriodMinVotes at the least; the leader alone unless BWTC_HIP_MULTI.
+int BwtEngine::find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask, PeriodCandidates* out) {
+  *out = PeriodCandidates{};
+  if (period_forced) { out->n = 1; out->at[0].p = period_forced; return 0; }
   if (m < 2) return 0;
   hipStream_t st = stream;
   const u64 need = std::max<u64>(kPeriodMinVotes, (u64)n / 64);
+  // (d_runK holds k_1[] where the run step is due: decide_step made it just now)
+  const bool runs_out = mixed_steps && blk.lengths_period == 1 && blk.steps[0].p == 1;
+  u32 found[2 * kPeriodCandidates] = {}, n_found = 0;   // (distance, votes) pairs, as the finder's kernels leave them (PeriodCandidates::at)
+  bool say_leader = false;
   if (long_periods) {
     // BWTC_HIP_LONG_PERIODS: the same pass over the list votes for the distances up to min(kLongPeriodMax, n / 8) too (a
     // longer period's stretch of kPeriodWorth periods has no room in the block), and the candidates are the merged ones
-    const bool runs_out = mixed_steps && blk.lengths_period == 1 && blk.steps[0].p == 1;
     const u32 dmax = (u32)std::min<u64>(kLongPeriodMax, (u64)n / kPeriodWorth);
-    u32 found[2 * kPeriodCandidates], n_found = 0;
     bool swept = false;
     const int rcl = long_period_votes(ks, vs, m, kmask, runs_out ? (const u32*)d_runK : nullptr, (u32)need, dmax, !multi_steps, found, &n_found, &swept);
     if (rcl) return rcl;
-    if (multi_steps) {
-      blk.n_cands = n_found;
-      for (u32 c = 0; c < blk.n_cands; ++c) { blk.cand_p[c] = found[2 * c]; blk.cand_votes[c] = found[2 * c + 1]; }
-    }
-    const u32 winner = found[0];
-    blk.period_votes = found[1];
-    blk.period_p = (winner >= 2 && (u64)blk.period_votes >= need) ? winner : 0u;
     // (what the short finder counts, so that a block without a long candidate counts what it did; sweep 2: the list again, its tables)
     stats.alg_bytes += (u64)m * (8 + 4) + (u64)kVoteBins * 8 + (multi_steps ? (u64)kVoteBins * 4 : 0) + (swept ? (u64)m * (8 + 4) + (u64)kLongSel * kFineBins * 4 : 0);
-    return 0;
-  }
-  PassTimer timer(st);
-  const bool timed = timer.on;
-  BWTC_HIP_TRY(hipMemsetAsync(d_votes, 0, (size_t)kVoteBins * 4, st));
-  BWTC_HIP_TRY(timer.start());
-  // (d_runK holds k_1[] where the run step is due: decide_step made it just now)
-  if (mixed_steps && blk.lengths_period == 1 && blk.steps[0].p == 1)
-    hipLaunchKernelGGL(k_period_votes<true>, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, (const u32*)d_runK);
-  else
-    hipLaunchKernelGGL(k_period_votes<false>, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, (const u32*)nullptr);
-  BWTC_HIP_TRY(timer.stop());
-  if (multi_steps) {
-    // BWTC_HIP_MULTI: the up to kPeriodCandidates distances whose votes reach the threshold, not the winner alone
-    u32 found[2 * kPeriodCandidates];
-    const int rcw = period_winners((u32)need, found, &blk.n_cands);
-    if (rcw) return rcw;
-    for (u32 c = 0; c < blk.n_cands; ++c) { blk.cand_p[c] = found[2 * c]; blk.cand_votes[c] = found[2 * c + 1]; }
   } else {
-    hipLaunchKernelGGL(k_period_winner, dim3(1), dim3(1024), 0, st, (const u32*)d_votes, d_small + kSmallPeriod + 2);
-    BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 2, d_small + kSmallPeriod + 2, 8, hipMemcpyDeviceToHost, st));
-    BWTC_HIP_TRY(wait());
+    PassTimer timer(st);
+    BWTC_HIP_TRY(hipMemsetAsync(d_votes, 0, (size_t)kVoteBins * 4, st));
+    BWTC_HIP_TRY(timer.start());
+    if (runs_out)
+      hipLaunchKernelGGL(k_period_votes<true>, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, (const u32*)d_runK);
+    else
+      hipLaunchKernelGGL(k_period_votes<false>, dim3(ceil_div(m, kVoteTile)), dim3(kVoteTPB), 0, st, ks, vs, m, kmask, d_votes, (const u32*)nullptr);
+    BWTC_HIP_TRY(timer.stop());
+    if (multi_steps) {
+      // BWTC_HIP_MULTI: the up to kPeriodCandidates distances whose votes reach the threshold, not the winner alone
+      const int rcw = period_winners((u32)need, found, &n_found);
+      if (rcw) return rcw;
+    } else {
+      hipLaunchKernelGGL(k_period_winner, dim3(1), dim3(1024), 0, st, (const u32*)d_votes, d_small + kSmallPeriod + 2);
+      BWTC_HIP_TRY(hipMemcpyAsync(h_small + kSmallPeriod + 2, d_small + kSmallPeriod + 2, 8, hipMemcpyDeviceToHost, st));
+      BWTC_HIP_TRY(wait());
+      found[0] = h_small[kSmallPeriod + 2]; found[1] = h_small[kSmallPeriod + 3];
+    }
+    if (timer.on) {
+      float ms = 0.f;
+      BWTC_HIP_TRY(timer.ms(&ms));
+      std::fprintf(stderr, "periods: the vote kernel took %.4f ms for %u entries\n", ms, m);
+    }
+    say_leader = timer.on;                              // (the long finder says what its sweeps found instead)
+    stats.alg_bytes += (u64)m * (8 + 4) + (u64)kVoteBins * 8;   // the list's keys and suffixes read; the table zeroed and read
   }
-  if (timed) {
-    float ms = 0.f;
-    BWTC_HIP_TRY(timer.ms(&ms));
-    std::fprintf(stderr, "periods: the vote kernel took %.4f ms for %u entries\n", ms, m);
-  }
-  const u32 winner = h_small[kSmallPeriod + 2];
-  blk.period_votes = h_small[kSmallPeriod + 3];
-  blk.period_p = (winner >= 2 && (u64)blk.period_votes >= need) ? winner : 0u;
-  if (!blk.period_p && timed) std::fprintf(stderr, "periods: distance %u leads with %u votes of the %llu a pass takes\n", winner, blk.period_votes, (unsigned long long)need);
-  stats.alg_bytes += (u64)m * (8 + 4) + (u64)kVoteBins * 8;   // the list's keys and suffixes read; the table zeroed and read
+  // the winner alone: one candidate, if its votes reach the threshold
+  if (!multi_steps) n_found = (found[0] >= 2 && (u64)found[1] >= need) ? 1u : 0u;
+  out->n = n_found;
+  for (u32 c = 0; c < kPeriodCandidates; ++c) { out->at[c].p = found[2 * c]; out->at[c].votes = found[2 * c + 1]; }
+  if (!out->n && say_leader) std::fprintf(stderr, "periods: distance %u leads with %u votes of the %llu a pass takes\n", found[0], found[1], (unsigned long long)need);
   return 0;
 }
 

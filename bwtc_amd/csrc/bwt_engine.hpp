@@ -446,14 +446,24 @@ struct BwtEngine {
   // (blocks for which can_carry() holds only; see k_rerank_apply).  allow_code_keys == false: the block's second go, with gram keys.
   struct EmitTarget { u8* out; u32 out_n; u32 n_lf; };
   int suffix_sort(u32 n, const u32* hist, bool lone_sentinel, const EmitTarget* em = nullptr, bool allow_code_keys = true);
-  // This block's state: suffix_sort begins a block by assigning BlockSort{} (so does test_finisher), and nothing else resets it.
+  // A period as weigh_period leaves it: the period behind the division (0: refused), its longest stretch, its longest
+  // proper stretch (0: no pass made it) and the candidate's votes.  The worth tests go by the proper stretch under
+  // BWTC_HIP_MIXED's rule (BwtEngine::mixed_rule), else by the longest.
+  struct WeighedPeriod { u32 p = 0, longest = 0, proper = 0, votes = 0; u32 gate(bool mixed) const { return mixed ? proper : longest; } };
   // A closed-form step (runs and periods, below): its period (1: the run step), when it is due (kWaiting: the first doubling
   // round whose depth reaches p; kNone: not any more), the depth it ran at (0: it has not), and whether it ranked the runs
-  // too (BWTC_HIP_MIXED: the first round is one period step over k_p[] in place of the run step that was due).
-  // BWTC_HIP_MULTI: gate is the length the entry's gate goes by (the longest run; a period's longest proper stretch), votes
-  // the finder's for it -- they live here and nowhere else -- and dropped says that its gate was shut when its depth came.
+  // too (BWTC_HIP_MIXED: the first round is one period step over k_p[] in place of the run step that was due).  Its facts,
+  // from the moment it is scheduled and under every switch: the longest stretch of its period (the run step: the longest
+  // run), the longest proper stretch and the finder's votes for it; dropped says that its gate was shut when its depth came.
   struct StretchStep { u32 p = 0; enum When { kNone, kThisRound, kWaiting } when = kNone; u32 depth = 0; bool ranks_runs = false;
-                       u32 gate = 0, votes = 0; bool dropped = false; };
+                       u32 longest = 0, proper = 0, votes = 0; bool dropped = false;
+                       // the length bwtc_hip_schedule_get and the merged block's debug line show as the entry's gate
+                       u32 shown_gate(bool mixed) const { return p == 1 || !mixed ? longest : proper; } };
+  // The finder's candidates (find_period), most votes first: n of them reach the threshold.  at[0] also holds what the
+  // finder says of a leader below it: the winner's pair as k_period_winner and the long finder leave it, zeros under
+  // BWTC_HIP_MULTI's short finder (k_period_winners names nothing below the threshold); a forced period has no votes.
+  struct PeriodCandidates { u32 n = 0; struct { u32 p, votes; } at[kPeriodCandidates] = {}; };
+  // This block's state: suffix_sort begins a block by assigning BlockSort{} (so does test_finisher), and nothing else resets it.
   struct BlockSort {
     bool ranks_live = false;   // rank[] has been completed (every ranking step keeps it exact from then on)
     bool fin_active = false;   // the block takes the finisher route: finished suffixes also go to d_SA
@@ -471,31 +481,36 @@ struct BwtEngine {
     } fin;
     u32 lengths_period = 0;    // the period d_runK's lengths were made for (0: none yet)
     u32 run_longest = 0;       // the longest run, once a pass of period 1 has found it (made at most once per block)
-    u32 proper_longest = 0;    // BWTC_HIP_MIXED: the longest proper stretch (0: no pass has made it)
+    // What bwtc_hip_period_get and bwtc_hip_steps_get report beside the steps, and say_no_period_step's line: the period the
+    // block's first period step is for, or, where none was accepted, p = 0 with the lengths of the last pass over a
+    // candidate and the leader's votes (decide_step)
+    WeighedPeriod weighed;
     // The block's closed-form steps in the order it takes them (decide_step): the run step, then one period step, or
     // either alone; with BWTC_HIP_MULTI the run step and up to three period steps, the first round's before those that
     // wait, by ascending period.  `current` is the entry whose lengths went into d_runK last and whose period and depth the
     // second keys take (RunKeys): the front, until a step behind it comes due (step_due).
     static constexpr int kMaxSteps = 4, kMaxPeriodSteps = 3;
     StretchStep steps[kMaxSteps]; int n_steps = 0, current = 0;
-    void schedule(u32 p, StretchStep::When when, u32 gate = 0, u32 votes = 0) {
-      if (n_steps < kMaxSteps) { steps[n_steps] = StretchStep{p, when}; steps[n_steps].gate = gate; steps[n_steps++].votes = votes; }
+    void schedule(const WeighedPeriod& w, StretchStep::When when) {
+      if (n_steps < kMaxSteps) steps[n_steps++] = StretchStep{w.p, when, 0, false, w.longest, w.proper, w.votes};
     }
+    // The length the gate of waiting entry i goes by when its depth comes (step_due).  Merged steps and a step behind the
+    // run step: the longest proper stretch -- a run is no stretch there.  One waiting step at the front: the longest
+    // stretch, even where BWTC_HIP_MIXED's rule decided it by the proper one (no run step is due, so none is in its way).
+    u32 due_gate(int i) const { return merged || i > 0 ? steps[i].proper : steps[i].longest; }
+    // ... and the length its debug line shows as the longest stretch: an unmerged block's is the longest, behind a run step too
+    u32 said_longest(const StretchStep& s) const { return merged ? s.proper : s.longest; }
     // BWTC_HIP_MULTI: d_runK holds merged look-up words (tests/multimodel.py), not one period's lengths.  merged: this
     // block's steps merge; merged_stored: a storing pass has written the words (the next one is not the first);
     // merged_ran: a step has run over them, so every round's second keys read them.
     bool merged = false, merged_stored = false, merged_ran = false;
     int period_steps_ran() const { int c = 0; for (int i = 0; i < n_steps; ++i) c += steps[i].p >= 2 && steps[i].depth; return c; }
-    // the finder's candidates (BWTC_HIP_MULTI: find_period), most votes first
-    u32 n_cands = 0, cand_p[kPeriodCandidates] = {}, cand_votes[kPeriodCandidates] = {};
     void set_step(const StretchStep& s) { steps[0] = s; n_steps = 1; current = 0; }   // the one step, in place of whatever was scheduled
     StretchStep& current_step() { return steps[current]; }                           // (no step scheduled: one of period 0 and depth 0)
     // what the block's steps did, for bwtc_hip_period_get, bwtc_hip_steps_get and the debug line: the depth the runs were
     // ranked at (0: they were not), and the period step that ran (period and depth 0: none did)
     u32 run_depth() const { for (int i = 0; i < n_steps; ++i) if (steps[i].p == 1 || steps[i].ranks_runs) return steps[i].depth; return 0; }
     StretchStep period_ran() const { for (int i = 0; i < n_steps; ++i) if (steps[i].p >= 2 && steps[i].depth) return steps[i]; return StretchStep{}; }
-    // the candidate period, its longest stretch, its votes: with the step's depth, what bwtc_hip_period_get reports until the next block begins
-    u32 period_p = 0, period_longest = 0, period_votes = 0;
     // BWTC_HIP_COPIES (bwt_engine.hip, "Copies"): a pass is taken every round that may until one finds a longest K below its
     // round's depth (the gate shuts); rounds: those whose look-ups went by K[]; first_depth: the depth of the first of them
     struct Copies { bool open = true; u32 passes = 0, rounds = 0, longest = 0, first_depth = 0; } copies;
@@ -637,9 +652,14 @@ struct BwtEngine {
   struct StepMerge { u32 h; bool fresh; };   // a storing pass over the merged look-up words: the step's depth; the block's first step
   int stretch_lengths(u32 n, u32 p, bool store, u32* longest, u32* proper = nullptr, const StepMerge* merge = nullptr);
   int period_winners(u32 need, u32* out, u32* n_out);   // the finder's up to 8 candidates over d_votes (distance, votes)
-  int find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask);
-  int decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask);   // -> blk.steps
-  int weigh_period(u32 n, u64 h_first, bool mixed, bool store);   // blk.period_p through the probe, the pass, the worth test and the division
+  bool mixed_rule() const { return mixed_steps && run_ranks && period_forced != 1; }   // BWTC_HIP_MIXED's rule holds: a run is no stretch
+  // decide_step goes on to look for a period (behind a run step that is due, under the rule only); bwtc_hip_schedule_get
+  // reports gate lengths and votes for these blocks alone
+  bool looks_for_period(bool run_due) const { return period_ranks && period_forced != 1 && (!run_due || mixed_rule()); }
+  int find_period(u32 n, const u64* ks, const u32* vs, u32 m, u64 kmask, PeriodCandidates* out);
+  int decide_step(u32 n, u32 m, u64 h_first, const u64* ks, const u32* vs, u64 kmask);   // -> blk.steps, blk.weighed
+  // candidate p through the probe, the pass, the worth test and the division -> *out (p == 0: refused)
+  int weigh_period(u32 n, u64 h_first, bool mixed, bool store, u32 p, u32 votes, WeighedPeriod* out);
   int store_step(u32 n, StretchStep& step, u64 h_round, bool behind_run);   // the storing pass of the step that is due
   // long periods (bwt_engine.hip, "Long periods"): the finder votes for distances up to kLongPeriodMax too, and a period
   // above kPeriodMax takes the wide probe; everything behind them is the code a short period goes through

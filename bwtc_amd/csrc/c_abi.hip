@@ -1121,9 +1121,9 @@ int bwtc_hip_test_radix_long(bwtc_hip_ctx* ctx, uint64_t* keys, void* vals, uint
 int bwtc_hip_period_get(bwtc_hip_ctx* ctx, uint32_t* p, uint32_t* longest, uint32_t* votes, uint32_t* step_depth) {
   if (!ctx) return -1;
   const BwtEngine& e = ctx->eng;
-  if (p) *p = e.blk.period_p;
-  if (longest) *longest = e.blk.period_longest;
-  if (votes) *votes = e.blk.period_votes;
+  if (p) *p = e.blk.weighed.p;
+  if (longest) *longest = e.blk.weighed.longest;
+  if (votes) *votes = e.blk.weighed.votes;
   if (step_depth) *step_depth = e.blk.period_ran().depth;
   return 0;
 }
@@ -1140,7 +1140,7 @@ int bwtc_hip_steps_get(bwtc_hip_ctx* ctx, uint32_t* run_depth, uint32_t* period_
   if (period_p) *period_p = period.p;
   if (period_depth) *period_depth = period.depth;
   if (longest_run) *longest_run = b.run_longest;
-  if (longest_proper) *longest_proper = b.proper_longest;
+  if (longest_proper) *longest_proper = b.weighed.proper;
   return 0;
 }
 
@@ -1166,15 +1166,19 @@ int bwtc_hip_test_copy_lengths(bwtc_hip_ctx* ctx, const uint32_t* suf, const uin
 
 // The last block's schedule of closed-form steps, in the order it took them: 5 words per entry -- the period (1: the run
 // step), the depth it ran at or 0, its gate length, its votes, flags (1: it ranked the runs too; 2: it was dropped).
-// Gate lengths and votes are made under BWTC_HIP_MULTI only.  *n_out: the block's entries, of which min(cap, *n_out) are written.
+// Gate lengths and votes are reported under BWTC_HIP_MULTI only, by the blocks that look for a period; else 0.
+// *n_out: the block's entries, of which min(cap, *n_out) are written.
 int bwtc_hip_schedule_get(bwtc_hip_ctx* ctx, uint32_t* entries, uint32_t cap, uint32_t* n_out) {
   if (!ctx || !n_out || (cap && !entries)) return -1;
-  const BwtEngine::BlockSort& b = ctx->eng.blk;
+  const BwtEngine& e = ctx->eng;
+  const BwtEngine::BlockSort& b = e.blk;
+  // (under the switch a run step is due only where the rule holds or BWTC_HIP_PERIOD=1, so run_due decides nothing here)
+  const bool reported = e.multi_steps && e.looks_for_period(false);
   *n_out = (uint32_t)b.n_steps;
   for (u32 i = 0; i < cap && i < (u32)b.n_steps; ++i) {
     const BwtEngine::StretchStep& s = b.steps[i];
     uint32_t* w = entries + 5 * i;
-    w[0] = s.p; w[1] = s.depth; w[2] = s.gate; w[3] = s.votes; w[4] = (s.ranks_runs ? 1u : 0u) | (s.dropped ? 2u : 0u);
+    w[0] = s.p; w[1] = s.depth; w[2] = reported ? s.shown_gate(e.mixed_rule()) : 0u; w[3] = reported ? s.votes : 0u; w[4] = (s.ranks_runs ? 1u : 0u) | (s.dropped ? 2u : 0u);
   }
   return 0;
 }

@@ -240,3 +240,46 @@ def test_random_mixed_blocks(oracle, monkeypatch):
             d, sp, p = mc.random_block(it)
             st = _same(ctx, d, sp, oracle.oracle_bwt_block(d, sp), (it, d.size, sp))
             assert st.route & BOTH == BOTH and ctx.steps()[1] == p, (it, p, d.size, hex(st.route), ctx.steps(), ctx.period())
+
+
+# ---- 9. the schedule beside steps() and period(), with no switch, MIXED and MULTI -------------------
+
+def test_the_schedule_agrees_with_steps_and_period(oracle, monkeypatch):
+    """One stretch (first round's and deferred) and a run beside one (merged into one step, and the step behind the run
+    step) on a context with no switch, one with BWTC_HIP_MIXED=1 and one with BWTC_HIP_MULTI=1: the bytes; schedule()'s
+    periods and depths are steps()'s and period()'s; gate and votes are 0 without MULTI, and with it a period entry's
+    gate is the longest proper stretch and the run entry's the longest run."""
+    from bwtc_amd import hip
+    blocks = [("stretch 9", pc.stretch(9, 1 << 16)), ("stretch 257", pc.stretch(257, 1 << 16)),
+              ("run and stretch 9", mc.run_and_stretch(9, 1 << 16, 1 << 16)), ("run and stretch 300", mc.run_and_stretch(300, 1 << 16, 1 << 16)),
+              # (the four above have one length for the longest run, stretch and proper stretch; this one has three)
+              ("short runs beside stretches", mc.short_runs_beside_stretches(64, 16))]
+    wants = [oracle.oracle_bwt_block(d, 8) for _, d in blocks]
+    stepped = set()
+    for switch in ("", "BWTC_HIP_MIXED", "BWTC_HIP_MULTI"):
+        if switch:
+            monkeypatch.setenv(switch, "1")
+        ctx = hip.Context(0, 1 << 20)
+        if switch:
+            monkeypatch.delenv(switch)
+        with ctx:
+            for (what, d), want in zip(blocks, wants):
+                _same(ctx, d, 8, want, (switch, what))
+                schedule, steps, period = ctx.schedule(), ctx.steps(), ctx.period()
+                print("%s [%s]: schedule %s steps %s period %s" % (what, switch, schedule, steps, period))
+                runs = [e for e in schedule if e[0] == 1 or e[4] & 1]
+                periods = [e for e in schedule if e[0] >= 2]
+                ran = [e for e in periods if e[1]]
+                assert len(runs) <= 1 and len(periods) <= 1, (switch, what, schedule)
+                assert steps[0] == (runs[0][1] if runs else 0), (switch, what, schedule, steps)
+                assert (steps[1], steps[2]) == (ran[0][:2] if ran else (0, 0)) and period[3] == steps[2], (switch, what, schedule, steps, period)
+                assert all(e[0] == period[0] for e in periods), (switch, what, schedule, period)
+                if switch == "BWTC_HIP_MULTI":
+                    assert all(e[2] == steps[4] for e in periods), (what, schedule, steps)
+                    assert all(e[2] == steps[3] for e in schedule if e[0] == 1), (what, schedule, steps)
+                else:
+                    assert all(e[2] == 0 and e[3] == 0 for e in schedule), (switch, what, schedule)
+                if ran:
+                    stepped.add((switch, what))
+    # (every block takes its period step on some context, so the words compared above are not all zeros)
+    assert {what for _, what in stepped} == {what for what, _ in blocks}, stepped
