@@ -4,6 +4,7 @@
 #include "huffman_decoder.hpp"
 #include "postprocess.hpp"
 #include "wavelet_rebuild.hpp"
+#include "batch_bwt.hpp"
 #include "prepr_host.hpp"
 #include <new>
 #include "radix_sort.hpp"
@@ -27,6 +28,7 @@ struct bwtc_hip_ctx {
   bwtc_hip::HDecoder* hdec = nullptr;   // 'H' decoder, made by the first decode call
   bwtc_hip::PostProcessor* post = nullptr;   // `--prepr` postprocessor, made by the first postprocess call
   bwtc_hip::WRebuild* wreb = nullptr;        // wavelet rebuild, made by the first 'B' / 'b' / 'u' decode call
+  bwtc_hip_batch_stats batch_stats = {};     // what the last batched transform did (batch_bwt.hip)
 };
 struct bwtc_hip_wavelet_decoder {
   bwtc_hip::WDecoderState* state;
@@ -397,6 +399,28 @@ int bwtc_hip_bwt_block_device(bwtc_hip_ctx* ctx, const uint8_t* d_in, uint8_t* d
   BwtEngine& e = ctx->eng;
   if (size > e.max_block) return -1;
   return e.transform(d_in, d_out, size, false, lf, n_lf, freqs);
+}
+
+// ---- batched block transform (batch_bwt.hip) ----
+int bwtc_hip_bwt_blocks(bwtc_hip_ctx* ctx, uint8_t* data, const bwtc_hip_batch_item* items, uint32_t k,
+                        uint32_t* lf, uint32_t* freqs) {
+  if (!ctx) return -1;
+  return batch_transform_host(ctx->eng, data, items, k, lf, freqs, &ctx->batch_stats);
+}
+int bwtc_hip_bwt_blocks_device(bwtc_hip_ctx* ctx, const uint8_t* d_in, uint8_t* d_out,
+                               const bwtc_hip_batch_item* items, uint32_t k, uint32_t* lf, uint32_t* freqs) {
+  if (!ctx) return -1;
+  return batch_transform_device(ctx->eng, d_in, d_out, items, k, lf, freqs, &ctx->batch_stats);
+}
+int bwtc_hip_batch_stats_get(bwtc_hip_ctx* ctx, bwtc_hip_batch_stats* out) {
+  if (!ctx || !out) return -1;
+  *out = ctx->batch_stats;
+  return 0;
+}
+int bwtc_hip_test_batch_keys(bwtc_hip_ctx* ctx, const uint8_t* data, const bwtc_hip_batch_item* items, uint32_t k,
+                             uint8_t* T_out, uint64_t* keys_out, uint32_t* freqs_out) {
+  if (!ctx) return -1;
+  return batch_test_keys(ctx->eng, data, items, k, T_out, keys_out, freqs_out);
 }
 
 int bwtc_hip_inverse_bwt_block(bwtc_hip_ctx* ctx, uint8_t* block, uint32_t size,

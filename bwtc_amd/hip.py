@@ -238,6 +238,17 @@ class ModelsOut(ctypes.Structure):
                [(f, _vp) for f in ("chunks", "cmap", "cstate", "base", "sb", "sbits", "smap", "snaps", "sstart")]
 
 
+class BatchItem(ctypes.Structure):
+    """bwtc_hip_batch_item: one block of a batched transform."""
+    _fields_ = [("offset", _u64), ("size", _u32), ("n_lf", _u32)]
+
+
+class BatchStats(ctypes.Structure):
+    """bwtc_hip_batch_stats: what the last batched transform on a context did."""
+    _fields_ = [("blocks", _u32), ("stride_log2", _u32), ("rounds", _u32), ("host_waits", _u32), ("suffixes", _u64),
+                ("active", _u64 * 32), ("ms_total", ctypes.c_float)]
+
+
 class KernelTimers(ctypes.Structure):
     _fields_ = [("scatter_launches", _u64), ("scatter_bytes", _u64), ("scatter_ms", ctypes.c_double)]
 
@@ -252,6 +263,7 @@ EXPORTS = [
     "bwtc_hip_memcpy_to_host", "bwtc_hip_host_alloc", "bwtc_hip_host_free",
     "bwtc_hip_memcpy_to_device_async", "bwtc_hip_copy_wait", "bwtc_hip_wavelet_host_clock", "bwtc_hip_wavelet_host_progress", "bwtc_hip_wavelet_latency", "bwtc_hip_wavelet_routes", "bwtc_hip_host_staging_bytes", "bwtc_hip_host_usable_cpus", "bwtc_hip_n_lf", "bwtc_hip_bwt",
     "bwtc_hip_bwt_block", "bwtc_hip_bwt_block_device", "bwtc_hip_inverse_bwt_block",
+    "bwtc_hip_bwt_blocks", "bwtc_hip_bwt_blocks_device", "bwtc_hip_batch_stats_get", "bwtc_hip_test_batch_keys",
     "bwtc_hip_inverse_bwt_block_device", "bwtc_hip_compress_bound",
     "bwtc_hip_huffman_encode_device", "bwtc_hip_huffman_encode", "bwtc_hip_transform_and_encode",
     "bwtc_hip_wavelet_section_stats", "bwtc_hip_transform_and_encode_wavelet", "bwtc_hip_wavelet_encode",
@@ -334,6 +346,10 @@ def load():
     L.bwtc_hip_bwt.argtypes = [_vp, _vp, _u32, _vp, _u32, _vp]
     L.bwtc_hip_bwt_block.argtypes = [_vp, _vp, _u32, _vp, _u32, _vp]
     L.bwtc_hip_bwt_block_device.argtypes = [_vp, _vp, _vp, _u32, _vp, _u32, _vp]
+    L.bwtc_hip_bwt_blocks.argtypes = [_vp, _vp, _vp, _u32, _vp, _vp]
+    L.bwtc_hip_bwt_blocks_device.argtypes = [_vp, _vp, _vp, _vp, _u32, _vp, _vp]
+    L.bwtc_hip_batch_stats_get.argtypes = [_vp, ctypes.POINTER(BatchStats)]
+    L.bwtc_hip_test_batch_keys.argtypes = [_vp, _vp, _vp, _u32, _vp, _vp, _vp]
     L.bwtc_hip_inverse_bwt_block.argtypes = [_vp, _vp, _u32, _vp, _u32]
     L.bwtc_hip_inverse_bwt_block_device.argtypes = [_vp, _vp, _vp, _u32, _vp, _u32]
     L.bwtc_hip_compress_bound.restype = _u64
@@ -801,6 +817,73 @@ class Context:
                                                   _ptr(lf), n_lf, _ptr(freqs)),
                "bwtc_hip_bwt_block_device")
         return lf, freqs
+
+    def _batch_items(self, offsets, sizes, starting_points):
+        items = (BatchItem * len(sizes))()
+        for i, (off, size) in enumerate(zip(offsets, sizes)):
+            items[i].offset, items[i].size = int(off), int(size)
+            items[i].n_lf = self.n_lf(int(size), starting_points) if size else 1
+        return items
+
+    def bwt_blocks(self, blocks, starting_points=8):
+        """bwtc_hip_bwt_blocks: every block of the list in one batched call; a list of (bwt bytes, LFpowers,
+        freqs), each as bwt_block gives it.  The blocks lie side by side in one buffer with a guard byte after each,
+        which is checked to be untouched."""
+        arrs = [np.ascontiguousarray(np.frombuffer(bytes(b), dtype=np.uint8) if not isinstance(b, np.ndarray) else b,
+                                     dtype=np.uint8) for b in blocks]
+        sizes = [a.size for a in arrs]
+        offsets = [0] * len(arrs)
+        for i in range(1, len(arrs)):
+            offsets[i] = offsets[i - 1] + sizes[i - 1] + 1
+        buf = np.full(sum(sizes) + len(sizes) + 1, 0xA5, np.uint8)
+        for a, off in zip(arrs, offsets):
+            buf[off:off + a.size] = a
+        items = self._batch_items(offsets, sizes, starting_points)
+        lf = np.zeros((max(len(arrs), 1), 256), np.uint32)
+        freqs = np.zeros((max(len(arrs), 1), 256), np.uint32)
+        _check(self.lib.bwtc_hip_bwt_blocks(self.handle, _ptr(buf), ctypes.cast(items, _vp), len(arrs), _ptr(lf), _ptr(freqs)),
+               "bwtc_hip_bwt_blocks")
+        for off, size in zip(offsets, sizes):
+            if buf[off + size] != 0xA5:
+                raise BwtcHipError("byte after a block was modified")
+        return [(buf[off:off + size].copy(), lf[i, :items[i].n_lf].copy(), freqs[i].copy())
+                for i, (off, size) in enumerate(zip(offsets, sizes))]
+
+    def bwt_blocks_device(self, d_in_ptr, d_out_ptr, offsets, sizes, starting_points=8, n_lf=None):
+        """bwtc_hip_bwt_blocks_device over device pointers (they may be the same): block i is `sizes[i]` bytes at
+        `offsets[i]` of both.  Returns (lf rows [k, 256], freqs rows [k, 256], the n_lf of every block); n_lf: the
+        blocks' numbers of LF powers where they are not to come from n_lf()."""
+        items = self._batch_items(offsets, sizes, starting_points)
+        if n_lf is not None:
+            for i, v in enumerate(n_lf):
+                items[i].n_lf = int(v)
+        k = len(sizes)
+        lf = np.zeros((max(k, 1), 256), np.uint32)
+        freqs = np.zeros((max(k, 1), 256), np.uint32)
+        _check(self.lib.bwtc_hip_bwt_blocks_device(self.handle, _vp(d_in_ptr), _vp(d_out_ptr), ctypes.cast(items, _vp), k,
+                                                   _ptr(lf), _ptr(freqs)), "bwtc_hip_bwt_blocks_device")
+        return lf, freqs, [int(items[i].n_lf) for i in range(k)]
+
+    def batch_stats(self):
+        """bwtc_hip_batch_stats_get as a dict (active: the entries left after the initial sort and after every round)."""
+        s = BatchStats()
+        _check(self.lib.bwtc_hip_batch_stats_get(self.handle, ctypes.byref(s)), "bwtc_hip_batch_stats_get")
+        d = {f: getattr(s, f) for f in ("blocks", "stride_log2", "rounds", "host_waits", "suffixes", "ms_total")}
+        d["active"] = [int(v) for v in s.active][:min(int(s.rounds), 31) + 1]
+        return d
+
+    def test_batch_keys(self, data, offsets, sizes):
+        """bwtc_hip_test_batch_keys: the load pass and the initial keys of the blocks at `offsets` of `data`:
+        (T of every block one after the other, keys in the same order, counts [k, 256])."""
+        data = np.ascontiguousarray(data, np.uint8)
+        items = self._batch_items(offsets, sizes, 1)
+        m = int(sum(sizes)) + len(sizes)
+        T = np.zeros(m, np.uint8)
+        keys = np.zeros(m, np.uint64)
+        freqs = np.zeros((max(len(sizes), 1), 256), np.uint32)
+        _check(self.lib.bwtc_hip_test_batch_keys(self.handle, _ptr(data), ctypes.cast(items, _vp), len(sizes), _ptr(T), _ptr(keys),
+                                                 _ptr(freqs)), "bwtc_hip_test_batch_keys")
+        return T, keys, freqs
 
     def inverse_bwt_block(self, bwt, lf):
         """InverseBWTransform::doTransform(BWTBlock&): returns the original block; raises

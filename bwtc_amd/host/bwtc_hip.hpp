@@ -252,6 +252,26 @@ class HipBWTransform : public BWTransform {
                                 (uint32)block.LFpowers().size(), freqs), "bwtc_hip_bwt_block");
     block.setTransformed(true);
   }
+  // Many blocks in one batched call (bwtc_hip_bwt_blocks): each block as doTransform(block, freqs) leaves it, LFpowers
+  // sized by the caller; freqs: blocks.size() rows of 256, incremented, or 0.  The blocks lie anywhere in host memory
+  // (they may touch, not overlap); the context must hold blocks.size() strides (bwtc_hip.h).
+  void doTransformBatch(std::vector<BWTBlock>& blocks, uint32* freqs) {
+    if (blocks.empty()) return;
+    byte* low = blocks[0].begin();
+    for (size_t i = 1; i < blocks.size(); ++i) low = std::min(low, blocks[i].begin());
+    std::vector<bwtc_hip_batch_item> items(blocks.size());
+    for (size_t i = 0; i < blocks.size(); ++i) {
+      items[i].offset = (uint64_t)(blocks[i].begin() - low);
+      items[i].size = (uint32)blocks[i].size();
+      items[i].n_lf = (uint32)blocks[i].LFpowers().size();
+    }
+    std::vector<uint32> lf(blocks.size() * 256);
+    hipFatal(bwtc_hip_bwt_blocks(m_ctx, low, &items[0], (uint32)items.size(), &lf[0], freqs), "bwtc_hip_bwt_blocks");
+    for (size_t i = 0; i < blocks.size(); ++i) {
+      std::copy(lf.begin() + i * 256, lf.begin() + i * 256 + items[i].n_lf, blocks[i].LFpowers().begin());
+      blocks[i].setTransformed(true);
+    }
+  }
   uint64 maxSizeInBytes(uint64 n) const { return bwtc_hip_workspace_bytes((uint32)n); }
   uint64 maxBlockSize(uint64) const { return 0x7fffffffu - 2; }
   uint64 suggestedBlockSize(uint64) const { return 256u << 20; }
@@ -274,6 +294,13 @@ class BWTManager {
     assert(!block.isTransformed());
     block.prepareLFpowers(m_startingPoints);
     m_transformers[0]->doTransform(block, freqs);
+  }
+  void doTransformBatch(std::vector<BWTBlock>& blocks, uint32* freqs) {
+    for (size_t i = 0; i < blocks.size(); ++i) {
+      assert(!blocks[i].isTransformed());
+      blocks[i].prepareLFpowers(m_startingPoints);
+    }
+    static_cast<HipBWTransform*>(m_transformers[0])->doTransformBatch(blocks, freqs);
   }
   // maxBlockSize / device are what the GPU back-end needs to size its workspace
   void setMaxBlockSize(uint32 n) { m_maxBlock = n; }
@@ -358,6 +385,14 @@ class EntropyEncoder {
   // how many blocks the caller should keep under way right now (never more than depth())
   virtual size_t inFlightLimit() const { return depth(); }
   virtual size_t finishOldest(OutStream*) { return 0; }
+  // Encode-only steps for a block that a batched transform left on the device (d_bwt: its size() transformed bytes;
+  // the block carries its LFpowers, freqs are its byte counts): what transformAndEncode / begin do behind the transform.
+  virtual size_t encodeTransformed(const uint8_t*, BWTBlock&, const uint32*, BWTManager&, OutStream*) {
+    std::fprintf(stderr, "bwtc-hip: this coder has no encode-only step\n"); std::exit(1);
+  }
+  virtual void beginTransformed(const uint8_t*, BWTBlock&, const uint32*, BWTManager&) {
+    std::fprintf(stderr, "bwtc-hip: this coder has no encode-only step\n"); std::exit(1);
+  }
 };
 
 class HuffmanEncoder : public EntropyEncoder {
@@ -376,8 +411,30 @@ class HuffmanEncoder : public EntropyEncoder {
     out->writeBlock(&m_record[0], &m_record[0] + n);
     return (size_t)n;
   }
+  ~HuffmanEncoder() { if (m_ctx && m_dev) bwtc_hip_free(m_ctx, m_dev); }
+  // the record is made on the device (bwtc_hip_huffman_encode_device) and copied down
+  size_t encodeTransformed(const uint8_t* d_bwt, BWTBlock& block, const uint32* freqs, BWTManager& bwtm, OutStream* out) {
+    m_ctx = bwtm.hipContext();
+    const uint64 cap = bwtc_hip_compress_bound((uint32)block.size());
+    if (m_devBytes < cap) {
+      if (m_dev) bwtc_hip_free(m_ctx, m_dev);
+      m_dev = bwtc_hip_malloc(m_ctx, cap);
+      if (!m_dev) hipFatal(-2, "bwtc_hip_malloc");
+      m_devBytes = cap;
+    }
+    uint64_t n = 0;
+    hipFatal(bwtc_hip_huffman_encode_device(m_ctx, d_bwt, (uint32)block.size(), &block.LFpowers()[0], (uint32)block.LFpowers().size(),
+                                            freqs, static_cast<uint8_t*>(m_dev), cap, &n), "bwtc_hip_huffman_encode_device");
+    m_record.resize(n);
+    hipFatal(bwtc_hip_memcpy_to_host(m_ctx, &m_record[0], m_dev, n), "bwtc_hip_memcpy_to_host");
+    out->writeBlock(&m_record[0], &m_record[0] + n);
+    return (size_t)n;
+  }
  private:
   std::vector<byte> m_record;
+  bwtc_hip_ctx* m_ctx = 0;
+  void* m_dev = 0;
+  uint64 m_devBytes = 0;
 };
 
 // WaveletCoders.hpp:48-77; the letter picks the main model (giveProbabilityModel).  The encoder object carries the main model's
@@ -456,6 +513,28 @@ class WaveletEncoder : public EntropyEncoder {
              "bwtc_hip_bwt_block_device");
     hipFatal(bwtc_hip_wavelet_encode_device_begin(m_ctx, static_cast<const uint8_t*>(m_dev), size,
                                                   &block.LFpowers()[0], (uint32)block.LFpowers().size(),
+                                                  freqs, 0, slot.rec, slot.cap, &slot.ticket),
+             "bwtc_hip_wavelet_encode_device_begin");
+    m_order.push_back(m_next % slots);
+    ++m_next;
+  }
+  // begin() for a block already transformed on the device: the run scanner and stream kernels read d_bwt, the models
+  // and range coders are queued; d_bwt must stay as it is until the block has been finished (finishOldest)
+  void beginTransformed(const uint8_t* d_bwt, BWTBlock& block, const uint32* freqs, BWTManager& bwtm) {
+    start(bwtm);
+    const size_t slots = depth();
+    assert(m_order.size() < slots);
+    const uint32 size = (uint32)block.size();
+    if (m_slots.size() < slots) m_slots.resize(slots);
+    Slot& slot = m_slots[m_next % slots];
+    const uint64 cap = bwtc_hip_compress_bound(size);
+    if (slot.cap < cap) {
+      std::free(slot.rec);
+      slot.rec = static_cast<byte*>(std::malloc(cap));
+      if (!slot.rec) hipFatal(-2, "malloc");
+      slot.cap = cap;
+    }
+    hipFatal(bwtc_hip_wavelet_encode_device_begin(m_ctx, d_bwt, size, &block.LFpowers()[0], (uint32)block.LFpowers().size(),
                                                   freqs, 0, slot.rec, slot.cap, &slot.ticket),
              "bwtc_hip_wavelet_encode_device_begin");
     m_order.push_back(m_next % slots);
@@ -608,6 +687,9 @@ inline size_t writePacked(uint64 v, OutStream* out) {             // utils::pack
 
 class Compressor {
  public:
+  // BWTC_HIP_BATCH_BLOCK's default: the largest block size at which the batched transform was measured to beat the
+  // loop of single transforms on text (README, "Batched transform")
+  enum { kBatchBlockDefault = 1 << 20 };
   // takes ownership of the streams, like the reference (Compressor.cpp:49-53)
   Compressor(InStream* in, OutStream* out, size_t memLimit, char entropyCoder)
       : m_in(in), m_out(out), m_coder(giveEntropyEncoder(entropyCoder)),
@@ -621,10 +703,27 @@ class Compressor {
     return std::min(static_cast<size_t>(m_options.memLimit * 0.185),
                     static_cast<size_t>(0x7fffffff - 1));
   }
+  // BWTC_HIP_BATCH=<k> (2 ... 4096; off by default): a stream without the pre-stage whose blocks are at most
+  // BWTC_HIP_BATCH_BLOCK bytes is transformed k blocks at a time (compressBatched).  0: not this stream.  k is cut so
+  // that the batch's strides stay below 2^26 positions (the context's workspace grows with them).
+  static size_t batchStride(size_t bs) { size_t S = 1; while (S < bs + 1) S <<= 1; return S; }
+  size_t batchBlocks() const {
+    const char* v = std::getenv("BWTC_HIP_BATCH");
+    if (!v || !m_precompressor.options().empty()) return 0;
+    const long k = std::atol(v);
+    const char* lim = std::getenv("BWTC_HIP_BATCH_BLOCK");
+    const size_t limit = lim ? (size_t)std::atoll(lim) : (size_t)kBatchBlockDefault;
+    const size_t bs = bwtBlockSize();
+    if (k < 2 || bs == 0 || bs > limit) return 0;
+    const size_t fit = ((size_t)1 << 26) / batchStride(bs);
+    const size_t n = std::min<size_t>(std::min<size_t>((size_t)k, 4096), fit);
+    return n >= 2 ? n : 0;
+  }
   void initializeBwtAlgorithm(char choice, uint32 startingPoints, int device = 0) {
     // with the pre-stage a BWT block is (memLimit - precompressed size) / 4.5 bytes (Compressor.cpp:94-97): at most memLimit / 4.5
-    const size_t largest = m_precompressor.options().empty() ? bwtBlockSize()
+    size_t largest = m_precompressor.options().empty() ? bwtBlockSize()
         : std::min(static_cast<size_t>(m_options.memLimit / 4.5) + 1, static_cast<size_t>(0x7fffffff - 1));
+    if (const size_t k = batchBlocks()) largest = k * batchStride(bwtBlockSize());   // the context holds k strides
     m_bwtmanager.setMaxBlockSize((uint32)largest);
     m_bwtmanager.setDevice(device);
     m_bwtmanager.initialize(choice);                              // Compressor.cpp:60-63
@@ -640,6 +739,7 @@ class Compressor {
   size_t compress(size_t threads) {
     if (threads != 1) { std::fprintf(stderr, "Supporting only single thread!\n"); return 0; }
     if (!m_precompressor.options().empty()) return compressPrecompressed();
+    if (const size_t k = batchBlocks()) return compressBatched(k);
     size_t compressedSize = writeGlobalHeader();
     const size_t bs = bwtBlockSize();
     std::vector<byte> buf(bs + 1);
@@ -694,6 +794,61 @@ class Compressor {
         buf[at + size] = keep;
       }
     }
+    m_out->writeByte(0); ++compressedSize;
+    m_out->flush();
+    return compressedSize;
+  }
+  // compress() with the transform batched: up to k blocks are read, uploaded once and transformed in one call
+  // (bwtc_hip_bwt_blocks_device); the coders then take them in stream order, block by block ('B', 'b' and 'u' carry
+  // their model state from block to block).  Same bytes as compress().
+  size_t compressBatched(size_t k) {
+    size_t compressedSize = writeGlobalHeader();
+    const size_t bs = bwtBlockSize();
+    bwtc_hip_ctx* ctx = m_bwtmanager.hipContext();
+    std::vector<byte> buf(k * bs + 1);
+    void* dev = bwtc_hip_malloc(ctx, k * bs + 64);
+    if (!dev) hipFatal(-2, "bwtc_hip_malloc");
+    std::vector<bwtc_hip_batch_item> items(k);
+    std::vector<uint32> lf(k * 256), freqs(k * 256);
+    std::vector<size_t> sizes;
+    size_t calls = 0, blocks = 0;
+    for (;;) {
+      size_t n = 0, total = 0;
+      while (n < k) {
+        const size_t got = m_in->readBlock(&buf[n * bs], bs);
+        if (got == 0) break;
+        BWTBlock shape(0, (uint32)got, false);
+        shape.prepareLFpowers(m_bwtmanager.getStartingPoints());
+        items[n].offset = n * bs; items[n].size = (uint32)got; items[n].n_lf = (uint32)shape.LFpowers().size();
+        total = n * bs + got;
+        ++n;
+      }
+      if (n == 0) break;
+      // the blocks of the batch before are finished: their coders read the device buffer that is written now
+      while (!sizes.empty()) { compressedSize += writeFinished(sizes.front()); sizes.erase(sizes.begin()); }
+      hipFatal(bwtc_hip_memcpy_to_device(ctx, dev, &buf[0], total), "bwtc_hip_memcpy_to_device");
+      std::fill(freqs.begin(), freqs.end(), 0u);
+      hipFatal(bwtc_hip_bwt_blocks_device(ctx, static_cast<const uint8_t*>(dev), static_cast<uint8_t*>(dev), &items[0], (uint32)n,
+                                          &lf[0], &freqs[0]), "bwtc_hip_bwt_blocks_device");
+      ++calls; blocks += n;
+      for (size_t i = 0; i < n; ++i) {
+        BWTBlock block(&buf[i * bs], items[i].size, true);
+        block.LFpowers().assign(lf.begin() + i * 256, lf.begin() + i * 256 + items[i].n_lf);
+        const uint8_t* d_bwt = static_cast<const uint8_t*>(dev) + items[i].offset;
+        if (m_coder->overlapsBlocks()) {
+          while (m_coder->pending() >= m_coder->inFlightLimit()) { compressedSize += writeFinished(sizes.front()); sizes.erase(sizes.begin()); }
+          m_coder->beginTransformed(d_bwt, block, &freqs[i * 256], m_bwtmanager);
+          sizes.push_back(items[i].size);
+        } else {
+          compressedSize += writeBlockPrefix(items[i].size);
+          compressedSize += m_coder->encodeTransformed(d_bwt, block, &freqs[i * 256], m_bwtmanager, m_out);
+        }
+      }
+      if (n < k) break;
+    }
+    while (!sizes.empty()) { compressedSize += writeFinished(sizes.front()); sizes.erase(sizes.begin()); }
+    bwtc_hip_free(ctx, dev);
+    if (std::getenv("BWTC_HIP_DEBUG")) std::fprintf(stderr, "batched transform: %zu blocks in %zu calls of up to %zu\n", blocks, calls, k);
     m_out->writeByte(0); ++compressedSize;
     m_out->flush();
     return compressedSize;

@@ -123,6 +123,38 @@ int bwtc_hip_bwt_block(bwtc_hip_ctx* ctx, uint8_t* block, uint32_t size, uint32_
 int bwtc_hip_bwt_block_device(bwtc_hip_ctx* ctx, const uint8_t* d_in, uint8_t* d_out,
                               uint32_t size, uint32_t* lf, uint32_t n_lf, uint32_t* freqs);
 
+/* ---- batched block transform (batch_bwt.hip; DESIGN.md section 3, "The batched sorter") -------
+ * k blocks in one set of launches: the same bytes, LF powers and counts as k calls of
+ * bwtc_hip_bwt_block, with one host wait per sorting round for the whole batch.
+ * Block i is data[offset .. offset + size), transformed in place (the device form: from
+ * d_in + offset to d_out + offset; d_in and d_out may be the same pointer).  Blocks may touch each
+ * other; no byte outside a block's `size` bytes is written.  lf: k rows of 256 words, row i
+ * holds block i's n_lf powers (the rest of the row is zeroed); freqs: k rows of 256, incremented;
+ * may be NULL.  Returns -1 with nothing written when k == 0 or k > 4096, a size is 0, an n_lf is 0
+ * or above 256, two blocks overlap, or k * S exceeds max_block_size + 1, where S is the smallest
+ * power of two that is >= the largest size + 1; -2 / -3 as the other entry points do.
+ * A context is driven by one thread, and no single-block transform is under way during the call. */
+typedef struct { uint64_t offset; uint32_t size; uint32_t n_lf; } bwtc_hip_batch_item;
+int bwtc_hip_bwt_blocks(bwtc_hip_ctx* ctx, uint8_t* data, const bwtc_hip_batch_item* items, uint32_t k,
+                        uint32_t* lf, uint32_t* freqs);
+int bwtc_hip_bwt_blocks_device(bwtc_hip_ctx* ctx, const uint8_t* d_in, uint8_t* d_out,
+                               const bwtc_hip_batch_item* items, uint32_t k, uint32_t* lf, uint32_t* freqs);
+/* What the last batched call on the context did.  active[0]: entries of tied groups after the initial sort,
+ * active[r]: after round r (the first 32); host_waits: every point of the call at which the host waited for
+ * the device; ms_total: device time between the call's first and last command (HIP events). */
+typedef struct {
+  uint32_t blocks, stride_log2, rounds, host_waits;
+  uint64_t suffixes;
+  uint64_t active[32];
+  float ms_total;
+} bwtc_hip_batch_stats;
+int bwtc_hip_batch_stats_get(bwtc_hip_ctx* ctx, bwtc_hip_batch_stats* out);
+/* Test hook: the load pass and the initial keys alone.  data: host bytes, uploaded at their own offsets (the
+ * largest offset + size must fit the context); T_out: the reversed, terminated blocks one after the other
+ * (sum of size + 1 bytes); keys_out: one 63-bit key per suffix in the same order; freqs_out: k rows of 256. */
+int bwtc_hip_test_batch_keys(bwtc_hip_ctx* ctx, const uint8_t* data, const bwtc_hip_batch_item* items, uint32_t k,
+                             uint8_t* T_out, uint64_t* keys_out, uint32_t* freqs_out);
+
 /* ---- inverse transform ---------------------------------------------------------------- */
 
 /* Replaces InverseBWTransform::doTransform(BWTBlock&) (bwtransforms/InverseBWT.cpp:47-51) and
